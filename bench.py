@@ -12,6 +12,12 @@ A step = what trainer/layerwise_trainer.py:220-239 of the reference does per bat
 ROCm), student forward (HIP engine), the four criteria (CE x2, KD, hint), loss = hint loss, backward, (N>1: bucketed
 RCCL all-reduce of the trainable gradients, overlapped with backward), RAdam step, zero_grad.  Inputs are resident in
 HBM before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the `--steps` steps and prints the line (metric, value, unit, ms_per_step, ...).  Everything
+else the benchmark measures -- per-launch HIP events with the roofline and per-class figures, the un-instrumented A/B, the batch
+sweep, the CPU baseline, the sub-records, the replica check of N > 1 and the full record file -- runs with `--full`.
+`--dump-outputs DIR` writes what the last timed step computed (losses, trainable parameters, seeded samples of both logits) as
+DIR/<name>.npy.
 """
 import argparse
 import json
@@ -75,9 +81,11 @@ def _filter_weight(i, channels, device):
     return _FW[key]
 
 
-def kd_step(model, crit, opt, data, target, mode="A", prefetch=True):
+def kd_step(model, crit, opt, data, target, mode="A", prefetch=True, keep=None):
     from kdcc_amd.losses import WeightedHintMSELoss
     out_st, out_tc = model(data)
+    if keep is not None:             # --dump-outputs: the logits of this step, read after the timed region
+        keep.update(student_logits=out_st, teacher_logits=out_tc)
     sup = crit[0](out_st, target)
     kd = crit[1](out_st, out_tc)
     tl = crit[0](out_tc, target)
@@ -94,6 +102,51 @@ def kd_step(model, crit, opt, data, target, mode="A", prefetch=True):
     opt.step()
     opt.zero_grad()
     return loss, sup, kd, tl
+
+
+DUMP_SAMPLE = 1 << 20          # elements kept of each logits tensor (4 MB)
+DUMP_PARAM_BUDGET = 8 << 20    # elements kept of all trainable parameters together (32 MB)
+
+
+def _sample_index(shape, k, seed):
+    """k flat indices into a tensor of `shape`, sorted; fixed by shape and seed (a CPU generator: the same on every run and box)."""
+    n = 1
+    for s in shape:
+        n *= int(s)
+    if n <= k:
+        return None
+    return torch.randint(n, (k,), generator=torch.Generator().manual_seed(seed)).sort().values
+
+
+def dump_outputs(path, model, keep, losses):
+    """--dump-outputs: what the last timed step handed its caller, as float32 / float64 .npy files (< 64 MB in all): the four
+    losses, the trainable parameters after the optimizer step (each in full while they fit DUMP_PARAM_BUDGET together, else a
+    seeded sample of each in proportion) and a seeded sample of the student's and the teacher's full-resolution logits."""
+    import numpy as np
+    from kdcc_amd.lazy import unwrap
+    os.makedirs(path, exist_ok=True)
+    for name, v in zip(("loss", "supervised", "kd", "teacher"), losses):
+        np.save(os.path.join(path, f"{name}.npy"), np.asarray(float(v.detach() if torch.is_tensor(v) else v), dtype=np.float64))
+    params = [(n, p) for n, p in model.student.named_parameters() if p.requires_grad]
+    total = sum(p.numel() for _, p in params)
+    for i, (n, p) in enumerate(params):
+        flat = p.detach().reshape(-1)
+        idx = None if total <= DUMP_PARAM_BUDGET else _sample_index(flat.shape, -(-p.numel() * DUMP_PARAM_BUDGET // total), 17 + i)
+        a = flat if idx is None else flat[idx.to(flat.device)]
+        a = a.float().cpu().numpy()
+        np.save(os.path.join(path, f"param.{n}.npy"), a.reshape(p.shape) if idx is None else a)
+    for i, name in enumerate(("student_logits", "teacher_logits")):
+        t = unwrap(keep[name]).detach()
+        idx = _sample_index(t.shape, DUMP_SAMPLE, 5 + i)
+        if idx is None:
+            a = t.float().cpu().numpy()
+        else:
+            coords = []
+            for s in reversed(t.shape):              # flat index of the logical (N, C, H, W) order -> one index per dimension
+                coords.append(idx % s)
+                idx = idx // s
+            a = t[tuple(c.to(t.device) for c in reversed(coords))].float().cpu().numpy()
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def cpu_share():
@@ -270,8 +323,10 @@ def class_rooflines(prof, steps, peak_tflops):
 
 
 def run_config(a, device, rank, world, plan_name=None, mode=None, arch=None, hint_loss="mse", steps=None, warmup=None,
-               batch_sweep=True, dtype_name=None, batch=None, share_prefix=None, ref_logging=None):
-    """Build one configuration, run `warmup` untimed + `steps` timed KD train steps, return (record, model, cpu_sd, plan)."""
+               batch_sweep=True, dtype_name=None, batch=None, share_prefix=None, ref_logging=None, dump=None):
+    """Build one configuration, run `warmup` untimed + `steps` timed KD train steps, return (record, model, cpu_sd, plan).
+    Without --full the record holds the headline only: no per-launch events, roofline, A/B, batch sweep or replica check.
+    `dump`: a directory for dump_outputs() of the last timed step (rank 0)."""
     from kdcc_amd import ops, parallel
     plan_name, mode, arch = plan_name or a.plan, mode or a.mode, arch or a.arch
     steps, warmup = steps or a.steps, a.warmup if warmup is None else warmup
@@ -307,20 +362,25 @@ def run_config(a, device, rank, world, plan_name=None, mode=None, arch=None, hin
         kd_step(model, crit, opt, data, target, mode)
     sync()
     prof = []
-    ops.PROFILER = None if a.no_profiler else prof      # two HIP events per kernel launch inside the timed region (--no-profiler: none)
+    profiled = a.full and not a.no_profiler
+    ops.PROFILER = prof if profiled else None      # --full: two HIP events per kernel launch inside the timed region (--no-profiler: none)
+    keep = {} if (dump and rank == 0) else None
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for i in range(steps):
         # (--teacher-stream backward: every step prefetches the next one's teacher, the last one included; the window is closed by
         # torch.cuda.synchronize(), a DEVICE-wide wait, so that last forward is finished inside it: the first step's teacher ran
         # during warm-up, the last step's extra one replaces it -- exactly `steps` teacher forwards are timed)
-        loss, sup, kd, tl = kd_step(model, crit, opt, data, target, mode)
+        loss, sup, kd, tl = kd_step(model, crit, opt, data, target, mode, keep=keep if i == steps - 1 else None)
         if a.ref_logging:
             _ = (loss.item(), sup.item(), kd.item(), loss.item(), tl.item())
     sync()
     dt = time.perf_counter() - t0
     ops.PROFILER = None
+    if keep is not None:
+        dump_outputs(dump, model, keep, (loss, sup, kd, tl))
+        del keep            # (frees the materialised full-resolution logits before anything else runs)
     # what the per-launch events cost: the same step, un-instrumented, right behind the timed region (same device, same clocks)
-    ab_steps = 0 if (a.no_profiler or a.no_profiler_ab or not batch_sweep) else min(8, steps)
+    ab_steps = 0 if (not profiled or a.no_profiler_ab or not batch_sweep) else min(8, steps)
     dt_plain = None
     if ab_steps:
         t1 = time.perf_counter()
@@ -357,6 +417,7 @@ def run_config(a, device, rank, world, plan_name=None, mode=None, arch=None, hin
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
+    if world > 1 and a.full:
         # every rank trained on its own shard: the replicas stay bit-identical only if every gradient bucket was
         # all-reduced before the optimizer read it (fp64 sums of the trainable parameters, min == max over ranks)
         cs = torch.stack([p.detach().double().sum() for p in model.student.parameters() if p.requires_grad])
@@ -368,7 +429,7 @@ def run_config(a, device, rank, world, plan_name=None, mode=None, arch=None, hin
     # SURVEY 8(d) defines the metric at 1 and 2 images per GPU; the headline uses --batch (fuller grids).  Measure both
     # side by side (short: 2 warm-up + 8 timed steps each) so one record carries all three.
     sweep = {}
-    if batch_sweep and not a.no_batch_sweep:
+    if a.full and batch_sweep and not a.no_batch_sweep:
         for nb in (1, 2, 4):
             if nb >= a.batch:
                 continue
@@ -409,7 +470,7 @@ def run_config(a, device, rank, world, plan_name=None, mode=None, arch=None, hin
                        else "images/sec KD train step, DeepLabV3+(WRN38) student 1024x2048"),
             "value": world * a.batch * steps / dt, "unit": "images/sec", "n_gpus": world, "steps": steps,
             "warmup": warmup, "ms_per_step": dt / steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "profiler": {"events_in_timed_region": not a.no_profiler,
+            "profiler": {"events_in_timed_region": profiled,
                          "ms_per_step_without_events": (dt_plain / ab_steps * 1e3 if ab_steps else None), "ab_steps": ab_steps},
             "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
             "config": {"workload": f"KD train step (frozen teacher fwd + student fwd + CE/KD/hint criteria, hint = {crit_name}, + "
@@ -441,6 +502,8 @@ def run_config(a, device, rank, world, plan_name=None, mode=None, arch=None, hin
                              "algorithmic_tflop_per_step": wg_flops / max(steps, 1) / 1e12} if wg_ms > 0 else None),
             "losses": {("hint" if mode == "A" else "kd+hint"): float(loss.detach()), "supervised": float(sup), "kd": float(kd), "teacher": float(tl)},
         }
+        if not a.full:      # the kernel figures come from the per-launch events of --full
+            del res["roofline"], res["dense_wgrad"]
     return res, model, cpu_sd, plan
 
 
@@ -454,7 +517,7 @@ def _r(x, nd=4):
 def compact_record(res, full_path=None):
     """The ONE stdout line: contract keys + roofline + cpu_baseline + one number per side measurement, < 4 KB.  Everything
     else (per-class detail, layer notes, sub-record rooflines) is in the full record file / on stderr."""
-    cfg, rf = res["config"], res["roofline"]
+    cfg, rf = res["config"], res.get("roofline")
     out = {k: _r(res[k]) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                                    "scaling", "vs_baseline", "dtype", "data")}
     out["config"] = {"workload": (f"KD train step (teacher fwd + student fwd + CE/KD/hint criteria + "
@@ -466,15 +529,16 @@ def compact_record(res, full_path=None):
                                             "teacher_backend", "share_frozen_prefix", "replicas_identical_after_run",
                                             "ranks_seen", "backend")},
                      "rank_devices": [d["device"] for d in cfg["rank_devices"]]}
-    out["roofline"] = {"bound": rf["bound"], "kernel": "kd_conv2d_fwd (dense conv fwd + dgrad: conv_row_lw / conv_igemm_persist / "
-                                                       "conv_row_tall / one-tile kernels)",
-                       **{k: _r(rf.get(k)) for k in ("achieved", "peak", "unit", "frac", "traffic", "traffic_src", "launches_per_step",
-                                                 "ms_per_step_in_kernel", "algorithmic_tflop_per_step")},
-                       "classes": {n: [_r(c["ms_per_step"], 3), _r(c["frac"], 3)] for n, c in rf["classes"].items()},
-                       "dw_floor_ms": {n: [_r(c["floor_ms"]["matrix"], 3), _r(c["floor_ms"]["bytes_at_6.3TBps"], 3), _r(c["floor_ms"]["bytes_at_2.5TBps_pattern"], 3)]
-                                       for n, c in rf["classes"].items() if "floor_ms" in c},
-                       "dw_floor_fmt": "[matrix, bytes / 6.3 TB/s, bytes / 2.5 TB/s (measured cap of 32-B channel slices)] ms per step",
-                       "classes_fmt": "[ms_per_step, frac of its roof (mfma 2500 TFLOP/s | hbm 8000 GB/s)]"}
+    if rf:
+        out["roofline"] = {"bound": rf["bound"], "kernel": "kd_conv2d_fwd (dense conv fwd + dgrad: conv_row_lw / conv_igemm_persist / "
+                                                           "conv_row_tall / one-tile kernels)",
+                           **{k: _r(rf.get(k)) for k in ("achieved", "peak", "unit", "frac", "traffic", "traffic_src", "launches_per_step",
+                                                     "ms_per_step_in_kernel", "algorithmic_tflop_per_step")},
+                           "classes": {n: [_r(c["ms_per_step"], 3), _r(c["frac"], 3)] for n, c in rf["classes"].items()},
+                           "dw_floor_ms": {n: [_r(c["floor_ms"]["matrix"], 3), _r(c["floor_ms"]["bytes_at_6.3TBps"], 3), _r(c["floor_ms"]["bytes_at_2.5TBps_pattern"], 3)]
+                                           for n, c in rf["classes"].items() if "floor_ms" in c},
+                           "dw_floor_fmt": "[matrix, bytes / 6.3 TB/s, bytes / 2.5 TB/s (measured cap of 32-B channel slices)] ms per step",
+                           "classes_fmt": "[ms_per_step, frac of its roof (mfma 2500 TFLOP/s | hbm 8000 GB/s)]"}
     if res.get("profiler"):
         out["profiler"] = {k: _r(v) for k, v in res["profiler"].items()}
     cb = res.get("cpu_baseline")
@@ -561,20 +625,28 @@ def main():
     ap.add_argument("--height", type=int, default=1024)
     ap.add_argument("--width", type=int, default=2048)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-launch HIP events in the timed region (roofline, "
+                         "per-class figures, --layer-table), the un-instrumented A/B, the batch sweep, the CPU baseline, the "
+                         "sub-records, the replica check of N > 1, the full record file; the --no-* options below trim it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy: the four losses (float64), the trainable "
+                         "parameters after the step and seeded 1M-element samples of the student / teacher logits (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline", default="step", choices=["step", "sample", "full"],
                     help="step (default): one measured 1024x2048 CPU step (~1 min) after a 512x1024 one; sample: the 512x1024 step only, "
                          "pixel-scaled; full: BASELINE.md section 3 (1 warm-up + 2 steps at 1024x2048 + 5 steps at 256x512)")
     ap.add_argument("--no-sub-records", action="store_true",
-                    help="skip the short P79 / mode B / GSCNN P86 / WeightedHintMSE side measurements of the default run")
+                    help="skip the short P79 / mode B / GSCNN P86 / WeightedHintMSE side measurements of --full")
     ap.add_argument("--layer-table", default=None, help="write a per-conv-shape timing table (tsv) to this path")
     ap.add_argument("--no-batch-sweep", action="store_true", help="skip the 1 and 2 images/GPU side measurements")
     ap.add_argument("--no-profiler", action="store_true",
-                    help="time the steps without the two HIP events per kernel launch (no roofline in the record); the default run "
-                         "measures the same un-instrumented step right behind the timed region and reports both")
+                    help="with --full: time the steps without the two HIP events per kernel launch (no roofline in the record); --full "
+                         "otherwise measures the same un-instrumented step right behind the timed region and reports both")
     ap.add_argument("--no-profiler-ab", action="store_true", help="skip that un-instrumented A/B measurement")
     ap.add_argument("--full-record", default=None,
-                    help="where the full record goes (default gpurun_out/bench_full.json); stdout carries the compact line only")
+                    help="where the full record goes (written with --full or when given; default bench_out/bench_full.json); stdout "
+                         "carries the compact line only")
     ap.add_argument("--no-overlap", action="store_true", help="with --teacher torch: run the teacher on the main stream")
     ap.add_argument("--ref-logging", action="store_true",
                     help="also do the reference's per-step host syncs (five .item() calls, layerwise_trainer.py:244-250); the "
@@ -591,6 +663,10 @@ def main():
                     help="hip: frozen teacher graph through the engine's HIP kernels (default); torch: teacher as a PyTorch-ROCm "
                          "module (MIOpen) on a side stream, the split north_star describes")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.layer_table and not a.full:
+        ap.error("--layer-table reads the per-launch events of --full")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` typed without a launcher: start the N ranks as FRESH child processes.  This process has not
@@ -606,13 +682,13 @@ def main():
         raise SystemExit("bench.py needs an MI355X (the HIP path has no CPU fallback)")
     device = torch.device("cuda", local)
 
-    res, model, cpu_sd, plan = run_config(a, device, rank, world, hint_loss=a.hint_loss)
+    res, model, cpu_sd, plan = run_config(a, device, rank, world, hint_loss=a.hint_loss, dump=a.dump_outputs)
     headline_default = (a.plan, a.mode, a.arch, a.hint_loss, a.dtype, a.teacher, (a.height, a.width)) == \
         ("P92", "A", "deeplab", "mse", "bf16", "hip", (1024, 2048)) and not a.share_prefix
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.arch == "deeplab":
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and a.arch == "deeplab":
         res["cpu_baseline"] = cpu_baseline(cpu_sd, model, plan, full=a.cpu_baseline)
     del model
-    if world == 1 and headline_default and not a.no_sub_records:
+    if a.full and world == 1 and headline_default and not a.no_sub_records:
         import gc
         subs = {}
         for name, kw, what in SUB_RECORDS:
@@ -629,17 +705,19 @@ def main():
         res["sub_records"] = subs
     if rank == 0:
         res["_hw"] = f"{a.height}x{a.width}"
-        # the full record (per-class rooflines with their notes, sub-record rooflines, the batch sweep) goes to a file and to
-        # stderr; stdout carries ONE compact line (the driver keeps a few KB of it)
-        full = a.full_record or os.path.join(ROOT, "gpurun_out", "bench_full.json")
-        try:
-            os.makedirs(os.path.dirname(full), exist_ok=True)
-            with open(full, "w") as f:
-                json.dump(res, f)
-            shown = os.path.relpath(full, ROOT)
-        except OSError:
-            shown = None
-        print("[bench] full record: " + json.dumps(res), file=sys.stderr, flush=True)
+        # --full: the full record (per-class rooflines with their notes, sub-record rooflines, the batch sweep) goes to a file and
+        # to stderr; stdout carries ONE compact line (< 4 KB)
+        shown = None
+        if a.full or a.full_record:
+            full = a.full_record or os.path.join(ROOT, "bench_out", "bench_full.json")
+            try:
+                os.makedirs(os.path.dirname(full), exist_ok=True)
+                with open(full, "w") as f:
+                    json.dump(res, f)
+                shown = os.path.relpath(full, ROOT)
+            except OSError:
+                pass
+            print("[bench] full record: " + json.dumps(res), file=sys.stderr, flush=True)
         line = json.dumps(compact_record(res, shown))
         assert len(line) < 4096, len(line)
         print(line, flush=True)

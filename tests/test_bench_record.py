@@ -72,3 +72,66 @@ def test_traffic_summary_follows_the_configuration():
         assert t and t > 1e9 and src.endswith(suffix), (mode, t, src)
     assert bench.conv_traffic("P79", 8, 1024, 2048, "bf16", "A", "deeplab") == (None, None)
     assert bench.conv_traffic("P92", 8, 512, 1024, "bf16", "A", "deeplab") == (None, None)
+
+
+def test_plain_record_carries_the_headline_only():
+    """A run without --full measures no kernel figures: its line has the contract keys and no roofline / cpu_baseline."""
+    import bench
+    full = _full_record()
+    plain = {k: v for k, v in full.items() if k not in ("roofline", "dense_wgrad", "cpu_baseline", "sub_records")}
+    plain["profiler"] = {"events_in_timed_region": False, "ms_per_step_without_events": None, "ab_steps": 0}
+    plain["config"] = dict(full["config"], per_gpu_batch_sweep={})
+    rec = json.loads(json.dumps(bench.compact_record(plain)))
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "losses"):
+        assert k in rec, k
+    assert "roofline" not in rec and "cpu_baseline" not in rec and "sub_records" not in rec and "batch_sweep" not in rec
+    assert rec["ms_per_step"] == 191.8 and rec["profiler"]["events_in_timed_region"] is False
+
+
+def test_dump_outputs_files_size_and_seeded_samples(tmp_path):
+    """--dump-outputs on the CPU with stand-in tensors: float32 / float64 .npy files, the trainable parameters whole while they fit the
+    budget and sampled (in proportion, seeded) beyond it, logits sampled at the same seeded (N, C, H, W) positions on every call."""
+    import numpy as np
+    import torch
+    import bench
+
+    class Net(torch.nn.Module):
+        def __init__(self, big):
+            super().__init__()
+            self.a = torch.nn.Parameter(torch.randn(big))
+            self.b = torch.nn.Parameter(torch.randn(4, 3, 3, 3))
+            self.frozen = torch.nn.Parameter(torch.randn(10), requires_grad=False)
+
+    model = type("M", (), {})()
+    logits = torch.randn(2, 19, 64, 48).permute(0, 1, 3, 2)          # non-contiguous, as the engine's channels-last logits
+    keep = {"student_logits": logits, "teacher_logits": logits * 2}
+    losses = (torch.tensor(1.5), torch.tensor(2.0), torch.tensor(0.25), 3.0)
+
+    model.student = Net(1000)
+    bench.dump_outputs(str(tmp_path / "small"), model, keep, losses)
+    d = tmp_path / "small"
+    assert sorted(p.name for p in d.iterdir()) == sorted(["loss.npy", "supervised.npy", "kd.npy", "teacher.npy", "param.a.npy", "param.b.npy",
+                                                         "student_logits.npy", "teacher_logits.npy"])
+    assert np.load(d / "loss.npy").dtype == np.float64 and float(np.load(d / "kd.npy")) == 0.25
+    np.testing.assert_array_equal(np.load(d / "param.b.npy"), model.student.b.detach().numpy())
+    assert np.load(d / "param.b.npy").dtype == np.float32
+    np.testing.assert_array_equal(np.load(d / "student_logits.npy"), logits.numpy())       # small: whole, logical (N, C, H, W)
+
+    old = bench.DUMP_SAMPLE, bench.DUMP_PARAM_BUDGET
+    try:
+        bench.DUMP_SAMPLE, bench.DUMP_PARAM_BUDGET = 500, 2000
+        model.student = Net(100000)
+        for run in ("x", "y"):
+            bench.dump_outputs(str(tmp_path / run), model, keep, losses)
+        x, y = tmp_path / "x", tmp_path / "y"
+        s = np.load(x / "student_logits.npy")
+        idx = bench._sample_index(logits.shape, 500, 5).numpy()
+        np.testing.assert_array_equal(s, logits.contiguous().reshape(-1).numpy()[idx])
+        np.testing.assert_array_equal(np.load(x / "teacher_logits.npy"), 2 * logits.contiguous().reshape(-1).numpy()[bench._sample_index(logits.shape, 500, 6).numpy()])
+        pa = np.load(x / "param.a.npy")
+        assert pa.dtype == np.float32 and 1990 <= pa.size <= 2000 and np.isin(pa, model.student.a.detach().numpy()).all()
+        assert sum(np.load(x / f).size for f in ("param.a.npy", "param.b.npy")) <= 2002
+        for f in x.iterdir():
+            np.testing.assert_array_equal(np.load(f), np.load(y / f.name))
+    finally:
+        bench.DUMP_SAMPLE, bench.DUMP_PARAM_BUDGET = old

@@ -429,7 +429,7 @@ def test_bench_two_ranks_child_process(tmp_path):
     env.pop("RANK", None); env.pop("WORLD_SIZE", None); env.pop("LOCAL_RANK", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", port, os.path.join(root, "bench.py"), "--gpus", "2", "--batch", "1", "--steps", "3", "--warmup", "1",
-           "--height", "512", "--width", "1024", "--no-batch-sweep", "--no-sub-records", "--full-record", str(tmp_path / "full.json")]
+           "--height", "512", "--width", "1024", "--full", "--no-batch-sweep", "--no-sub-records", "--full-record", str(tmp_path / "full.json")]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -453,7 +453,7 @@ def test_bench_gpus_2_without_a_launcher(tmp_path):
     env = dict(os.environ, KDCC_DIST_SHARE_GPU="1", KDCC_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
            "--no-sub-records", "--no-batch-sweep", "--batch", "1", "--height", "512", "--width", "1024",
            "--full-record", str(tmp_path / "full.json")]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)

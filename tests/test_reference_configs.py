@@ -1,7 +1,7 @@
 """Every shipped Cityscapes config of the reference (cfg/cityscapes/*.json) is a drop-in at the plan level: teacher type
 resolves, every pruning-plan / hint / unfreeze name of every epoch applies to the fused student, parameter counts match the
-README rows.  Reads the reference's JSON files as data when /root/reference is present (the build container); skipped on
-boxes without it.  CPU only (meta device)."""
+README rows.  The reference's JSON files are stored as data under tests/golden/cfg/ (verbatim copies of its cfg/ files).
+CPU only (meta device)."""
 import glob
 import json
 import os
@@ -13,13 +13,19 @@ import kdcc_amd  # noqa: F401
 from kdcc_amd import models
 from kdcc_amd.models.students import DepthwiseStudent
 
-CFG_DIR = "/root/reference/cfg/cityscapes"
+GOLDEN_CFG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cfg")
+CFG_DIR = os.path.join(GOLDEN_CFG, "cityscapes")
 CONFIGS = sorted(glob.glob(os.path.join(CFG_DIR, "*.json")))
 EXPECTED = {"58M_deeplab_all.json": 79752256, "51M_deeplab_all.json": 85960768, "51M_gscnn_all.json": 86135022,
             "51M_deeplab_incremental.json": 85960768}
+TAYLOR_CFG = os.path.join(GOLDEN_CFG, "taylor_importance_track.json")
 
 
-@pytest.mark.skipif(not CONFIGS, reason="reference configs not present on this box")
+def test_the_stored_configs_are_all_there():
+    assert [os.path.basename(p) for p in CONFIGS] == ["10M_hrnet_all.json", *sorted(EXPECTED)]
+    assert os.path.exists(TAYLOR_CFG)
+
+
 @pytest.mark.parametrize("path", CONFIGS, ids=[os.path.basename(p) for p in CONFIGS])
 def test_shipped_config_plan_applies(path):
     cfg = json.load(open(path))
@@ -49,10 +55,6 @@ def test_shipped_config_plan_applies(path):
     assert hasattr(kdcc_amd.trainer, cfg["trainer"]["name"])
 
 
-TAYLOR_CFG = "/root/reference/cfg/taylor_importance_track.json"
-
-
-@pytest.mark.skipif(not os.path.exists(TAYLOR_CFG), reason="reference configs not present on this box")
 def test_shipped_taylor_config_plan_applies():
     """cfg/taylor_importance_track.json -- the only Taylor config the reference ships: `pruning` has just {args, pruning_plan},
     and the plan gates block convs, bnrelu ReLUs (`...bn2.1`, `...bn3.1`) and ASPP branch ReLUs (`aspp.features.N.2`).  Every

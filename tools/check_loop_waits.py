@@ -7,10 +7,11 @@ blocks that sits in a depth-2 loop of a persistent kernel.  usage: python tools/
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(ROOT, "knowledge-distillation-by-replacing-cheap-conv_amd", "csrc", "conv_igemm.hip")
-out = os.path.join(tempfile.gettempdir(), "conv_igemm_check.s")
-subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", src, "-o", out],
-                      stderr=subprocess.DEVNULL)
-lines = open(out).read().split("\n")
+with tempfile.TemporaryDirectory() as td:     # a private directory: a fixed name in the shared temp dir may belong to another user
+    out = os.path.join(td, "conv_igemm_check.s")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", src, "-o", out],
+                          stderr=subprocess.DEVNULL)
+    lines = open(out).read().split("\n")
 starts = [(i, l) for i, l in enumerate(lines) if re.match(r"^_ZN\S*:", l)]
 def production(name):
     """the instantiations kd_conv2d_fwd dispatches by default: ping-pong, no debug stamps"""

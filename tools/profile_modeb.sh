@@ -6,7 +6,7 @@ tag=${1:-profB}
 out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
-B="python bench.py --no-cpu-baseline --no-batch-sweep --no-sub-records --no-profiler-ab --mode B"
+B="python bench.py --full --no-cpu-baseline --no-batch-sweep --no-sub-records --no-profiler-ab --mode B"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/profB -o modeB -- $B --steps 5 --warmup 2 > $out/b.log 2>&1 || exit 1
 echo "[profile] mode B stats done"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/fetchB -o f -- $B --steps 2 --warmup 1 > $out/fb.log 2>&1 || exit 1

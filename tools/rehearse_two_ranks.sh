@@ -8,4 +8,4 @@
 set -o pipefail
 KDCC_DIST_BACKEND=gloo KDCC_DIST_SHARE_GPU=1 timeout -k 10 400 \
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port "${1:-29513}" \
-  bench.py --gpus 2 --steps 3 --warmup 1 --batch 1 --no-batch-sweep
+  bench.py --gpus 2 --steps 3 --warmup 1 --batch 1 --full --no-batch-sweep
