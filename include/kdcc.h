@@ -505,6 +505,60 @@ int kd_ce2d_weighted_grad(const kd_view3 *x, const int64_t *target, const float 
                           int32_t N, int32_t C, int64_t P, const kd_mview3 *grad, float grad_scale, void *workspace,
                           size_t workspace_bytes, kd_stream_t stream);
 
+/* The reference's other criteria (losses/__init__.py:2,5-7), same conventions as above; fp32 / bf16 operands, fp32 arithmetic,
+ * fixed-order fp64 reductions (bit-reproducible), the loss stays on the device.  p = softmax over C, lp = log p.
+ *
+ * kd_jsdiv: JSDivergenceLoss.forward, losses/JSDiv.py:19-26.  ps = softmax(s/T), pt = softmax(t/T), q = (ps + pt)/2 with
+ *   log q = log 1/2 + logaddexp(lps, lpt):
+ *   loss = T^2/(2N) * sum_{n,c,p} [ps (lps - log q) + pt (lpt - log q)]      (divided by the batch size N only)
+ *   grad = T/(2N) * ps * (a - <ps, a>_c), a = lps - log q                      (t is a constant, as in kd_kldiv)
+ *   Deliberate difference: log q is evaluated as log((ps + pt)/2) -- one hardware log -- while ps + pt > 1e-30 (a normal
+ *   number, where the two forms agree to a few ulp), and as log 1/2 + logaddexp(lps, lpt) below that, where ps + pt underflows.
+ * kd_jsdiv_up: kd_jsdiv's forward from the two low-resolution logit tensors (see kd_kldiv_up: same limits, C <= 24).
+ * kd_ensemble_kldiv: EnsembleKLDivergenceLoss.forward, losses/EnsembleKLDiv.py:17-21; t holds probabilities:
+ *   loss = kl_div(log_softmax(s,1), t, 'mean') * C = 1/(N*P) * sum [xlogy(t, t) - t lps]   (0 log 0 = 0)
+ *   grad = (ps * sum_c t - t) / (N*P)
+ * kd_focal: FocalLoss.forward, losses/FocalLoss.py:15-28.  The inner nn.CrossEntropyLoss is already reduced (the class overwrites
+ *   `reduction` after __init__, :10-12).  Per pixel, y' = y at a valid label and 0 at an ignored one (:21-22):
+ *     a = (1 - p_y')^gamma at every pixel; ce = alpha_y * -lp_y at valid pixels, 0 at ignored ones; w = alpha_y at valid pixels
+ *   (alpha: fp32 (C) on the device, or NULL for 1).  reduction 1 'mean': loss = mean(a) * sum ce / sum w;
+ *   2 'sum': loss = sum a * sum ce; 0 'none': no scalar, a_map / ce_map (fp32 (N,P), required) hold a and ce, the caller forms
+ *   the (N,N,P) product a[i] * ce[j] the reference returns.  stats (3 fp64 on the device, may be NULL): sum a, sum ce, sum w --
+ *   what kd_focal_grad reads.  A label outside [0, C) that is not ignore_index counts as ignored (the reference raises).
+ * kd_focal_grad: its gradient, in a second launch that reads stats and the upstream gradient on the device (no host sync):
+ *   grad = u_a * da/dx + u_c * dce/dx, da/dx_c = -gamma (1-p_y')^(gamma-1) p_y' (delta_cy' - p_c), dce/dx_c = alpha_y (p_c - delta_cy)
+ *   'mean': u_a = g * CE_mean / (N*P), u_c = g * mean(a) / sum w;  'sum': u_a = g * sum ce, u_c = g * sum a  (upstream: 1 fp32);
+ *   'none': upstream is the dense (N,N,P) fp32 gradient G, u_a[n] = sum_j G[n,j] ce[j], u_c[n] = sum_i G[i,n] a[i] (per pixel).
+ *   Deliberate difference: for gamma < 1 at p_y' == 1 (1 - p_y' rounds to 0) da/dx is 0, its limit, where the reference's autograd
+ *   gives NaN (0 * inf); gamma == 0 gives da/dx = 0 everywhere.
+ * kd_focal_up: kd_focal 'mean' / 'sum' from the low-resolution logits (see kd_ce2d_up: same limits, C <= 48).
+ * kd_topk_hint_mse: TopkHintMSELoss.forward, losses/WeightedHintMSELoss.py:28-44, 4-D targets only.  Per sample the channels are
+ *   ranked by the L2 norm of t over the P pixels and the first K kept (K = int(topk * C), computed by the caller as the reference
+ *   does; 1 <= K <= C, else KD_ERR_INVALID where the reference returns NaN); num_classes is not applied:
+ *   loss = sum_{n,c} mask * mean_p (s-t)^2 / (N*K) ; grad = 2 * mask * (s-t) / (P*N*K)
+ *   Deliberate difference: equal norms keep the lower channel index first (the reference's argsort order is unspecified).
+ *   The selection runs on the device (rank by count in LDS, C <= 4096); mask: fp32 (N,C) output or NULL.  workspace of
+ *   kd_topk_hint_workspace() bytes. */
+int kd_jsdiv(const kd_view3 *s, const kd_view3 *t, float temperature, int32_t N, int32_t C, int64_t P, float *loss,
+             const kd_mview3 *grad, float grad_scale, void *workspace, size_t workspace_bytes, kd_stream_t stream);
+int kd_jsdiv_up(const float *s_lo, const float *t_lo, float temperature, int32_t N, int32_t h, int32_t w, int32_t C, int32_t H,
+                int32_t W, int32_t align_corners, float *loss, void *workspace, size_t workspace_bytes, kd_stream_t stream);
+int kd_ensemble_kldiv(const kd_view3 *s, const kd_view3 *t, int32_t N, int32_t C, int64_t P, float *loss, const kd_mview3 *grad,
+                      float grad_scale, void *workspace, size_t workspace_bytes, kd_stream_t stream);
+int kd_focal(const kd_view3 *x, const int64_t *target, const float *alpha, float gamma, int32_t ignore_index, int32_t reduction,
+             int32_t N, int32_t C, int64_t P, float *loss, double *stats, float *a_map, float *ce_map, void *workspace,
+             size_t workspace_bytes, kd_stream_t stream);
+int kd_focal_grad(const kd_view3 *x, const int64_t *target, const float *alpha, float gamma, int32_t ignore_index, int32_t reduction,
+                  int32_t N, int32_t C, int64_t P, const double *stats, const float *upstream, const float *a_map, const float *ce_map,
+                  const kd_mview3 *grad, kd_stream_t stream);
+int kd_focal_up(const float *x_lo, const int64_t *target, const float *alpha, float gamma, int32_t ignore_index, int32_t reduction,
+                int32_t N, int32_t h, int32_t w, int32_t C, int32_t H, int32_t W, int32_t align_corners, float *loss, double *stats,
+                void *workspace, size_t workspace_bytes, kd_stream_t stream);
+size_t kd_topk_hint_workspace(int32_t N, int32_t C, int64_t P);
+int kd_topk_hint_mse(const kd_view3 *s, const kd_view3 *t, int32_t K, int32_t N, int32_t C, int64_t P, float *loss,
+                     const kd_mview3 *grad, float grad_scale, float *mask, void *workspace, size_t workspace_bytes,
+                     kd_stream_t stream);
+
 /* CityscapesMetricTracker.update / confusion_for_batch (utils/util.py:108-128), the logged train mIoU, without the
  * reference's two full-logit D2H copies per step (trainer/layerwise_trainer.py:249-250):
  *   for every pixel with 0 <= target < C:  conf[target][argmax_c x(n,c,p)] += 1

@@ -144,6 +144,15 @@ _SIGS = {
     "kd_ce2d_grad": (c_int, [_P(View3), c_vp, c_int, c_int, c_int, c_i64, _P(View3), c_f, c_vp, c_sz, c_vp]),
     "kd_ce2d_weighted": (c_int, [_P(View3), c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_vp, c_vp, c_sz, c_vp]),
     "kd_ce2d_weighted_grad": (c_int, [_P(View3), c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, _P(View3), c_f, c_vp, c_sz, c_vp]),
+    "kd_jsdiv": (c_int, [_P(View3), _P(View3), c_f, c_int, c_int, c_i64, c_vp, _P(View3), c_f, c_vp, c_sz, c_vp]),
+    "kd_jsdiv_up": (c_int, [c_vp, c_vp, c_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_sz, c_vp]),
+    "kd_ensemble_kldiv": (c_int, [_P(View3), _P(View3), c_int, c_int, c_i64, c_vp, _P(View3), c_f, c_vp, c_sz, c_vp]),
+    "kd_focal": (c_int, [_P(View3), c_vp, c_vp, c_f, c_int, c_int, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "kd_focal_grad": (c_int, [_P(View3), c_vp, c_vp, c_f, c_int, c_int, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, _P(View3), c_vp]),
+    "kd_focal_up": (c_int, [c_vp, c_vp, c_vp, c_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,
+                            c_sz, c_vp]),
+    "kd_topk_hint_workspace": (c_sz, [c_int, c_int, c_i64]),
+    "kd_topk_hint_mse": (c_int, [_P(View3), _P(View3), c_int, c_int, c_int, c_i64, c_vp, _P(View3), c_f, c_vp, c_vp, c_sz, c_vp]),
     "kd_confusion": (c_int, [_P(View3), c_vp, c_int, c_int, c_i64, c_vp, c_int, c_vp]),
     "kd_radam_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_f, c_f, c_f, c_f, c_f, c_vp]),
     "kd_radam_step_multi": (c_int, [_P(RadamTensor), c_int, c_vp]),

@@ -1,5 +1,6 @@
 // KD losses, forward + gradient fused in one pass (kd_kldiv, kd_hint_mse,
-// kd_weighted_hint_mse, kd_ce2d) and the RAdam update (kd_radam_step).
+// kd_weighted_hint_mse, kd_ce2d, kd_jsdiv, kd_ensemble_kldiv, kd_focal, kd_topk_hint_mse)
+// and the RAdam update (kd_radam_step).
 // All are HBM-bound streaming kernels.  Loss scalars are reduced in two fixed-order
 // stages (per-block partials in fp64 -> one finishing block), so results are
 // bit-reproducible run to run.
@@ -669,6 +670,481 @@ __global__ __launch_bounds__(256) void scale_by_device_scalar_kernel(T *x, long 
     }
 }
 
+// ---- JSD / ensemble KL: the two-distribution criteria beside KLDiv -----------------------------------------------------------
+// One pixel's C-vector through an accessor (LDS row, register array, strided global or in-register interpolation): ls(c) / lt(c)
+// return the student / target value at channel c (already divided by T), sg(c, v) stores the gradient.  CT > 0: the class count
+// at compile time (loops unrolled, register arrays stay registers).
+//   PAIR_JSD (losses/JSDiv.py:19-26): value sum_c ps (lps - lq) + pt (lpt - lq), lq = log 1/2 + logaddexp(lps, lpt)
+//                                      grad  gscale * ps * (a - <ps, a>), a = lps - lq
+//   PAIR_EKL (losses/EnsembleKLDiv.py:17-21): t holds probabilities; value sum_c xlogy(t, t) - t lps
+//                                      grad  gscale * (ps * sum_c t - t)
+enum { PAIR_JSD = 1, PAIR_EKL = 2 };
+
+__device__ __forceinline__ float log_half_sum(float x, float y)
+{
+    const float mx = fmaxf(x, y), mn = fminf(x, y);
+    return -0.693147180559945309f + mx + log1pf(__expf(mn - mx));
+}
+
+// log q = log (ps + pt)/2: one hardware log while ps + pt is a normal number, log space (log 1/2 + logaddexp) below that
+__device__ __forceinline__ float jsd_log_q(float lps, float lpt, float ps, float pt)
+{
+    const float sum = ps + pt;
+    return sum > 1e-30f ? __logf(0.5f * sum) : log_half_sum(lps, lpt);
+}
+
+// STASH: the caller's rows are writable (LDS): the forward pass parks ps and a in them (put), the gradient pass reads them back
+// (get) instead of recomputing two exponentials and a logarithm per element
+template <int KIND, int CT, bool STASH, typename LS, typename LT, typename SG, typename PUT, typename GET>
+__device__ __forceinline__ float pair_pixel(int C_, LS ls, LT lt, SG sg, PUT put, GET get, bool want_grad, float gscale)
+{
+    const int C = CT > 0 ? CT : C_;
+    constexpr int UR = CT > 0 ? CT : 1;   // (fully unrolled at a compile-time class count only)
+    float ms = -INFINITY;
+#pragma unroll UR
+    for (int c = 0; c < C; ++c) ms = fmaxf(ms, ls(c));
+    float zs = 0.f;
+#pragma unroll UR
+    for (int c = 0; c < C; ++c) zs += __expf(ls(c) - ms);
+    const float lzs = __logf(zs) + ms;
+    float val = 0.f;
+    if constexpr (KIND == PAIR_JSD) {
+        float mt = -INFINITY;
+#pragma unroll UR
+        for (int c = 0; c < C; ++c) mt = fmaxf(mt, lt(c));
+        float zt = 0.f;
+#pragma unroll UR
+        for (int c = 0; c < C; ++c) zt += __expf(lt(c) - mt);
+        const float lzt = __logf(zt) + mt;
+        float dot = 0.f;
+#pragma unroll UR
+        for (int c = 0; c < C; ++c) {
+            const float lps = ls(c) - lzs, lpt = lt(c) - lzt, ps = __expf(lps), pt = __expf(lpt);
+            const float lq = jsd_log_q(lps, lpt, ps, pt), a = lps - lq;
+            const float psa = ps > 0.f ? ps * a : 0.f;
+            val += psa + (pt > 0.f ? pt * (lpt - lq) : 0.f);
+            dot += psa;
+            if constexpr (STASH) put(c, ps, a);
+        }
+        if (want_grad) {
+#pragma unroll UR
+            for (int c = 0; c < C; ++c) {
+                float ps, a;
+                if constexpr (STASH) {
+                    get(c, ps, a);
+                } else {
+                    const float lps = ls(c) - lzs, lpt = lt(c) - lzt, pt = __expf(lpt);
+                    ps = __expf(lps);
+                    a = lps - jsd_log_q(lps, lpt, ps, pt);
+                }
+                sg(c, ps > 0.f ? gscale * ps * (a - dot) : 0.f);
+            }
+        }
+    } else {
+        float tsum = 0.f;
+#pragma unroll UR
+        for (int c = 0; c < C; ++c) {
+            const float t = lt(c);
+            val += (t > 0.f ? t * __logf(t) : 0.f) - t * (ls(c) - lzs);
+            tsum += t;
+        }
+        if (want_grad) {
+#pragma unroll UR
+            for (int c = 0; c < C; ++c) sg(c, gscale * (__expf(ls(c) - lzs) * tsum - lt(c)));
+        }
+    }
+    return val;
+}
+
+struct PairNoPut { __device__ void operator()(int, float, float) const {} };
+struct PairNoGet { __device__ void operator()(int, float &, float &) const {} };
+constexpr PairNoPut pair_noput{};
+constexpr PairNoGet pair_noget{};
+
+template <int KIND>
+__global__ __launch_bounds__(256) void pair_kernel(V3 s, V3 t, M3 g, float invT, float gscale, int N, int C, long long P, double *partial)
+{
+    double acc = 0.0;
+    const long long total = (long long)N * P;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long n = i / P, p = i - n * P;
+        const long long bs = n * s.sN + p * s.sP, bt = n * t.sN + p * t.sP, bg = n * g.sN + p * g.sP;
+        const float tmul = KIND == PAIR_JSD ? invT : 1.f;
+        acc += (double)pair_pixel<KIND, 0, false>(
+            C, [&](int c) { return kd_ld(s.p, s.dt, bs + c * s.sC) * invT; },
+            [&](int c) { return kd_ld(t.p, t.dt, bt + c * t.sC) * tmul; },
+            [&](int c, float v) { kd_st(g.p, g.dt, bg + c * g.sC, v); }, pair_noput, pair_noget, g.p != nullptr, gscale);
+    }
+    block_partial(acc, partial);
+}
+
+// NHWC-dense fast path: the staging of kldiv_nhwc_kernel (256 pixels x C channels of both operands in LDS, one pixel per thread,
+// the gradient back out through the student's LDS rows)
+template <int KIND, typename TS, typename TT, typename TG>
+__global__ __launch_bounds__(256) void pair_nhwc_kernel(const TS *__restrict__ s, const TT *__restrict__ t, TG *__restrict__ g, int C,
+                                                        long long npix, float invT, float gscale, double *partial)
+{
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float *ss = sm, *st = sm + 256 * C;
+    double acc = 0.0;
+    for (long long base = (long long)blockIdx.x * 256; base < npix; base += (long long)gridDim.x * 256) {
+        const int np = (int)min((long long)256, npix - base);
+        const int nel = np * C;
+        stage_scaled(ss, s + base * C, nel, invT);
+        stage_scaled(st, t + base * C, nel, KIND == PAIR_JSD ? invT : 1.f);
+        __syncthreads();
+        if ((int)threadIdx.x < np) {
+            float *a = ss + threadIdx.x * C, *b = st + threadIdx.x * C;
+            acc += (double)pair_pixel<KIND, 0, true>(
+                C, [&](int c) { return a[c]; }, [&](int c) { return b[c]; }, [&](int c, float v) { a[c] = v; },
+                [&](int c, float ps, float av) { a[c] = ps; b[c] = av; }, [&](int c, float &ps, float &av) { ps = a[c]; av = b[c]; },
+                g != nullptr, gscale);
+        }
+        __syncthreads();
+        if (g) unstage(g + base * C, ss, nel);
+        __syncthreads();
+    }
+    block_partial(acc, partial);
+}
+
+// JSD from the two low-resolution logit tensors: kldiv_up_kernel's staging and interpolation, pair_pixel's arithmetic
+template <int CT>
+__global__ __launch_bounds__(256) void jsdiv_up_kernel(const float *__restrict__ s, const float *__restrict__ t, UpGeom g, float invT,
+                                                       long long nchunks, int cpr, double *partial)
+{
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float *ss = sm, *st = sm + 2 * UP_NW * g.C;
+    double acc = 0.0;
+    auto nostore = [](int, float) {};
+    for (long long chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+        const UpChunk k = up_chunk(g, chunk, cpr);
+        up_stage(ss, s, g, k.n, k.h0, k.h1, k.wlo, k.nw);
+        up_stage(st, t, g, k.n, k.h0, k.h1, k.wlo, k.nw);
+        __syncthreads();
+        const int wo = k.wo0 + threadIdx.x;
+        if (wo < g.W) {
+            const float fw = fmaxf(wo * g.sw + g.ow, 0.f);
+            int w0 = (int)fw; w0 = w0 > g.w - 1 ? g.w - 1 : w0;
+            const int w1 = w0 + 1 < g.w ? w0 + 1 : g.w - 1;
+            const float aw = fw - w0;
+            const int o0 = (w0 - k.wlo) * g.C, o1 = (w1 - k.wlo) * g.C, nr = k.nw * g.C;
+            if constexpr (CT > 0) {
+                float a[CT], b[CT];
+#pragma unroll
+                for (int c = 0; c < CT; ++c) {
+                    a[c] = up_val(ss, nr, o0, o1, c, aw, k.ah) * invT;
+                    b[c] = up_val(st, nr, o0, o1, c, aw, k.ah) * invT;
+                }
+                acc += (double)pair_pixel<PAIR_JSD, CT, false>(CT, [&](int c) { return a[c]; }, [&](int c) { return b[c]; }, nostore,
+                                                               pair_noput, pair_noget, false, 0.f);
+            } else {
+                acc += (double)pair_pixel<PAIR_JSD, 0, false>(
+                    g.C, [&](int c) { return up_val(ss, nr, o0, o1, c, aw, k.ah) * invT; },
+                    [&](int c) { return up_val(st, nr, o0, o1, c, aw, k.ah) * invT; }, nostore, pair_noput, pair_noget, false, 0.f);
+            }
+        }
+        __syncthreads();
+    }
+    block_partial(acc, partial);
+}
+
+// ---- focal loss (losses/FocalLoss.py:15-28) ------------------------------------------------------------------------------------
+// Per pixel, with y' = y if y is a valid label else 0 (the gather index of FocalLoss.py:21):
+//   a  = (1 - p_y')^gamma            (every pixel, ignored ones included)
+//   ce = alpha_y * -log p_y           (valid pixels; 0 at ignored ones) and w = alpha_y (valid pixels)
+// The three sums go to fixed-order partials; the finishing block writes stats = (sum a, sum ce, sum w) and the loss.
+constexpr int FOCAL_MAX_BLOCKS = 2 * MAX_BLOCKS / 3;    // three partial arrays inside kd_loss_workspace's 2 * MAX_BLOCKS doubles
+
+// x^g for x in [0, 1], g >= -1 through the hardware exp / log (powf is a long library sequence); 0^0 = 1 like torch.pow
+__device__ __forceinline__ float focal_pow(float x, float g)
+{
+    if (g == 0.f) return 1.f;
+    if (x <= 0.f) return g > 0.f ? 0.f : INFINITY;
+    return __expf(g * __logf(x));
+}
+
+template <int CT, typename LX>
+__device__ __forceinline__ void focal_pixel(int C_, LX lx, int y, bool valid, float wy, float gamma, float &a, float &ce)
+{
+    const int C = CT > 0 ? CT : C_;
+    constexpr int UR = CT > 0 ? CT : 1;
+    const int yg = valid ? y : 0;
+    float m = -INFINITY;
+#pragma unroll UR
+    for (int c = 0; c < C; ++c) m = fmaxf(m, lx(c));
+    float z = 0.f, vy = 0.f, eg = 0.f;
+#pragma unroll UR
+    for (int c = 0; c < C; ++c) {
+        const float v = lx(c), e = __expf(v - m);
+        z += e;
+        eg = c == yg ? e : eg;
+        vy = c == y ? v : vy;
+    }
+    a = focal_pow(1.f - eg / z, gamma);
+    ce = valid ? wy * -(vy - m - __logf(z)) : 0.f;
+}
+
+__device__ __forceinline__ void block_partial3(double a, double b, double c, double *pa, double *pb, double *pc)
+{
+    __shared__ double w[3][4];
+    a = wave_sum_d(a); b = wave_sum_d(b); c = wave_sum_d(c);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) { w[0][wv] = a; w[1][wv] = b; w[2][wv] = c; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        pa[blockIdx.x] = w[0][0] + w[0][1] + w[0][2] + w[0][3];
+        pb[blockIdx.x] = w[1][0] + w[1][1] + w[1][2] + w[1][3];
+        pc[blockIdx.x] = w[2][0] + w[2][1] + w[2][2] + w[2][3];
+    }
+}
+
+__device__ __forceinline__ bool focal_valid(int64_t y, int ignore_index, int C) { return !(y == ignore_index || y < 0 || y >= C); }
+
+__global__ __launch_bounds__(256) void focal_kernel(V3 x, const int64_t *__restrict__ target, const float *__restrict__ cw, float gamma,
+                                                    int ignore_index, int N, int C, long long P, float *amap, float *cemap, double *partial)
+{
+    double sa = 0.0, sc = 0.0, sw = 0.0;
+    const long long total = (long long)N * P;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int64_t y = target[i];
+        const bool valid = focal_valid(y, ignore_index, C);
+        const float wy = valid ? (cw ? cw[y] : 1.f) : 0.f;
+        const long long n = i / P, p = i - n * P;
+        const long long b = n * x.sN + p * x.sP;
+        float a, ce;
+        focal_pixel<0>(C, [&](int c) { return kd_ld(x.p, x.dt, b + c * x.sC); }, valid ? (int)y : 0, valid, wy, gamma, a, ce);
+        if (amap) { amap[i] = a; cemap[i] = ce; }
+        sa += (double)a; sc += (double)ce; sw += (double)wy;
+    }
+    block_partial3(sa, sc, sw, partial, partial + FOCAL_MAX_BLOCKS, partial + 2 * FOCAL_MAX_BLOCKS);
+}
+
+template <int CT>
+__global__ __launch_bounds__(256) void focal_up_kernel(const float *__restrict__ x, const int64_t *__restrict__ target, const float *__restrict__ cw,
+                                                       float gamma, int ignore_index, UpGeom g, long long nchunks, int cpr, double *partial)
+{
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    double sa = 0.0, sc = 0.0, sw = 0.0;
+    for (long long chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+        const UpChunk k = up_chunk(g, chunk, cpr);
+        up_stage(sm, x, g, k.n, k.h0, k.h1, k.wlo, k.nw);
+        __syncthreads();
+        const int wo = k.wo0 + threadIdx.x;
+        if (wo < g.W) {
+            const int64_t y = target[((size_t)k.n * g.H + k.ho) * g.W + wo];
+            const bool valid = focal_valid(y, ignore_index, g.C);
+            const float wy = valid ? (cw ? cw[y] : 1.f) : 0.f;
+            const float fw = fmaxf(wo * g.sw + g.ow, 0.f);
+            int w0 = (int)fw; w0 = w0 > g.w - 1 ? g.w - 1 : w0;
+            const int w1 = w0 + 1 < g.w ? w0 + 1 : g.w - 1;
+            const float aw = fw - w0;
+            const int o0 = (w0 - k.wlo) * g.C, o1 = (w1 - k.wlo) * g.C, nr = k.nw * g.C;
+            float a, ce;
+            if constexpr (CT > 0) {
+                float v[CT];
+#pragma unroll
+                for (int c = 0; c < CT; ++c) v[c] = up_val(sm, nr, o0, o1, c, aw, k.ah);
+                focal_pixel<CT>(CT, [&](int c) { return v[c]; }, valid ? (int)y : 0, valid, wy, gamma, a, ce);
+            } else {
+                focal_pixel<0>(g.C, [&](int c) { return up_val(sm, nr, o0, o1, c, aw, k.ah); }, valid ? (int)y : 0, valid, wy, gamma, a, ce);
+            }
+            sa += (double)a; sc += (double)ce; sw += (double)wy;
+        }
+        __syncthreads();
+    }
+    block_partial3(sa, sc, sw, partial, partial + FOCAL_MAX_BLOCKS, partial + 2 * FOCAL_MAX_BLOCKS);
+}
+
+// stats = (sum a, sum ce, sum w) in fixed order; loss: 'mean' mean(a) * (sum ce / sum w), 'sum' sum a * sum ce ('none': none)
+__global__ __launch_bounds__(256) void focal_finish_kernel(const double *partial, int n, int reduction, double npix, double *stats, float *loss)
+{
+    __shared__ double sh[3][256];
+    double v[3] = {0.0, 0.0, 0.0};
+    for (int i = threadIdx.x; i < n; i += 256)
+        for (int q = 0; q < 3; ++q) v[q] += partial[q * FOCAL_MAX_BLOCKS + i];
+    for (int q = 0; q < 3; ++q) sh[q][threadIdx.x] = v[q];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o)
+            for (int q = 0; q < 3; ++q) sh[q][threadIdx.x] += sh[q][threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        if (stats) { stats[0] = sh[0][0]; stats[1] = sh[1][0]; stats[2] = sh[2][0]; }
+        if (loss) *loss = (float)(reduction == 1 ? sh[0][0] / npix * (sh[1][0] / sh[2][0]) : sh[0][0] * sh[1][0]);
+    }
+}
+
+// d loss / d x = u_a * da/dx + u_c * dce/dx, per pixel:
+//   da/dx_c  = -gamma (1 - p_y')^(gamma-1) p_y' (delta_cy' - p_c)   (0 when gamma == 0, and when gamma < 1 at p_y' == 1, the limit)
+//   dce/dx_c = alpha_y (p_c - delta_cy) at valid pixels, 0 at ignored ones
+// 'mean': u_a = g * CE_mean / (N P), u_c = g * mean(a) / sum w;  'sum': u_a = g * CE_sum, u_c = g * sum a  (g: the upstream scalar)
+// 'none': the loss is the (N,N,P) outer product L[i,j,p] = a[i,p] ce[j,p], so u_a[n,p] = sum_j G[n,j,p] ce[j,p] and
+//         u_c[n,p] = sum_i G[i,n,p] a[i,p] with G the upstream (N,N,P) gradient
+__global__ __launch_bounds__(256) void focal_grad_kernel(V3 x, const int64_t *__restrict__ target, const float *__restrict__ cw, float gamma,
+                                                         int ignore_index, int reduction, int N, int C, long long P, const double *stats,
+                                                         const float *up, const float *amap, const float *cemap, M3 g)
+{
+    float ua = 0.f, uc = 0.f;
+    if (reduction != 0) {
+        const double gu = (double)up[0], sa = stats[0], sc = stats[1], sw = stats[2], np = (double)N * (double)P;
+        ua = (float)(reduction == 1 ? gu * (sc / sw) / np : gu * sc);
+        uc = (float)(reduction == 1 ? gu * (sa / np) / sw : gu * sa);
+    }
+    const long long total = (long long)N * P;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long n = i / P, p = i - n * P;
+        if (reduction == 0) {
+            float fa = 0.f, fc = 0.f;
+            for (int j = 0; j < N; ++j) {
+                fa += up[((long long)n * N + j) * P + p] * cemap[(long long)j * P + p];
+                fc += up[((long long)j * N + n) * P + p] * amap[(long long)j * P + p];
+            }
+            ua = fa; uc = fc;
+        }
+        const int64_t y = target[i];
+        const bool valid = focal_valid(y, ignore_index, C);
+        const int yg = valid ? (int)y : 0;
+        const float wy = valid ? (cw ? cw[y] : 1.f) : 0.f;
+        const long long b = n * x.sN + p * x.sP, gb = n * g.sN + p * g.sP;
+        float m = -INFINITY;
+        for (int c = 0; c < C; ++c) m = fmaxf(m, kd_ld(x.p, x.dt, b + c * x.sC));
+        float z = 0.f;
+        for (int c = 0; c < C; ++c) z += __expf(kd_ld(x.p, x.dt, b + c * x.sC) - m);
+        const float iz = 1.f / z;
+        const float pg = __expf(kd_ld(x.p, x.dt, b + yg * x.sC) - m) * iz, om = 1.f - pg;
+        const float da = (gamma == 0.f || (om <= 0.f && gamma < 1.f)) ? 0.f : -gamma * focal_pow(om, gamma - 1.f) * pg;
+        const float ka = ua * da, kc = uc * wy;
+        for (int c = 0; c < C; ++c) {
+            const float pc = __expf(kd_ld(x.p, x.dt, b + c * x.sC) - m) * iz;
+            kd_st(g.p, g.dt, gb + c * g.sC, ka * ((c == yg ? 1.f : 0.f) - pc) + kc * (pc - (c == yg && valid ? 1.f : 0.f)));
+        }
+    }
+}
+
+// ---- top-k hint MSE (losses/WeightedHintMSELoss.py:19-44) ------------------------------------------------------------------------
+// 1. topk_sums_kernel: per (n, c, pixel chunk) sums of t^2 and (s-t)^2 from one read of s and t.  grid (chunks, ceil(C/64), N);
+//    thread = channel (tid & 63) x pixel lane (tid >> 6, every 4th pixel of the chunk); the 4 lanes are added in a fixed order.
+// 2. topk_select_kernel: one 1024-thread block per sample; channel sums in fixed chunk order, then rank by count in LDS:
+//    rank(c) = #{c' : v[c'] > v[c] or (v[c'] == v[c] and c' < c)}, kept iff rank < K (ties: the lower channel first).
+//    Writes the (N,C) mask and the sample's sum over kept channels of sum_p (s-t)^2.
+// 3. topk_grad_kernel: grad = gscale * mask * (s - t).
+constexpr int TOPK_MAX_C = 4096;      // the select block keeps C doubles in LDS (32 KiB)
+constexpr int TOPK_MAX_CHUNKS = 64;
+
+static int topk_chunks(int N, int C, long long P)
+{
+    const long long groups = (long long)N * ((C + 63) / 64);
+    long long ch = 2048 / (groups > 0 ? groups : 1);
+    ch = ch < 1 ? 1 : (ch > TOPK_MAX_CHUNKS ? TOPK_MAX_CHUNKS : ch);
+    return (int)(ch > P ? P : ch);
+}
+
+__global__ __launch_bounds__(256) void topk_sums_kernel(V3 s, V3 t, int C, long long P, long long per_chunk, int nchunk, double *pt2, double *pd2)
+{
+    __shared__ double sh[2][4][64];
+    const int ci = threadIdx.x & 63, pj = threadIdx.x >> 6;
+    const int c = blockIdx.y * 64 + ci, n = blockIdx.z, chunk = blockIdx.x;
+    double dt2 = 0.0, dd2 = 0.0;
+    if (c < C) {
+        const long long p0 = (long long)chunk * per_chunk, p1 = min(P, p0 + per_chunk);
+        const long long bs = n * s.sN + c * s.sC, bt = n * t.sN + c * t.sC;
+        // fp64 accumulation: the ranking compares these sums, and neighbouring norms of a wide hint can be 1e-6 apart
+        for (long long p = p0 + pj; p < p1; p += 4) {
+            const float tv = kd_ld(t.p, t.dt, bt + p * t.sP), d = kd_ld(s.p, s.dt, bs + p * s.sP) - tv;
+            dt2 = fma((double)tv, (double)tv, dt2);
+            dd2 = fma((double)d, (double)d, dd2);
+        }
+    }
+    sh[0][pj][ci] = dt2; sh[1][pj][ci] = dd2;
+    __syncthreads();
+    if (pj == 0 && c < C) {
+        const long long o = ((long long)n * C + c) * nchunk + chunk;
+        pt2[o] = ((sh[0][0][ci] + sh[0][1][ci]) + sh[0][2][ci]) + sh[0][3][ci];
+        pd2[o] = ((sh[1][0][ci] + sh[1][1][ci]) + sh[1][2][ci]) + sh[1][3][ci];
+    }
+}
+
+__global__ __launch_bounds__(1024) void topk_select_kernel(const double *pt2, const double *pd2, int C, int nchunk, int K, float *mask,
+                                                           double *partial)
+{
+    extern __shared__ double v[];
+    __shared__ double wsum[16];
+    const int n = blockIdx.x;
+    for (int c = threadIdx.x; c < C; c += 1024) {
+        const double *q = pt2 + ((long long)n * C + c) * nchunk;
+        double a = 0.0;
+        for (int k = 0; k < nchunk; ++k) a += q[k];
+        v[c] = a;
+    }
+    __syncthreads();
+    double contrib = 0.0;
+    for (int c = threadIdx.x; c < C; c += 1024) {
+        const double vc = v[c];
+        int rank = 0;
+        for (int j = 0; j < C; ++j) {
+            const double vj = v[j];
+            rank += (vj > vc || (vj == vc && j < c)) ? 1 : 0;
+        }
+        const bool keep = rank < K;
+        mask[(long long)n * C + c] = keep ? 1.f : 0.f;
+        if (keep) {
+            const double *q = pd2 + ((long long)n * C + c) * nchunk;
+            double d = 0.0;
+            for (int k = 0; k < nchunk; ++k) d += q[k];
+            contrib += d;
+        }
+    }
+    contrib = wave_sum_d(contrib);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = contrib;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int w = 0; w < 16; ++w) s += wsum[w];
+        partial[n] = s;
+    }
+}
+
+// dense fast path (s, t, g share one dense layout, as dense_same checks): 8 elements per thread and step, all in one (n, c) row
+// of the mask -- CFAST (NHWC): C % 8 == 0, the 8 are consecutive channels of one pixel; else (NCHW): P % 8 == 0, one channel
+template <typename T, bool CFAST>
+__global__ __launch_bounds__(256) void topk_grad_vec_kernel(const T *__restrict__ s, const T *__restrict__ t, T *__restrict__ g,
+                                                            const float *__restrict__ mask, float gscale, int C, long long P, long long n8)
+{
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
+        const long long e = i * 8;
+        float mk[8];
+        if constexpr (CFAST) {
+            const long long pix = e / C, c0 = e - pix * C, n = pix / P;
+            const float4 m0 = *(const float4 *)(mask + n * C + c0), m1 = *(const float4 *)(mask + n * C + c0 + 4);
+            mk[0] = m0.x; mk[1] = m0.y; mk[2] = m0.z; mk[3] = m0.w; mk[4] = m1.x; mk[5] = m1.y; mk[6] = m1.z; mk[7] = m1.w;
+        } else {
+            const float m = mask[e / P];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) mk[q] = m;
+        }
+        float a[8], b[8], d[8];
+        ld8(s + e, a);
+        ld8(t + e, b);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) d[q] = mk[q] != 0.f ? gscale * mk[q] * (a[q] - b[q]) : 0.f;
+        st8(g + e, d);
+    }
+}
+
+__global__ __launch_bounds__(256) void topk_grad_kernel(V3 s, V3 t, M3 g, const float *mask, float gscale, int N, int C, long long P, int c_fast)
+{
+    const long long total = (long long)N * C * P;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        long long n, c, p;
+        if (c_fast) { c = i % C; const long long r = i / C; p = r % P; n = r / P; }
+        else { p = i % P; const long long r = i / P; c = r % C; n = r / C; }
+        const float mk = mask[n * C + c];
+        const float d = mk != 0.f ? kd_ld(s.p, s.dt, n * s.sN + c * s.sC + p * s.sP) - kd_ld(t.p, t.dt, n * t.sN + c * t.sC + p * t.sP) : 0.f;
+        kd_st(g.p, g.dt, n * g.sN + c * g.sC + p * g.sP, gscale * mk * d);
+    }
+}
+
 }  // namespace
 
 extern "C" size_t kd_loss_workspace(int32_t N, int32_t C, int64_t P)
@@ -883,6 +1359,215 @@ extern "C" int kd_kldiv_up(const float *s_lo, const float *t_lo, float temperatu
     const double scale = (double)temperature * temperature / ((double)N * (double)H * (double)W);
     hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, nb, scale, (const double *)nullptr, loss);
     KD_CHECK_LAUNCH("kd_kldiv_up(finish)");
+    return KD_OK;
+}
+
+// ---- kd_jsdiv / kd_ensemble_kldiv / kd_jsdiv_up -----------------------------------------------------------------------------------
+static int pair_impl(const char *who, int kind, const kd_view3 *s, const kd_view3 *t, float invT, int32_t N, int32_t C, int64_t P,
+                     float *loss, const kd_mview3 *grad, float gscale, double loss_scale, void *workspace, kd_stream_t stream)
+{
+    double *partial = (double *)workspace;
+    const int nb = blocks_for((long long)N * P);
+    hipStream_t st = (hipStream_t)stream;
+    auto nhwc = [&](long long sN, long long sC, long long sP) { return sC == 1 && sP == C && (sN == (long long)C * P || N == 1); };
+    const bool fast = (size_t)2 * 256 * C * sizeof(float) <= 65536 && nhwc(s->sN, s->sC, s->sP) && nhwc(t->sN, t->sC, t->sP) &&
+                      (!grad || nhwc(grad->sN, grad->sC, grad->sP));
+    if (fast) {
+        const long long npix = (long long)N * P;
+        const size_t lds = (size_t)2 * 256 * C * sizeof(float);
+        void *gp = grad ? grad->ptr : nullptr;
+        const int gdt = grad ? grad->dtype : s->dtype;
+#define KD_PAIR(K, TS, TT, TG) hipLaunchKernelGGL((pair_nhwc_kernel<K, TS, TT, TG>), dim3(nb), dim3(256), lds, st, (const TS *)s->ptr, \
+                                                  (const TT *)t->ptr, (TG *)gp, C, npix, invT, gscale, partial)
+#define KD_PAIR_DT(K)                                                                                       \
+        if (s->dtype == KD_F32 && t->dtype == KD_F32 && gdt == KD_F32) KD_PAIR(K, float, float, float);       \
+        else if (s->dtype == KD_F32 && t->dtype == KD_BF16 && gdt == KD_F32) KD_PAIR(K, float, bf16_t, float); \
+        else if (s->dtype == KD_BF16 && t->dtype == KD_BF16 && gdt == KD_BF16) KD_PAIR(K, bf16_t, bf16_t, bf16_t); \
+        else if (s->dtype == KD_BF16 && t->dtype == KD_F32 && gdt == KD_BF16) KD_PAIR(K, bf16_t, float, bf16_t); \
+        else if (s->dtype == KD_F32 && t->dtype == KD_F32) KD_PAIR(K, float, float, bf16_t);                  \
+        else if (s->dtype == KD_F32 && t->dtype == KD_BF16) KD_PAIR(K, float, bf16_t, bf16_t);                \
+        else if (s->dtype == KD_BF16 && t->dtype == KD_BF16) KD_PAIR(K, bf16_t, bf16_t, float);               \
+        else KD_PAIR(K, bf16_t, float, float)
+        if (kind == PAIR_JSD) { KD_PAIR_DT(PAIR_JSD); }
+        else { KD_PAIR_DT(PAIR_EKL); }
+#undef KD_PAIR_DT
+#undef KD_PAIR
+    } else if (kind == PAIR_JSD) {
+        hipLaunchKernelGGL(pair_kernel<PAIR_JSD>, dim3(nb), dim3(256), 0, st, v3(s), v3(t), m3(grad), invT, gscale, N, C, (long long)P, partial);
+    } else {
+        hipLaunchKernelGGL(pair_kernel<PAIR_EKL>, dim3(nb), dim3(256), 0, st, v3(s), v3(t), m3(grad), invT, gscale, N, C, (long long)P, partial);
+    }
+    KD_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, nb, loss_scale, (const double *)nullptr, loss);
+    KD_CHECK_LAUNCH(who);
+    return KD_OK;
+}
+
+extern "C" int kd_jsdiv(const kd_view3 *s, const kd_view3 *t, float temperature, int32_t N, int32_t C, int64_t P, float *loss,
+                        const kd_mview3 *grad, float grad_scale, void *workspace, size_t workspace_bytes, kd_stream_t stream)
+{
+    KD_LOSS_COMMON("kd_jsdiv");
+    KD_REQUIRE(temperature > 0.f, KD_ERR_INVALID, "kd_jsdiv: temperature must be positive");
+    // loss = T^2 / (2N) * sum ; d/ds = T / (2N) * ps (a - <ps, a>)   (divided by the batch size only, losses/JSDiv.py:24-25)
+    const float gscale = grad_scale * temperature / (2.f * (float)N);
+    const double scale = (double)temperature * temperature / (2.0 * (double)N);
+    return pair_impl("kd_jsdiv", PAIR_JSD, s, t, 1.f / temperature, N, C, P, loss, grad, gscale, scale, workspace, stream);
+}
+
+extern "C" int kd_ensemble_kldiv(const kd_view3 *s, const kd_view3 *t, int32_t N, int32_t C, int64_t P, float *loss, const kd_mview3 *grad,
+                                 float grad_scale, void *workspace, size_t workspace_bytes, kd_stream_t stream)
+{
+    KD_LOSS_COMMON("kd_ensemble_kldiv");
+    // 'mean' over N*C*P elements, then * C  ==  1 / (N*P) * sum
+    const float gscale = grad_scale / ((float)N * (float)P);
+    const double scale = 1.0 / ((double)N * (double)P);
+    return pair_impl("kd_ensemble_kldiv", PAIR_EKL, s, t, 1.f, N, C, P, loss, grad, gscale, scale, workspace, stream);
+}
+
+extern "C" int kd_jsdiv_up(const float *s_lo, const float *t_lo, float temperature, int32_t N, int32_t h, int32_t w, int32_t C, int32_t H,
+                           int32_t W, int32_t align_corners, float *loss, void *workspace, size_t workspace_bytes, kd_stream_t stream)
+{
+    KD_REQUIRE(s_lo && t_lo && loss && workspace, KD_ERR_INVALID, "kd_jsdiv_up: null argument");
+    KD_REQUIRE(N > 0 && h > 0 && w > 0 && C > 0 && C <= 24 && H > 0 && W > 0 && temperature > 0.f, KD_ERR_INVALID, "kd_jsdiv_up: bad argument (C <= 24: two staged patches fit 64 KiB of LDS)");
+    KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, (int64_t)H * W), KD_ERR_WORKSPACE, "kd_jsdiv_up: workspace too small");
+    UpGeom g;
+    KD_REQUIRE(up_geom(g, N, h, w, C, H, W, align_corners), KD_ERR_UNSUPPORTED,
+               "kd_jsdiv_up: a 256-pixel chunk spans more than %d source columns: materialise the logits", UP_NW);
+    double *partial = (double *)workspace;
+    const int cpr = (W + 255) / 256;
+    const long long nchunks = (long long)N * H * cpr;
+    const int nb = (int)(nchunks < MAX_BLOCKS ? nchunks : MAX_BLOCKS);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t lds = (size_t)4 * UP_NW * C * sizeof(float);
+    if (C == 19) hipLaunchKernelGGL(jsdiv_up_kernel<19>, dim3(nb), dim3(256), lds, st, s_lo, t_lo, g, 1.f / temperature, nchunks, cpr, partial);
+    else hipLaunchKernelGGL(jsdiv_up_kernel<0>, dim3(nb), dim3(256), lds, st, s_lo, t_lo, g, 1.f / temperature, nchunks, cpr, partial);
+    KD_CHECK_LAUNCH("kd_jsdiv_up");
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, nb, (double)temperature * temperature / (2.0 * (double)N),
+                       (const double *)nullptr, loss);
+    KD_CHECK_LAUNCH("kd_jsdiv_up(finish)");
+    return KD_OK;
+}
+
+// ---- kd_focal / kd_focal_grad / kd_focal_up -----------------------------------------------------------------------------------------
+extern "C" int kd_focal(const kd_view3 *x, const int64_t *target, const float *alpha, float gamma, int32_t ignore_index, int32_t reduction,
+                        int32_t N, int32_t C, int64_t P, float *loss, double *stats, float *a_map, float *ce_map, void *workspace,
+                        size_t workspace_bytes, kd_stream_t stream)
+{
+    KD_REQUIRE(x && x->ptr && target && workspace, KD_ERR_INVALID, "kd_focal: null argument");
+    KD_REQUIRE(ok_dt(x->dtype) && N > 0 && C > 0 && P > 0 && gamma >= 0.f, KD_ERR_INVALID, "kd_focal: bad argument");
+    KD_REQUIRE(reduction >= 0 && reduction <= 2, KD_ERR_INVALID, "kd_focal: reduction is 0 (none), 1 (mean) or 2 (sum)");
+    KD_REQUIRE(reduction == 0 || loss, KD_ERR_INVALID, "kd_focal: 'mean' / 'sum' need a loss pointer");
+    KD_REQUIRE(reduction != 0 || (a_map && ce_map), KD_ERR_INVALID, "kd_focal: 'none' needs both per-pixel maps");
+    KD_REQUIRE((a_map == nullptr) == (ce_map == nullptr), KD_ERR_INVALID, "kd_focal: a_map and ce_map go together");
+    KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, P), KD_ERR_WORKSPACE, "kd_focal: workspace too small");
+    KD_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)stats & 7) == 0, KD_ERR_INVALID, "kd_focal: workspace / stats must be 8-B aligned");
+    double *partial = (double *)workspace;
+    const long long total = (long long)N * P;
+    const int nb = (int)min((total + 255) / 256, (long long)FOCAL_MAX_BLOCKS);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(focal_kernel, dim3(nb), dim3(256), 0, st, v3(x), target, alpha, gamma, ignore_index, N, C, (long long)P, a_map, ce_map, partial);
+    KD_CHECK_LAUNCH("kd_focal");
+    hipLaunchKernelGGL(focal_finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, nb, (int)reduction, (double)total, stats,
+                       reduction == 0 ? (float *)nullptr : loss);
+    KD_CHECK_LAUNCH("kd_focal(finish)");
+    return KD_OK;
+}
+
+extern "C" int kd_focal_grad(const kd_view3 *x, const int64_t *target, const float *alpha, float gamma, int32_t ignore_index, int32_t reduction,
+                             int32_t N, int32_t C, int64_t P, const double *stats, const float *upstream, const float *a_map,
+                             const float *ce_map, const kd_mview3 *grad, kd_stream_t stream)
+{
+    KD_REQUIRE(x && x->ptr && target && upstream && grad && grad->ptr, KD_ERR_INVALID, "kd_focal_grad: null argument");
+    KD_REQUIRE(ok_dt(x->dtype) && ok_dt(grad->dtype) && N > 0 && C > 0 && P > 0 && gamma >= 0.f, KD_ERR_INVALID, "kd_focal_grad: bad argument");
+    KD_REQUIRE(reduction >= 0 && reduction <= 2, KD_ERR_INVALID, "kd_focal_grad: reduction is 0 (none), 1 (mean) or 2 (sum)");
+    KD_REQUIRE(reduction == 0 ? (a_map && ce_map) : stats != nullptr, KD_ERR_INVALID,
+               "kd_focal_grad: 'none' needs the forward's per-pixel maps, 'mean' / 'sum' its stats");
+    hipLaunchKernelGGL(focal_grad_kernel, dim3(blocks_for((long long)N * P)), dim3(256), 0, (hipStream_t)stream, v3(x), target, alpha, gamma,
+                       ignore_index, (int)reduction, N, C, (long long)P, stats, upstream, a_map, ce_map, m3(grad));
+    KD_CHECK_LAUNCH("kd_focal_grad");
+    return KD_OK;
+}
+
+extern "C" int kd_focal_up(const float *x_lo, const int64_t *target, const float *alpha, float gamma, int32_t ignore_index, int32_t reduction,
+                           int32_t N, int32_t h, int32_t w, int32_t C, int32_t H, int32_t W, int32_t align_corners, float *loss, double *stats,
+                           void *workspace, size_t workspace_bytes, kd_stream_t stream)
+{
+    KD_REQUIRE(x_lo && target && loss && workspace, KD_ERR_INVALID, "kd_focal_up: null argument");
+    KD_REQUIRE(N > 0 && h > 0 && w > 0 && C > 0 && C <= 48 && H > 0 && W > 0 && gamma >= 0.f, KD_ERR_INVALID,
+               "kd_focal_up: bad argument (C <= 48: the staged patch fits 64 KiB of LDS)");
+    KD_REQUIRE(reduction == 1 || reduction == 2, KD_ERR_INVALID, "kd_focal_up: reduction is 1 (mean) or 2 (sum)");
+    KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, (int64_t)H * W), KD_ERR_WORKSPACE, "kd_focal_up: workspace too small");
+    KD_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)stats & 7) == 0, KD_ERR_INVALID, "kd_focal_up: workspace / stats must be 8-B aligned");
+    UpGeom g;
+    KD_REQUIRE(up_geom(g, N, h, w, C, H, W, align_corners), KD_ERR_UNSUPPORTED,
+               "kd_focal_up: a 256-pixel chunk spans more than %d source columns: materialise the logits", UP_NW);
+    double *partial = (double *)workspace;
+    const int cpr = (W + 255) / 256;
+    const long long nchunks = (long long)N * H * cpr;
+    const int nb = (int)(nchunks < FOCAL_MAX_BLOCKS ? nchunks : FOCAL_MAX_BLOCKS);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t lds = (size_t)2 * UP_NW * C * sizeof(float);
+    if (C == 19)
+        hipLaunchKernelGGL(focal_up_kernel<19>, dim3(nb), dim3(256), lds, st, x_lo, target, alpha, gamma, ignore_index, g, nchunks, cpr, partial);
+    else
+        hipLaunchKernelGGL(focal_up_kernel<0>, dim3(nb), dim3(256), lds, st, x_lo, target, alpha, gamma, ignore_index, g, nchunks, cpr, partial);
+    KD_CHECK_LAUNCH("kd_focal_up");
+    hipLaunchKernelGGL(focal_finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, nb, (int)reduction, (double)N * H * W, stats, loss);
+    KD_CHECK_LAUNCH("kd_focal_up(finish)");
+    return KD_OK;
+}
+
+// ---- kd_topk_hint_mse ------------------------------------------------------------------------------------------------------------
+extern "C" size_t kd_topk_hint_workspace(int32_t N, int32_t C, int64_t P)
+{
+    if (N <= 0 || C <= 0 || P <= 0) return 64;
+    const size_t nc = (size_t)N * C, ch = (size_t)topk_chunks(N, C, P);
+    return 2 * nc * ch * sizeof(double) + (size_t)N * sizeof(double) + nc * sizeof(float) + 64;
+}
+
+extern "C" int kd_topk_hint_mse(const kd_view3 *s, const kd_view3 *t, int32_t K, int32_t N, int32_t C, int64_t P, float *loss,
+                                const kd_mview3 *grad, float grad_scale, float *mask, void *workspace, size_t workspace_bytes, kd_stream_t stream)
+{
+    KD_REQUIRE(s && t && s->ptr && t->ptr && loss && workspace, KD_ERR_INVALID, "kd_topk_hint_mse: null argument");
+    KD_REQUIRE(ok_dt(s->dtype) && ok_dt(t->dtype) && (!grad || ok_dt(grad->dtype)), KD_ERR_INVALID, "kd_topk_hint_mse: bad dtype");
+    KD_REQUIRE(N > 0 && C > 0 && P > 0, KD_ERR_INVALID, "kd_topk_hint_mse: bad shape");
+    KD_REQUIRE(K >= 1 && K <= C, KD_ERR_INVALID, "kd_topk_hint_mse: K = %d channels kept of %d: need 1 <= K <= C", K, C);
+    KD_REQUIRE(C <= TOPK_MAX_C, KD_ERR_UNSUPPORTED, "kd_topk_hint_mse: C = %d > %d channels", C, TOPK_MAX_C);
+    KD_REQUIRE(workspace_bytes >= kd_topk_hint_workspace(N, C, P), KD_ERR_WORKSPACE, "kd_topk_hint_mse: workspace too small");
+    KD_REQUIRE(((uintptr_t)workspace & 7) == 0, KD_ERR_INVALID, "kd_topk_hint_mse: workspace must be 8-B aligned");
+    const int nchunk = topk_chunks(N, C, P);
+    const long long per_chunk = (P + nchunk - 1) / nchunk;
+    const size_t nc = (size_t)N * C;
+    double *pt2 = (double *)workspace, *pd2 = pt2 + nc * nchunk, *part = pd2 + nc * nchunk;
+    float *mk = mask ? mask : (float *)(part + N + (N & 1));   // (16-B aligned: the dense gradient path reads it as float4)
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(topk_sums_kernel, dim3((unsigned)nchunk, (unsigned)((C + 63) / 64), (unsigned)N), dim3(256), 0, st, v3(s), v3(t), C,
+                       (long long)P, per_chunk, nchunk, pt2, pd2);
+    KD_CHECK_LAUNCH("kd_topk_hint_mse(sums)");
+    hipLaunchKernelGGL(topk_select_kernel, dim3(N), dim3(1024), (size_t)C * sizeof(double), st, (const double *)pt2, (const double *)pd2, C,
+                       nchunk, (int)K, mk, part);
+    KD_CHECK_LAUNCH("kd_topk_hint_mse(select)");
+    // loss = sum_n sum_kept mean_p (s-t)^2 / (N K) ; grad = 2 mask (s-t) / (P N K)
+    const double denom = (double)N * (double)K;
+    if (grad) {
+        const float gscale = (float)((double)grad_scale * 2.0 / ((double)P * denom));
+        const long long numel = (long long)nc * P;
+        const bool cfast = s->sC == 1 && s->sP == C;
+        if (dense_same(s, t, grad, N, C, P) && (cfast ? C % 8 == 0 : P % 8 == 0) && kd_aligned16(mk)) {
+            const long long n8 = numel / 8;
+#define KD_TOPK_VEC(T, CF) hipLaunchKernelGGL((topk_grad_vec_kernel<T, CF>), dim3(blocks_for(n8)), dim3(256), 0, st, (const T *)s->ptr, \
+                                              (const T *)t->ptr, (T *)grad->ptr, (const float *)mk, gscale, C, (long long)P, n8)
+            if (s->dtype == KD_BF16) { if (cfast) KD_TOPK_VEC(bf16_t, true); else KD_TOPK_VEC(bf16_t, false); }
+            else { if (cfast) KD_TOPK_VEC(float, true); else KD_TOPK_VEC(float, false); }
+#undef KD_TOPK_VEC
+        } else {
+            hipLaunchKernelGGL(topk_grad_kernel, dim3(blocks_for(numel)), dim3(256), 0, st, v3(s), v3(t), m3(grad), (const float *)mk, gscale,
+                               N, C, (long long)P, s->sC == 1 ? 1 : 0);
+        }
+        KD_CHECK_LAUNCH("kd_topk_hint_mse(grad)");
+    }
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)part, (int)N, 1.0 / ((double)P * denom), (const double *)nullptr, loss);
+    KD_CHECK_LAUNCH("kd_topk_hint_mse(finish)");
     return KD_OK;
 }
 

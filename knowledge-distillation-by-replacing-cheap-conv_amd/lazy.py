@@ -4,7 +4,7 @@
 (N,19,H,W) fp32 tensors: the classifier's half-resolution output, bilinearly up-sampled (models/deeplabv3/deeplabv3.py:160-162).
 In the KD trainers their only readers are the logged criteria -- CrossEntropyLoss2d x2, KLDivergenceLoss
 (trainer/layerwise_trainer.py:222-227) -- and this library's criteria interpolate a pixel's logits in registers (kd_ce2d_up /
-kd_kldiv_up): 2 x 1.27 GB per 8 images are neither written nor read back.  `LazyLogits` keeps the drop-in signature: it IS a
+kd_kldiv_up, and kd_jsdiv_up / kd_focal_up for JSDivergenceLoss / FocalLoss): 2 x 1.27 GB per 8 images are neither written nor read back.  `LazyLogits` keeps the drop-in signature: it IS a
 tensor of the full-resolution shape; the criteria recognise it and read `low`; ANY other use (a torch op, the mIoU kernel,
 `.cpu()`, indexing ...) materialises the up-sampled tensor once through kd_upsample_bilinear and proceeds on it.  Only tensors
 nothing differentiates through are wrapped (the engine returns a plain tensor when a logit loss is back-propagated)."""
@@ -77,9 +77,20 @@ class _DeferredLogitLoss(torch.autograd.Function):
         if ctx.kind == "kld":
             t = ctx.other.materialize() if isinstance(ctx.other, LazyLogits) else ctx.other
             _, grad = ops.kldiv(s, t, ctx.arg, want_grad=True)
-        else:
+            grad = grad * g.to(grad.dtype)
+        elif ctx.kind == "ce":
             grad = ops.ce2d_grad(s, ctx.other, ctx.arg)
-        grad = grad * g.to(grad.dtype)
+            grad = grad * g.to(grad.dtype)
+        elif ctx.kind == "jsd":
+            t = ctx.other.materialize() if isinstance(ctx.other, LazyLogits) else ctx.other
+            _, grad = ops.jsdiv(s, t, ctx.arg, want_grad=True)
+            grad = grad * g.to(grad.dtype)
+        elif ctx.kind == "focal":
+            # the sums kd_focal_up produced in the forward, then the gradient times the upstream scalar on the device
+            gamma, alpha, ignore_index, reduction, stats = ctx.arg
+            grad = ops.focal_grad(s, ctx.other, gamma, alpha, ignore_index, reduction, g, stats)
+        else:
+            raise ValueError(f"_DeferredLogitLoss: unknown loss kind {ctx.kind!r}")
         ls = ctx.lazy_s
         ls.pending_grad = grad if ls.pending_grad is None else ls.pending_grad + grad
         ctx.lazy_s = ctx.other = None

@@ -1,5 +1,6 @@
 """KD criteria with the reference's class names and constructor arguments (losses/__init__.py:1-7 of the
-reference), so `config.init_obj('kd_loss' | 'hint_loss' | 'supervised_loss', losses)` resolves unchanged.
+reference), so `config.init_obj('kd_loss' | 'hint_loss' | 'supervised_loss', losses)` resolves unchanged: CrossEntropyLoss2d,
+JSDivergenceLoss, KLDivergenceLoss, MSELoss, FocalLoss, WeightedHintMSELoss, TopkHintMSELoss, EnsembleKLDivergenceLoss.
 Each forward is one fused HIP pass producing the loss and its gradient (include/kdcc.h, losses section)."""
 import torch
 from torch import nn
@@ -20,6 +21,12 @@ class _FusedLoss(torch.autograd.Function):
             loss, grad = ops.kldiv(s, t, arg, want_grad=want)
         elif kind == "mse":
             loss, grad = ops.hint_mse(s, t, arg, want_grad=want)
+        elif kind == "jsd":
+            loss, grad = ops.jsdiv(s, t, arg, want_grad=want)
+        elif kind == "ekl":
+            loss, grad = ops.ensemble_kldiv(s, t, want_grad=want)
+        elif kind == "topk":
+            loss, grad, _ = ops.topk_hint_mse(s, t, arg, want_grad=want)
         else:
             loss, grad = ops.weighted_hint_mse(s, t, weight, want_grad=want)
         ctx.grad = grad
@@ -133,3 +140,108 @@ class CrossEntropyLoss2d(nn.Module):
         if inputs.requires_grad and torch.is_grad_enabled():
             return _CEFunction.apply(inputs, targets, self.ignore_index)
         return ops.ce2d(inputs, targets, self.ignore_index)
+
+
+class JSDivergenceLoss(nn.Module):
+    """T^2/(2N) * sum [KL(p_t || q) + KL(p_s || q)], q = (p_s + p_t)/2, p = softmax(./T, 1)  (losses/JSDiv.py:17-26): divided by the
+    batch size only; the targets are constants (kd_jsdiv)."""
+
+    def __init__(self, temperature=1):
+        super().__init__()
+        self.temperature = temperature
+
+    def forward(self, inputs, targets):
+        if isinstance(inputs, LazyLogits) and isinstance(targets, LazyLogits) and inputs.pending and targets.pending and \
+                inputs.size_hw == targets.size_hw and inputs.align_corners == targets.align_corners:
+            try:      # both sides are the classifier's half-resolution logits (kd_jsdiv_up)
+                return deferred(ops.jsdiv_up(inputs.low, targets.low, inputs.size_hw, float(self.temperature), inputs.align_corners),
+                                "jsd", inputs, targets, float(self.temperature))
+            except KdccError:
+                pass      # resampling ratio / class count outside the kernel's range: materialise
+        return _FusedLoss.apply("jsd", inputs, _same_device_dtype(inputs, targets), float(self.temperature), None)
+
+
+class EnsembleKLDivergenceLoss(nn.Module):
+    """kl_div(log_softmax(inputs, 1), targets, 'mean') * C with `targets` already probabilities (losses/EnsembleKLDiv.py:15-21;
+    kd_ensemble_kldiv)."""
+
+    def __init__(self):
+        super().__init__()
+
+    def forward(self, inputs, targets):
+        return _FusedLoss.apply("ekl", inputs, _same_device_dtype(inputs, targets), None, None)
+
+
+class TopkHintMSELoss(nn.Module):
+    """Hint MSE over each sample's K = int(topk * C) channels of largest target L2 norm: sum mask * mean_hw (s-t)^2 / (N*K)
+    (losses/WeightedHintMSELoss.py:19-44; num_classes is not applied).  4-D targets only; equal norms keep the lower channel; K == 0
+    raises (the reference divides by zero).  The selection runs on the device (kd_topk_hint_mse)."""
+
+    def __init__(self, reduction='mean', num_classes=19, topk=0.5):
+        super().__init__()
+        self.reduction = reduction
+        self.num_classes = num_classes
+        self.topk = topk
+
+    def forward(self, inputs, targets):
+        if targets.dim() != 4 or inputs.shape != targets.shape:
+            raise ValueError(f"TopkHintMSELoss: (N,C,H,W) inputs and targets of one shape only, got {tuple(inputs.shape)} and "
+                             f"{tuple(targets.shape)}")
+        num_channels = targets.shape[1]
+        k = int(self.topk * num_channels)          # the reference's idx_pivot (WeightedHintMSELoss.py:35)
+        if k <= 0:
+            raise ValueError(f"TopkHintMSELoss: topk={self.topk} keeps no channel of {num_channels}")
+        return _FusedLoss.apply("topk", inputs, _same_device_dtype(inputs, targets), min(k, num_channels), None)
+
+
+class _FocalFunction(torch.autograd.Function):
+    """FocalLoss value (kd_focal) and, in backward, its gradient scaled by the upstream one on the device (kd_focal_grad)."""
+
+    @staticmethod
+    def forward(ctx, inputs, targets, gamma, alpha, ignore_index, reduction):
+        x = inputs.detach()
+        loss, stats, amap, cemap = ops.focal(x, targets, gamma, alpha, ignore_index, reduction)
+        ctx.save_for_backward(x, targets)
+        ctx.args, ctx.stats, ctx.maps = (gamma, alpha, ignore_index, reduction), stats, (amap, cemap)
+        if reduction == 'none':
+            # the reference's broadcast (N,1,*sp) * (N,*sp) -> (N,N,*sp): element [i,j] = a_i * ce_j (FocalLoss.py:23)
+            N, sp = x.shape[0], tuple(x.shape[2:])
+            return amap.view(N, 1, *sp) * cemap.view(N, *sp)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        x, tgt = ctx.saved_tensors
+        gamma, alpha, ignore_index, reduction = ctx.args
+        grad = ops.focal_grad(x, tgt, gamma, alpha, ignore_index, reduction, g, ctx.stats, *ctx.maps)
+        ctx.stats = ctx.maps = None
+        return grad, None, None, None, None, None
+
+
+class FocalLoss(nn.CrossEntropyLoss):
+    """pow(1 - p_y', gamma) * CE with the inner nn.CrossEntropyLoss(weight=alpha, ignore_index) already reduced by `reduction`
+    (losses/FocalLoss.py:7-28: the class overwrites `reduction` after __init__).  'mean': mean(a) * CE_mean; 'sum': sum(a) * CE_sum;
+    'none' (the default): the (N,N,H,W) broadcast product a_i * ce_j the reference returns.  y' = target where valid, 0 where ignored.
+    For gamma < 1 the gradient at p_y' == 1 is 0 (its limit) where the reference's is NaN."""
+
+    def __init__(self, gamma, alpha=None, ignore_index=-100, reduction='none'):
+        if alpha is not None and not torch.is_tensor(alpha):
+            alpha = torch.as_tensor(alpha, dtype=torch.float32)       # (a config gives a list)
+        super().__init__(weight=alpha, ignore_index=ignore_index, reduction='none')
+        if reduction not in ('none', 'mean', 'sum'):
+            raise ValueError(f"FocalLoss: reduction must be 'none', 'mean' or 'sum', got {reduction!r}")
+        self.reduction = reduction
+        self.gamma = gamma
+
+    def forward(self, input_, target):
+        if self.weight is not None and self.weight.device != input_.device:
+            self.weight = self.weight.to(input_.device)
+        gamma = float(self.gamma)
+        if isinstance(input_, LazyLogits) and input_.pending and self.reduction in ('mean', 'sum'):
+            try:      # the classifier's half-resolution logits, interpolated in registers (kd_focal_up)
+                loss, stats = ops.focal_up(input_.low, target, input_.size_hw, gamma, self.weight, self.ignore_index, self.reduction,
+                                           input_.align_corners)
+                return deferred(loss, "focal", input_, target, (gamma, self.weight, self.ignore_index, self.reduction, stats))
+            except KdccError:
+                pass
+        return _FocalFunction.apply(input_, target, gamma, self.weight, self.ignore_index, self.reduction)

@@ -1307,6 +1307,160 @@ def confusion(x, target, conf=None, accumulate=False):
     return conf
 
 
+def jsdiv(s, t, temperature=1.0, want_grad=True, grad_scale=1.0):
+    """JSDivergenceLoss (losses/JSDiv.py:19-26) and its gradient w.r.t. s (t constant), one pass (kd_jsdiv)."""
+    vs, vt, (N, Cc, P) = _loss_common(s, t)
+    loss = torch.empty((), dtype=torch.float32, device=s.device)
+    grad = torch.empty_like(s) if want_grad else None
+    vg = view3(grad)[0] if want_grad else None
+    ws, need = loss_workspace(N, Cc, P, s.device)
+    e0 = _prof_start()
+    check(_lib.lib().kd_jsdiv(C.byref(vs), C.byref(vt), C.c_float(temperature), N, Cc, P, _ptr(loss),
+                              C.byref(vg) if vg is not None else None, C.c_float(grad_scale), _ptr(ws), need, stream_ptr()), "kd_jsdiv")
+    _prof_stop(e0, "loss", _nbytes(s, t, grad), f"jsdiv {N}x{Cc}x{P}", "pair_kernel<jsd>")
+    return loss, grad
+
+
+def jsdiv_up(s_lo, t_lo, size, temperature=1.0, align_corners=True):
+    """jsdiv(upsample_bilinear(s_lo, size), upsample_bilinear(t_lo, size)) forward, without the full-resolution tensors."""
+    _need_cuda(s_lo, t_lo)
+    _lowres_ok(s_lo, t_lo)
+    if s_lo.shape != t_lo.shape:
+        raise ValueError("jsdiv_up: shape mismatch")
+    N, h, w, Cc = s_lo.shape
+    H, W = size
+    loss = torch.empty((), dtype=torch.float32, device=s_lo.device)
+    ws, need = loss_workspace(N, Cc, H * W, s_lo.device)
+    e0 = _prof_start()
+    check(_lib.lib().kd_jsdiv_up(_ptr(s_lo), _ptr(t_lo), C.c_float(temperature), N, h, w, Cc, H, W, int(bool(align_corners)), _ptr(loss),
+                                 _ptr(ws), need, stream_ptr()), "kd_jsdiv_up")
+    _prof_stop(e0, "loss", _nbytes(s_lo, t_lo), f"jsdiv from {h}x{w} logits at {H}x{W}", "jsdiv_up_kernel")
+    return loss
+
+
+def ensemble_kldiv(s, t, want_grad=True, grad_scale=1.0):
+    """EnsembleKLDivergenceLoss (losses/EnsembleKLDiv.py:17-21): t are probabilities (kd_ensemble_kldiv)."""
+    vs, vt, (N, Cc, P) = _loss_common(s, t)
+    loss = torch.empty((), dtype=torch.float32, device=s.device)
+    grad = torch.empty_like(s) if want_grad else None
+    vg = view3(grad)[0] if want_grad else None
+    ws, need = loss_workspace(N, Cc, P, s.device)
+    e0 = _prof_start()
+    check(_lib.lib().kd_ensemble_kldiv(C.byref(vs), C.byref(vt), N, Cc, P, _ptr(loss), C.byref(vg) if vg is not None else None,
+                                       C.c_float(grad_scale), _ptr(ws), need, stream_ptr()), "kd_ensemble_kldiv")
+    _prof_stop(e0, "loss", _nbytes(s, t, grad), f"ensemble kldiv {N}x{Cc}x{P}", "pair_kernel<ekl>")
+    return loss, grad
+
+
+_FOCAL_RED = {"none": 0, "mean": 1, "sum": 2}
+
+
+def _focal_red(reduction, allowed=("none", "mean", "sum")):
+    if reduction not in allowed:
+        raise ValueError(f"focal: reduction must be one of {allowed}, got {reduction!r}")
+    return _FOCAL_RED[reduction]
+
+
+def _focal_target(x_shape_np, target):
+    N, P = x_shape_np
+    tgt = target.contiguous()
+    if tgt.dtype != torch.int64 or tgt.numel() != N * P:
+        raise ValueError("focal: target must be int64 with one label per pixel")
+    return tgt
+
+
+def focal(x, target, gamma, alpha=None, ignore_index=-100, reduction="mean", want_maps=False):
+    """FocalLoss (losses/FocalLoss.py:15-28) forward (kd_focal) -> (loss or None for 'none', stats, a_map, ce_map).  stats: fp64 (3,)
+    device sums (a, ce, weight) for focal_grad; a_map / ce_map: fp32 (N,P) per-pixel (1-p_y')^gamma and weighted CE, when
+    want_maps or reduction == 'none'."""
+    _need_cuda(x, target)
+    red = _focal_red(reduction)
+    vx, (N, Cc, P) = view3(x)
+    tgt = _focal_target((N, P), target)
+    w = _class_weight(alpha, Cc, x.device) if alpha is not None else None
+    loss = torch.empty((), dtype=torch.float32, device=x.device) if red else None
+    stats = torch.empty(3, dtype=torch.float64, device=x.device)
+    maps = want_maps or red == 0
+    amap = torch.empty((N, P), dtype=torch.float32, device=x.device) if maps else None
+    cemap = torch.empty((N, P), dtype=torch.float32, device=x.device) if maps else None
+    ws, need = loss_workspace(N, Cc, P, x.device)
+    e0 = _prof_start()
+    check(_lib.lib().kd_focal(C.byref(vx), _ptr(tgt), _ptr(w), C.c_float(gamma), int(ignore_index), red, N, Cc, P, _ptr(loss), _ptr(stats),
+                              _ptr(amap), _ptr(cemap), _ptr(ws), need, stream_ptr()), "kd_focal")
+    _prof_stop(e0, "loss", _nbytes(x, tgt, amap, cemap), f"focal {N}x{Cc}x{P}", "focal_kernel")
+    return loss, stats, amap, cemap
+
+
+def focal_grad(x, target, gamma, alpha, ignore_index, reduction, upstream, stats=None, a_map=None, ce_map=None):
+    """d focal / d x times the upstream gradient (kd_focal_grad): a device scalar for 'mean' / 'sum' (with the forward's stats),
+    the (N,N,*spatial) gradient of the outer product for 'none' (with the forward's maps).  No host sync."""
+    _need_cuda(x, target, upstream)
+    red = _focal_red(reduction)
+    vx, (N, Cc, P) = view3(x)
+    tgt = _focal_target((N, P), target)
+    w = _class_weight(alpha, Cc, x.device) if alpha is not None else None
+    up = upstream.detach().to(torch.float32).contiguous()
+    if (red and up.numel() != 1) or (not red and up.numel() != N * N * P):
+        raise ValueError(f"focal_grad: upstream gradient of {up.numel()} elements for reduction {reduction!r}")
+    if red and stats is None or not red and (a_map is None or ce_map is None):
+        raise ValueError("focal_grad: needs the forward's stats ('mean' / 'sum') or maps ('none')")
+    grad = torch.empty_like(x)
+    vg, _ = view3(grad)
+    e0 = _prof_start()
+    check(_lib.lib().kd_focal_grad(C.byref(vx), _ptr(tgt), _ptr(w), C.c_float(gamma), int(ignore_index), red, N, Cc, P, _ptr(stats), _ptr(up),
+                                   _ptr(a_map), _ptr(ce_map), C.byref(vg), stream_ptr()), "kd_focal_grad")
+    _prof_stop(e0, "loss", _nbytes(x, tgt, grad), f"focal grad {N}x{Cc}x{P}", "focal_grad_kernel")
+    return grad
+
+
+def focal_up(x_lo, target, size, gamma, alpha=None, ignore_index=-100, reduction="mean", align_corners=True):
+    """focal(upsample_bilinear(x_lo, size), target) 'mean' / 'sum' forward without the full-resolution tensor (kd_focal_up)
+    -> (loss, stats)."""
+    _need_cuda(x_lo, target)
+    _lowres_ok(x_lo)
+    red = _focal_red(reduction, ("mean", "sum"))
+    N, h, w, Cc = x_lo.shape
+    H, W = size
+    tgt = _focal_target((N, H * W), target)
+    wt = _class_weight(alpha, Cc, x_lo.device) if alpha is not None else None
+    loss = torch.empty((), dtype=torch.float32, device=x_lo.device)
+    stats = torch.empty(3, dtype=torch.float64, device=x_lo.device)
+    ws, need = loss_workspace(N, Cc, H * W, x_lo.device)
+    e0 = _prof_start()
+    check(_lib.lib().kd_focal_up(_ptr(x_lo), _ptr(tgt), _ptr(wt), C.c_float(gamma), int(ignore_index), red, N, h, w, Cc, H, W,
+                                 int(bool(align_corners)), _ptr(loss), _ptr(stats), _ptr(ws), need, stream_ptr()), "kd_focal_up")
+    _prof_stop(e0, "loss", _nbytes(x_lo, tgt), f"focal from {h}x{w} logits at {H}x{W}", "focal_up_kernel")
+    return loss, stats
+
+
+_topk_ws = {}
+
+
+def topk_hint_mse(s, t, k, want_grad=True, grad_scale=1.0, want_mask=False):
+    """TopkHintMSELoss (losses/WeightedHintMSELoss.py:28-44) with k channels kept per sample (kd_topk_hint_mse) ->
+    (loss, grad, mask or None)."""
+    vs, vt, (N, Cc, P) = _loss_common(s, t)
+    if s.dim() != 4:
+        raise ValueError(f"topk_hint_mse: 4-D (N,C,H,W) operands only, got {tuple(s.shape)}")
+    k = int(k)
+    if not 1 <= k <= Cc:
+        raise ValueError(f"topk_hint_mse: keeps k = {k} of {Cc} channels; need 1 <= k <= C (topk * C rounded down is 0?)")
+    loss = torch.empty((), dtype=torch.float32, device=s.device)
+    grad = torch.empty_like(s) if want_grad else None
+    vg = view3(grad)[0] if want_grad else None
+    mask = torch.empty((N, Cc), dtype=torch.float32, device=s.device) if want_mask else None
+    need = _lib.lib().kd_topk_hint_workspace(N, Cc, P)
+    key = (s.device, torch.cuda.current_stream().cuda_stream)
+    ws = _topk_ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _topk_ws[key] = torch.empty(need, dtype=torch.uint8, device=s.device)
+    e0 = _prof_start()
+    check(_lib.lib().kd_topk_hint_mse(C.byref(vs), C.byref(vt), k, N, Cc, P, _ptr(loss), C.byref(vg) if vg is not None else None,
+                                      C.c_float(grad_scale), _ptr(mask), _ptr(ws), need, stream_ptr()), "kd_topk_hint_mse")
+    _prof_stop(e0, "loss", _nbytes(s, t, grad), f"top-{k} hint mse {N}x{Cc}x{P}", "topk_sums_kernel")
+    return loss, grad, mask
+
+
 def radam_step_multi(items):
     """items: [(p, g, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, weight_decay), ...] -- kd_radam_step for all of them in one
     launch per 48 tensors; same arithmetic per element as radam_step."""
