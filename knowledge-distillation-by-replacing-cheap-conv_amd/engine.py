@@ -813,7 +813,8 @@ class StudentEngine:
         ncls = f[6].out_channels
         d3 = self._new(N, h2, w2, ncls, dtype=torch.float32)
         # Where nothing differentiates through the head's last activation (the frozen teacher; the student when the loss is the hints alone),
-        # the classifier runs in the epilogue of final[3] and the 256-channel tensor is neither written nor read back (kd_conv_epilogue.cls_w)
+        # the classifier runs in the epilogue of final[3] and the 256-channel tensor is neither written nor read back (kd_conv_epilogue.cls_w);
+        # should a logit loss be back-propagated after all, _decoder_bwd recomputes it from d1
         fuse_cls = (not self.logits_need_grad and not any(q.requires_grad for q in list(f[3].parameters()) + list(f[6].parameters())) and
                     f[6].bias is None and ncls <= 32 and f[6].kernel_size == (1, 1) and ops.conv_cls_ok(d1, f[3].out_channels, 3, 1))
         d2 = None
@@ -895,7 +896,8 @@ class StudentEngine:
                     kw.update(out_act=a_next, act_scale=sc, act_shift=sh, act_relu=True)
                 kw["out_raw"] = raw
                 x_out = raw
-                if out_sums is not None and not site.cheap and site.gate is None:
+                # (aspp_image_pool(sums=) takes 128-pixel rows that lie within one image: not every crop's trunk output has them)
+                if out_sums is not None and not site.cheap and site.gate is None and (ho * wo) % 128 == 0:
                     kw["out_sums"] = out_sums
             else:
                 sc, sh = self._act_fold(bns[f"bn{i + 2}"], _act_gate(bns[f"bn{i + 2}"]))
@@ -913,6 +915,8 @@ class StudentEngine:
                     # _dual_ok asked for dense operands of these sizes; the real epilogue / views can still be refused (raised
                     # before anything is launched).  kdcc.h's contract: fall back to the two launches.
                     rec["dual"] = False
+                    if kw.get("out_sums") is not None:
+                        del kw["out_sums"][:]
                     shortcut = self._new(N, ho, wo, site.cout)
                     ops.conv2d(a1, self._w_fwd(blk.proj_conv), 1, 0, 1, out_raw=shortcut)
                     ops.conv2d(a, self._w_fwd(site.mod, gate=site.gate), site.stride, site.pad, site.dil, res_pre=shortcut, **kw)
@@ -1465,13 +1469,19 @@ class StudentEngine:
                               "trainer.backprop = 'kd+hint', TaylorPruneTrainer always); the shipped GSCNN plan back-propagates hint "
                               "losses only (cfg/cityscapes/51M_gscnn_all.json)")
         f = self._final()
-        N, h2, w2, _ = dec["d2"].shape
+        N, h2, w2, _ = dec["d1"].shape
         cdec, nf = dec["cdec"], dec["nf"]
         rg_dec0 = dec["rg_cat"] or dec["rg_m2"] or _is_trainable(net.bot_aspp) or _is_trainable(net.bot_fine)
         rg_d1 = rg_dec0 or _is_trainable(f[0]) or _is_trainable(f[1])
         rg_d2 = rg_d1 or _is_trainable(f[3]) or _is_trainable(f[4])
         if not (rg_d2 or _is_trainable(f[6])):
             return None, None
+        if dec["d2"] is None:
+            # the forward ran the classifier in final[3]'s epilogue (_decoder_fwd: nothing was to differentiate through the head),
+            # yet a logit loss is back-propagated: final[3]'s activation -- the classifier's input and the ReLU mask -- once more from d1
+            sc, sh = self._bn_fold(f[4])
+            dec["d2"] = self._new(N, h2, w2, f[3].out_channels)
+            ops.conv2d(dec["d1"], self._w_fwd(f[3]), 1, 1, 1, out_act=dec["d2"], act_scale=sc, act_shift=sh, act_relu=True)
         ncls = f[6].out_channels
         kpad = ((ncls + 63) // 64) * 64
         g_d3 = self._new(N, h2, w2, kpad, zero=True)               # classes padded to the GEMM K granule

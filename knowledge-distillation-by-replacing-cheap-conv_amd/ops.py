@@ -132,7 +132,7 @@ def conv2d(x, w_packed, stride=1, pad=0, dil=1, *, res_pre=None, mask=None, mask
     channel_sums(out_raw, sub=res_post, a=mask) would return from another pass over the tensors; otherwise it stays empty.
     out_sums: an empty list (forward, no epilogue operand, out_raw alone): when the selected kernel can sum its output per channel
     over blocks of 128 pixels in its epilogue, the [M/128][2][Cout] partial rows are appended (aspp_image_pool(..., sums=) takes
-    them: the global average pool of the tensor without another pass over it); otherwise it stays empty."""
+    them: the global average pool of the tensor without another pass over it); otherwise, and when the call raises, it stays empty."""
     _need_cuda(x, w_packed)
     N, H, W, Cin = x.shape
     Cout, kh, kw, Cin_w = w_packed.shape
@@ -198,7 +198,6 @@ def conv2d(x, w_packed, stride=1, pad=0, dil=1, *, res_pre=None, mask=None, mask
         if out_rows > 0:
             opart = torch.empty((out_rows, 2, Cout), dtype=torch.float32, device=x.device)
             ep.bn_sums = _ptr(opart)
-            out_sums.append(opart)
     prof = PROFILER
     if prof is not None:
         e0 = torch.cuda.Event(enable_timing=True)
@@ -210,6 +209,8 @@ def conv2d(x, w_packed, stride=1, pad=0, dil=1, *, res_pre=None, mask=None, mask
         check(_lib.lib().kd_conv1x1_dual_fwd(C.byref(d), _ptr(x), _ptr(x2), Cin2, ld2, _ptr(w_packed), C.byref(ep), stream_ptr()), "kd_conv1x1_dual_fwd")
     else:
         check(_lib.lib().kd_conv2d_fwd(C.byref(d), _ptr(x), _ptr(w_packed), C.byref(ep), stream_ptr()), "kd_conv2d_fwd")
+    if out_rows > 0:
+        out_sums.append(opart)      # (only once the launch was accepted: a refused one leaves the list empty)
     if prof is not None:
         e1 = torch.cuda.Event(enable_timing=True)
         e1.record()

@@ -4,7 +4,7 @@ import os
 
 import torch
 
-from _seeded import seeded_value
+from _seeded import seeded_fill_, seeded_value
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -74,3 +74,85 @@ def canny_stub_map(shape, seed):
     """The seeded 0/255 edge map the GSCNN goldens were generated with in place of cv2.Canny (tools/make_golden.py)."""
     g = torch.Generator().manual_seed(seed)
     return (torch.rand(shape, generator=g) < 0.12).float() * 255.0
+
+
+# ------------------------------------------------------- the engine's bf16 step against oracle/net_ref.py (GPU tests)
+P92 = ["mod4.block2.convs.conv2", "mod4.block3.convs.conv1", "mod7.block1.convs.conv2",
+       "aspp.features.1.0", "aspp.features.2.0", "aspp.features.3.0"]
+
+
+def oracle_threads():
+    torch.set_num_threads(max(1, min(16, len(os.sched_getaffinity(0)))))
+
+
+def build_student(plan, dtype, arch="deeplab"):
+    import kdcc_amd
+    from kdcc_amd.models import GSCNN, DeepWV3Plus
+    from kdcc_amd.models.students import DepthwiseStudent
+    teacher = GSCNN(num_classes=19) if arch == "gscnn" else DeepWV3Plus(num_classes=19)
+    seeded_fill_(teacher, "gscnn." if arch == "gscnn" else "teacher.")
+    teacher.eval()
+    model = DepthwiseStudent(teacher, None, dtype=dtype)
+    model.replace([{"name": n, "epoch": 1} for n in plan], kernel_size=9, padding=20, dilation=5)
+    model.register_hint_layers(plan)
+    model.unfreeze(plan)
+    for n in plan:
+        seeded_fill_(model.get_block(n, model.student), f"student.{n}.")
+    return model.cuda()
+
+
+def rel_l2(got, ref):
+    got, ref = got.detach().float().cpu().double(), ref.detach().float().cpu().double()
+    return float((got - ref).norm() / ref.norm().clamp_min(1e-30))
+
+
+def worst_tile(got, ref, px=256, ch=256):
+    """Worst relative L2 error over the conv kernels' output tiles of an NCHW-logical tensor: blocks of `px` consecutive pixels of one
+    image row x `ch` channels (256 x 256 = the workgroup tile of the persistent kernels; a narrower tensor is one channel block).  A
+    global norm averages one wrong tile away (1 of ~2000 at these sizes moves the global relative L2 by 2 %); here it is the maximum.
+    The denominator is the tile's own reference norm, floored at a quarter of the mean tile norm (near-empty tiles)."""
+    got, ref = got.detach().float().cpu(), ref.detach().float().cpu()
+    N, Cc, H, W = ref.shape
+    px, ch = min(px, W), min(ch, Cc)
+    Wt, Ct = W // px * px, Cc // ch * ch
+    e = ((got - ref)[:, :Ct, :, :Wt].double() ** 2).reshape(N, Ct // ch, ch, H, Wt // px, px).sum(dim=(2, 5))
+    r = (ref[:, :Ct, :, :Wt].double() ** 2).reshape(N, Ct // ch, ch, H, Wt // px, px).sum(dim=(2, 5))
+    floor = r.mean() / 16.0
+    return float((e / torch.maximum(r, floor)).max().sqrt())
+
+
+def grad_report(model, ref_grads, names=None):
+    """[(name, cosine, norm ratio)] of every trainable tensor's gradient against the fp32 oracle's."""
+    rows = []
+    for n, p in model.student.named_parameters():
+        if not p.requires_grad or (names is not None and n not in names):
+            continue
+        assert p.grad is not None and torch.isfinite(p.grad).all(), n
+        g, r = p.grad.detach().cpu().double().reshape(-1), ref_grads[n].double().reshape(-1)
+        cos = float((g @ r) / (g.norm() * r.norm()).clamp_min(1e-300))
+        rows.append((n, cos, float(g.norm() / r.norm().clamp_min(1e-300))))
+    return rows
+
+
+def check_step(model, r, hint, kd, out_st, out_tc, n_grads, what):
+    """A bf16 engine step against net_ref.kd_step's result r: logits and hints (global and worst tile), hint and KD losses, and the
+    cosine and norm ratio of every trainable gradient, at the bars of test_bf16_path_gpu.py's P92 test."""
+    errs = {"student logits": rel_l2(out_st, r["student_logits"]), "teacher logits": rel_l2(out_tc, r["teacher_logits"])}
+    for i, (s, t) in enumerate(zip(model.student_hidden_outputs, model.teacher_hidden_outputs)):
+        errs[f"student hint {i}"] = rel_l2(s, r["student_hints"][i])
+        errs[f"teacher hint {i}"] = rel_l2(t, r["teacher_hints"][i])
+    tiles = {"student logits": worst_tile(out_st, r["student_logits"], px=512), "teacher logits": worst_tile(out_tc, r["teacher_logits"], px=512)}
+    for i, (s, t) in enumerate(zip(model.student_hidden_outputs, model.teacher_hidden_outputs)):
+        tiles[f"student hint {i}"] = worst_tile(s, r["student_hints"][i])
+        tiles[f"teacher hint {i}"] = worst_tile(t, r["teacher_hints"][i])
+    rows = grad_report(model, r["grads"])
+    print(what, {k: f"{v:.2e}" for k, v in errs.items()}, "worst tile", {k: f"{v:.2e}" for k, v in tiles.items()}, "hint", hint.item(),
+          r["hint_loss"].item(), "worst gradients", sorted(rows, key=lambda t: t[1])[:3])
+    assert tiles["student logits"] < 1.5e-2 and tiles["teacher logits"] < 1.5e-2 and max(tiles.values()) < 3e-2, tiles   # (see the P92 test)
+    # the bars of the P92 test: logits 1e-2, hints 2e-2 relative L2, hint loss 5e-3, gradient cosine 0.9995, norm within 1 %
+    assert errs["student logits"] < 1e-2 and errs["teacher logits"] < 1e-2 and max(errs.values()) < 2e-2, errs
+    assert abs(hint.item() - r["hint_loss"].item()) <= 5e-3 * abs(r["hint_loss"].item())
+    assert abs(kd.item() - r["kd_loss"].item()) <= 5e-2 * abs(r["kd_loss"].item()) + 1e-6
+    assert len(rows) == n_grads
+    bad = [(n, c, q) for n, c, q in rows if c < 0.9995 or abs(q - 1) > 0.01]
+    assert not bad, bad

@@ -1374,6 +1374,52 @@ def test_conv_output_sums_feed_the_image_pooling(K, dual):
     assert float((b.float() - b[:, :1, :1, :].float()).abs().max()) == 0.0                  # broadcast over the pixels
 
 
+def test_refused_dual_conv_hands_out_no_output_sums(K):
+    """conv2d(x2=, out_sums=) on views the K-concatenated kernel refuses (a second source whose pixel stride is not a multiple of 16 B)
+    raises DualUnsupported before anything is launched -- and leaves the list empty: the caller falls back to two launches and then
+    pools the map itself (engine._block_fwd), so a partial-sums buffer the kernel never wrote must not be handed out."""
+    dt = "bf16"
+    N, H, W, C1, C2, Cout = 3, 64, 256, 128, 64, 512
+    x1, x2 = q(rnd(N, C1, H, W), dt), q(rnd(N, C2, H, W), dt)
+    wp = K.pack_conv_weight(torch.from_numpy(q(rnd(Cout, C1 + C2, 1, 1, scale=0.08), dt)).cuda(), DT[dt])
+    out = torch.zeros((N, H, W, Cout), dtype=DT[dt], device="cuda")
+    x1d = dev_nhwc(x1, dt)
+    sums = []
+    K.conv2d(x1d, wp, x2=dev_nhwc(x2, dt, ld=C2 + 16), out_raw=out, out_sums=sums)      # premise: the aligned view takes the sums
+    selected("conv_igemm_persist_kernel<pp,dual>", "dual with output sums")
+    assert len(sums) == 1
+    bad = dev_nhwc(x2, dt, ld=C2 + 12)             # 152-B pixel stride
+    assert not K.conv1x1_dual_ok(x1d, bad, Cout)
+    sums = []
+    with pytest.raises(K.DualUnsupported):
+        K.conv2d(x1d, wp, x2=bad, out_raw=out, out_sums=sums)
+    assert sums == []
+
+
+def test_image_pool_refuses_sums_across_images(K):
+    """aspp_image_pool(sums=) needs every 128-pixel row of partial sums inside one image.  At 4 x 24 x 40 (a 192 x 320 crop's trunk
+    output: 960 = 7.5 x 128 pixels per image) the conv kernel still takes output sums -- its rows only need N*H*W % 128 -- but the rows
+    straddle images, and the pooling must refuse them rather than average across images; without sums it pools the map."""
+    dt = "bf16"
+    N, H, W, C1, Cout, red = 4, 24, 40, 128, 4096, 64
+    x = dev_nhwc(q(rnd(N, C1, H, W), dt), dt)
+    wp = K.pack_conv_weight(torch.from_numpy(q(rnd(Cout, C1, 1, 1, scale=0.08), dt)).cuda(), DT[dt])
+    out = torch.zeros((N, H, W, Cout), dtype=DT[dt], device="cuda")
+    sums = []
+    K.conv2d(x, wp, out_raw=out, out_sums=sums)
+    selected("conv_igemm_persist_kernel<pp>", "output sums at 960 pixels per image")
+    assert len(sums) == 1 and tuple(sums[0].shape) == (N * H * W // 128, 2, Cout)      # premise: the conv hands them out
+    wi = torch.from_numpy(rnd(red, Cout, scale=0.05)).cuda()
+    sc, sh = torch.from_numpy(rnd(red) * 0.2 + 1.0).cuda(), torch.from_numpy(rnd(red) * 0.1).cuda()
+    a = torch.zeros((N, H, W, red), dtype=DT[dt], device="cuda")
+    with pytest.raises(ValueError):
+        K.aspp_image_pool(out, wi, sc, sh, a, sums=sums[0])
+    K.aspp_image_pool(out, wi, sc, sh, a)
+    mean = host_nchw(out).mean(axis=(2, 3))
+    want = np.maximum((mean @ wi.cpu().numpy().T) * sc.cpu().numpy() + sh.cpu().numpy(), 0)
+    np.testing.assert_allclose(a.float().cpu().numpy()[:, 0, 0, :], want, rtol=2e-2, atol=2e-3)
+
+
 @pytest.mark.parametrize("case", [(1, 224, 256, 64, 19, 1), (2, 128, 256, 128, 19, 2), (1, 240, 512, 64, 32, 1), (1, 224, 256, 64, 5, 1)])
 def test_conv_classifier_epilogue(K, case):
     """conv2d(cls_w=, cls_out=): the 1x1 classifier of the reference's `final` head (models/deeplabv3/deeplabv3.py:127-139: conv3x3 -> BN ->
