@@ -399,6 +399,34 @@ int kd_bn2d_bwd(const float *dy, const float *x, const float *y, const float *ga
                 const float *save_invstd, float *dx, float *dgamma, float *dbeta, int32_t training, int32_t relu,
                 int32_t accumulate, int32_t N, int32_t C, int32_t HW, kd_stream_t stream);
 
+/* ------------------------------------------------- BatchNorm2d on NHWC fp32 views (Wide-ResNet CIFAR path)
+ * nn.BatchNorm2d between the MFMA convolutions of models/cifar_models/wrn.py (16 / 160 / 320 / 640 channels, channels-last),
+ * forward and backward, train and eval mode, optional fused ReLU.  x / y / gy / res / dx are (M = N*H*W, C) fp32 views with
+ * pixel strides ld* >= C (element (m, c) at base[m*ld + c]).  Any M >= 1 and C >= 1 (float4 path when C % 4 == 0 and every
+ * view allows it).
+ * kd_bn_nhwc_fwd, training != 0: mean[c] = (1/M) sum_m x,  var[c] = (1/M) sum_m (x - mean)^2  (biased), from per-128-pixel
+ *   partials of x - k and (x - k)^2 around k = the block's first pixel, merged in a fixed order in fp64 (Chan's pairwise
+ *   update) -- no fp32 E[x^2] - E[x]^2, no atomics, bit-reproducible;
+ *   save_mean = mean, save_invstd = 1/sqrt(var + eps);
+ *   running_mean = (1-momentum) running_mean + momentum mean,  running_var = (1-momentum) running_var + momentum var*M/(M-1)
+ *   (each optional; trainer/classification_trainer.py:21 runs the student in train mode).
+ *   training == 0: mean / var are the running statistics (save_mean / save_invstd written from them).
+ *   y = relu?((x - mean) * gamma * invstd + beta).
+ * kd_bn_nhwc_bwd: g' = relu ? g * [y > 0] : g,  xhat = (x - save_mean) * save_invstd;
+ *   training: dx = gamma * invstd * (g' - mean_m(g') - xhat * mean_m(g' xhat)) (+ res);   eval: dx = gamma * invstd * g' (+ res);
+ *   dbeta (+)= sum_m g',  dgamma (+)= sum_m g' xhat   (accumulate != 0: added).  res (the gradient over an identity shortcut
+ *   that shares the BN's input) may be NULL; dx, dgamma, dbeta may each be NULL (frozen layers still need dx).  Same fixed-order
+ *   two-stage reductions as the forward.
+ * workspace: kd_bn_nhwc_workspace(M, C) bytes (train-mode forward; backward whenever a reduction is needed). */
+size_t kd_bn_nhwc_workspace(int64_t M, int32_t C);
+int kd_bn_nhwc_fwd(const float *x, int32_t ldx, float *y, int32_t ldy, int64_t M, int32_t C, const float *gamma, const float *beta,
+                   float *save_mean, float *save_invstd, float *running_mean, float *running_var, float momentum, float eps,
+                   int32_t training, int32_t relu, void *workspace, size_t workspace_bytes, kd_stream_t stream);
+int kd_bn_nhwc_bwd(const float *gy, int32_t ldg, const float *x, int32_t ldx, const float *y, int32_t ldy, const float *res,
+                   int32_t ldres, float *dx, int32_t lddx, int64_t M, int32_t C, const float *gamma, const float *save_mean,
+                   const float *save_invstd, float *dgamma, float *dbeta, int32_t accumulate, int32_t training, int32_t relu,
+                   void *workspace, size_t workspace_bytes, kd_stream_t stream);
+
 /* ------------------------------------------------- Gated-SCNN shape stream (BASELINE config 5)
  * The full-resolution pieces of models/gscnn/gscnn.py:183-325 that are not MFMA-sized convolutions.
  * kd_gated_conv: GatedSpatialConv2d.forward (models/gscnn/gate_spatial_conv.py:50-60) fused per pixel, C in {8,16,32}:

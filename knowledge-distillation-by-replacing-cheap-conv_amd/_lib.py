@@ -99,6 +99,11 @@ _SIGS = {
     "kd_conv2d_direct_wgrad": (c_int, [_P(DConvDesc), c_vp, c_vp, c_vp, c_vp, c_int, c_vp]),
     "kd_bn2d_fwd": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f, c_f, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "kd_bn2d_bwd": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp]),
+    "kd_bn_nhwc_workspace": (c_sz, [c_i64, c_int]),
+    "kd_bn_nhwc_fwd": (c_int, [c_vp, c_int, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f, c_f, c_int, c_int,
+                               c_vp, c_sz, c_vp]),
+    "kd_bn_nhwc_bwd": (c_int, [c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp,
+                               c_vp, c_int, c_int, c_int, c_vp, c_sz, c_vp]),
     "kd_pack_dw_weight": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "kd_dwconv_fwd": (c_int, [_P(DwDesc), c_vp, c_vp, c_vp, _P(DwEpilogue), c_vp, c_vp]),
     "kd_dwconv_fwd_sum": (c_int, [_P(DwDesc), c_int, c_vp, c_vp, c_vp, c_vp]),

@@ -1,1 +1,2 @@
 from .resnet import ResNet, resnet20, resnet32, resnet44, resnet56, resnet110  # noqa: F401
+from .wrn import WideResNet, wrn  # noqa: F401

@@ -106,3 +106,235 @@ class BatchNorm2d(nn.BatchNorm2d):
             self.num_batches_tracked.add_(1)
         return _BatchNorm.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.training, float(self.momentum),
                                 float(self.eps), bool(relu))
+
+
+# ------------------------------------------------------------------ channels-last modules (Wide-ResNet CIFAR path)
+# NCHW-logical tensors with NHWC strides (torch.channels_last): the MFMA implicit-GEMM convolutions (kd_conv2d_fwd /
+# kd_conv2d_wgrad / kd_pw_wgrad, fp32) and BatchNorm on NHWC views (kd_bn_nhwc_*) read and write them without a layout copy.
+_CIN_GRANULE = 32      # fp32 K granule of kd_conv2d_fwd: fewer input channels are zero-padded up to it (the 3->16 stem, 16->160)
+
+
+def _nhwc(t):
+    """(N,C,H,W)-logical tensor -> (N,H,W,C) view; a kd_copy_cast copy only when t is not channels_last-strided."""
+    v = t.permute(0, 2, 3, 1)
+    try:
+        ops.nhwc_ld(v)
+        if v.data_ptr() % 16 == 0 and v.stride(2) % 4 == 0:
+            return v
+    except ValueError:
+        pass
+    N, Cc, H, W = t.shape
+    out = torch.empty((N, H, W, Cc), dtype=t.dtype, device=t.device)
+    try:
+        ops.copy_cast(t, out.permute(0, 3, 1, 2))
+    except ValueError:              # (rows that are not one plane: make them so first)
+        ops.copy_cast(t.contiguous(), out.permute(0, 3, 1, 2))
+    return out
+
+
+def _nhwc_padded(t, cpad):
+    """(N,C,H,W)-logical tensor -> (N,H,W,cpad) fp32 buffer, channels >= C zero (the conv's K granule)."""
+    N, Cc, H, W = t.shape
+    out = torch.zeros((N, H, W, cpad), dtype=t.dtype, device=t.device)
+    src = t if t.dim() == 4 else t.reshape(N, Cc, H, W)
+    try:
+        ops.copy_cast(src, out[..., :Cc].permute(0, 3, 1, 2))
+    except ValueError:
+        ops.copy_cast(src.contiguous(), out[..., :Cc].permute(0, 3, 1, 2))
+    return out
+
+
+class _ConvNHWCFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, res, mod):
+        xh = mod._input(x)
+        out = mod._run(xh, res_pre=None if res is None else _nhwc(res))
+        ctx.mod = mod
+        ctx.in_shape = tuple(x.shape)
+        ctx.save_for_backward(xh if weight.requires_grad else None)
+        return out.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, gy):
+        mod = ctx.mod
+        (xh,) = ctx.saved_tensors
+        g = _nhwc(gy)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = mod._dgrad(g, ctx.in_shape).permute(0, 3, 1, 2)
+        if ctx.needs_input_grad[1]:
+            dw = mod._wgrad(xh, g)
+        return dx, dw, gy if ctx.needs_input_grad[2] else None, None
+
+
+class Conv2dNHWC(nn.Conv2d):
+    """nn.Conv2d (3x3 or 1x1, square stride / padding, no groups, no bias) on channels-last fp32 device tensors:
+    forward kd_conv2d_fwd; input gradient kd_conv2d_fwd on KD_PACK_DGRAD weights (zero-inserted first for stride 2);
+    weight gradient kd_conv2d_wgrad / kd_pw_wgrad, computed only for a weight that requires grad.  Packed weights are cached
+    per parameter version: a frozen weight is packed once, a trained one once per optimizer step.  Fewer than 32 input
+    channels are zero-padded to 32 (weights packed with cin_pad, the input copied into a zeroed 32-channel buffer).
+    forward(x, residual=None): residual (the block's shortcut) is added in the conv's epilogue."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._packs = {}
+
+    def __deepcopy__(self, memo):
+        import copy
+        new = self.__class__.__new__(self.__class__)      # (the cached device packs are not carried over)
+        memo[id(self)] = new
+        new.__dict__.update({k: copy.deepcopy(v, memo) for k, v in self.__dict__.items() if k != "_packs"})
+        new._packs = {}
+        return new
+
+    def _check(self):
+        k, s, p = self.kernel_size, self.stride, self.padding
+        if self.padding_mode != "zeros" or isinstance(p, str) or k[0] != k[1] or k[0] not in (1, 3) or s[0] != s[1] or p[0] != p[1] \
+                or self.dilation != (1, 1) or self.groups != 1 or self.bias is not None:
+            raise NotImplementedError("Conv2dNHWC: 1x1 / 3x3, square stride and padding, no dilation, groups or bias")
+
+    @property
+    def cin_pad(self):
+        return -(-self.in_channels // _CIN_GRANULE) * _CIN_GRANULE
+
+    def _pack(self, mode):
+        from ._lib import KD_PACK_FWD
+        w = self.weight
+        key = (mode, w._version, w.data_ptr())
+        hit = self._packs.get(mode)
+        if hit is None or hit[0] != key:
+            cin_pad = self.cin_pad if mode == KD_PACK_FWD else None
+            hit = (key, ops.pack_conv_weight(w, torch.float32, mode, cin_pad=cin_pad))
+            self._packs[mode] = hit
+        return hit[1]
+
+    def _input(self, x):
+        if self.in_channels != self.cin_pad:
+            return _nhwc_padded(x, self.cin_pad)
+        return _nhwc(x)
+
+    def _run(self, xh, res_pre=None, out_act=False, act_scale=None, act_shift=None, act_relu=False, want_raw=True):
+        """Forward on an (N,H,W,cin_pad) view -> out_raw [, out_act] (N,Ho,Wo,Cout) fp32 buffers."""
+        from ._lib import KD_PACK_FWD
+        N, H, W, _ = xh.shape
+        k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
+        Ho, Wo = ops.conv_out_size(H, k, s, p, 1), ops.conv_out_size(W, k, s, p, 1)
+        new = lambda: torch.empty((N, Ho, Wo, self.out_channels), dtype=torch.float32, device=xh.device)
+        raw = new() if want_raw else None
+        act = new() if out_act else None
+        ops.conv2d(xh, self._pack(KD_PACK_FWD), s, p, res_pre=res_pre, out_raw=raw, out_act=act, act_scale=act_scale,
+                   act_shift=act_shift, act_relu=act_relu)
+        return (raw, act) if out_act else raw
+
+    def _dgrad(self, g, in_shape):
+        from ._lib import KD_PACK_DGRAD
+        N, Cin, H, W = in_shape
+        k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
+        if s != 1:
+            g = ops.zero_insert(g, s, (H - k + 1 + 2 * p, W - k + 1 + 2 * p))
+        dx = torch.empty((N, H, W, Cin), dtype=torch.float32, device=g.device)
+        ops.conv2d(g, self._pack(KD_PACK_DGRAD), 1, k - 1 - p, 1, out_raw=dx)
+        return dx
+
+    def _wgrad(self, xh, g):
+        k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
+        dw = torch.empty((self.out_channels, xh.shape[3], k, k), dtype=torch.float32, device=g.device)
+        if k == 1 and s == 1:
+            ops.pw_wgrad(xh, g, dw)
+        else:
+            ops.conv2d_wgrad(xh, g, dw, s, p, 1)
+        return dw if xh.shape[3] == self.in_channels else dw[:, :self.in_channels].contiguous()
+
+    def forward(self, x, residual=None):
+        if _host(x):
+            y = super().forward(x)
+            return y if residual is None else y + residual
+        self._check()
+        if x.dtype != torch.float32:
+            raise TypeError("Conv2dNHWC is fp32 (the CIFAR path of the reference is fp32)")
+        return _ConvNHWCFn.apply(x, self.weight, residual, self)
+
+
+class _BatchNormNHWCFn(torch.autograd.Function):
+    """y = relu?(bn(x)); with `shortcut` also returns x itself, whose gradient (the identity shortcut's, when x is a residual block's
+    input) is then added to dx by kd_bn_nhwc_bwd's `res` operand instead of by a separate autograd sum."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, training, momentum, eps, relu, shortcut):
+        ctx.set_materialize_grads(False)
+        xh = _nhwc(x)
+        y, mean, invstd = ops.bn_nhwc_fwd(xh, gamma.contiguous(), beta.contiguous(), running_mean, running_var, training, momentum,
+                                          eps, relu)
+        ctx.save_for_backward(xh, y if relu else None, gamma, mean, invstd)
+        ctx.flags = (training, relu)
+        y = y.permute(0, 3, 1, 2)
+        return (y, x) if shortcut else y
+
+    @staticmethod
+    def backward(ctx, gy, gsc=None):
+        xh, y, gamma, mean, invstd = ctx.saved_tensors
+        training, relu = ctx.flags
+        Cc = xh.shape[3]
+        dg = torch.empty(Cc, device=xh.device) if ctx.needs_input_grad[1] else None
+        db = torch.empty(Cc, device=xh.device) if ctx.needs_input_grad[2] else None
+        res = None if gsc is None or not ctx.needs_input_grad[0] else _nhwc(gsc)
+        if gy is None:
+            if dg is not None:
+                dg.zero_()
+            if db is not None:
+                db.zero_()
+            return None if res is None else gsc, dg, db, None, None, None, None, None, None, None
+        dx = ops.bn_nhwc_bwd(_nhwc(gy), xh, y, gamma.contiguous(), mean, invstd, training, relu, res=res,
+                             need_dx=ctx.needs_input_grad[0], dgamma=dg, dbeta=db)
+        return None if dx is None else dx.permute(0, 3, 1, 2), dg, db, None, None, None, None, None, None, None
+
+
+class BatchNorm2dNHWC(nn.BatchNorm2d):
+    """nn.BatchNorm2d on channels-last fp32 device tensors (kd_bn_nhwc_fwd / kd_bn_nhwc_bwd): batch statistics in train mode,
+    running statistics in eval mode, optional fused ReLU (forward(x, relu=True)).  folded() gives the eval-mode
+    (scale, shift) a conv epilogue applies instead, cached per version of the parameters and statistics."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._fold = None
+
+    def __deepcopy__(self, memo):
+        import copy
+        new = self.__class__.__new__(self.__class__)      # (the cached folded vectors are not carried over)
+        memo[id(self)] = new
+        new.__dict__.update({k: copy.deepcopy(v, memo) for k, v in self.__dict__.items() if k != "_fold"})
+        new._fold = None
+        return new
+
+    def _check(self, x):
+        if not (self.affine and self.track_running_stats) or self.momentum is None:
+            raise NotImplementedError("BatchNorm2dNHWC: affine, running statistics, fixed momentum")
+        if x.dtype != torch.float32:
+            raise TypeError("BatchNorm2dNHWC is fp32")
+
+    def folded(self):
+        ts = (self.weight, self.bias, self.running_mean, self.running_var)
+        key = tuple((t._version, t.data_ptr()) for t in ts) + (self.eps,)
+        if self._fold is None or self._fold[0] != key:
+            self._fold = (key, ops.bn_fold(self))
+        return self._fold[1]
+
+    def _apply_fn(self, x, relu, shortcut):
+        self._check(x)
+        if self.training:
+            self.num_batches_tracked.add_(1)
+        return _BatchNormNHWCFn.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.training,
+                                      float(self.momentum), float(self.eps), bool(relu), shortcut)
+
+    def forward(self, x, relu=False):
+        if _host(x):
+            y = super().forward(x)
+            return F.relu(y) if relu else y
+        return self._apply_fn(x, relu, False)
+
+    def forward_with_shortcut(self, x, relu=False):
+        """(forward(x, relu), s) where s is x for an identity shortcut: the gradient reaching s joins dx inside kd_bn_nhwc_bwd
+        (its `res` operand).  Not a module call: forward hooks of this BN do not fire."""
+        if _host(x):
+            return self.forward(x, relu), x
+        return self._apply_fn(x, relu, True)

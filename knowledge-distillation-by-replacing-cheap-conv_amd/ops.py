@@ -910,6 +910,85 @@ def bn2d_bwd(dy, x, y, gamma, mean, invstd, training, relu=False, need_dx=True):
     return dx, dg, db
 
 
+# ------------------------------------------------------------------------- BatchNorm2d on NHWC fp32 views (WRN path)
+def _f32vec(*vs):
+    for v in vs:
+        if v is not None and (not v.is_cuda or v.dtype != torch.float32 or not v.is_contiguous()):
+            raise ValueError("bn_nhwc: parameters / statistics must be contiguous fp32 device vectors")
+
+
+def _bn_ws(M, Cc, device):
+    return _ws(_lib.lib().kd_bn_nhwc_workspace(M, Cc), device)
+
+
+def bn_nhwc_fwd(x, gamma, beta, running_mean, running_var, training, momentum, eps, relu=False, out=None):
+    """x (N,H,W,C) fp32 view -> (y, save_mean, save_invstd); y into `out` (an (N,H,W,C) view) when given.
+    Train mode updates the running statistics in place (either may be None)."""
+    _need_cuda(x, out)
+    _f32vec(gamma, beta, running_mean, running_var)
+    if x.dtype != torch.float32:
+        raise TypeError("bn_nhwc_fwd: fp32 only")
+    N, H, W, Cc = x.shape
+    if gamma.numel() != Cc or beta.numel() != Cc:
+        raise ValueError(f"bn_nhwc_fwd: {Cc} channels, gamma / beta of {gamma.numel()} / {beta.numel()}")
+    y = torch.empty((N, H, W, Cc), dtype=torch.float32, device=x.device) if out is None else out
+    if tuple(y.shape) != (N, H, W, Cc) or y.dtype != torch.float32:
+        raise ValueError("bn_nhwc_fwd: out must be an fp32 view of the input's shape")
+    mean, invstd = torch.empty(Cc, device=x.device), torch.empty(Cc, device=x.device)
+    M = N * H * W
+    ws = _bn_ws(M, Cc, x.device) if training else None
+    check(_lib.lib().kd_bn_nhwc_fwd(_ptr(x), nhwc_ld(x), _ptr(y), nhwc_ld(y), M, Cc, _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd),
+                                    _ptr(running_mean), _ptr(running_var), C.c_float(momentum), C.c_float(eps), int(bool(training)),
+                                    int(bool(relu)), _ptr(ws), 0 if ws is None else ws.numel(), stream_ptr()), "kd_bn_nhwc_fwd")
+    if training:    # the kernel updated the running statistics through raw pointers: tell version-keyed caches (BN folds)
+        for t in (running_mean, running_var):
+            if t is not None:
+                torch.autograd.graph.increment_version(t)
+    if out is not None:
+        torch.autograd.graph.increment_version(out)
+    return y, mean, invstd
+
+
+def bn_nhwc_bwd(gy, x, y, gamma, mean, invstd, training, relu=False, res=None, need_dx=True, dgamma=None, dbeta=None,
+                accumulate=False):
+    """Returns dx (N,H,W,C) | None; dgamma / dbeta (contiguous fp32 (C,)) receive sum g' xhat / sum g' when given (+= with
+    accumulate).  res: a gradient view added to dx.  y (the forward output) is read only with relu."""
+    _need_cuda(gy, x, y, res)
+    _f32vec(gamma, mean, invstd, dgamma, dbeta)
+    N, H, W, Cc = x.shape
+    for t in (gy, y, res):
+        if t is not None and (tuple(t.shape) != (N, H, W, Cc) or t.dtype != torch.float32):
+            raise ValueError("bn_nhwc_bwd: operand mismatch")
+    M = N * H * W
+    dx = torch.empty((N, H, W, Cc), dtype=torch.float32, device=x.device) if need_dx else None
+    ws = _bn_ws(M, Cc, x.device) if ((need_dx and training) or dgamma is not None or dbeta is not None) else None
+    ld = lambda t: nhwc_ld(t) if t is not None else 0
+    check(_lib.lib().kd_bn_nhwc_bwd(_ptr(gy), ld(gy), _ptr(x), ld(x), _ptr(y if relu else None), ld(y) if relu else 0, _ptr(res), ld(res),
+                                    _ptr(dx), ld(dx), M, Cc, _ptr(gamma), _ptr(mean), _ptr(invstd), _ptr(dgamma), _ptr(dbeta),
+                                    int(bool(accumulate)), int(bool(training)), int(bool(relu)), _ptr(ws),
+                                    0 if ws is None else ws.numel(), stream_ptr()), "kd_bn_nhwc_bwd")
+    return dx
+
+
+def copy_cast(src, dst):
+    """dst = src for two (N,C,H,W)-logical fp32/bf16 device tensors of the same shape with any dense-plane layout
+    (NCHW <-> channels_last, a channel slice of a wider NHWC buffer) -- kd_copy_cast."""
+    _need_cuda(src, dst)
+    if src.shape != dst.shape or src.dim() != 4:
+        raise ValueError("copy_cast: shape mismatch")
+    N, Cc, H, W = src.shape
+
+    def strides(t):
+        sN, sC, sH, sW = t.stride()
+        if H > 1 and sH != W * sW:
+            raise ValueError(f"copy_cast: rows of {tuple(t.shape)} stride {t.stride()} are not one plane")
+        return sN, sC, sW
+    (a, b, c), (d, e, f) = strides(src), strides(dst)
+    check(_lib.lib().kd_copy_cast(_ptr(src), dt_of(src), a, b, c, _ptr(dst), dt_of(dst), d, e, f, N, Cc, H * W, stream_ptr()),
+          "kd_copy_cast")
+    return dst
+
+
 # ------------------------------------------------------------------------- Gated-SCNN shape stream
 def pointwise_small(x, w, bias=None, out=None):
     """1x1 conv + bias, bf16, (Cin, Cout) in {(64, 32), (32, 16), (16, 8)}: x (N,H,W,Cin) view, w fp32 (Cout,Cin[,1,1]) (gscnn.py:232-235)."""
