@@ -655,6 +655,11 @@ int kd_rank1_add(int32_t dtype, void *y, int32_t ldy, const float *g, const floa
 int kd_debug_kernel_log_enable(int32_t on);
 int64_t kd_debug_kernel_log_read(char *buf, size_t bytes);
 const char *kd_debug_last_kernel(void);
+/* The same for the plumbing dispatchers (pooling, resampling, ReLU/BN backward, channel reductions, stem, image pooling,
+ * strided copy, the NCHW small-shape BatchNorm / weight gradient): the device kernel the calling thread's last such dispatch
+ * picked, e.g. "channel_sums_partial_kernel<bf16,8>" ("" before any).  A slot of its own: none of these names ever enters the
+ * log or kd_debug_last_kernel above.  A dispatcher that launches two kernels names the first, shape-selected one. */
+const char *kd_debug_last_plumbing_kernel(void);
 
 #ifdef __cplusplus
 }

@@ -172,6 +172,7 @@ _SIGS = {
     "kd_debug_kernel_log_enable": (c_int, [c_int]),
     "kd_debug_kernel_log_read": (c_i64, [C.c_char_p, c_sz]),
     "kd_debug_last_kernel": (C.c_char_p, []),
+    "kd_debug_last_plumbing_kernel": (C.c_char_p, []),
 }
 
 _lib = None
@@ -224,6 +225,12 @@ class kernel_log:
 def last_kernel():
     """Name of the device kernel the calling thread's last dispatch selected."""
     return lib().kd_debug_last_kernel().decode()
+
+
+def last_plumbing_kernel():
+    """Name of the device kernel the calling thread's last plumbing dispatch selected (trunk_ops / bwd_ops / small_ops);
+    independent of last_kernel() and of the counted log."""
+    return lib().kd_debug_last_plumbing_kernel().decode()
 
 
 def exported_symbols():

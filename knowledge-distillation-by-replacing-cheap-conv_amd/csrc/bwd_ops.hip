@@ -586,6 +586,8 @@ extern "C" int kd_relu_bn_bwd(int32_t dtype, const void *g, int32_t ldg, const v
                KD_ERR_INVALID, "kd_relu_bn_bwd: C %% 8 and 16-B aligned views required");
     const int nb = grid_for((long long)M * (C / 8));
     hipStream_t s = (hipStream_t)stream;
+    if (dtype == KD_BF16) KD_NOTE_PLUMBING("relu_bn_bwd_kernel<bf16>");
+    else KD_NOTE_PLUMBING("relu_bn_bwd_kernel<f32>");
     if (dtype == KD_BF16)
         hipLaunchKernelGGL(relu_bn_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t *)g, ldg, (const bf16_t *)mask, ldm,
                            scale, (const bf16_t *)res, ldres, (bf16_t *)y, ldy, (long long)M, C / 8);
@@ -631,6 +633,13 @@ extern "C" int kd_channel_sums(int32_t dtype, const void *g, int32_t ldg, const 
     }
     const dim3 grid((unsigned)chunks, (unsigned)((nvec + lc - 1) / lc), (unsigned)groups);
     hipStream_t s = (hipStream_t)stream;
+    if (dtype == KD_BF16) {
+        if (vec) KD_NOTE_PLUMBING("channel_sums_partial_kernel<bf16,8>");
+        else KD_NOTE_PLUMBING("channel_sums_partial_kernel<bf16,1>");
+    } else {
+        if (vec) KD_NOTE_PLUMBING("channel_sums_partial_kernel<f32,8>");
+        else KD_NOTE_PLUMBING("channel_sums_partial_kernel<f32,1>");
+    }
     if (dtype == KD_BF16) {
         if (vec) hipLaunchKernelGGL((channel_sums_partial_kernel<bf16_t, 8>), grid, dim3(256), 0, s, (const bf16_t *)g, ldg, (const bf16_t *)sub, ldsub, (const bf16_t *)a, lda, (long long)rows_per_group, C, chunks, (float *)workspace);
         else hipLaunchKernelGGL((channel_sums_partial_kernel<bf16_t, 1>), grid, dim3(256), 0, s, (const bf16_t *)g, ldg, (const bf16_t *)sub, ldsub, (const bf16_t *)a, lda, (long long)rows_per_group, C, chunks, (float *)workspace);
@@ -694,10 +703,14 @@ extern "C" int kd_bn_sums_finish(const float *part, int32_t rows, int32_t C, flo
         // (C / 16 blocks walking 2048 rows each took 36 us per call, 41 calls per mode-B step: the rows are split first)
         KD_REQUIRE(workspace && workspace_bytes >= kd_bn_sums_finish_workspace(rows, C), KD_ERR_WORKSPACE, "kd_bn_sums_finish: workspace too small");
         const int per = bn_sums_chunk(rows), chunks = (rows + per - 1) / per;
+        if (per == 256) KD_NOTE_PLUMBING("bn_sums_stage_kernel<256 rows>");
+        else KD_NOTE_PLUMBING("bn_sums_stage_kernel<64 rows>");
         hipLaunchKernelGGL(bn_sums_stage_kernel, dim3((unsigned)((C + 15) / 16), (unsigned)chunks), dim3(256), 0, s, part, rows, C, per, (float *)workspace);
         KD_CHECK_LAUNCH("kd_bn_sums_finish(stage)");
         part = (const float *)workspace;
         rows = chunks;
+    } else {
+        KD_NOTE_PLUMBING("channel_sums_finish_kernel");
     }
     hipLaunchKernelGGL(channel_sums_finish_kernel, dim3((unsigned)((C + 15) / 16)), dim3(256), 0, s, part, 1, rows, C, s1, s2);
     KD_CHECK_LAUNCH("kd_bn_sums_finish");
@@ -708,6 +721,7 @@ extern "C" int kd_bn_eval_param_grads(const float *s1, const float *s2, const fl
                                       float *dgamma, float *dbeta, int32_t C, int32_t accumulate, kd_stream_t stream)
 {
     KD_REQUIRE(s1 && s2 && scale && gamma && beta && dgamma && dbeta && C > 0, KD_ERR_INVALID, "kd_bn_eval_param_grads: bad argument");
+    KD_NOTE_PLUMBING("bn_eval_param_grads_kernel");
     hipLaunchKernelGGL(bn_eval_param_grads_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, s1, s2, scale, gamma, beta,
                        dgamma, dbeta, C, accumulate);
     KD_CHECK_LAUNCH("kd_bn_eval_param_grads");
@@ -732,6 +746,8 @@ extern "C" int kd_maxpool3x3s2_bwd(int32_t dtype, const void *x, int32_t ldx, co
     if (vec && workspace && workspace_bytes >= kd_maxpool3x3s2_bwd_workspace(N, H, W, C) && ((uintptr_t)workspace & 7) == 0) {
         const int C8 = C / 8;
         const dim3 g1((unsigned)((Wo * C8 + 255) / 256), (unsigned)Ho, (unsigned)N), g2((unsigned)((W * C8 + 255) / 256), (unsigned)H, (unsigned)N);
+        if (dtype == KD_BF16) KD_NOTE_PLUMBING("maxpool_argmax_kernel<bf16>");
+        else KD_NOTE_PLUMBING("maxpool_argmax_kernel<f32>");
         if (dtype == KD_BF16) {
             hipLaunchKernelGGL(maxpool_argmax_kernel<bf16_t>, g1, dim3(256), 0, s, (const bf16_t *)x, ldx, (uint2 *)workspace, N, H, W, C8, Ho, Wo);
             hipLaunchKernelGGL(maxpool_bwd_gather_kernel<bf16_t>, g2, dim3(256), 0, s, (const uint2 *)workspace, (const bf16_t *)gy, ldgy, (bf16_t *)gx, ldgx, N, H, W, C8, Ho, Wo);
@@ -743,6 +759,13 @@ extern "C" int kd_maxpool3x3s2_bwd(int32_t dtype, const void *x, int32_t ldx, co
         return KD_OK;
     }
     const dim3 g((unsigned)((W * (vec ? C / 8 : C) + 255) / 256), (unsigned)H, (unsigned)N);
+    if (dtype == KD_BF16) {
+        if (vec) KD_NOTE_PLUMBING("maxpool_bwd_kernel<bf16,8>");
+        else KD_NOTE_PLUMBING("maxpool_bwd_kernel<bf16,1>");
+    } else {
+        if (vec) KD_NOTE_PLUMBING("maxpool_bwd_kernel<f32,8>");
+        else KD_NOTE_PLUMBING("maxpool_bwd_kernel<f32,1>");
+    }
     if (dtype == KD_BF16) {
         if (vec) hipLaunchKernelGGL((maxpool_bwd_kernel<bf16_t, 8>), g, dim3(256), 0, s, (const bf16_t *)x, ldx, (const bf16_t *)gy, ldgy, (bf16_t *)gx, ldgx, N, H, W, C, Ho, Wo);
         else hipLaunchKernelGGL((maxpool_bwd_kernel<bf16_t, 1>), g, dim3(256), 0, s, (const bf16_t *)x, ldx, (const bf16_t *)gy, ldgy, (bf16_t *)gx, ldgx, N, H, W, C, Ho, Wo);
@@ -792,6 +815,20 @@ extern "C" int kd_upsample_bilinear_bwd(const void *gy, int32_t gy_dtype, int32_
     const bool vec = C % 8 == 0 && vec_ok(gy, ldgy, kd_elem_size(gy_dtype)) && vec_ok(gx, ldgx, kd_elem_size(gx_dtype)) && kd_aligned16(tmp);
     const int cv = vec ? C / 8 : C;
     const dim3 g1((unsigned)((W * cv + 255) / 256), (unsigned)Ho, (unsigned)N);
+    // <gy dtype (pass 1 reads it), gx dtype (pass 2 writes it), VEC of both passes>
+    if (gy_dtype == KD_BF16 && gx_dtype == KD_BF16) {
+        if (vec) KD_NOTE_PLUMBING("upsample_bwd_kernel<bf16,bf16,8>");
+        else KD_NOTE_PLUMBING("upsample_bwd_kernel<bf16,bf16,1>");
+    } else if (gy_dtype == KD_BF16) {
+        if (vec) KD_NOTE_PLUMBING("upsample_bwd_kernel<bf16,f32,8>");
+        else KD_NOTE_PLUMBING("upsample_bwd_kernel<bf16,f32,1>");
+    } else if (gx_dtype == KD_BF16) {
+        if (vec) KD_NOTE_PLUMBING("upsample_bwd_kernel<f32,bf16,8>");
+        else KD_NOTE_PLUMBING("upsample_bwd_kernel<f32,bf16,1>");
+    } else {
+        if (vec) KD_NOTE_PLUMBING("upsample_bwd_kernel<f32,f32,8>");
+        else KD_NOTE_PLUMBING("upsample_bwd_kernel<f32,f32,1>");
+    }
     if (vec) {
         if (gy_dtype == KD_BF16) hipLaunchKernelGGL((upsample_bwd_w_kernel<bf16_t, 8>), g1, dim3(256), 0, s, (const bf16_t *)gy, ldgy, tmp, N, Ho, Wo, W, C, sw, ow);
         else hipLaunchKernelGGL((upsample_bwd_w_kernel<float, 8>), g1, dim3(256), 0, s, (const float *)gy, ldgy, tmp, N, Ho, Wo, W, C, sw, ow);
@@ -822,6 +859,8 @@ extern "C" int kd_zero_insert(int32_t dtype, const void *x, int32_t ldx, void *y
     KD_REQUIRE(C % 8 == 0 && vec_ok(x, ldx, es) && vec_ok(y, ldy, es), KD_ERR_INVALID, "kd_zero_insert: C %% 8 and 16-B alignment required");
     const dim3 g((unsigned)((Wy * (C / 8) + 255) / 256), (unsigned)Hy, (unsigned)N);
     hipStream_t s = (hipStream_t)stream;
+    if (dtype == KD_BF16) KD_NOTE_PLUMBING("zero_insert_kernel<bf16>");
+    else KD_NOTE_PLUMBING("zero_insert_kernel<f32>");
     if (dtype == KD_BF16) hipLaunchKernelGGL(zero_insert_kernel<bf16_t>, g, dim3(256), 0, s, (const bf16_t *)x, ldx, (bf16_t *)y, ldy, H, W, C / 8, stride, Hy, Wy);
     else hipLaunchKernelGGL(zero_insert_kernel<float>, g, dim3(256), 0, s, (const float *)x, ldx, (float *)y, ldy, H, W, C / 8, stride, Hy, Wy);
     KD_CHECK_LAUNCH("kd_zero_insert");
@@ -837,6 +876,8 @@ extern "C" int kd_broadcast_add(int32_t dtype, const float *v, void *y, int32_t 
                "kd_broadcast_add: C %% 8 and 16-B alignment required");
     const int nb = grid_for((long long)N * HW * (C / 8));
     hipStream_t s = (hipStream_t)stream;
+    if (dtype == KD_BF16) KD_NOTE_PLUMBING("broadcast_add_kernel<bf16>");
+    else KD_NOTE_PLUMBING("broadcast_add_kernel<f32>");
     if (dtype == KD_BF16) hipLaunchKernelGGL(broadcast_add_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, v, (bf16_t *)y, ldy, N, (long long)HW, C / 8, alpha, accumulate);
     else hipLaunchKernelGGL(broadcast_add_kernel<float>, dim3(nb), dim3(256), 0, s, v, (float *)y, ldy, N, (long long)HW, C / 8, alpha, accumulate);
     KD_CHECK_LAUNCH("kd_broadcast_add");
@@ -864,9 +905,15 @@ extern "C" int kd_stem_wgrad(int32_t dtype, const float *x_nchw, const void *dy,
     hipStream_t s = (hipStream_t)stream;
     if (dtype == KD_BF16 && ld_dy % 8 == 0 && kd_aligned16(dy)) {
         KD_NOTE_KERNEL("stem_wgrad_mfma_kernel");
+        KD_NOTE_PLUMBING("stem_wgrad_mfma_kernel");
         hipLaunchKernelGGL(stem_wgrad_mfma_kernel, dim3(nb), dim3(256), 0, s, x_nchw, (const bf16_t *)dy, ld_dy, N, H, W, (float *)workspace);
-    } else if (dtype == KD_BF16) hipLaunchKernelGGL(stem_wgrad_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, x_nchw, (const bf16_t *)dy, ld_dy, N, H, W, (float *)workspace);
-    else hipLaunchKernelGGL(stem_wgrad_kernel<float>, dim3(nb), dim3(256), 0, s, x_nchw, (const float *)dy, ld_dy, N, H, W, (float *)workspace);
+    } else if (dtype == KD_BF16) {
+        KD_NOTE_PLUMBING("stem_wgrad_kernel<bf16>");
+        hipLaunchKernelGGL(stem_wgrad_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, x_nchw, (const bf16_t *)dy, ld_dy, N, H, W, (float *)workspace);
+    } else {
+        KD_NOTE_PLUMBING("stem_wgrad_kernel<f32>");
+        hipLaunchKernelGGL(stem_wgrad_kernel<float>, dim3(nb), dim3(256), 0, s, x_nchw, (const float *)dy, ld_dy, N, H, W, (float *)workspace);
+    }
     KD_CHECK_LAUNCH("kd_stem_wgrad");
     hipLaunchKernelGGL(stem_wgrad_finish_kernel, dim3((64 * 27 + 255) / 256), dim3(256), 0, s, (const float *)workspace, nb, dw, accumulate);
     KD_CHECK_LAUNCH("kd_stem_wgrad(finish)");

@@ -47,6 +47,13 @@ static inline int kd_tuning_env_int(const char *name)
 void kd_note_kernel(const char *name);
 #define KD_NOTE_KERNEL(name) kd_note_kernel(name)
 
+// The plumbing dispatchers (trunk_ops.hip, bwd_ops.hip, small_ops.hip) say which device kernel they picked through a slot of
+// their own (kd_debug_last_plumbing_kernel): one thread-local pointer, stored and nothing else -- no counters, no table, and
+// the conv log above (its readers attribute time and assert exact name sets by it) never sees these names.  `name` is a string
+// literal, one per distinguishable dispatch branch; tests/test_plumbing_host.py requires a test case for every one of them.
+void kd_note_plumbing(const char *name);
+#define KD_NOTE_PLUMBING(name) kd_note_plumbing(name)
+
 static inline bool kd_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int kd_elem_size(int dtype) { return dtype == KD_BF16 ? 2 : 4; }
 

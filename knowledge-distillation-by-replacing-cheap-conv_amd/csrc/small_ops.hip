@@ -270,6 +270,7 @@ extern "C" int kd_conv2d_direct_wgrad(const kd_dconv_desc *s, const float *x, co
     KD_REQUIRE(x && dy && (dw || dbias), KD_ERR_INVALID, "kd_conv2d_direct_wgrad: null argument");
     hipStream_t st = (hipStream_t)stream;
     if (dw) {
+        KD_NOTE_PLUMBING("dconv_wgrad_kernel");
         hipLaunchKernelGGL(dconv_wgrad_kernel, dim3((unsigned)(d.K * d.Cg)), dim3(256), 0, st, d, x, dy, dw, accumulate);
         KD_CHECK_LAUNCH("kd_conv2d_direct_wgrad");
     }
@@ -287,6 +288,8 @@ extern "C" int kd_bn2d_fwd(const float *x, const float *gamma, const float *beta
     KD_REQUIRE(x && gamma && beta && y && N > 0 && C > 0 && HW > 0, KD_ERR_INVALID, "kd_bn2d_fwd: bad argument");
     KD_REQUIRE(training || (running_mean && running_var), KD_ERR_INVALID, "kd_bn2d_fwd: eval mode needs the running statistics");
     KD_REQUIRE((long long)N * C * HW < (1ll << 31), KD_ERR_UNSUPPORTED, "kd_bn2d_fwd: tensor exceeds 2^31 elements");
+    if (training) KD_NOTE_PLUMBING("bn2d_fwd_kernel<train>");
+    else KD_NOTE_PLUMBING("bn2d_fwd_kernel<eval>");
     hipLaunchKernelGGL(bn2d_fwd_kernel, dim3((unsigned)C), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, save_mean, save_invstd,
                        running_mean, running_var, momentum, eps, training, relu, N, C, HW);
     KD_CHECK_LAUNCH("kd_bn2d_fwd");
@@ -299,6 +302,8 @@ extern "C" int kd_bn2d_bwd(const float *dy, const float *x, const float *y, cons
 {
     KD_REQUIRE(dy && x && gamma && save_mean && save_invstd && N > 0 && C > 0 && HW > 0, KD_ERR_INVALID, "kd_bn2d_bwd: bad argument");
     KD_REQUIRE(!relu || y, KD_ERR_INVALID, "kd_bn2d_bwd: the fused-ReLU backward needs the forward output");
+    if (training) KD_NOTE_PLUMBING("bn2d_bwd_kernel<train>");
+    else KD_NOTE_PLUMBING("bn2d_bwd_kernel<eval>");
     hipLaunchKernelGGL(bn2d_bwd_kernel, dim3((unsigned)C), dim3(256), 0, (hipStream_t)stream, dy, x, y, gamma, save_mean, save_invstd, dx,
                        dgamma, dbeta, training, relu, accumulate, N, C, HW);
     KD_CHECK_LAUNCH("kd_bn2d_bwd");

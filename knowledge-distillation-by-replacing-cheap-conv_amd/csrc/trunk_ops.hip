@@ -33,7 +33,10 @@ int g_klog_n = 0;
 volatile int g_klog_on = 0;
 pthread_mutex_t g_klog_mu = PTHREAD_MUTEX_INITIALIZER;
 thread_local const char *g_klog_last = "";
+thread_local const char *g_plumbing_last = "";
 }  // namespace
+
+void kd_note_plumbing(const char *name) { g_plumbing_last = name; }
 
 void kd_note_kernel(const char *name)
 {
@@ -58,6 +61,7 @@ extern "C" int kd_debug_kernel_log_enable(int32_t on)
 }
 
 extern "C" const char *kd_debug_last_kernel(void) { return g_klog_last; }
+extern "C" const char *kd_debug_last_plumbing_kernel(void) { return g_plumbing_last; }
 
 extern "C" int64_t kd_debug_kernel_log_read(char *buf, size_t bytes)
 {
@@ -658,9 +662,11 @@ extern "C" int kd_stem_conv(int32_t dtype, const float *x_nchw, const float *w, 
         const long long want = (ngroups + 3) / 4;
         const unsigned blocks = (unsigned)(want < 256 * 16 ? want : 256 * 16);   // persistent-ish: 16 workgroups per CU
         KD_NOTE_KERNEL("stem_conv_mfma_kernel");
+        KD_NOTE_PLUMBING("stem_conv_mfma_kernel");
         hipLaunchKernelGGL(stem_conv_mfma_kernel, dim3(blocks), dim3(256), 0, s, x_nchw, w, (bf16_t *)y, N, H, W, gpr);
     } else {
         KD_NOTE_KERNEL("stem_conv_kernel<f32>");
+        KD_NOTE_PLUMBING("stem_conv_kernel<f32>");
         hipLaunchKernelGGL(stem_conv_kernel<float>, grid, dim3(256), 0, s, x_nchw, w, (float *)y, N, H, W);
     }
     KD_CHECK_LAUNCH("kd_stem_conv");
@@ -679,6 +685,7 @@ extern "C" int kd_stem_conv_pool(const float *x_nchw, const float *w, void *y_ra
     const long long waves = (long long)N * ngx * nseg;
     KD_REQUIRE((waves + 3) / 4 <= 0x7fffffffLL, KD_ERR_UNSUPPORTED, "kd_stem_conv_pool: image too large");
     KD_NOTE_KERNEL("stem_pool_kernel");
+    KD_NOTE_PLUMBING("stem_pool_kernel");
     hipLaunchKernelGGL(stem_pool_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x_nchw, w,
                        (bf16_t *)y_raw, (bf16_t *)y_act, scale, shift, N, H, W, Ho, Wo, ngx, nseg);
     KD_CHECK_LAUNCH("kd_stem_conv_pool");
@@ -699,6 +706,8 @@ extern "C" int kd_maxpool3x3s2(int32_t dtype, const void *x, int32_t ldx, void *
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const dim3 g((unsigned)((Wo * (C / 8) + 255) / 256), (unsigned)Ho, (unsigned)N);
     hipStream_t s = (hipStream_t)stream;
+    if (dtype == KD_BF16) KD_NOTE_PLUMBING("maxpool_kernel<bf16>");
+    else KD_NOTE_PLUMBING("maxpool_kernel<f32>");
     if (dtype == KD_BF16)
         hipLaunchKernelGGL(maxpool_kernel<bf16_t>, g, dim3(256), 0, s, (const bf16_t *)x, ldx, (bf16_t *)y_raw, ld_raw,
                            (bf16_t *)y_act, ld_act, scale, shift, N, H, W, C, Ho, Wo);
@@ -711,7 +720,7 @@ extern "C" int kd_maxpool3x3s2(int32_t dtype, const void *x, int32_t ldx, void *
 
 template <typename TI, typename TO>
 static void launch_up(const void *x, int ldx, void *y, int ldy, int N, int H, int W, int C, int Ho, int Wo, bool vec,
-                      hipStream_t s, bool align = true)
+                      bool flat4, hipStream_t s, bool align = true)
 {
     float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
     float sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
@@ -720,7 +729,9 @@ static void launch_up(const void *x, int ldx, void *y, int ldy, int N, int H, in
         sh = (float)H / (float)Ho; sw = (float)W / (float)Wo;
         oh = 0.5f * sh - 0.5f; ow = 0.5f * sw - 0.5f;
     }
-    if (!vec && std::is_same<TO, float>::value && ldy == C && ((long long)Wo * C) % 4 == 0 && kd_aligned16(y)) {
+    // (the caller's flat4 already implies an fp32 output; the is_same term only keeps the bf16-output instantiations from
+    // compiling a call of the fp32-only flat kernel)
+    if (std::is_same<TO, float>::value && flat4) {
         const dim3 g((unsigned)((Wo * C / 4 + 255) / 256), (unsigned)((Ho + UP_RO - 1) / UP_RO), (unsigned)N);
         hipLaunchKernelGGL((upsample_flat4_kernel<TI>), g, dim3(256), 0, s, (const TI *)x, ldx, (float *)y, N, H, W, C, Ho, Wo, sh, sw, oh, ow);
     } else if (vec) {
@@ -754,11 +765,28 @@ extern "C" int kd_upsample_bilinear(const void *x, int32_t x_dtype, int32_t ldx,
                "kd_upsample_bilinear_ac: bad dtype");
     const bool vec = C % 8 == 0 && kd_aligned16(x) && kd_aligned16(y) && (ldx * kd_elem_size(x_dtype)) % 16 == 0 &&
                      (ldy * kd_elem_size(y_dtype)) % 16 == 0;
+    // dense fp32 rows of an odd channel count (the logits): four floats of the flattened (wo, c) row per thread
+    const bool flat4 = !vec && y_dtype == KD_F32 && ldy == C && ((long long)Wo * C) % 4 == 0 && kd_aligned16(y);
     hipStream_t s = (hipStream_t)stream;
-    if (x_dtype == KD_BF16 && y_dtype == KD_BF16) launch_up<bf16_t, bf16_t>(x, ldx, y, ldy, N, H, W, C, Ho, Wo, vec, s, al);
-    else if (x_dtype == KD_BF16) launch_up<bf16_t, float>(x, ldx, y, ldy, N, H, W, C, Ho, Wo, vec, s, al);
-    else if (y_dtype == KD_BF16) launch_up<float, bf16_t>(x, ldx, y, ldy, N, H, W, C, Ho, Wo, vec, s, al);
-    else launch_up<float, float>(x, ldx, y, ldy, N, H, W, C, Ho, Wo, vec, s, al);
+    if (x_dtype == KD_BF16 && y_dtype == KD_BF16) {
+        if (vec) KD_NOTE_PLUMBING("upsample_kernel<bf16,bf16,8>");
+        else KD_NOTE_PLUMBING("upsample_kernel<bf16,bf16,1>");
+        launch_up<bf16_t, bf16_t>(x, ldx, y, ldy, N, H, W, C, Ho, Wo, vec, flat4, s, al);
+    } else if (x_dtype == KD_BF16) {
+        if (flat4) KD_NOTE_PLUMBING("upsample_flat4_kernel<bf16>");
+        else if (vec) KD_NOTE_PLUMBING("upsample_kernel<bf16,f32,8>");
+        else KD_NOTE_PLUMBING("upsample_kernel<bf16,f32,1>");
+        launch_up<bf16_t, float>(x, ldx, y, ldy, N, H, W, C, Ho, Wo, vec, flat4, s, al);
+    } else if (y_dtype == KD_BF16) {
+        if (vec) KD_NOTE_PLUMBING("upsample_kernel<f32,bf16,8>");
+        else KD_NOTE_PLUMBING("upsample_kernel<f32,bf16,1>");
+        launch_up<float, bf16_t>(x, ldx, y, ldy, N, H, W, C, Ho, Wo, vec, flat4, s, al);
+    } else {
+        if (flat4) KD_NOTE_PLUMBING("upsample_flat4_kernel<f32>");
+        else if (vec) KD_NOTE_PLUMBING("upsample_kernel<f32,f32,8>");
+        else KD_NOTE_PLUMBING("upsample_kernel<f32,f32,1>");
+        launch_up<float, float>(x, ldx, y, ldy, N, H, W, C, Ho, Wo, vec, flat4, s, al);
+    }
     KD_CHECK_LAUNCH("kd_upsample_bilinear_ac");
     return KD_OK;
 }
@@ -785,6 +813,8 @@ extern "C" int kd_aspp_image_pool(int32_t dtype, const void *x, int32_t ldx, con
     const int HW = H * W;
     hipStream_t s = (hipStream_t)stream;
     const dim3 g1(GAP_CHUNKS, (Cin + 255) / 256, N);
+    if (dtype == KD_BF16) KD_NOTE_PLUMBING("gap_partial_kernel<bf16>");
+    else KD_NOTE_PLUMBING("gap_partial_kernel<f32>");
     if (dtype == KD_BF16) hipLaunchKernelGGL(gap_partial_kernel<bf16_t>, g1, dim3(256), 0, s, (const bf16_t *)x, ldx, partial, N, HW, Cin);
     else hipLaunchKernelGGL(gap_partial_kernel<float>, g1, dim3(256), 0, s, (const float *)x, ldx, partial, N, HW, Cin);
     KD_CHECK_LAUNCH("kd_aspp_image_pool(partial)");
@@ -827,6 +857,7 @@ extern "C" int kd_bn_fold(const float *gamma, const float *beta, const float *me
                           float *scale, float *shift, int32_t C, kd_stream_t stream)
 {
     KD_REQUIRE(gamma && beta && mean && var && scale && shift && C > 0, KD_ERR_INVALID, "kd_bn_fold: bad argument");
+    KD_NOTE_PLUMBING("bn_fold_kernel");
     hipLaunchKernelGGL(bn_fold_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, gamma, beta, mean, var, eps,
                        scale, shift, C);
     KD_CHECK_LAUNCH("kd_bn_fold");
@@ -841,6 +872,8 @@ extern "C" int kd_copy_cast(const void *src, int32_t src_dtype, int64_t s_sN, in
     KD_REQUIRE((src_dtype == KD_F32 || src_dtype == KD_BF16) && (dst_dtype == KD_F32 || dst_dtype == KD_BF16),
                KD_ERR_INVALID, "kd_copy_cast: bad dtype");
     const long long total = (long long)N * C * P;
+    if (d_sC == 1) KD_NOTE_PLUMBING("copy_cast_kernel<c_fast>");
+    else KD_NOTE_PLUMBING("copy_cast_kernel<p_fast>");
     hipLaunchKernelGGL(copy_cast_kernel, dim3(grid_for(total, 1 << 20)), dim3(256), 0, (hipStream_t)stream, src, src_dtype,
                        (long long)s_sN, (long long)s_sC, (long long)s_sP, dst, dst_dtype, (long long)d_sN, (long long)d_sC,
                        (long long)d_sP, N, C, (long long)P, d_sC == 1 ? 1 : 0);

@@ -663,13 +663,22 @@ def stem_conv_pool(x_nchw, w, scale=None, shift=None, want_raw=True):
     return y_raw, y_act
 
 
-def maxpool3x3s2(x, scale=None, shift=None, want_raw=True):
-    _need_cuda(x, scale, shift)
+def maxpool3x3s2(x, scale=None, shift=None, want_raw=True, out_raw=None, out_act=None):
+    """out_raw / out_act: (N,Ho,Wo,C) views (channel slices of wider buffers) to write instead of fresh tensors."""
+    _need_cuda(x, scale, shift, out_raw, out_act)
     N, H, W, Cc = x.shape
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    y_raw = torch.empty((N, Ho, Wo, Cc), dtype=x.dtype, device=x.device) if want_raw else None
-    y_act = torch.empty((N, Ho, Wo, Cc), dtype=x.dtype, device=x.device) if scale is not None else None
-    check(_lib.lib().kd_maxpool3x3s2(dt_of(x), _ptr(x), nhwc_ld(x), _ptr(y_raw), Cc, _ptr(y_act), Cc, _ptr(scale), _ptr(shift),
+    for t in (out_raw, out_act):
+        if t is not None and (tuple(t.shape) != (N, Ho, Wo, Cc) or t.dtype != x.dtype):
+            raise ValueError("maxpool3x3s2: bad output view")
+    if out_act is not None and (scale is None or shift is None):
+        raise ValueError("maxpool3x3s2: out_act needs scale and shift")
+    if out_raw is not None and not want_raw:
+        raise ValueError("maxpool3x3s2: out_raw given with want_raw=False")
+    y_raw = out_raw if out_raw is not None else (torch.empty((N, Ho, Wo, Cc), dtype=x.dtype, device=x.device) if want_raw else None)
+    y_act = out_act if out_act is not None else (torch.empty((N, Ho, Wo, Cc), dtype=x.dtype, device=x.device) if scale is not None else None)
+    ld = lambda t: nhwc_ld(t) if t is not None else Cc
+    check(_lib.lib().kd_maxpool3x3s2(dt_of(x), _ptr(x), nhwc_ld(x), _ptr(y_raw), ld(y_raw), _ptr(y_act), ld(y_act), _ptr(scale), _ptr(shift),
                                      N, H, W, Cc, stream_ptr()), "kd_maxpool3x3s2")
     return y_raw, y_act
 
@@ -729,7 +738,8 @@ def stem_wgrad(x_nchw, dy, dw, accumulate=False):
     return dw
 
 
-def maxpool3x3s2_bwd(x, gy, out=None):
+def maxpool3x3s2_bwd(x, gy, out=None, workspace=True):
+    """workspace=False hands the kernel no arg-max workspace: the one-pass gather kernel runs instead of the two-pass one."""
     _need_cuda(x, gy, out)
     N, H, W, Cc = x.shape
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
@@ -738,9 +748,9 @@ def maxpool3x3s2_bwd(x, gy, out=None):
     if out is None:
         out = torch.empty((N, H, W, Cc), dtype=x.dtype, device=x.device)
     need = _lib.lib().kd_maxpool3x3s2_bwd_workspace(N, H, W, Cc)
-    ws = _ws(need, x.device)
+    ws = _ws(need, x.device) if workspace else None
     check(_lib.lib().kd_maxpool3x3s2_bwd(dt_of(x), _ptr(x), nhwc_ld(x), _ptr(gy), nhwc_ld(gy), _ptr(out), nhwc_ld(out), N, H, W, Cc,
-                                         _ptr(ws), need, stream_ptr()), "kd_maxpool3x3s2_bwd")
+                                         _ptr(ws), need if workspace else 0, stream_ptr()), "kd_maxpool3x3s2_bwd")
     return out
 
 
@@ -809,6 +819,20 @@ def channel_sums(g, sub=None, a=None, per_image=False):
     return s1, s2
 
 
+def bn_sums_finish(part):
+    """part: the contiguous fp32 [rows][2][C] partial rows a conv epilogue wrote (conv2d(bn_sums=)) -> (s1, s2) fp32 (C,):
+    the column sums of part[:, 0] and part[:, 1] (kd_bn_sums_finish: fp64 accumulators, fixed order)."""
+    _need_cuda(part)
+    if part.dim() != 3 or part.shape[1] != 2 or part.dtype != torch.float32 or not part.is_contiguous():
+        raise ValueError("bn_sums_finish: part must be contiguous fp32 [rows][2][C]")
+    rows, _, Cc = part.shape
+    s1, s2 = torch.empty(Cc, device=part.device), torch.empty(Cc, device=part.device)
+    need = _lib.lib().kd_bn_sums_finish_workspace(rows, Cc)
+    ws = _ws(need, part.device)
+    check(_lib.lib().kd_bn_sums_finish(_ptr(part), rows, Cc, _ptr(s1), _ptr(s2), _ptr(ws), need, stream_ptr()), "kd_bn_sums_finish")
+    return s1, s2
+
+
 def bn_eval_param_grads(s1, s2, scale, gamma, beta, dgamma, dbeta, accumulate=False):
     _need_cuda(s1, s2, scale, gamma, beta, dgamma, dbeta)
     Cc = s1.numel()
@@ -874,14 +898,22 @@ def conv2d_direct_dgrad(dy, w, x_shape, stride=1, pad=0, dil=1, groups=1):
     return dx
 
 
-def conv2d_direct_wgrad(x, dy, w_shape, stride=1, pad=0, dil=1, groups=1, want_bias=False):
-    _nchw32(x, dy)
+def conv2d_direct_wgrad(x, dy, w_shape, stride=1, pad=0, dil=1, groups=1, want_bias=False, dw=None, db=None, accumulate=False):
+    """Returns (dw, db | None).  dw / db: contiguous fp32 tensors to write (+= with accumulate) instead of fresh ones."""
+    _nchw32(x, dy, dw, db)
     d, oshape = _dconv_desc(x.shape, w_shape, stride, pad, dil, groups)
     if tuple(dy.shape) != oshape:
         raise ValueError(f"direct wgrad: dy {tuple(dy.shape)} != {oshape}")
-    dw = torch.empty(tuple(w_shape), dtype=torch.float32, device=x.device)
-    db = torch.empty(w_shape[0], dtype=torch.float32, device=x.device) if want_bias else None
-    check(_lib.lib().kd_conv2d_direct_wgrad(C.byref(d), _ptr(x), _ptr(dy), _ptr(dw), _ptr(db), 0, stream_ptr()), "kd_conv2d_direct_wgrad")
+    if (dw is not None and tuple(dw.shape) != tuple(w_shape)) or (db is not None and db.numel() != w_shape[0]):
+        raise ValueError("direct wgrad: dw / db do not match the weight shape")
+    if accumulate and (dw is None or (db is None and want_bias)):
+        raise ValueError("direct wgrad: accumulate needs the tensors to add to")
+    if dw is None:
+        dw = torch.empty(tuple(w_shape), dtype=torch.float32, device=x.device)
+    if db is None and want_bias:
+        db = torch.empty(w_shape[0], dtype=torch.float32, device=x.device)
+    check(_lib.lib().kd_conv2d_direct_wgrad(C.byref(d), _ptr(x), _ptr(dy), _ptr(dw), _ptr(db), int(bool(accumulate)), stream_ptr()),
+          "kd_conv2d_direct_wgrad")
     return dw, db
 
 
@@ -898,15 +930,22 @@ def bn2d_fwd(x, gamma, beta, running_mean, running_var, training, momentum, eps,
     return y, mean, invstd
 
 
-def bn2d_bwd(dy, x, y, gamma, mean, invstd, training, relu=False, need_dx=True):
-    """Returns (dx | None, dgamma, dbeta)."""
-    _nchw32(dy, x, y, gamma, mean, invstd)
+def bn2d_bwd(dy, x, y, gamma, mean, invstd, training, relu=False, need_dx=True, dgamma=None, dbeta=None, accumulate=False):
+    """Returns (dx | None, dgamma, dbeta).  dgamma / dbeta: contiguous fp32 (C,) vectors to write (+= with accumulate) instead
+    of fresh ones."""
+    _nchw32(dy, x, y, gamma, mean, invstd, dgamma, dbeta)
     N, Cc = x.shape[0], x.shape[1]
     HW = x.numel() // (N * Cc)
     dx = torch.empty_like(x) if need_dx else None
-    dg, db = torch.empty(Cc, device=x.device), torch.empty(Cc, device=x.device)
+    if accumulate and (dgamma is None or dbeta is None):
+        raise ValueError("bn2d_bwd: accumulate needs dgamma and dbeta to add to")
+    for t in (dgamma, dbeta):
+        if t is not None and t.numel() != Cc:
+            raise ValueError("bn2d_bwd: dgamma / dbeta must hold one value per channel")
+    dg = torch.empty(Cc, device=x.device) if dgamma is None else dgamma
+    db = torch.empty(Cc, device=x.device) if dbeta is None else dbeta
     check(_lib.lib().kd_bn2d_bwd(_ptr(dy), _ptr(x), _ptr(y), _ptr(gamma), _ptr(mean), _ptr(invstd), _ptr(dx), _ptr(dg), _ptr(db),
-                                 int(training), int(relu), 0, N, Cc, HW, stream_ptr()), "kd_bn2d_bwd")
+                                 int(training), int(relu), int(bool(accumulate)), N, Cc, HW, stream_ptr()), "kd_bn2d_bwd")
     return dx, dg, db
 
 

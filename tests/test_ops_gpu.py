@@ -1222,7 +1222,8 @@ def test_relu_bn_bwd_channel_sums_bn_params_stem_wgrad(K, dt):
     ref = orc.bn_eval_bwd(g, act, gamma, var, relu=True)
     got = K.relu_bn_bwd(dev_nhwc(g, dt), dev_nhwc(act, dt, ld=Cc + 16), torch.from_numpy(scale).cuda(), res=dev_nhwc(res, dt))
     assert_close(host_nchw(got), ref + res, dt, "relu_bn_bwd")
-    # channel sums (+ product sums), global and per image, with the `sub` operand
+    # channel sums (+ product sums), global and per image, with the `sub` operand (a smoke check in passing: the tolerance of
+    # kd_channel_sums is owned by tests/test_plumbing_gpu.py, which holds every branch to the recursive-summation bound)
     gq = host_nchw(got)                      # as stored: g_x + res
     s1, s2 = K.channel_sums(got, sub=dev_nhwc(res, dt), a=dev_nhwc(act, dt))
     gx = gq.astype(np.float64) - res
