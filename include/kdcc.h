@@ -587,6 +587,34 @@ int kd_topk_hint_mse(const kd_view3 *s, const kd_view3 *t, int32_t K, int32_t N,
                      const kd_mview3 *grad, float grad_scale, float *mask, void *workspace, size_t workspace_bytes,
                      kd_stream_t stream);
 
+/* The ensemble step's criterion (trainer/ensemble_trainer.py:80-85) in one pass over the student logits, and ensemble_predict
+ * (:145-164).  Up to KD_MULTI_MAX operand views travel BY VALUE (`ts` is a host struct; nothing is copied to the device besides
+ * the kernel arguments), each with one fp32 weight w_k >= 0; W = sum_k w_k > 0.  Operands as in kd_kldiv (fp32 / bf16, any of the
+ * (N,C), NCHW, NHWC stridings, mixed freely), fp32 arithmetic, fixed-order fp64 reductions, no synchronisation.
+ *
+ * kd_kldiv_multi: losses[0] = kd    = (1/W) sum_k w_k * kd_kldiv(s, t_k, T)          (each KL accumulated per target)
+ *                 losses[1] = sup   = kd_ce2d(s, labels, ignore_index)                (0 when labels == NULL or no pixel is valid)
+ *                 losses[2] = total = kd_scale * kd + sup_scale * sup                 (three fp32 on the device)
+ *   grad (when != NULL) = d total / d s
+ *        = kd_scale * T/(N*P) * (softmax(s/T) - (1/W) sum_k w_k softmax(t_k/T)) + sup_scale * (softmax(s) - onehot) / #valid
+ *   with a zero cross-entropy part on ignored pixels.  s and every t_k are read once where the class stride is 1 (C <= 1024: a row
+ *   per wave in registers; dense NHWC with C < 22 and >= 16384 pixels: 256 pixels per block through LDS) and grad is written once;
+ *   other stridings (NCHW) and larger C take one pixel per thread and re-read from cache as kd_kldiv does.  labels: int64 (N,P) or
+ *   NULL.  workspace of kd_loss_workspace() bytes.  n outside [1, KD_MULTI_MAX]: KD_ERR_INVALID.
+ * kd_softmax_mean: out = (1/W) sum_k w_k softmax(x_k / T, dim C), fp32, written once; out's strides are the caller's (the layout of
+ *   the first view for ensemble_predict).  This is the target kd_ensemble_kldiv expects. */
+#define KD_MULTI_MAX 16
+typedef struct kd_multi_targets {
+    int32_t n;
+    kd_view3 t[KD_MULTI_MAX];
+    float w[KD_MULTI_MAX];
+} kd_multi_targets;
+int kd_kldiv_multi(const kd_view3 *s, const kd_multi_targets *targets, float temperature, const int64_t *labels,
+                   int32_t ignore_index, float kd_scale, float sup_scale, int32_t N, int32_t C, int64_t P, float *losses,
+                   const kd_mview3 *grad, void *workspace, size_t workspace_bytes, kd_stream_t stream);
+int kd_softmax_mean(const kd_multi_targets *logits, float temperature, int32_t N, int32_t C, int64_t P, const kd_mview3 *out,
+                    kd_stream_t stream);
+
 /* CityscapesMetricTracker.update / confusion_for_batch (utils/util.py:108-128), the logged train mIoU, without the
  * reference's two full-logit D2H copies per step (trainer/layerwise_trainer.py:249-250):
  *   for every pixel with 0 <= target < C:  conf[target][argmax_c x(n,c,p)] += 1

@@ -64,6 +64,13 @@ class View3(C.Structure):
     _fields_ = [("ptr", c_vp), ("dtype", c_int), ("sN", c_i64), ("sC", c_i64), ("sP", c_i64)]
 
 
+KD_MULTI_MAX = 16
+
+
+class MultiTargets(C.Structure):
+    _fields_ = [("n", c_int), ("t", View3 * KD_MULTI_MAX), ("w", c_f * KD_MULTI_MAX)]
+
+
 _P = C.POINTER
 _SIGS = {
     "kd_version": (c_int, []),
@@ -152,6 +159,8 @@ _SIGS = {
     "kd_jsdiv": (c_int, [_P(View3), _P(View3), c_f, c_int, c_int, c_i64, c_vp, _P(View3), c_f, c_vp, c_sz, c_vp]),
     "kd_jsdiv_up": (c_int, [c_vp, c_vp, c_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_sz, c_vp]),
     "kd_ensemble_kldiv": (c_int, [_P(View3), _P(View3), c_int, c_int, c_i64, c_vp, _P(View3), c_f, c_vp, c_sz, c_vp]),
+    "kd_kldiv_multi": (c_int, [_P(View3), _P(MultiTargets), c_f, c_vp, c_int, c_f, c_f, c_int, c_int, c_i64, c_vp, _P(View3), c_vp, c_sz, c_vp]),
+    "kd_softmax_mean": (c_int, [_P(MultiTargets), c_f, c_int, c_int, c_i64, _P(View3), c_vp]),
     "kd_focal": (c_int, [_P(View3), c_vp, c_vp, c_f, c_int, c_int, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "kd_focal_grad": (c_int, [_P(View3), c_vp, c_vp, c_f, c_int, c_int, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, _P(View3), c_vp]),
     "kd_focal_up": (c_int, [c_vp, c_vp, c_vp, c_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp,

@@ -1,9 +1,10 @@
 // KD losses, forward + gradient fused in one pass (kd_kldiv, kd_hint_mse,
-// kd_weighted_hint_mse, kd_ce2d, kd_jsdiv, kd_ensemble_kldiv, kd_focal, kd_topk_hint_mse)
-// and the RAdam update (kd_radam_step).
+// kd_weighted_hint_mse, kd_ce2d, kd_jsdiv, kd_ensemble_kldiv, kd_focal, kd_topk_hint_mse, kd_kldiv_multi),
+// the ensemble's mean softmax (kd_softmax_mean) and the RAdam update (kd_radam_step).
 // All are HBM-bound streaming kernels.  Loss scalars are reduced in two fixed-order
 // stages (per-block partials in fp64 -> one finishing block), so results are
 // bit-reproducible run to run.
+#include <algorithm>
 #include <type_traits>
 
 #include "kd_common.h"
@@ -1145,6 +1146,401 @@ __global__ __launch_bounds__(256) void topk_grad_kernel(V3 s, V3 t, M3 g, const 
     }
 }
 
+// ---- multi-target KL + cross entropy in one pass (kd_kldiv_multi) and the ensemble's mean softmax (kd_softmax_mean) ----------------
+// trainer/ensemble_trainer.py:80-85 back-propagates sum_k w_k KLDiv(s, t_k) / W + CE(s, y); its gradient is linear in the targets:
+//   gk * (softmax(s/T) - sum_k w_k softmax(t_k/T) / W) + gs * (softmax(s) - onehot)
+// so the student row is read once, every target row once (its KL value accumulated per target, its probabilities into q) and the
+// gradient is written once.  The target views travel by value in the kernel argument (w already divided by W).  Three shapes:
+//   mt_wave_kernel   class stride 1, a row of C <= 1024 classes held in one wave's registers, reductions by lane shuffles;
+//   kldm_nhwc_kernel dense NHWC with few classes and many pixels: 256 pixels per block staged through LDS, one pixel per thread;
+//   kldm_kernel      any strides / any C: one pixel per thread, the operands re-read from cache as kldiv_kernel does.
+struct MT { V3 t[KD_MULTI_MAX]; float w[KD_MULTI_MAX]; int n; };
+constexpr int MT_MAX_BLOCKS = 2 * MAX_BLOCKS / 3;      // kd / ce / count partials inside kd_loss_workspace's 2 * MAX_BLOCKS doubles
+
+__device__ __forceinline__ float wave_max(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// sup_scale / #valid from the count partials: every wave adds them in the same order, so every wave holds the same bits
+__device__ __forceinline__ float mt_sup_scale(const double *count, int ncount, float sup_scale)
+{
+    double c = 0.0;
+    for (int i = threadIdx.x & 63; i < ncount; i += 64) c += count[i];
+    c = wave_sum_d(c);
+    return c > 0.0 ? sup_scale / (float)c : 0.f;
+}
+
+__device__ __forceinline__ void block_partial2(double a, double b, double *pa, double *pb)
+{
+    __shared__ double w1[4], w2[4];
+    a = wave_sum_d(a); b = wave_sum_d(b);
+    if ((threadIdx.x & 63) == 0) { w1[threadIdx.x >> 6] = a; w2[threadIdx.x >> 6] = b; }
+    __syncthreads();
+    if (threadIdx.x == 0) { pa[blockIdx.x] = w1[0] + w1[1] + w1[2] + w1[3]; pb[blockIdx.x] = w2[0] + w2[1] + w2[2] + w2[3]; }
+}
+
+// A row of C classes in one wave: lane l holds 4 * NCH elements.  VEC: element (j, q) is class (j * 64 + l) * 4 + q, one 16-B (fp32)
+// or 8-B (bf16) access per j (C % 4 == 0, the row 4-element aligned); otherwise class (j * 4 + q) * 64 + l, scalar and coalesced.
+template <bool VEC> __device__ __forceinline__ int row_cls(int j, int q, int lane)
+{
+    return VEC ? (j * 64 + lane) * 4 + q : (j * 4 + q) * 64 + lane;
+}
+template <int NCH, bool VEC>
+__device__ __forceinline__ void row_load(const void *p, int dt, long long base, int C, int lane, float (&v)[NCH * 4])
+{
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        if (VEC) {
+            const int c0 = (j * 64 + lane) * 4;
+            if (c0 < C) {
+                if (dt == KD_BF16) {
+                    const uint2 u = *(const uint2 *)((const bf16_t *)p + base + c0);
+                    v[j * 4] = __uint_as_float(u.x << 16); v[j * 4 + 1] = __uint_as_float(u.x & 0xffff0000u);
+                    v[j * 4 + 2] = __uint_as_float(u.y << 16); v[j * 4 + 3] = __uint_as_float(u.y & 0xffff0000u);
+                } else {
+                    const float4 f = *(const float4 *)((const float *)p + base + c0);
+                    v[j * 4] = f.x; v[j * 4 + 1] = f.y; v[j * 4 + 2] = f.z; v[j * 4 + 3] = f.w;
+                }
+            } else {
+                v[j * 4] = v[j * 4 + 1] = v[j * 4 + 2] = v[j * 4 + 3] = -INFINITY;
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int c = (j * 4 + q) * 64 + lane;
+                v[j * 4 + q] = c < C ? kd_ld(p, dt, base + c) : -INFINITY;
+            }
+        }
+    }
+}
+template <int NCH, bool VEC>
+__device__ __forceinline__ void row_store(void *p, int dt, long long base, int C, int lane, const float (&v)[NCH * 4])
+{
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+        if (VEC) {
+            const int c0 = (j * 64 + lane) * 4;
+            if (c0 < C) {
+                if (dt == KD_BF16)
+                    *(uint2 *)((bf16_t *)p + base + c0) = make_uint2(pack_bf16x2(v[j * 4], v[j * 4 + 1]), pack_bf16x2(v[j * 4 + 2], v[j * 4 + 3]));
+                else
+                    *(float4 *)((float *)p + base + c0) = make_float4(v[j * 4], v[j * 4 + 1], v[j * 4 + 2], v[j * 4 + 3]);
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int c = (j * 4 + q) * 64 + lane;
+                if (c < C) kd_st(p, dt, base + c, v[j * 4 + q]);
+            }
+        }
+    }
+}
+
+// one target row: q += w * softmax(t / T); returns this lane's share of sum_c pt (lpt - lps) when lps is given
+template <int NCH, bool VEC, bool WITH_KL>
+__device__ __forceinline__ float row_target(const V3 &t, long long n, long long p, int C, int lane, float invT, float w,
+                                            const float (&lps)[NCH * 4], float (&q)[NCH * 4])
+{
+    constexpr int E = NCH * 4;
+    float xt[E];
+    row_load<NCH, VEC>(t.p, t.dt, n * t.sN + p * t.sP, C, lane, xt);
+    float m = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < E; ++e) m = fmaxf(m, xt[e]);
+    const float mt = wave_max(m) * invT;
+    float z = 0.f;
+#pragma unroll
+    for (int e = 0; e < E; ++e) z += __expf(xt[e] * invT - mt);
+    const float lzt = __logf(wave_sum(z)) + mt;
+    float kl = 0.f;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const float lpt = xt[e] * invT - lzt, pt = __expf(lpt);
+        if (WITH_KL) kl += pt > 0.f ? pt * (lpt - lps[e]) : 0.f;
+        q[e] += w * pt;
+    }
+    return kl;
+}
+
+// SMEAN: kd_softmax_mean (s unused, g = the fp32 output); otherwise kd_kldiv_multi
+template <int NCH, bool VEC, bool SMEAN>
+__global__ __launch_bounds__(256) void mt_wave_kernel(V3 s, const MT tg, M3 g, const int64_t *__restrict__ labels, int ignore_index,
+                                                      float invT, float gk, float sup_scale, int C, long long P, long long rows,
+                                                      const double *count, int ncount, double *pkd, double *pce)
+{
+    constexpr int E = NCH * 4;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const float gs = (!SMEAN && labels) ? mt_sup_scale(count, ncount, sup_scale) : 0.f;
+    double akd = 0.0, ace = 0.0;
+    for (long long row = (long long)blockIdx.x * 4 + wv; row < rows; row += (long long)gridDim.x * 4) {
+        const long long n = row / P, p = row - n * P;
+        float sr[E], lps[E], q[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) { q[e] = 0.f; lps[e] = 0.f; sr[e] = 0.f; }
+        float lz1 = 0.f;
+        bool valid = false;
+        int y = -1;
+        if (!SMEAN) {
+            row_load<NCH, VEC>(s.p, s.dt, n * s.sN + p * s.sP, C, lane, sr);
+            float m = -INFINITY;
+#pragma unroll
+            for (int e = 0; e < E; ++e) m = fmaxf(m, sr[e]);
+            m = wave_max(m);
+            const float ms = m * invT;
+            float z = 0.f;
+#pragma unroll
+            for (int e = 0; e < E; ++e) z += __expf(sr[e] * invT - ms);
+            const float lzs = __logf(wave_sum(z)) + ms;
+#pragma unroll
+            for (int e = 0; e < E; ++e) lps[e] = sr[e] * invT - lzs;
+            lz1 = lzs;
+            if (labels) {
+                const int64_t yy = labels[row];
+                valid = !(yy == ignore_index || yy < 0 || yy >= C);      // (one row per wave: uniform)
+                y = (int)yy;
+                if (valid) {
+                    if (invT != 1.f) {
+                        float z1 = 0.f;
+#pragma unroll
+                        for (int e = 0; e < E; ++e) z1 += __expf(sr[e] - m);
+                        lz1 = __logf(wave_sum(z1)) + m;
+                    }
+#pragma unroll
+                    for (int e = 0; e < E; ++e)
+                        if (row_cls<VEC>(e >> 2, e & 3, lane) == y) ace += (double)(lz1 - sr[e]);
+                }
+            }
+        }
+        float kl = 0.f;
+        for (int k = 0; k < tg.n; ++k) kl += tg.w[k] * row_target<NCH, VEC, !SMEAN>(tg.t[k], n, p, C, lane, invT, tg.w[k], lps, q);
+        akd += (double)kl;
+        if (g.p) {
+            if (!SMEAN) {
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    float v = gk * (__expf(lps[e]) - q[e]);
+                    if (valid) v += gs * (__expf(sr[e] - lz1) - (row_cls<VEC>(e >> 2, e & 3, lane) == y ? 1.f : 0.f));
+                    q[e] = v;
+                }
+            }
+            row_store<NCH, VEC>(g.p, g.dt, n * g.sN + p * g.sP, C, lane, q);
+        }
+    }
+    if (!SMEAN) block_partial2(akd, ace, pkd, pce);
+}
+
+// global <-> LDS staging of `nel` consecutive elements of either storage type: 16-B accesses when the chunk is whole and aligned
+__device__ __forceinline__ void stage_any(float *dst, const void *src, int dt, long long off, int nel)
+{
+    if (dt == KD_BF16) {
+        const bf16_t *sp = (const bf16_t *)src + off;
+        if ((nel & 7) == 0 && ((uintptr_t)sp & 15) == 0) {
+            for (int i = threadIdx.x; i < (nel >> 3); i += 256) {
+                float v[8];
+                ld8(sp + i * 8, v);
+                ((float4 *)dst)[i * 2] = make_float4(v[0], v[1], v[2], v[3]);
+                ((float4 *)dst)[i * 2 + 1] = make_float4(v[4], v[5], v[6], v[7]);
+            }
+        } else {
+            for (int i = threadIdx.x; i < nel; i += 256) dst[i] = bf16_to_f32(sp[i]);
+        }
+    } else {
+        stage_scaled(dst, (const float *)src + off, nel, 1.0f);
+    }
+}
+__device__ __forceinline__ void unstage_any(void *dst, int dt, long long off, const float *src, int nel)
+{
+    if (dt == KD_BF16) {
+        bf16_t *dp = (bf16_t *)dst + off;
+        if ((nel & 7) == 0 && ((uintptr_t)dp & 15) == 0) {
+            for (int i = threadIdx.x; i < (nel >> 3); i += 256) {
+                const float4 a = ((const float4 *)src)[i * 2], b = ((const float4 *)src)[i * 2 + 1];
+                const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+                st8(dp + i * 8, v);
+            }
+        } else {
+            for (int i = threadIdx.x; i < nel; i += 256) dp[i] = f32_to_bf16(src[i]);
+        }
+    } else {
+        unstage((float *)dst + off, src, nel);
+    }
+}
+
+// dense NHWC, 3 * 256 * C floats of LDS (student rows, the current target's rows, q / the gradient)
+__global__ __launch_bounds__(256) void kldm_nhwc_kernel(V3 s, const MT tg, M3 g, const int64_t *__restrict__ labels, int ignore_index,
+                                                        float invT, float gk, float sup_scale, int C, long long npix,
+                                                        const double *count, int ncount, double *pkd, double *pce)
+{
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float *A = sm, *B = sm + 256 * C, *Q = sm + 512 * C;
+    const float gs = labels ? mt_sup_scale(count, ncount, sup_scale) : 0.f;
+    double akd = 0.0, ace = 0.0;
+    for (long long base = (long long)blockIdx.x * 256; base < npix; base += (long long)gridDim.x * 256) {
+        const int np = (int)min((long long)256, npix - base);
+        const int nel = np * C;
+        const bool mine = (int)threadIdx.x < np;
+        float *a = A + threadIdx.x * C, *b = B + threadIdx.x * C, *q = Q + threadIdx.x * C;
+        float lzs = 0.f, lz1 = 0.f, kl = 0.f;
+        bool valid = false;
+        int y = -1;
+        stage_any(A, s.p, s.dt, base * C, nel);
+        for (int k = 0; k < tg.n; ++k) {
+            stage_any(B, tg.t[k].p, tg.t[k].dt, base * C, nel);
+            __syncthreads();
+            if (mine && k == 0) {
+                float m = -INFINITY;
+                for (int c = 0; c < C; ++c) m = fmaxf(m, a[c]);
+                const float ms = m * invT;
+                float z = 0.f;
+                for (int c = 0; c < C; ++c) { z += __expf(a[c] * invT - ms); q[c] = 0.f; }
+                lzs = __logf(z) + ms;
+                lz1 = lzs;
+                if (labels) {
+                    const int64_t yy = labels[base + threadIdx.x];
+                    valid = !(yy == ignore_index || yy < 0 || yy >= C);
+                    y = (int)yy;
+                    if (valid) {
+                        if (invT != 1.f) {
+                            float z1 = 0.f;
+                            for (int c = 0; c < C; ++c) z1 += __expf(a[c] - m);
+                            lz1 = __logf(z1) + m;
+                        }
+                        ace += (double)(lz1 - a[y]);
+                    }
+                }
+            }
+            if (mine) {
+                const float w = tg.w[k];
+                float m = -INFINITY;
+                for (int c = 0; c < C; ++c) m = fmaxf(m, b[c]);
+                const float mt = m * invT;
+                float z = 0.f;
+                for (int c = 0; c < C; ++c) z += __expf(b[c] * invT - mt);
+                const float lzt = __logf(z) + mt;
+                float klk = 0.f;
+                for (int c = 0; c < C; ++c) {
+                    const float lpt = b[c] * invT - lzt, pt = __expf(lpt);
+                    klk += pt > 0.f ? pt * (lpt - (a[c] * invT - lzs)) : 0.f;
+                    q[c] += w * pt;
+                }
+                kl += w * klk;
+            }
+            __syncthreads();
+        }
+        akd += (double)kl;
+        if (g.p) {
+            if (mine) {
+                for (int c = 0; c < C; ++c) {
+                    float v = gk * (__expf(a[c] * invT - lzs) - q[c]);
+                    if (valid) v += gs * (__expf(a[c] - lz1) - (c == y ? 1.f : 0.f));
+                    q[c] = v;
+                }
+            }
+            __syncthreads();
+            unstage_any(g.p, g.dt, base * C, Q, nel);
+        }
+        __syncthreads();
+    }
+    block_partial2(akd, ace, pkd, pce);
+}
+
+// any strides, any C: one pixel per thread; log Z of every target parked in LDS ([target][thread]: conflict-free)
+template <bool SMEAN>
+__global__ __launch_bounds__(256) void kldm_kernel(V3 s, const MT tg, M3 g, const int64_t *__restrict__ labels, int ignore_index, float invT,
+                                                   float gk, float sup_scale, int C, long long P, long long rows, const double *count,
+                                                   int ncount, double *pkd, double *pce)
+{
+    __shared__ float lz[KD_MULTI_MAX][256];
+    const float gs = (!SMEAN && labels) ? mt_sup_scale(count, ncount, sup_scale) : 0.f;
+    double akd = 0.0, ace = 0.0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < rows; i += (long long)gridDim.x * 256) {
+        const long long n = i / P, p = i - n * P;
+        const long long bs = n * s.sN + p * s.sP, bg = n * g.sN + p * g.sP;
+        float lzs = 0.f, lz1 = 0.f;
+        bool valid = false;
+        int y = -1;
+        if (!SMEAN) {
+            float m = -INFINITY;
+            for (int c = 0; c < C; ++c) m = fmaxf(m, kd_ld(s.p, s.dt, bs + c * s.sC));
+            const float ms = m * invT;
+            float z = 0.f;
+            for (int c = 0; c < C; ++c) z += __expf(kd_ld(s.p, s.dt, bs + c * s.sC) * invT - ms);
+            lzs = __logf(z) + ms;
+            lz1 = lzs;
+            if (labels) {
+                const int64_t yy = labels[i];
+                valid = !(yy == ignore_index || yy < 0 || yy >= C);
+                y = (int)yy;
+                if (valid) {
+                    if (invT != 1.f) {
+                        float z1 = 0.f;
+                        for (int c = 0; c < C; ++c) z1 += __expf(kd_ld(s.p, s.dt, bs + c * s.sC) - m);
+                        lz1 = __logf(z1) + m;
+                    }
+                    ace += (double)(lz1 - kd_ld(s.p, s.dt, bs + y * s.sC));
+                }
+            }
+        }
+        for (int k = 0; k < tg.n; ++k) {
+            const V3 t = tg.t[k];
+            const long long bt = n * t.sN + p * t.sP;
+            float m = -INFINITY;
+            for (int c = 0; c < C; ++c) m = fmaxf(m, kd_ld(t.p, t.dt, bt + c * t.sC));
+            const float mt = m * invT;
+            float z = 0.f;
+            for (int c = 0; c < C; ++c) z += __expf(kd_ld(t.p, t.dt, bt + c * t.sC) * invT - mt);
+            lz[k][threadIdx.x] = __logf(z) + mt;
+        }
+        float kl = 0.f;
+        for (int c = 0; c < C; ++c) {
+            const float sv = SMEAN ? 0.f : kd_ld(s.p, s.dt, bs + c * s.sC);
+            const float lps = sv * invT - lzs;
+            float q = 0.f;
+            for (int k = 0; k < tg.n; ++k) {
+                const V3 t = tg.t[k];
+                const float lpt = kd_ld(t.p, t.dt, n * t.sN + p * t.sP + c * t.sC) * invT - lz[k][threadIdx.x], pt = __expf(lpt);
+                if (!SMEAN) kl += tg.w[k] * (pt > 0.f ? pt * (lpt - lps) : 0.f);
+                q += tg.w[k] * pt;
+            }
+            if (g.p) {
+                float v = q;
+                if (!SMEAN) {
+                    v = gk * (__expf(lps) - q);
+                    if (valid) v += gs * (__expf(sv - lz1) - (c == y ? 1.f : 0.f));
+                }
+                kd_st(g.p, g.dt, bg + c * g.sC, v);
+            }
+        }
+        akd += (double)kl;
+    }
+    if (!SMEAN) block_partial2(akd, ace, pkd, pce);
+}
+
+// out[0] = kd, out[1] = sup, out[2] = kd_scale * kd + sup_scale * sup
+__global__ __launch_bounds__(256) void mt_finish_kernel(const double *pkd, const double *pce, int n, const double *count, int ncount,
+                                                        double kd_mul, float kd_scale, float sup_scale, float *out)
+{
+    __shared__ double sh[3][256];
+    double a = 0.0, b = 0.0, c = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) { a += pkd[i]; b += pce[i]; }
+    for (int i = threadIdx.x; i < ncount; i += 256) c += count[i];
+    sh[0][threadIdx.x] = a; sh[1][threadIdx.x] = b; sh[2][threadIdx.x] = c;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o)
+            for (int r = 0; r < 3; ++r) sh[r][threadIdx.x] += sh[r][threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float kd = (float)(sh[0][0] * kd_mul);
+        const float sup = sh[2][0] > 0.0 ? (float)(sh[1][0] / sh[2][0]) : 0.f;
+        out[0] = kd; out[1] = sup; out[2] = kd_scale * kd + sup_scale * sup;
+    }
+}
+
 }  // namespace
 
 extern "C" size_t kd_loss_workspace(int32_t N, int32_t C, int64_t P)
@@ -1422,6 +1818,145 @@ extern "C" int kd_ensemble_kldiv(const kd_view3 *s, const kd_view3 *t, int32_t N
     const float gscale = grad_scale / ((float)N * (float)P);
     const double scale = 1.0 / ((double)N * (double)P);
     return pair_impl("kd_ensemble_kldiv", PAIR_EKL, s, t, 1.f, N, C, P, loss, grad, gscale, scale, workspace, stream);
+}
+
+// ---- kd_kldiv_multi / kd_softmax_mean ---------------------------------------------------------------------------------------
+namespace {
+// 4-element vector accesses on a class-contiguous row: whole groups of 4 and every row start 4-element aligned
+inline bool row_vec_ok(const void *p, int dt, long long sN, long long sP, int N, int C, long long P)
+{
+    return (C & 3) == 0 && ((uintptr_t)p & (dt == KD_BF16 ? 7u : 15u)) == 0 && (P == 1 || (sP & 3) == 0) && (N == 1 || (sN & 3) == 0);
+}
+inline bool nhwc_dense(long long sN, long long sC, long long sP, int N, int C, long long P)
+{
+    return sC == 1 && sP == C && (sN == (long long)C * P || N == 1);
+}
+// the targets by value, weights divided by their sum; false (error set) on a bad argument
+bool mt_pack(const char *who, const kd_multi_targets *ts, MT &mt)
+{
+    if (!ts || ts->n < 1 || ts->n > KD_MULTI_MAX) {
+        kd_set_error("%s: 1 to %d operands, got %d", who, KD_MULTI_MAX, ts ? (int)ts->n : 0);
+        return false;
+    }
+    double W = 0.0;
+    for (int k = 0; k < ts->n; ++k) {
+        if (!ts->t[k].ptr || !ok_dt(ts->t[k].dtype) || !(ts->w[k] >= 0.f)) {
+            kd_set_error("%s: operand %d: null pointer, bad dtype or negative weight", who, k);
+            return false;
+        }
+        W += (double)ts->w[k];
+    }
+    if (!(W > 0.0) || W > 3.0e38) {
+        kd_set_error("%s: the weights must have a positive finite sum", who);
+        return false;
+    }
+    mt.n = ts->n;
+    for (int k = 0; k < KD_MULTI_MAX; ++k) {
+        mt.t[k] = k < ts->n ? v3(&ts->t[k]) : V3{nullptr, 0, 0, 0, 0};
+        mt.w[k] = k < ts->n ? (float)((double)ts->w[k] / W) : 0.f;
+    }
+    return true;
+}
+enum { MT_WAVE = 0, MT_NHWC = 1, MT_ANY = 2 };
+}  // namespace
+
+extern "C" int kd_kldiv_multi(const kd_view3 *s, const kd_multi_targets *targets, float temperature, const int64_t *labels,
+                              int32_t ignore_index, float kd_scale, float sup_scale, int32_t N, int32_t C, int64_t P, float *losses,
+                              const kd_mview3 *grad, void *workspace, size_t workspace_bytes, kd_stream_t stream)
+{
+    KD_REQUIRE(s && s->ptr && losses && workspace, KD_ERR_INVALID, "kd_kldiv_multi: null argument");
+    KD_REQUIRE(ok_dt(s->dtype) && (!grad || (grad->ptr && ok_dt(grad->dtype))), KD_ERR_INVALID, "kd_kldiv_multi: bad dtype");
+    KD_REQUIRE(N > 0 && C > 0 && P > 0, KD_ERR_INVALID, "kd_kldiv_multi: bad shape");
+    KD_REQUIRE(temperature > 0.f, KD_ERR_INVALID, "kd_kldiv_multi: temperature must be positive");
+    KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, P), KD_ERR_WORKSPACE, "kd_kldiv_multi: workspace too small");
+    KD_REQUIRE(((uintptr_t)workspace & 7) == 0, KD_ERR_INVALID, "kd_kldiv_multi: workspace must be 8-B aligned");
+    MT mt;
+    if (!mt_pack("kd_kldiv_multi", targets, mt)) return KD_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    double *pkd = (double *)workspace, *pce = pkd + MT_MAX_BLOCKS, *count = pce + MT_MAX_BLOCKS;
+    const long long rows = (long long)N * P;
+    const V3 sv = v3(s);
+    const M3 gv = m3(grad);
+    bool unit = s->sC == 1 && (!grad || grad->sC == 1);
+    bool dense = nhwc_dense(s->sN, s->sC, s->sP, N, C, P) && (!grad || nhwc_dense(grad->sN, grad->sC, grad->sP, N, C, P));
+    bool vec = row_vec_ok(s->ptr, s->dtype, s->sN, s->sP, N, C, P) &&
+               (!grad || row_vec_ok(grad->ptr, grad->dtype, grad->sN, grad->sP, N, C, P));
+    for (int k = 0; k < mt.n; ++k) {
+        const V3 &t = mt.t[k];
+        unit = unit && t.sC == 1;
+        dense = dense && nhwc_dense(t.sN, t.sC, t.sP, N, C, P);
+        vec = vec && row_vec_ok(t.p, t.dt, t.sN, t.sP, N, C, P);
+    }
+    // few classes and many pixels: a wave per pixel would idle most of its lanes
+    const bool narrow = C < 22 && rows >= 16384;
+    const int path = narrow && dense ? MT_NHWC : (unit && C <= 1024 && !narrow ? MT_WAVE : MT_ANY);
+    const float invT = 1.f / temperature;
+    const float gk = kd_scale * temperature / ((float)N * (float)P);
+    int ncount = 0;
+    if (labels) {
+        ncount = (int)std::min<long long>((rows + 255) / 256, MT_MAX_BLOCKS);
+        hipLaunchKernelGGL(ce2d_count_kernel, dim3(ncount), dim3(256), 0, st, labels, ignore_index, C, rows, count, (const float *)nullptr);
+        KD_CHECK_LAUNCH("kd_kldiv_multi(count)");
+    }
+    const double *cnt = labels ? count : nullptr;
+    int nb;
+    if (path == MT_WAVE) {
+        nb = (int)std::min<long long>((rows + 3) / 4, MT_MAX_BLOCKS);
+#define KD_MTW(NCH, VEC) hipLaunchKernelGGL((mt_wave_kernel<NCH, VEC, false>), dim3(nb), dim3(256), 0, st, sv, mt, gv, labels, ignore_index, \
+                                            invT, gk, sup_scale, C, (long long)P, rows, cnt, ncount, pkd, pce)
+        if (C <= 256) { if (vec) KD_MTW(1, true); else KD_MTW(1, false); }
+        else { if (vec) KD_MTW(4, true); else KD_MTW(4, false); }
+#undef KD_MTW
+    } else if (path == MT_NHWC) {
+        nb = (int)std::min<long long>((rows + 255) / 256, MT_MAX_BLOCKS);
+        hipLaunchKernelGGL(kldm_nhwc_kernel, dim3(nb), dim3(256), (size_t)3 * 256 * C * sizeof(float), st, sv, mt, gv, labels, ignore_index,
+                           invT, gk, sup_scale, C, rows, cnt, ncount, pkd, pce);
+    } else {
+        nb = (int)std::min<long long>((rows + 255) / 256, MT_MAX_BLOCKS);
+        hipLaunchKernelGGL(kldm_kernel<false>, dim3(nb), dim3(256), 0, st, sv, mt, gv, labels, ignore_index, invT, gk, sup_scale, C,
+                           (long long)P, rows, cnt, ncount, pkd, pce);
+    }
+    KD_CHECK_LAUNCH("kd_kldiv_multi");
+    // per target 'mean' over N*C*P elements, then * T^2 * C  ==  T^2 / (N*P) * sum; the weights already sum to 1
+    const double kd_mul = (double)temperature * temperature / ((double)N * (double)P);
+    hipLaunchKernelGGL(mt_finish_kernel, dim3(1), dim3(256), 0, st, (const double *)pkd, (const double *)pce, nb, cnt, ncount, kd_mul,
+                       kd_scale, sup_scale, losses);
+    KD_CHECK_LAUNCH("kd_kldiv_multi(finish)");
+    return KD_OK;
+}
+
+extern "C" int kd_softmax_mean(const kd_multi_targets *logits, float temperature, int32_t N, int32_t C, int64_t P, const kd_mview3 *out,
+                               kd_stream_t stream)
+{
+    KD_REQUIRE(out && out->ptr && out->dtype == KD_F32, KD_ERR_INVALID, "kd_softmax_mean: out must be an fp32 view");
+    KD_REQUIRE(N > 0 && C > 0 && P > 0, KD_ERR_INVALID, "kd_softmax_mean: bad shape");
+    KD_REQUIRE(temperature > 0.f, KD_ERR_INVALID, "kd_softmax_mean: temperature must be positive");
+    MT mt;
+    if (!mt_pack("kd_softmax_mean", logits, mt)) return KD_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const long long rows = (long long)N * P;
+    const M3 gv = m3(out);
+    bool unit = out->sC == 1, vec = row_vec_ok(out->ptr, out->dtype, out->sN, out->sP, N, C, P);
+    for (int k = 0; k < mt.n; ++k) {
+        unit = unit && mt.t[k].sC == 1;
+        vec = vec && row_vec_ok(mt.t[k].p, mt.t[k].dt, mt.t[k].sN, mt.t[k].sP, N, C, P);
+    }
+    const V3 none{nullptr, 0, 0, 0, 0};
+    const float invT = 1.f / temperature;
+    if (unit && C <= 1024 && !(C < 22 && rows >= 16384)) {
+        const int nb = (int)std::min<long long>((rows + 3) / 4, MT_MAX_BLOCKS);
+#define KD_SMW(NCH, VEC) hipLaunchKernelGGL((mt_wave_kernel<NCH, VEC, true>), dim3(nb), dim3(256), 0, st, none, mt, gv, (const int64_t *)nullptr, 0, \
+                                            invT, 0.f, 0.f, C, (long long)P, rows, (const double *)nullptr, 0, (double *)nullptr, (double *)nullptr)
+        if (C <= 256) { if (vec) KD_SMW(1, true); else KD_SMW(1, false); }
+        else { if (vec) KD_SMW(4, true); else KD_SMW(4, false); }
+#undef KD_SMW
+    } else {
+        const int nb = (int)std::min<long long>((rows + 255) / 256, MT_MAX_BLOCKS);
+        hipLaunchKernelGGL(kldm_kernel<true>, dim3(nb), dim3(256), 0, st, none, mt, gv, (const int64_t *)nullptr, 0, invT, 0.f, 0.f, C,
+                           (long long)P, rows, (const double *)nullptr, 0, (double *)nullptr, (double *)nullptr);
+    }
+    KD_CHECK_LAUNCH("kd_softmax_mean");
+    return KD_OK;
 }
 
 extern "C" int kd_jsdiv_up(const float *s_lo, const float *t_lo, float temperature, int32_t N, int32_t h, int32_t w, int32_t C, int32_t H,

@@ -11,7 +11,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (KD_BF16, KD_F32, KD_PACK_DGRAD, KD_PACK_FWD, ConvDesc, ConvEpilogue, DConvDesc, DwDesc, DwEpilogue, View3,
+from ._lib import (KD_BF16, KD_F32, KD_PACK_DGRAD, KD_PACK_FWD, ConvDesc, ConvEpilogue, DConvDesc, DwDesc, DwEpilogue, MultiTargets, View3,
                    check)
 
 
@@ -1469,6 +1469,69 @@ def ensemble_kldiv(s, t, want_grad=True, grad_scale=1.0):
                                        C.c_float(grad_scale), _ptr(ws), need, stream_ptr()), "kd_ensemble_kldiv")
     _prof_stop(e0, "loss", _nbytes(s, t, grad), f"ensemble kldiv {N}x{Cc}x{P}", "pair_kernel<ekl>")
     return loss, grad
+
+
+def _multi_views(ts, weights, dims, what):
+    """kd_multi_targets of `ts` (each of logical shape `dims`) with one weight each.  The count is passed on as it is -- the
+    library refuses 0 or more than KD_MULTI_MAX operands with an error code."""
+    ts, weights = list(ts), [float(w) for w in weights]
+    if len(weights) != len(ts):
+        raise ValueError(f"{what}: {len(ts)} operands but {len(weights)} weights")
+    mt = MultiTargets()
+    mt.n = len(ts)
+    for k, t in enumerate(ts[:_lib.KD_MULTI_MAX]):
+        v, d = view3(t)
+        if d != dims:
+            raise ValueError(f"{what}: operand {k} is {d}, expected {dims}")
+        mt.t[k] = v
+        mt.w[k] = weights[k]
+    return mt
+
+
+def kldiv_multi(s, targets, weights, temperature=1.0, labels=None, ignore_index=255, kd_scale=1.0, sup_scale=1.0, want_grad=True):
+    """The ensemble criterion in one pass (kd_kldiv_multi): kd = sum_k w_k KLDivergenceLoss(T)(s, t_k) / sum_k w_k,
+    sup = CrossEntropyLoss2d(ignore_index)(s, labels) (0 without labels), total = kd_scale * kd + sup_scale * sup and
+    d total / d s.  -> (kd, sup, total, grad): three 0-dim fp32 views of one device buffer, grad like s (None without want_grad)."""
+    targets = list(targets)
+    _need_cuda(s, labels, *targets)
+    vs, dims = view3(s)
+    N, Cc, P = dims
+    mt = _multi_views(targets, weights, dims, "kldiv_multi")
+    tgt = None
+    if labels is not None:
+        tgt = labels.contiguous()
+        if tgt.dtype != torch.int64 or tgt.numel() != N * P:
+            raise ValueError("kldiv_multi: labels must be int64 with one label per pixel")
+    losses = torch.empty(3, dtype=torch.float32, device=s.device)
+    grad = torch.empty_like(s) if want_grad else None
+    vg = view3(grad)[0] if want_grad else None
+    ws, need = loss_workspace(N, Cc, P, s.device)
+    e0 = _prof_start()
+    check(_lib.lib().kd_kldiv_multi(C.byref(vs), C.byref(mt), C.c_float(temperature), _ptr(tgt), int(ignore_index), C.c_float(kd_scale),
+                                    C.c_float(sup_scale), N, Cc, P, _ptr(losses), C.byref(vg) if vg is not None else None, _ptr(ws), need,
+                                    stream_ptr()), "kd_kldiv_multi")
+    _prof_stop(e0, "loss", _nbytes(s, grad, tgt, *targets), f"kldiv multi x{len(targets)} {N}x{Cc}x{P}", "kd_kldiv_multi")
+    return losses[0], losses[1], losses[2], grad
+
+
+def softmax_mean(logits, weights, temperature=1.0):
+    """sum_k w_k softmax(x_k / T, dim=1) / sum_k w_k as fp32 in the layout of the first operand (kd_softmax_mean): the reference's
+    ensemble_predict, and the probabilities EnsembleKLDivergenceLoss takes as its target."""
+    logits = list(logits)
+    _need_cuda(*logits)
+    if not logits:
+        mt = MultiTargets()
+        check(_lib.lib().kd_softmax_mean(C.byref(mt), C.c_float(temperature), 1, 1, 1, None, stream_ptr()), "kd_softmax_mean")
+    dims = view3(logits[0])[1]
+    N, Cc, P = dims
+    mt = _multi_views(logits, weights, dims, "softmax_mean")
+    first = logits[0].materialize() if hasattr(logits[0], "materialize") else logits[0]
+    out = torch.empty_like(first, dtype=torch.float32)
+    vo, _ = view3(out)
+    e0 = _prof_start()
+    check(_lib.lib().kd_softmax_mean(C.byref(mt), C.c_float(temperature), N, Cc, P, C.byref(vo), stream_ptr()), "kd_softmax_mean")
+    _prof_stop(e0, "loss", _nbytes(out, *logits), f"softmax mean x{len(logits)} {N}x{Cc}x{P}", "kd_softmax_mean")
+    return out
 
 
 _FOCAL_RED = {"none": 0, "mean": 1, "sum": 2}
