@@ -517,6 +517,19 @@ int kd_ce2d_up(const float *x_lo, const int64_t *target, int32_t ignore_index, i
 int kd_kldiv_up(const float *s_lo, const float *t_lo, float temperature, int32_t N, int32_t h, int32_t w, int32_t C, int32_t H,
                 int32_t W, int32_t align_corners, float *loss, void *workspace, size_t workspace_bytes, kd_stream_t stream);
 
+/* Everything the layer-compressibility analysis logs per step (trainer/analysis_trainer.py:55-81), in ONE pass over the student's
+ * and the teacher's low-resolution logits (dense fp32 (N,h,w,C), interpolated in registers as kd_ce2d_up does):
+ *   out[0] = kd_ce2d(up(s), target, ignore_index)      out[1] = kd_ce2d(up(t), target, ignore_index)
+ *   out[2] = mean over N*C*H*W of (up(s) - up(t))^2    (losses/MSELoss.py with reduction 'mean', num_classes 1)
+ *   conf_s / conf_t: int64 (C,C) [label][prediction] of argmax_c up(s) / up(t) (first maximum), pixels whose label is outside
+ *   [0, C) skipped -- kd_confusion of each tensor; accumulate != 0 adds to the matrices, else they are overwritten.
+ * Forward only.  The float outputs are reduced in a fixed order (bit-reproducible), the counts are integer atomics (exact).
+ * KD_ERR_UNSUPPORTED for C > 48 and for kd_ce2d_up's resampling-ratio limit: the caller then composes kd_ce2d_up / kd_hint_mse /
+ * kd_confusion.  workspace as kd_loss_workspace(N, C, H*W), 8-B aligned. */
+int kd_logit_metrics_up(const float *s_lo, const float *t_lo, const int64_t *target, int32_t ignore_index, int32_t N, int32_t h,
+                        int32_t w, int32_t C, int32_t H, int32_t W, int32_t align_corners, float *out, int64_t *conf_s,
+                        int64_t *conf_t, int32_t accumulate, void *workspace, size_t workspace_bytes, kd_stream_t stream);
+
 /* gradient of kd_ce2d w.r.t. x (needed when the supervised loss is back-propagated: trainer/taylor_prune_trainer.py:204-206,
  * or any loss = supervised + kd + hint mix): grad[n,c,p] = grad_scale * (softmax_c(x[n,:,p]) - [c == target[n,p]]) / #valid,
  * zero for ignored pixels. */

@@ -23,6 +23,7 @@ def build_tuning():
 
 KD_F32, KD_BF16 = 0, 1
 KD_PACK_FWD, KD_PACK_DGRAD = 0, 1
+KD_ERR_UNSUPPORTED = -2
 
 c_int, c_i64, c_f, c_vp, c_sz = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
 
@@ -153,6 +154,8 @@ _SIGS = {
     "kd_ce2d": (c_int, [_P(View3), c_vp, c_int, c_int, c_int, c_i64, c_vp, c_vp, c_sz, c_vp]),
     "kd_ce2d_up": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_sz, c_vp]),
     "kd_kldiv_up": (c_int, [c_vp, c_vp, c_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_sz, c_vp]),
+    "kd_logit_metrics_up": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int,
+                                    c_vp, c_sz, c_vp]),
     "kd_ce2d_grad": (c_int, [_P(View3), c_vp, c_int, c_int, c_int, c_i64, _P(View3), c_f, c_vp, c_sz, c_vp]),
     "kd_ce2d_weighted": (c_int, [_P(View3), c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, c_vp, c_vp, c_sz, c_vp]),
     "kd_ce2d_weighted_grad": (c_int, [_P(View3), c_vp, c_vp, c_int, c_int, c_int, c_int, c_i64, _P(View3), c_f, c_vp, c_sz, c_vp]),

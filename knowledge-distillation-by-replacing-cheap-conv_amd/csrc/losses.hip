@@ -408,6 +408,123 @@ __global__ __launch_bounds__(256) void kldiv_up_kernel(const float *__restrict__
     block_partial(acc, partial);
 }
 
+// ---- the analysis step's logged metrics from both low-resolution logit tensors (trainer/analysis_trainer.py:55-81) ---------------------
+// One pass: CE(student), CE(teacher), sum (s - t)^2 and both confusion matrices (argmax = first maximum, as confusion_nhwc_kernel).
+// Partials: [ce_s | ce_t | count | sq] x MET_MAX_BLOCKS doubles inside kd_loss_workspace's 2 * MAX_BLOCKS; the histograms are LDS
+// integer atomics flushed once per block (exact in any order).
+constexpr int MET_MAX_BLOCKS = MAX_BLOCKS / 2;
+
+template <int CT>
+__global__ __launch_bounds__(256) void logit_metrics_up_kernel(const float *__restrict__ s, const float *__restrict__ t,
+                                                               const int64_t *__restrict__ target, int ignore_index, UpGeom g,
+                                                               long long nchunks, int cpr, double *partial,
+                                                               unsigned long long *conf_s, unsigned long long *conf_t)
+{
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float *ss = sm, *st = sm + 2 * UP_NW * g.C;
+    unsigned int *hs = (unsigned int *)(sm + 4 * UP_NW * g.C), *ht = hs + g.C * g.C;
+    for (int i = threadIdx.x; i < 2 * g.C * g.C; i += 256) hs[i] = 0u;
+    double ces = 0.0, cet = 0.0, cnt = 0.0, sq = 0.0;
+    for (long long chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+        const UpChunk k = up_chunk(g, chunk, cpr);
+        up_stage(ss, s, g, k.n, k.h0, k.h1, k.wlo, k.nw);
+        up_stage(st, t, g, k.n, k.h0, k.h1, k.wlo, k.nw);
+        __syncthreads();
+        const int wo = k.wo0 + threadIdx.x;
+        if (wo < g.W) {
+            const int64_t y = target[((size_t)k.n * g.H + k.ho) * g.W + wo];
+            const bool lab = y >= 0 && y < g.C;                    // counted by the confusion matrices (kd_confusion)
+            const bool valid = lab && y != ignore_index;           // counted by the cross entropies (kd_ce2d)
+            const int yc = lab ? (int)y : 0;
+            const float fw = fmaxf(wo * g.sw + g.ow, 0.f);
+            int w0 = (int)fw; w0 = w0 > g.w - 1 ? g.w - 1 : w0;
+            const int w1 = w0 + 1 < g.w ? w0 + 1 : g.w - 1;
+            const float aw = fw - w0;
+            const int o0 = (w0 - k.wlo) * g.C, o1 = (w1 - k.wlo) * g.C, nr = k.nw * g.C;
+            float ms, mt, zs = 0.f, zt = 0.f, vs = 0.f, vt = 0.f, d2 = 0.f;
+            int as = 0, at = 0;
+            if constexpr (CT > 0) {
+                float a[CT], b[CT];
+#pragma unroll
+                for (int c = 0; c < CT; ++c) { a[c] = up_val(ss, nr, o0, o1, c, aw, k.ah); b[c] = up_val(st, nr, o0, o1, c, aw, k.ah); }
+                ms = a[0]; mt = b[0];
+#pragma unroll
+                for (int c = 0; c < CT; ++c) {
+                    if (c > 0 && arg_better(a[c], ms)) { ms = a[c]; as = c; }
+                    if (c > 0 && arg_better(b[c], mt)) { mt = b[c]; at = c; }
+                    const float d = a[c] - b[c];
+                    d2 += d * d;
+                }
+#pragma unroll
+                for (int c = 0; c < CT; ++c) {
+                    zs += __expf(a[c] - ms); zt += __expf(b[c] - mt);
+                    vs = c == yc ? a[c] : vs; vt = c == yc ? b[c] : vt;
+                }
+            } else {
+                ms = up_val(ss, nr, o0, o1, 0, aw, k.ah); mt = up_val(st, nr, o0, o1, 0, aw, k.ah);
+                for (int c = 0; c < g.C; ++c) {
+                    const float a = up_val(ss, nr, o0, o1, c, aw, k.ah), b = up_val(st, nr, o0, o1, c, aw, k.ah);
+                    if (c > 0 && arg_better(a, ms)) { ms = a; as = c; }
+                    if (c > 0 && arg_better(b, mt)) { mt = b; at = c; }
+                    const float d = a - b;
+                    d2 += d * d;
+                }
+                for (int c = 0; c < g.C; ++c) {
+                    zs += __expf(up_val(ss, nr, o0, o1, c, aw, k.ah) - ms);
+                    zt += __expf(up_val(st, nr, o0, o1, c, aw, k.ah) - mt);
+                }
+                vs = up_val(ss, nr, o0, o1, yc, aw, k.ah); vt = up_val(st, nr, o0, o1, yc, aw, k.ah);
+            }
+            sq += (double)d2;
+            if (valid) {
+                ces += (double)(-(vs - ms - __logf(zs)));
+                cet += (double)(-(vt - mt - __logf(zt)));
+                cnt += 1.0;
+            }
+            if (lab) {
+                atomicAdd(&hs[yc * g.C + as], 1u);
+                atomicAdd(&ht[yc * g.C + at], 1u);
+            }
+        }
+        __syncthreads();
+    }
+    __shared__ double wsum[4][4];
+    ces = wave_sum_d(ces); cet = wave_sum_d(cet); cnt = wave_sum_d(cnt); sq = wave_sum_d(sq);
+    if ((threadIdx.x & 63) == 0) {
+        double *r = wsum[threadIdx.x >> 6];
+        r[0] = ces; r[1] = cet; r[2] = cnt; r[3] = sq;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4)
+        partial[threadIdx.x * MET_MAX_BLOCKS + blockIdx.x] = wsum[0][threadIdx.x] + wsum[1][threadIdx.x] + wsum[2][threadIdx.x] + wsum[3][threadIdx.x];
+    for (int i = threadIdx.x; i < g.C * g.C; i += 256) {
+        if (hs[i]) atomicAdd(&conf_s[i], (unsigned long long)hs[i]);
+        if (ht[i]) atomicAdd(&conf_t[i], (unsigned long long)ht[i]);
+    }
+}
+
+// out[0] = CE(student), out[1] = CE(teacher) (0 when no pixel is valid, like finish_kernel), out[2] = sum sq / numel
+__global__ __launch_bounds__(256) void logit_metrics_finish_kernel(const double *partial, int n, double inv_numel, float *out)
+{
+    __shared__ double sh[4][256];
+    double v[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = threadIdx.x; i < n; i += 256)
+        for (int q = 0; q < 4; ++q) v[q] += partial[q * MET_MAX_BLOCKS + i];
+    for (int q = 0; q < 4; ++q) sh[q][threadIdx.x] = v[q];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o)
+            for (int q = 0; q < 4; ++q) sh[q][threadIdx.x] += sh[q][threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double c = sh[2][0];
+        out[0] = (float)(c > 0.0 ? sh[0][0] / c : 0.0);
+        out[1] = (float)(c > 0.0 ? sh[1][0] / c : 0.0);
+        out[2] = (float)(sh[3][0] * inv_numel);
+    }
+}
+
 // ---- hint MSE -----------------------------------------------------------------------------
 // contiguous fast path: s, t, g share one dense layout -> 8 elements per thread per step
 template <typename T>
@@ -1755,6 +1872,50 @@ extern "C" int kd_kldiv_up(const float *s_lo, const float *t_lo, float temperatu
     const double scale = (double)temperature * temperature / ((double)N * (double)H * (double)W);
     hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, nb, scale, (const double *)nullptr, loss);
     KD_CHECK_LAUNCH("kd_kldiv_up(finish)");
+    return KD_OK;
+}
+
+extern "C" int kd_logit_metrics_up(const float *s_lo, const float *t_lo, const int64_t *target, int32_t ignore_index, int32_t N, int32_t h,
+                                   int32_t w, int32_t C, int32_t H, int32_t W, int32_t align_corners, float *out, int64_t *conf_s,
+                                   int64_t *conf_t, int32_t accumulate, void *workspace, size_t workspace_bytes, kd_stream_t stream)
+{
+    KD_REQUIRE(s_lo && t_lo && target && out && conf_s && conf_t && workspace, KD_ERR_INVALID, "kd_logit_metrics_up: null argument");
+    KD_REQUIRE(N > 0 && h > 0 && w > 0 && C > 0 && H > 0 && W > 0, KD_ERR_INVALID, "kd_logit_metrics_up: bad argument");
+    KD_REQUIRE(conf_s != conf_t && (((uintptr_t)conf_s | (uintptr_t)conf_t | (uintptr_t)workspace) & 7) == 0, KD_ERR_INVALID,
+               "kd_logit_metrics_up: conf_s / conf_t must be two 8-B aligned matrices, the workspace 8-B aligned");
+    KD_REQUIRE(C <= 48, KD_ERR_UNSUPPORTED, "kd_logit_metrics_up: C <= 48 (got %d): materialise the logits", C);
+    KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, (int64_t)H * W), KD_ERR_WORKSPACE, "kd_logit_metrics_up: workspace too small");
+    UpGeom g;
+    KD_REQUIRE(up_geom(g, N, h, w, C, H, W, align_corners), KD_ERR_UNSUPPORTED,
+               "kd_logit_metrics_up: a 256-pixel chunk spans more than %d source columns (scale %dx%d -> %dx%d): materialise the logits", UP_NW, h, w, H, W);
+    hipStream_t st = (hipStream_t)stream;
+    if (!accumulate) {
+        if (hipMemsetAsync(conf_s, 0, (size_t)C * C * sizeof(int64_t), st) != hipSuccess ||
+            hipMemsetAsync(conf_t, 0, (size_t)C * C * sizeof(int64_t), st) != hipSuccess) {
+            kd_set_error("kd_logit_metrics_up: hipMemsetAsync failed");
+            return KD_ERR_HIP;
+        }
+    }
+    double *partial = (double *)workspace;
+    const int cpr = (W + 255) / 256;
+    const long long nchunks = (long long)N * H * cpr;
+    const int nb = (int)(nchunks < MET_MAX_BLOCKS ? nchunks : MET_MAX_BLOCKS);
+    // two staged patches + two C x C histograms: 50.3 KiB at 19 classes, 138 KiB at 48 (of the CU's 160 KiB)
+    const size_t lds = (size_t)4 * UP_NW * C * sizeof(float) + (size_t)2 * C * C * sizeof(unsigned int);
+    auto fn = C == 19 ? logit_metrics_up_kernel<19> : logit_metrics_up_kernel<0>;
+    if (lds > 65536) {
+        if (hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+            (void)hipGetLastError();
+            kd_set_error("kd_logit_metrics_up: cannot reserve %zu B of LDS", lds);
+            return KD_ERR_UNSUPPORTED;
+        }
+    }
+    hipLaunchKernelGGL(fn, dim3(nb), dim3(256), lds, st, s_lo, t_lo, target, ignore_index, g, nchunks, cpr, partial,
+                       (unsigned long long *)conf_s, (unsigned long long *)conf_t);
+    KD_CHECK_LAUNCH("kd_logit_metrics_up");
+    hipLaunchKernelGGL(logit_metrics_finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, nb,
+                       1.0 / ((double)N * (double)C * (double)H * (double)W), out);
+    KD_CHECK_LAUNCH("kd_logit_metrics_up(finish)");
     return KD_OK;
 }
 

@@ -39,7 +39,7 @@ from torch import nn
 from . import ops
 from ._lib import KD_PACK_DGRAD, KD_PACK_FWD
 from .lazy import LazyLogits
-from .models.students.transform_blocks import DepthwiseSeparableBlock, GateLayer
+from .models.students.transform_blocks import DepthwiseSeparableBlock, GateLayer, RandomMask2d
 from .models.wider_resnet import IdentityResidualBlock
 
 _SMALL_CONV = os.environ.get("KDCC_SMALL_CONV", "1") != "0"  # A/B: 0 = GSCNN res2 / res3 zero-padded to 64 channels on the GEMM kernels
@@ -74,6 +74,13 @@ def _gate_split(mod):
     return mod, None
 
 
+def _is_masked(mod):
+    """Sequential(conv, RandomMask2d, 1x1 conv), as AnalysisStudent.replace builds it (models/students/analysis_student.py:33-39
+    of the reference)."""
+    return (isinstance(mod, nn.Sequential) and len(mod) == 3 and isinstance(mod[0], nn.Conv2d) and isinstance(mod[1], RandomMask2d)
+            and isinstance(mod[2], nn.Conv2d))
+
+
 def _act_gate(bn_seq):
     """The gate behind the ReLU of a bnrelu Sequential(BatchNorm2d, ReLU) -- i.e. Sequential(BN, Sequential(ReLU, GateLayer))."""
     if isinstance(bn_seq, nn.Sequential) and len(bn_seq) > 1:
@@ -82,12 +89,17 @@ def _act_gate(bn_seq):
 
 
 class _Site:
-    """One convolution site of a residual block / ASPP branch: dense nn.Conv2d or a cheap-conv block."""
+    """One convolution site of a residual block / ASPP branch: dense nn.Conv2d, a cheap-conv block, or the analysis probe's
+    masked site Sequential(frozen conv, RandomMask2d, trainable 1x1) -- whose frozen conv computes the kept filters only."""
 
     def __init__(self, name, mod):
         mod, self.gate = _gate_split(mod)     # a Taylor gate behind the conv: folded into its packed weights
         self.name, self.mod = name, mod
         self.cheap = isinstance(mod, DepthwiseSeparableBlock)
+        self.masked = _is_masked(mod)
+        if self.masked:
+            self._init_masked(name, mod)
+            return
         if self.cheap and self.gate is not None:
             raise EngineError(f"{name}: a gate behind a cheap-conv block is not supported (gates rank the TEACHER's filters)")
         if not self.cheap and not isinstance(mod, nn.Conv2d):
@@ -105,6 +117,19 @@ class _Site:
                 raise EngineError(f"{name}: only bias-free dense convs are supported")
             self.k, self.pad, self.dil, self.stride = conv.kernel_size[0], conv.padding[0], conv.dilation[0], conv.stride[0]
         self.trainable = _is_trainable(mod) or (self.gate is not None and self.gate.weight.requires_grad)
+
+    def _init_masked(self, name, mod):
+        conv, mask, pw = mod[0], mod[1], mod[2]
+        if self.gate is not None:
+            raise EngineError(f"{name}: a gate behind a masked site is not supported")
+        if conv.bias is not None or conv.groups != 1 or _is_trainable(conv):
+            raise EngineError(f"{name}: the conv in front of a RandomMask2d must be a frozen, bias-free dense conv")
+        if pw.bias is not None or pw.kernel_size != (1, 1) or pw.stride != (1, 1) or pw.padding != (0, 0) or pw.groups != 1 or \
+                pw.in_channels != conv.out_channels or mask.in_channels != conv.out_channels:
+            raise EngineError(f"{name}: the conv behind a RandomMask2d must be a bias-free 1x1 over the masked channels")
+        self.cin, self.cout = conv.in_channels, pw.out_channels
+        self.k, self.pad, self.dil, self.stride = conv.kernel_size[0], conv.padding[0], conv.dilation[0], conv.stride[0]
+        self.trainable = pw.weight.requires_grad
 
 
 class StudentEngine:
@@ -240,10 +265,72 @@ class StudentEngine:
         for c in (conv_a, conv_b):
             if not isinstance(c, nn.Conv2d) or c.kernel_size != (1, 1) or c.stride != (1, 1) or c.padding != (0, 0) or c.bias is not None:
                 return False
-        if site is not None and (site.cheap or site.gate is not None or site.name in self._probes):
+        if site is not None and (site.cheap or site.masked or site.gate is not None or site.name in self._probes):
             return False
         N, H, W = a_shape[:3]
         return ops.conv1x1_dual_ok_dims(N, H, W, cin_a, cin_b, cout, self.dtype, operands)
+
+    # ---- masked site (analysis probe): the frozen conv's kept filters, the 1x1's kept columns -------------------------
+    def _keep(self, site):
+        """(kept channel indices on the device, K' of them, Kp = K' rounded up to the conv kernels' input-channel granule)."""
+        mask, dev = site.mod[1], site.mod[2].weight.device
+        keep = getattr(mask, "_keep_dev", None)          # the device copy lives on the mask module and goes with it
+        if keep is None or keep.device != dev:
+            keep = mask._keep_dev = mask.keep.to(dev)
+        kk = int(keep.numel())
+        gran = 64 if self.dtype == torch.bfloat16 else 32
+        return keep, kk, max(gran, ((kk + gran - 1) // gran) * gran)
+
+    def _w_masked_conv(self, site):
+        """The frozen conv packed from the `keep` rows of its weight, rows K'..Kp zero (packed once per replace())."""
+        conv = site.mod[0]
+        keep, kk, kp = self._keep(site)
+
+        def make():
+            w = conv.weight.detach().float()
+            wp = torch.zeros((kp,) + tuple(w.shape[1:]), dtype=torch.float32, device=w.device)
+            wp[:kk] = w.index_select(0, keep)
+            return ops.pack_conv_weight(wp, self.dtype, KD_PACK_FWD)
+        return self._packed(conv.weight, ("masked_fwd", self.dtype, kp, id(site.mod[1])), make)
+
+    def _w_masked_pw(self, site):
+        """The trainable 1x1 packed from the `keep` columns of its weight, input channels padded to Kp (per weight version)."""
+        pw = site.mod[2]
+        keep, kk, kp = self._keep(site)
+        return self._packed(pw.weight, ("masked_pw", self.dtype, kp, id(site.mod[1])),
+                            lambda: ops.pack_conv_weight(pw.weight.detach().float().index_select(1, keep).contiguous(), self.dtype,
+                                                         KD_PACK_FWD, kp))
+
+    def _masked_fwd(self, site, a, **kw):
+        """frozen conv -> compact (N,Ho,Wo,Kp) tensor of the kept channels -> 1x1 with the site's epilogue `kw`.  The dropped
+        channels are never computed or stored.  Returns the compact tensor (the 1x1's weight gradient reads it)."""
+        _, _, kp = self._keep(site)
+        ho = ops.conv_out_size(a.shape[1], site.k, site.stride, site.pad, site.dil)
+        wo = ops.conv_out_size(a.shape[2], site.k, site.stride, site.pad, site.dil)
+        mid = self._new(a.shape[0], ho, wo, kp)
+        ops.conv2d(a, self._w_masked_conv(site), site.stride, site.pad, site.dil, out_raw=mid)
+        ops.conv2d(mid, self._w_masked_pw(site), **kw)
+        return mid
+
+    def _masked_bwd(self, site, mid, g, grads, need_in):
+        """Weight gradient of a masked site's 1x1: pw_wgrad against the compact tensor, scattered into the full (C,C,1,1) gradient
+        with exact zeros in the dropped columns (what autograd gives behind a zero mask)."""
+        if need_in:
+            raise EngineError(f"{site.name}: a masked site (frozen conv -> RandomMask2d -> 1x1) was asked for its input gradient; "
+                              "the layer-compressibility analysis trains the 1x1 alone, nothing upstream of it, and no input-"
+                              "gradient path through the compacted conv exists")
+        pw = site.mod[2]
+        if not pw.weight.requires_grad:
+            return None
+        keep, kk, kp = self._keep(site)
+        gc_ = torch.empty((site.cout, kp, 1, 1), dtype=torch.float32, device=mid.device)
+        ops.pw_wgrad(mid, g if g.is_contiguous() else g.contiguous(), gc_)
+        gw = self._grad_like(pw.weight)
+        gw.zero_()
+        gw.view(site.cout, -1).index_copy_(1, keep, gc_.view(site.cout, kp)[:, :kk])
+        grads[pw.weight] = gw
+        self._grad_done(pw.weight)
+        return None
 
     def _w_dw(self, conv, flip):
         return self._packed(conv.weight, ("dw", flip), lambda: ops.pack_dw_weight(conv.weight, flip))
@@ -480,6 +567,8 @@ class StudentEngine:
                     mid = ops.dwconv(x7, self._w_dw(site.mod.separable_conv, False), site.k, site.pad, site.dil)
                 ops.conv2d(mid, self._w_fwd(site.mod.pointwise_conv), out_raw=raw, out_act=out, act_scale=sc, act_shift=sh,
                            act_relu=True)
+            elif site.masked:
+                mid = self._masked_fwd(site, x7, out_raw=raw, out_act=out, act_scale=sc, act_shift=sh, act_relu=True)
             else:
                 ops.conv2d(x7, self._w_fwd(site.mod, gate=site.gate), 1, site.pad, site.dil, out_raw=raw, out_act=out, act_scale=sc,
                            act_shift=sh, act_relu=True)
@@ -897,7 +986,7 @@ class StudentEngine:
                 kw["out_raw"] = raw
                 x_out = raw
                 # (aspp_image_pool(sums=) takes 128-pixel rows that lie within one image: not every crop's trunk output has them)
-                if out_sums is not None and not site.cheap and site.gate is None and (ho * wo) % 128 == 0:
+                if out_sums is not None and not site.cheap and not site.masked and site.gate is None and (ho * wo) % 128 == 0:
                     kw["out_sums"] = out_sums
             else:
                 sc, sh = self._act_fold(bns[f"bn{i + 2}"], _act_gate(bns[f"bn{i + 2}"]))
@@ -907,6 +996,8 @@ class StudentEngine:
             if site.cheap:
                 mid = ops.dwconv(a, self._w_dw(site.mod.separable_conv, False), site.k, site.pad, site.dil)
                 ops.conv2d(mid, self._w_fwd(site.mod.pointwise_conv), **kw)
+            elif site.masked:
+                mid = self._masked_fwd(site, a, **kw)
             elif last and dual:
                 mid = None
                 try:
@@ -961,6 +1052,8 @@ class StudentEngine:
                 add_p(gate.weight)
             if isinstance(mod, DepthwiseSeparableBlock):
                 add_p(mod.pointwise_conv.weight, mod.separable_conv.weight)
+            elif _is_masked(mod):
+                add_p(mod[2].weight)     # (the conv in front of the mask is frozen: _Site refuses anything else)
             else:
                 add_p(mod.weight)
 
@@ -1225,6 +1318,8 @@ class StudentEngine:
         """Weight gradient(s) of one conv site and, when need_in, its input gradient through epilogue `ep`."""
         if site.cheap:
             return self._cheap_bwd(site, a_in, mid, g, grads, need_in, **ep)
+        if site.masked:
+            return self._masked_bwd(site, mid, g, grads, need_in)
         self._conv_wgrad(site.mod, a_in, g, grads, gate=site.gate)
         if not need_in:
             return None

@@ -95,3 +95,36 @@ class GateLayer(nn.Module):
 
     def forward(self, input):
         return input * self.weight.view(1, -1, 1, 1)
+
+
+class RandomMask2d(nn.Module):
+    """Fixed random channel mask (models/students/transform_blocks/mask.py:7-32): int(in_channels * droprate) channels, drawn
+    once without replacement from numpy's GLOBAL random state exactly as the reference draws them, are multiplied by zero.
+    The layer-compressibility analysis puts it between a frozen teacher conv and a trainable 1x1 (AnalysisStudent.replace).
+    `mask` is a (1,C,1,1) fp32 tensor kept as a plain attribute -- absent from state_dict(), like the reference's -- that
+    follows the module's device; `keep` holds the surviving channel indices (ascending, int64, on the host): inside the fused
+    student graph the engine computes and stores those channels only."""
+
+    def __init__(self, in_channels, droprate=0.9):
+        super().__init__()
+        self.in_channels = in_channels
+        self.droprate = droprate
+        self.mask = self.create_mask()
+
+    def create_mask(self):
+        import numpy as np
+        num_dropped_filters = int(self.in_channels * self.droprate)
+        mask = np.ones((1, self.in_channels, 1, 1), dtype=np.float32)
+        dropped_idx = np.random.choice(self.in_channels, num_dropped_filters, False)
+        mask[0, dropped_idx] = 0
+        # the surviving channels, ascending (a host tensor whatever the module's device: plan-time code reads it)
+        self.keep = torch.from_numpy(np.flatnonzero(mask.reshape(-1)).astype(np.int64))
+        return torch.from_numpy(mask)
+
+    def _apply(self, fn, *args, **kwargs):
+        super()._apply(fn, *args, **kwargs)
+        self.mask = fn(self.mask).to(torch.float32)
+        return self
+
+    def forward(self, x):
+        return self.mask.to(x.dtype) * x

@@ -1391,6 +1391,46 @@ def kldiv_up(s_lo, t_lo, size, temperature=1.0, align_corners=True):
     return loss
 
 
+class MetricsUnsupported(_lib.KdccError):
+    """logit_metrics_up on a class count / resampling ratio kd_logit_metrics_up does not take: compose ce2d_up / hint_mse / confusion."""
+
+
+def logit_metrics_up(s_lo, t_lo, target, size, ignore_index=255, align_corners=True, conf_s=None, conf_t=None, accumulate=False):
+    """The analysis step's logged metrics in one pass over both low-resolution logit tensors (kd_logit_metrics_up).
+    Returns (out, conf_s, conf_t): out fp32 (3,) = [ce2d(up(s), target), ce2d(up(t), target), mean (up(s) - up(t))^2]; conf_*
+    int64 (C,C) [label][prediction] as confusion() of each up-sampled tensor (added to the given matrices when accumulate).
+    Raises MetricsUnsupported (nothing launched) outside the kernel's limits."""
+    _need_cuda(s_lo, t_lo, target)
+    _lowres_ok(s_lo, t_lo)
+    if s_lo.shape != t_lo.shape:
+        raise ValueError("logit_metrics_up: shape mismatch")
+    N, h, w, Cc = s_lo.shape
+    H, W = size
+    tgt = target.contiguous()
+    if tgt.dtype != torch.int64 or tgt.numel() != N * H * W:
+        raise ValueError("logit_metrics_up: target must be int64 (N,H,W)")
+    if conf_s is None or conf_t is None:
+        if accumulate:
+            raise ValueError("logit_metrics_up: accumulate needs both confusion matrices")
+        conf_s = torch.empty((Cc, Cc), dtype=torch.int64, device=s_lo.device)
+        conf_t = torch.empty((Cc, Cc), dtype=torch.int64, device=s_lo.device)
+    for cf in (conf_s, conf_t):
+        _need_cuda(cf)
+        if cf.dtype != torch.int64 or tuple(cf.shape) != (Cc, Cc) or not cf.is_contiguous():
+            raise ValueError("logit_metrics_up: conf must be a contiguous int64 (C, C) tensor")
+    out = torch.empty(3, dtype=torch.float32, device=s_lo.device)
+    ws, need = loss_workspace(N, Cc, H * W, s_lo.device)
+    e0 = _prof_start()
+    rc = _lib.lib().kd_logit_metrics_up(_ptr(s_lo), _ptr(t_lo), _ptr(tgt), ignore_index, N, h, w, Cc, H, W, int(bool(align_corners)), _ptr(out),
+                                        _ptr(conf_s), _ptr(conf_t), int(bool(accumulate)), _ptr(ws), need, stream_ptr())
+    if rc == _lib.KD_ERR_UNSUPPORTED:
+        msg = _lib.lib().kd_last_error()
+        raise MetricsUnsupported(f"kd_logit_metrics_up: {msg.decode() if msg else ''}")
+    check(rc, "kd_logit_metrics_up")
+    _prof_stop(e0, "loss", _nbytes(s_lo, t_lo, tgt), f"logit metrics from {h}x{w} logits at {H}x{W}", "logit_metrics_up_kernel")
+    return out, conf_s, conf_t
+
+
 def ce2d_grad(x, target, ignore_index=255, grad_scale=1.0, weight=None, size_average=True):
     """d ce2d / d x, same layout as x."""
     _need_cuda(x, target)

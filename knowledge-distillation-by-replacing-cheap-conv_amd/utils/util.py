@@ -116,6 +116,13 @@ class CityscapesMetricTracker:
         hist = torch.bincount(idx, minlength=self.num_classes ** 2).reshape(self.num_classes, self.num_classes)
         self.conf = hist if self.conf is None else self.conf + hist
 
+    def add_confusion(self, conf):
+        """Add a ready (C,C) int64 [label][prediction] matrix (ops.logit_metrics_up builds the student's and the teacher's in the
+        pass that computes the logged losses); same state as update() on the logits it was counted from."""
+        if tuple(conf.shape) != (self.num_classes, self.num_classes) or conf.dtype != torch.int64:
+            raise ValueError(f"expected an int64 ({self.num_classes},{self.num_classes}) confusion matrix")
+        self.conf = conf.clone() if self.conf is None else self.conf + conf.to(self.conf.device)
+
     def get_iou(self):
         if self.conf is None or not bool(self.conf.any()):
             return 1.
