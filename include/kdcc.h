@@ -427,6 +427,28 @@ int kd_bn_nhwc_bwd(const float *gy, int32_t ldg, const float *x, int32_t ldx, co
                    const float *save_invstd, float *dgamma, float *dbeta, int32_t accumulate, int32_t training, int32_t relu,
                    void *workspace, size_t workspace_bytes, kd_stream_t stream);
 
+/* ------------------------------------------------- DenseNet-BC CIFAR path (models/cifar_models/densenet.py, csrc/dense_ops.hip)
+ * All fp32 on (M = N*H*W, C) views with pixel strides ld* >= C, like kd_bn_nhwc_*.
+ * kd_bn_nhwc_stats: the train-mode batch statistics of kd_bn_nhwc_fwd alone -- mean, invstd = 1/sqrt(var + eps) and
+ *   var_unbiased = var*M/(M-1) (var when M == 1) per channel, by the same fixed-order reduction (per channel the same bits as
+ *   kd_bn_nhwc_fwd's save_mean / save_invstd on any view that holds the channel).  workspace: kd_bn_nhwc_workspace(M, C) bytes.
+ * kd_bn_nhwc_apply: train-mode BatchNorm with SUPPLIED statistics, one pass: y = relu?((x - mean) * gamma * invstd + beta);
+ *   running_mean = (1-momentum) running_mean + momentum mean, running_var likewise from var_unbiased, exactly as
+ *   kd_bn_nhwc_fwd updates them (each optional; var_unbiased may be NULL when running_var is).  A dense block computes the
+ *   statistics of each 32-channel slice of its buffer once and every later layer's norm1 applies them to its prefix.
+ *   The backward is kd_bn_nhwc_bwd with mean / invstd as save_mean / save_invstd.
+ * kd_avgpool2x2_nhwc / _bwd: AvgPool2d(2, 2): y (N, H/2, W/2, C), floor sizes; an odd last row / column of x is not read and
+ *   its gradient is 0.  gx (N, H, W, C) is written whole.  H, W >= 2.  float4 when C % 4 == 0 and the views allow it. */
+int kd_bn_nhwc_stats(const float *x, int32_t ldx, int64_t M, int32_t C, float *mean, float *invstd, float *var_unbiased, float eps,
+                     void *workspace, size_t workspace_bytes, kd_stream_t stream);
+int kd_bn_nhwc_apply(const float *x, int32_t ldx, float *y, int32_t ldy, int64_t M, int32_t C, const float *gamma, const float *beta,
+                     const float *mean, const float *invstd, const float *var_unbiased, float *running_mean, float *running_var,
+                     float momentum, int32_t relu, kd_stream_t stream);
+int kd_avgpool2x2_nhwc(const float *x, int32_t ldx, float *y, int32_t ldy, int32_t N, int32_t H, int32_t W, int32_t C,
+                       kd_stream_t stream);
+int kd_avgpool2x2_nhwc_bwd(const float *gy, int32_t ldg, float *gx, int32_t ldgx, int32_t N, int32_t H, int32_t W, int32_t C,
+                           kd_stream_t stream);
+
 /* ------------------------------------------------- Gated-SCNN shape stream (BASELINE config 5)
  * The full-resolution pieces of models/gscnn/gscnn.py:183-325 that are not MFMA-sized convolutions.
  * kd_gated_conv: GatedSpatialConv2d.forward (models/gscnn/gate_spatial_conv.py:50-60) fused per pixel, C in {8,16,32}:

@@ -112,6 +112,10 @@ _SIGS = {
                                c_vp, c_sz, c_vp]),
     "kd_bn_nhwc_bwd": (c_int, [c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp,
                                c_vp, c_int, c_int, c_int, c_vp, c_sz, c_vp]),
+    "kd_bn_nhwc_stats": (c_int, [c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_f, c_vp, c_sz, c_vp]),
+    "kd_bn_nhwc_apply": (c_int, [c_vp, c_int, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f, c_int, c_vp]),
+    "kd_avgpool2x2_nhwc": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
+    "kd_avgpool2x2_nhwc_bwd": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "kd_pack_dw_weight": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     "kd_dwconv_fwd": (c_int, [_P(DwDesc), c_vp, c_vp, c_vp, _P(DwEpilogue), c_vp, c_vp]),
     "kd_dwconv_fwd_sum": (c_int, [_P(DwDesc), c_int, c_vp, c_vp, c_vp, c_vp]),

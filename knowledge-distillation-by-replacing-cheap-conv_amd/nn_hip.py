@@ -146,9 +146,9 @@ def _nhwc_padded(t, cpad):
 
 class _ConvNHWCFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, res, mod):
+    def forward(ctx, x, weight, res, mod, out=None):
         xh = mod._input(x)
-        out = mod._run(xh, res_pre=None if res is None else _nhwc(res))
+        out = mod._run(xh, res_pre=None if res is None else _nhwc(res), raw_into=out)
         ctx.mod = mod
         ctx.in_shape = tuple(x.shape)
         ctx.save_for_backward(xh if weight.requires_grad else None)
@@ -164,7 +164,7 @@ class _ConvNHWCFn(torch.autograd.Function):
             dx = mod._dgrad(g, ctx.in_shape).permute(0, 3, 1, 2)
         if ctx.needs_input_grad[1]:
             dw = mod._wgrad(xh, g)
-        return dx, dw, gy if ctx.needs_input_grad[2] else None, None
+        return dx, dw, gy if ctx.needs_input_grad[2] else None, None, None
 
 
 class Conv2dNHWC(nn.Conv2d):
@@ -173,7 +173,8 @@ class Conv2dNHWC(nn.Conv2d):
     weight gradient kd_conv2d_wgrad / kd_pw_wgrad, computed only for a weight that requires grad.  Packed weights are cached
     per parameter version: a frozen weight is packed once, a trained one once per optimizer step.  Fewer than 32 input
     channels are zero-padded to 32 (weights packed with cin_pad, the input copied into a zeroed 32-channel buffer).
-    forward(x, residual=None): residual (the block's shortcut) is added in the conv's epilogue."""
+    forward(x, residual=None, out=None): residual (the block's shortcut) is added in the conv's epilogue; out, an (N,Ho,Wo,Cout)
+    fp32 NHWC view (a channel slice of a wider buffer: a dense block's), receives the result instead of a fresh tensor."""
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -213,14 +214,14 @@ class Conv2dNHWC(nn.Conv2d):
             return _nhwc_padded(x, self.cin_pad)
         return _nhwc(x)
 
-    def _run(self, xh, res_pre=None, out_act=False, act_scale=None, act_shift=None, act_relu=False, want_raw=True):
-        """Forward on an (N,H,W,cin_pad) view -> out_raw [, out_act] (N,Ho,Wo,Cout) fp32 buffers."""
+    def _run(self, xh, res_pre=None, out_act=False, act_scale=None, act_shift=None, act_relu=False, want_raw=True, raw_into=None):
+        """Forward on an (N,H,W,cin_pad) view -> out_raw [, out_act] (N,Ho,Wo,Cout) fp32 buffers (out_raw is raw_into when given)."""
         from ._lib import KD_PACK_FWD
         N, H, W, _ = xh.shape
         k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
         Ho, Wo = ops.conv_out_size(H, k, s, p, 1), ops.conv_out_size(W, k, s, p, 1)
         new = lambda: torch.empty((N, Ho, Wo, self.out_channels), dtype=torch.float32, device=xh.device)
-        raw = new() if want_raw else None
+        raw = raw_into if raw_into is not None else (new() if want_raw else None)
         act = new() if out_act else None
         ops.conv2d(xh, self._pack(KD_PACK_FWD), s, p, res_pre=res_pre, out_raw=raw, out_act=act, act_scale=act_scale,
                    act_shift=act_shift, act_relu=act_relu)
@@ -245,28 +246,40 @@ class Conv2dNHWC(nn.Conv2d):
             ops.conv2d_wgrad(xh, g, dw, s, p, 1)
         return dw if xh.shape[3] == self.in_channels else dw[:, :self.in_channels].contiguous()
 
-    def forward(self, x, residual=None):
+    def forward(self, x, residual=None, out=None):
         if _host(x):
+            if out is not None:
+                raise ValueError("Conv2dNHWC: out= is a device view")
             y = super().forward(x)
             return y if residual is None else y + residual
         self._check()
         if x.dtype != torch.float32:
             raise TypeError("Conv2dNHWC is fp32 (the CIFAR path of the reference is fp32)")
-        return _ConvNHWCFn.apply(x, self.weight, residual, self)
+        return _ConvNHWCFn.apply(x, self.weight, residual, self, out)
 
 
 class _BatchNormNHWCFn(torch.autograd.Function):
     """y = relu?(bn(x)); with `shortcut` also returns x itself, whose gradient (the identity shortcut's, when x is a residual block's
-    input) is then added to dx by kd_bn_nhwc_bwd's `res` operand instead of by a separate autograd sum."""
+    input) is then added to dx by kd_bn_nhwc_bwd's `res` operand instead of by a separate autograd sum.
+    stats: (mean, invstd, var_unbiased) of x's channels computed beforehand (ops.bn_nhwc_stats; train mode only): the forward is
+    then one kd_bn_nhwc_apply pass and the backward uses them as the saved statistics.
+    chain: a GradChain shared by the BNs of one dense block.  The shortcut gradient of such a BN is a channel prefix of the
+    gradient buffer the next layer's BN wrote its dx into; when that is what arrives, dx is accumulated into it in place
+    (ops.bn_nhwc_bwd(out=res)) and the whole block's input gradients live in one buffer."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, running_mean, running_var, training, momentum, eps, relu, shortcut):
+    def forward(ctx, x, gamma, beta, running_mean, running_var, training, momentum, eps, relu, shortcut, stats=None, chain=None):
         ctx.set_materialize_grads(False)
         xh = _nhwc(x)
-        y, mean, invstd = ops.bn_nhwc_fwd(xh, gamma.contiguous(), beta.contiguous(), running_mean, running_var, training, momentum,
-                                          eps, relu)
+        if stats is not None and training:
+            mean, invstd, var = stats
+            y = ops.bn_nhwc_apply(xh, gamma.contiguous(), beta.contiguous(), mean, invstd, var, running_mean, running_var, momentum, relu)
+        else:
+            y, mean, invstd = ops.bn_nhwc_fwd(xh, gamma.contiguous(), beta.contiguous(), running_mean, running_var, training, momentum,
+                                              eps, relu)
         ctx.save_for_backward(xh, y if relu else None, gamma, mean, invstd)
         ctx.flags = (training, relu)
+        ctx.chain = chain
         y = y.permute(0, 3, 1, 2)
         return (y, x) if shortcut else y
 
@@ -283,10 +296,28 @@ class _BatchNormNHWCFn(torch.autograd.Function):
                 dg.zero_()
             if db is not None:
                 db.zero_()
-            return None if res is None else gsc, dg, db, None, None, None, None, None, None, None
+            return None if res is None else gsc, dg, db, None, None, None, None, None, None, None, None, None
+        chain = ctx.chain
+        into = res if chain is not None and res is not None and chain.owns(res) else None
         dx = ops.bn_nhwc_bwd(_nhwc(gy), xh, y, gamma.contiguous(), mean, invstd, training, relu, res=res,
-                             need_dx=ctx.needs_input_grad[0], dgamma=dg, dbeta=db)
-        return None if dx is None else dx.permute(0, 3, 1, 2), dg, db, None, None, None, None, None, None, None
+                             need_dx=ctx.needs_input_grad[0], dgamma=dg, dbeta=db, out=into)
+        if chain is not None and dx is not None:
+            chain.buf = dx
+        return None if dx is None else dx.permute(0, 3, 1, 2), dg, db, None, None, None, None, None, None, None, None, None
+
+
+class GradChain:
+    """The gradient buffer of one dense block's backward: the dx the block's last BN allocated, which every earlier BN of the
+    chain then accumulates into in place.  A gradient that is not a prefix view of that very buffer (autograd summed another
+    consumer's gradient into a tensor of its own, a caller's grad_output) is never written: that BN allocates afresh."""
+
+    def __init__(self):
+        self.buf = None
+
+    def owns(self, g):
+        b = self.buf
+        return (b is not None and g.data_ptr() == b.data_ptr() and g.stride() == b.stride()
+                and g.untyped_storage().data_ptr() == b.untyped_storage().data_ptr() and g.shape[3] <= b.shape[3])
 
 
 class BatchNorm2dNHWC(nn.BatchNorm2d):
@@ -319,18 +350,19 @@ class BatchNorm2dNHWC(nn.BatchNorm2d):
             self._fold = (key, ops.bn_fold(self))
         return self._fold[1]
 
-    def _apply_fn(self, x, relu, shortcut):
+    def _apply_fn(self, x, relu, shortcut, stats=None, chain=None):
         self._check(x)
         if self.training:
             self.num_batches_tracked.add_(1)
         return _BatchNormNHWCFn.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.training,
-                                      float(self.momentum), float(self.eps), bool(relu), shortcut)
+                                      float(self.momentum), float(self.eps), bool(relu), shortcut, stats, chain)
 
-    def forward(self, x, relu=False):
+    def forward(self, x, relu=False, stats=None):
+        """stats: (mean, invstd, var_unbiased) of x's channels when the caller has them (see forward_with_stats); device only."""
         if _host(x):
             y = super().forward(x)
             return F.relu(y) if relu else y
-        return self._apply_fn(x, relu, False)
+        return self._apply_fn(x, relu, False, stats if self.training else None)
 
     def forward_with_shortcut(self, x, relu=False):
         """(forward(x, relu), s) where s is x for an identity shortcut: the gradient reaching s joins dx inside kd_bn_nhwc_bwd
@@ -338,3 +370,66 @@ class BatchNorm2dNHWC(nn.BatchNorm2d):
         if _host(x):
             return self.forward(x, relu), x
         return self._apply_fn(x, relu, True)
+
+    def forward_with_stats(self, x, stats, relu=False, shortcut=False, chain=None):
+        """forward(x, relu) in train mode from batch statistics the caller already has: stats = (mean, invstd, var_unbiased) of
+        x's channels (ops.bn_nhwc_stats with this BN's eps) -- one elementwise pass, the running statistics and
+        num_batches_tracked updated as forward() does; stats=None (or eval mode) is forward() itself.  shortcut=True returns
+        (y, s) as forward_with_shortcut; `chain` (a GradChain) lets a dense block's backward accumulate in one buffer.
+        Device tensors only, and not a module call: forward hooks of this BN do not fire."""
+        if _host(x):
+            raise KdccError("BatchNorm2dNHWC.forward_with_stats takes device tensors")
+        return self._apply_fn(x, relu, bool(shortcut), stats if self.training else None, chain)
+
+
+class _MaxPool3x3s2Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        xh = _nhwc(x)
+        ctx.save_for_backward(xh)
+        return ops.maxpool3x3s2(xh)[0].permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, gy):
+        (xh,) = ctx.saved_tensors
+        return ops.maxpool3x3s2_bwd(xh, _nhwc(gy)).permute(0, 3, 1, 2)
+
+
+class MaxPool3x3s2NHWC(nn.MaxPool2d):
+    """nn.MaxPool2d(3, 2, 1) on channels-last fp32 device tensors: kd_maxpool3x3s2 / kd_maxpool3x3s2_bwd (C % 8 == 0)."""
+
+    def forward(self, x):
+        if _host(x):
+            return super().forward(x)
+        one = lambda v: v[0] if isinstance(v, (tuple, list)) and len({*v}) == 1 else v
+        if (one(self.kernel_size), one(self.stride), one(self.padding), one(self.dilation)) != (3, 2, 1, 1) or self.ceil_mode \
+                or self.return_indices:
+            raise NotImplementedError("MaxPool3x3s2NHWC: kernel 3, stride 2, padding 1 only")
+        if x.dtype != torch.float32:
+            raise TypeError("MaxPool3x3s2NHWC is fp32")
+        return _MaxPool3x3s2Fn.apply(x)
+
+
+class _AvgPool2x2Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        ctx.size = tuple(x.shape[2:])
+        return ops.avgpool2x2(_nhwc(x)).permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, gy):
+        return ops.avgpool2x2_bwd(_nhwc(gy), ctx.size).permute(0, 3, 1, 2)
+
+
+class AvgPool2x2NHWC(nn.AvgPool2d):
+    """nn.AvgPool2d(2, 2) on channels-last fp32 device tensors: kd_avgpool2x2_nhwc / kd_avgpool2x2_nhwc_bwd."""
+
+    def forward(self, x):
+        if _host(x):
+            return super().forward(x)
+        one = lambda v: v[0] if isinstance(v, (tuple, list)) and len({*v}) == 1 else v
+        if (one(self.kernel_size), one(self.stride), one(self.padding)) != (2, 2, 0) or self.ceil_mode or self.divisor_override:
+            raise NotImplementedError("AvgPool2x2NHWC: kernel 2, stride 2, no padding only")
+        if x.dtype != torch.float32:
+            raise TypeError("AvgPool2x2NHWC is fp32")
+        return _AvgPool2x2Fn.apply(x)

@@ -989,24 +989,115 @@ def bn_nhwc_fwd(x, gamma, beta, running_mean, running_var, training, momentum, e
 
 
 def bn_nhwc_bwd(gy, x, y, gamma, mean, invstd, training, relu=False, res=None, need_dx=True, dgamma=None, dbeta=None,
-                accumulate=False):
+                accumulate=False, out=None):
     """Returns dx (N,H,W,C) | None; dgamma / dbeta (contiguous fp32 (C,)) receive sum g' xhat / sum g' when given (+= with
-    accumulate).  res: a gradient view added to dx.  y (the forward output) is read only with relu."""
-    _need_cuda(gy, x, y, res)
+    accumulate).  res: a gradient view added to dx.  y (the forward output) is read only with relu.
+    out: an (N,H,W,C) fp32 view (a channel prefix of a wider buffer) that receives dx instead of a fresh tensor.  `out` MAY
+    alias `res` exactly (same base pointer and strides: dx accumulates in place into the gradient it is added to): the dx
+    kernel computes element (m, c) in one thread, which loads res[m][c] before it stores dx[m][c] and touches no other element
+    of either, and the reductions that precede it read neither.  Any other overlap of `out` with an operand is refused."""
+    _need_cuda(gy, x, y, res, out)
     _f32vec(gamma, mean, invstd, dgamma, dbeta)
     N, H, W, Cc = x.shape
-    for t in (gy, y, res):
+    for t in (gy, y, res, out):
         if t is not None and (tuple(t.shape) != (N, H, W, Cc) or t.dtype != torch.float32):
             raise ValueError("bn_nhwc_bwd: operand mismatch")
     M = N * H * W
-    dx = torch.empty((N, H, W, Cc), dtype=torch.float32, device=x.device) if need_dx else None
+    if out is not None:
+        if not need_dx:
+            raise ValueError("bn_nhwc_bwd: out given with need_dx=False")
+        lo, hi = out.data_ptr(), out.data_ptr() + 4 * ((M - 1) * nhwc_ld(out) + Cc)
+        for t in (gy, x, y if relu else None, res):
+            if t is None or (t is res and t.data_ptr() == lo and t.stride() == out.stride()):
+                continue
+            if t.data_ptr() < hi and lo < t.data_ptr() + 4 * ((M - 1) * nhwc_ld(t) + Cc):
+                raise ValueError("bn_nhwc_bwd: out overlaps an operand (only an exact alias of res is allowed)")
+        dx = out
+    else:
+        dx = torch.empty((N, H, W, Cc), dtype=torch.float32, device=x.device) if need_dx else None
     ws = _bn_ws(M, Cc, x.device) if ((need_dx and training) or dgamma is not None or dbeta is not None) else None
     ld = lambda t: nhwc_ld(t) if t is not None else 0
     check(_lib.lib().kd_bn_nhwc_bwd(_ptr(gy), ld(gy), _ptr(x), ld(x), _ptr(y if relu else None), ld(y) if relu else 0, _ptr(res), ld(res),
                                     _ptr(dx), ld(dx), M, Cc, _ptr(gamma), _ptr(mean), _ptr(invstd), _ptr(dgamma), _ptr(dbeta),
                                     int(bool(accumulate)), int(bool(training)), int(bool(relu)), _ptr(ws),
                                     0 if ws is None else ws.numel(), stream_ptr()), "kd_bn_nhwc_bwd")
+    if out is not None:
+        torch.autograd.graph.increment_version(out)
     return dx
+
+
+# ------------------------------------------------------------------------- DenseNet path (csrc/dense_ops.hip)
+def bn_nhwc_stats(x, eps, mean=None, invstd=None, var_unbiased=None):
+    """Train-mode batch statistics of an (N,H,W,C) fp32 view -> (mean, invstd, var_unbiased), each a contiguous fp32 (C,) vector
+    (written into the given ones: slices of a dense block's per-channel vectors).  Per channel the bits kd_bn_nhwc_fwd saves."""
+    _need_cuda(x)
+    if x.dtype != torch.float32:
+        raise TypeError("bn_nhwc_stats: fp32 only")
+    N, H, W, Cc = x.shape
+    new = lambda v: torch.empty(Cc, device=x.device) if v is None else v
+    mean, invstd, var_unbiased = new(mean), new(invstd), new(var_unbiased)
+    _f32vec(mean, invstd, var_unbiased)
+    if not (mean.numel() == invstd.numel() == var_unbiased.numel() == Cc):
+        raise ValueError(f"bn_nhwc_stats: {Cc} channels need vectors of {Cc}")
+    M = N * H * W
+    ws = _bn_ws(M, Cc, x.device)
+    check(_lib.lib().kd_bn_nhwc_stats(_ptr(x), nhwc_ld(x), M, Cc, _ptr(mean), _ptr(invstd), _ptr(var_unbiased), C.c_float(eps), _ptr(ws),
+                                      ws.numel(), stream_ptr()), "kd_bn_nhwc_stats")
+    return mean, invstd, var_unbiased
+
+
+def bn_nhwc_apply(x, gamma, beta, mean, invstd, var_unbiased, running_mean, running_var, momentum, relu=False, out=None):
+    """Train-mode BatchNorm with supplied batch statistics (bn_nhwc_stats), one pass: y = relu?((x - mean) gamma invstd + beta),
+    into `out` when given; the running statistics (either may be None) are updated in place as bn_nhwc_fwd would."""
+    _need_cuda(x, out)
+    _f32vec(gamma, beta, mean, invstd, var_unbiased, running_mean, running_var)
+    if x.dtype != torch.float32:
+        raise TypeError("bn_nhwc_apply: fp32 only")
+    N, H, W, Cc = x.shape
+    for v in (gamma, beta, mean, invstd, var_unbiased, running_mean, running_var):
+        if v is not None and v.numel() != Cc:
+            raise ValueError(f"bn_nhwc_apply: {Cc} channels, a vector of {v.numel()}")
+    if running_var is not None and var_unbiased is None:
+        raise ValueError("bn_nhwc_apply: running_var needs var_unbiased")
+    y = torch.empty((N, H, W, Cc), dtype=torch.float32, device=x.device) if out is None else out
+    if tuple(y.shape) != (N, H, W, Cc) or y.dtype != torch.float32:
+        raise ValueError("bn_nhwc_apply: out must be an fp32 view of the input's shape")
+    check(_lib.lib().kd_bn_nhwc_apply(_ptr(x), nhwc_ld(x), _ptr(y), nhwc_ld(y), N * H * W, Cc, _ptr(gamma), _ptr(beta), _ptr(mean),
+                                      _ptr(invstd), _ptr(var_unbiased), _ptr(running_mean), _ptr(running_var), C.c_float(momentum),
+                                      int(bool(relu)), stream_ptr()), "kd_bn_nhwc_apply")
+    for t in (running_mean, running_var, out):
+        if t is not None:
+            torch.autograd.graph.increment_version(t)
+    return y
+
+
+def _pool_views(x, other, shape, who):
+    _need_cuda(x, other)
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise TypeError(f"{who}: (N,H,W,C) fp32 views only")
+    if other is not None and (tuple(other.shape) != shape or other.dtype != torch.float32):
+        raise ValueError(f"{who}: out must be an fp32 {shape} view")
+    return torch.empty(shape, dtype=torch.float32, device=x.device) if other is None else other
+
+
+def avgpool2x2(x, out=None):
+    """AvgPool2d(2, 2) of an (N,H,W,C) fp32 view -> (N, H//2, W//2, C) (an odd last row / column is dropped)."""
+    N, H, W, Cc = x.shape
+    y = _pool_views(x, out, (N, H // 2, W // 2, Cc), "avgpool2x2")
+    check(_lib.lib().kd_avgpool2x2_nhwc(_ptr(x), nhwc_ld(x), _ptr(y), nhwc_ld(y), N, H, W, Cc, stream_ptr()), "kd_avgpool2x2_nhwc")
+    return y
+
+
+def avgpool2x2_bwd(gy, size, out=None):
+    """gy (N, H//2, W//2, C) -> the gradient (N,H,W,C) of avgpool2x2's input, size = (H, W); dropped rows / columns get 0."""
+    N, Ho, Wo, Cc = gy.shape
+    H, W = size
+    if (Ho, Wo) != (H // 2, W // 2):
+        raise ValueError(f"avgpool2x2_bwd: gy {tuple(gy.shape)} is not the pooled size of {H}x{W}")
+    gx = _pool_views(gy, out, (N, H, W, Cc), "avgpool2x2_bwd")
+    check(_lib.lib().kd_avgpool2x2_nhwc_bwd(_ptr(gy), nhwc_ld(gy), _ptr(gx), nhwc_ld(gx), N, H, W, Cc, stream_ptr()),
+          "kd_avgpool2x2_nhwc_bwd")
+    return gx
 
 
 def copy_cast(src, dst):
