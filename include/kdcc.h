@@ -724,6 +724,47 @@ const char *kd_debug_last_kernel(void);
  * log or kd_debug_last_kernel above.  A dispatcher that launches two kernels names the first, shape-selected one. */
 const char *kd_debug_last_plumbing_kernel(void);
 
+/* ------------------------------------------------- HRNetV2 + OCR (models/hrnet_ocr/seg_hrnet_ocr.py)
+ * fp32 NHWC only; C % 4 == 0, views 16-byte aligned with ld % 4 == 0; deterministic (fixed-order reductions, no float atomics).
+ *
+ * kd_hr_fuse_fwd: the exchange unit of HighResolutionModule.forward (:399-414): y = relu(sum_s sample(src_s)) for 1..4 sources
+ *   of C channels.  A source of the output's size is read directly; a coarser one is sampled bilinearly with
+ *   align_corners=True by the coordinate rule of kd_upsample_bilinear_ac (scale 0 when an output extent is 1).  Sources are
+ *   added in order.  The 1x1 conv + BN of a coarser branch and the strided 3x3 chains of a finer branch stay convolutions.
+ * kd_hr_fuse_bwd: g = gy * (y > 0); gsrc[s] of the output's size receives g, a coarser one the bilinear adjoint in gather form
+ *   (each source pixel sums the output pixels whose footprint touches it).  gsrc[s].ptr == NULL: that gradient is not wanted. */
+typedef struct kd_hr_view {
+    void *ptr;
+    int32_t H, W, ld;
+} kd_hr_view;
+int kd_hr_fuse_fwd(const kd_hr_view *src, int32_t nsrc, void *y, int32_t ldy, int32_t N, int32_t Ho, int32_t Wo, int32_t C,
+                   kd_stream_t stream);
+int kd_hr_fuse_bwd(const void *gy, int32_t ldgy, const void *y, int32_t ldy, const kd_hr_view *gsrc, int32_t nsrc, int32_t N,
+                   int32_t Ho, int32_t Wo, int32_t C, kd_stream_t stream);
+
+/* SpatialGather_Module (:65-73): logits (N,HW,K) pixel stride ldl, feats (N,HW,C) pixel stride ldf, K <= 32 ->
+ *   ctx (N,K,C) dense = softmax_over_HW(logits)^T . feats, and mx / lse (N,K): per class the maximum and the log-sum-exp of its
+ *   logits, from which the backward recomputes the probabilities (the K x HW map is never stored).
+ * kd_ocr_gather_bwd: gctx (N,K,C) and the forward's ctx, lse -> d_feats (N,HW,C), d_logits (N,HW,K); K * C * 4 <= 64 KiB.
+ * workspace (both): kd_ocr_gather_workspace() bytes, 16-byte aligned. */
+size_t kd_ocr_gather_workspace(int32_t N, int64_t HW, int32_t K, int32_t C);
+int kd_ocr_gather_fwd(const float *logits, int32_t ldl, const float *feats, int32_t ldf, float *ctx, float *mx, float *lse, int32_t N,
+                      int64_t HW, int32_t K, int32_t C, void *workspace, size_t workspace_bytes, kd_stream_t stream);
+int kd_ocr_gather_bwd(const float *gctx, const float *ctx, const float *logits, int32_t ldl, const float *feats, int32_t ldf,
+                      const float *lse, float *d_feats, int32_t lddf, float *d_logits, int32_t lddl, int32_t N, int64_t HW, int32_t K,
+                      int32_t C, void *workspace, size_t workspace_bytes, kd_stream_t stream);
+
+/* The core of _ObjectAttentionBlock.forward (:138-143): query (N,HW,Ck) pixel stride ldq, key / value (N,K,Ck) dense, K <= 32,
+ *   2 * K * Ck * 4 <= 64 KiB -> ctx (N,HW,Ck) = softmax_K(scale * query . key^T) . value (scale = Ck^-0.5 in the reference).
+ * kd_ocr_attend_bwd: g = d ctx -> d_query (N,HW,Ck), d_key, d_value (N,K,Ck); the K probabilities are recomputed per pixel;
+ *   the two reductions over HW run in two fixed-order stages through `workspace` (kd_ocr_attend_workspace() bytes). */
+size_t kd_ocr_attend_workspace(int32_t N, int64_t HW, int32_t K, int32_t Ck);
+int kd_ocr_attend_fwd(const float *query, int32_t ldq, const float *key, const float *value, float *ctx, int32_t ldc, int32_t N, int64_t HW,
+                      int32_t K, int32_t Ck, float scale, kd_stream_t stream);
+int kd_ocr_attend_bwd(const float *g, int32_t ldg, const float *query, int32_t ldq, const float *key, const float *value, float *d_query,
+                      int32_t lddq, float *d_key, float *d_value, int32_t N, int64_t HW, int32_t K, int32_t Ck, float scale, void *workspace,
+                      size_t workspace_bytes, kd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,10 @@ class View3(C.Structure):
     _fields_ = [("ptr", c_vp), ("dtype", c_int), ("sN", c_i64), ("sC", c_i64), ("sP", c_i64)]
 
 
+class HrView(C.Structure):
+    _fields_ = [("ptr", c_vp), ("H", c_int), ("W", c_int), ("ld", c_int)]
+
+
 KD_MULTI_MAX = 16
 
 
@@ -185,6 +189,16 @@ _SIGS = {
     "kd_gate_mix_bwd": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_i64, c_vp]),
     "kd_edge_attention_bwd": (c_int, [c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "kd_rank1_add": (c_int, [c_int, c_vp, c_int, c_vp, c_vp, c_int, c_i64, c_int, c_vp]),
+    "kd_hr_fuse_fwd": (c_int, [_P(HrView), c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
+    "kd_hr_fuse_bwd": (c_int, [c_vp, c_int, c_vp, c_int, _P(HrView), c_int, c_int, c_int, c_int, c_int, c_vp]),
+    "kd_ocr_gather_workspace": (c_sz, [c_int, c_i64, c_int, c_int]),
+    "kd_ocr_gather_fwd": (c_int, [c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_i64, c_int, c_int, c_vp, c_sz, c_vp]),
+    "kd_ocr_gather_bwd": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_i64, c_int, c_int, c_vp,
+                                  c_sz, c_vp]),
+    "kd_ocr_attend_workspace": (c_sz, [c_int, c_i64, c_int, c_int]),
+    "kd_ocr_attend_fwd": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_i64, c_int, c_int, c_f, c_vp]),
+    "kd_ocr_attend_bwd": (c_int, [c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_i64, c_int, c_int, c_f, c_vp, c_sz,
+                                  c_vp]),
     "kd_debug_kernel_log_enable": (c_int, [c_int]),
     "kd_debug_kernel_log_read": (c_i64, [C.c_char_p, c_sz]),
     "kd_debug_last_kernel": (C.c_char_p, []),

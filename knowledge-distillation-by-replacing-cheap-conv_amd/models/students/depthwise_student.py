@@ -6,6 +6,10 @@ reset :261-273, train :275-283).  What differs is how forward executes:
   * a DeepWV3Plus student runs through engine.StudentEngine (hand-written HIP kernels, hints captured by name);
   * the teacher stays a PyTorch-ROCm module under no_grad, in channels_last at the engine's dtype, on a side
     HIP stream so its kernels overlap the student's (its logits / hints are only needed by the losses);
+  * a HighResolutionNet (HRNetV2 + OCR) student is a channels-last fp32 module graph on this project's kernels
+    (models/hrnet_ocr.py): `fused` is true for it too -- GPU only, hint names validated when they are registered -- but it
+    has no StudentEngine plan (`engine_plan` is false): forward runs the frozen teacher under no_grad, then the student's
+    modules, and hints are captured by forward hooks;
   * any other architecture (e.g. the CIFAR ResNet-20 plumbing config) falls back to the reference's own
     mechanism -- module forward + hooks -- with the replaced blocks still HIP-backed.
 """
@@ -18,6 +22,7 @@ from torch import nn
 
 from ..deeplabv3 import DeepWV3Plus
 from ..gscnn import GSCNN
+from ..hrnet_ocr import HighResolutionNet
 from ...lazy import LazyLogits
 from .transform_blocks import DepthwiseSeparableBlock
 
@@ -46,6 +51,7 @@ class DepthwiseStudent(nn.Module):
         self.save_hidden = True
 
         # compute dtype of the fused path: bf16 (measured path) unless the config / caller asks for fp32 parity mode
+        self._dtype_explicit = dtype is not None
         if dtype is None:
             dtype = torch.bfloat16
             try:
@@ -53,6 +59,10 @@ class DepthwiseStudent(nn.Module):
                     dtype = torch.float32
             except (KeyError, TypeError, AttributeError):
                 pass
+        if isinstance(self.student, HighResolutionNet):     # fp32 module graph: bf16 is not implemented for this network
+            if self._dtype_explicit and dtype != torch.float32:
+                raise TypeError("a HighResolutionNet student is fp32 only (bf16 is not implemented for this network)")
+            dtype = torch.float32
         self.dtype = dtype
         self._engine = None
         self._teacher_ready = None
@@ -75,9 +85,11 @@ class DepthwiseStudent(nn.Module):
 
     # ------------------------------------------------------------------ model surgery (host side)
     def register_hint_layers(self, block_names):
-        if self.fused and len(block_names) > 0:
+        if self.engine_plan and len(block_names) > 0:
             from ...engine import StudentEngine
             StudentEngine(self.student, self.dtype).check_hint_names(block_names)   # fail at plan time, not mid-run
+        elif self.fused and len(block_names) > 0:
+            self._check_module_hint_names(block_names)
         if len(block_names) > 0:
             self._remove_hooks()
             self.hint_block_names = []
@@ -100,6 +112,27 @@ class DepthwiseStudent(nn.Module):
             # only reached on the non-fused path; the engine captures student hints by name
             self._student_hook_handlers.append(student_block.register_forward_hook(student_handle))
         gc.collect()
+
+    def _check_module_hint_names(self, block_names):
+        """HRNet: a hint name must resolve, in teacher and student, to a conv (or the cheap-conv block that replaced it), a
+        residual block or a branch -- raised at plan time, like the engine's check."""
+        from ...engine import EngineError
+        from .. import hrnet_ocr
+        # (what forward really calls as a module, so that the hook fires: not e.g. the BN + ReLU pair inside an OCR transform)
+        kinds = (nn.Conv2d, DepthwiseSeparableBlock, hrnet_ocr.BasicBlock, hrnet_ocr.Bottleneck, hrnet_ocr.HighResolutionModule,
+                 hrnet_ocr._ConvBN, hrnet_ocr._ConvBNReLUChain, hrnet_ocr._AuxHead)
+        called = lambda b: isinstance(b, kinds) or type(b) is nn.Sequential      # (plain Sequentials: branches, stages, chains)
+        bad = []
+        for name in block_names:
+            try:
+                blocks = [self.get_block(name, self.teacher), self.get_block(name, self.student)]
+            except (AttributeError, IndexError, KeyError, TypeError, ValueError):
+                bad.append(name)
+                continue
+            if not all(called(b) for b in blocks):
+                bad.append(name)
+        if bad:
+            raise EngineError(f"hint layers that do not resolve to a conv, a block or a branch of {type(self.student).__name__}: {bad}")
 
     def unfreeze(self, block_names):
         for block_name in block_names:
@@ -152,8 +185,15 @@ class DepthwiseStudent(nn.Module):
 
     # ------------------------------------------------------------------ execution
     @property
-    def fused(self):
+    def engine_plan(self):
+        """The student executes through a StudentEngine plan (DeepWV3Plus / GSCNN)."""
         return isinstance(self.student, (DeepWV3Plus, GSCNN))
+
+    @property
+    def fused(self):
+        """The student runs on this project's kernels: GPU only, hint names validated when they are registered.  True for the
+        engine-planned networks and for HighResolutionNet, whose module graph is built from the HIP layers."""
+        return self.engine_plan or isinstance(self.student, HighResolutionNet)
 
     def _student_engine(self):
         from ...engine import StudentEngine
@@ -180,7 +220,7 @@ class DepthwiseStudent(nn.Module):
             eng.edge_prior = getattr(self, "_shared_prior", None) if eng.is_gscnn else None
             eng.hint_names = list(self.hint_block_names) if self.save_hidden else []
             k = 0
-            if self.share_frozen_prefix and self.fused and not self.hip_teacher_side_stream:
+            if self.share_frozen_prefix and self.engine_plan and not self.hip_teacher_side_stream:
                 k = self._student_engine().shareable_prefix(eng)
             eng._lazy_call = True          # the trainer's criteria read the half-resolution logits (lazy.LazyLogits)
             try:
@@ -208,7 +248,7 @@ class DepthwiseStudent(nn.Module):
         frozen and deterministic).  Returns False where it does not apply (non-fused students, Gated-SCNN's shared Canny prior,
         `share_frozen_prefix`)."""
         self._prefetched = None
-        if not self.fused or not x.is_cuda or self.share_frozen_prefix or isinstance(self.teacher, GSCNN):
+        if not self.engine_plan or not x.is_cuda or self.share_frozen_prefix or isinstance(self.teacher, GSCNN):
             return False
         if self._side_stream is None or self._side_stream.device != x.device:
             self._side_stream = torch.cuda.Stream(device=x.device)
@@ -245,7 +285,9 @@ class DepthwiseStudent(nn.Module):
         self.student_hidden_outputs = []
         self.teacher_hidden_outputs = []
         pre, self._prefetched = getattr(self, "_prefetched", None), None
-        if not self.fused:
+        if not self.engine_plan:
+            if self.fused:
+                self._check_module_graph_input(x)
             with torch.no_grad():
                 teacher_pred = self.teacher(x)
             return self.student(x), teacher_pred
@@ -304,10 +346,18 @@ class DepthwiseStudent(nn.Module):
             self._teacher_engine.edge_prior = None
         return student_pred, teacher_pred
 
+    def _check_module_graph_input(self, x):
+        if not x.is_cuda:
+            raise RuntimeError(f"the {type(self.student).__name__} student runs on the GPU only (no CPU fallback)")
+        if x.dtype != torch.float32:
+            raise TypeError(f"the {type(self.student).__name__} student is fp32 only (bf16 is not implemented for this network)")
+
     def inference(self, x):
         self.student_hidden_outputs = []
         self.teacher_hidden_outputs = []
-        if not self.fused:
+        if not self.engine_plan:
+            if self.fused:
+                self._check_module_graph_input(x)
             return self.student(x)
         from ...engine import run_student
         engine = self._student_engine()

@@ -36,7 +36,7 @@ class TaylorPruneStudent(DepthwiseStudent):
 
     def _channels_behind(self, name, block):
         """Channel count of the tensor the gate multiplies; raises for a site the fused graph cannot fold a gate into."""
-        if self.fused:
+        if self.engine_plan:
             if _CONV_SITE.match(name) and isinstance(block, nn.Conv2d):
                 return block.out_channels
             if _RELU_SITE.match(name) and isinstance(block, nn.ReLU):

@@ -433,3 +433,186 @@ class AvgPool2x2NHWC(nn.AvgPool2d):
         if x.dtype != torch.float32:
             raise TypeError("AvgPool2x2NHWC is fp32")
         return _AvgPool2x2Fn.apply(x)
+
+
+# ------------------------------------------------------------------ biased channels-last conv (HRNet-OCR heads)
+_PADDED = "_nhwc_pad"     # tensor attribute: its NHWC storage continues with zero channels up to this pixel stride
+
+
+def new_padded(shape, device):
+    """(N,H,W,C) fp32 view for a kernel to fill.  When C is no multiple of the conv granule the view is the channel prefix of a
+    buffer whose pixel stride is the granule above C, with a zero tail: tagged with mark_padded(), a conv reads it in place."""
+    N, H, W, Cc = shape
+    cpad = -(-Cc // _CIN_GRANULE) * _CIN_GRANULE
+    if cpad == Cc:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    buf = torch.empty((N, H, W, cpad), dtype=torch.float32, device=device)
+    buf[..., Cc:].zero_()
+    return buf[..., :Cc]
+
+
+def mark_padded(t):
+    """Tag an NCHW-logical tensor whose storage came from new_padded() (and was written through its view only)."""
+    v = t.permute(0, 2, 3, 1)
+    cpad = -(-v.shape[3] // _CIN_GRANULE) * _CIN_GRANULE
+    if cpad != v.shape[3] and v.stride(3) == 1 and v.stride(2) == cpad:
+        setattr(t, _PADDED, cpad)
+    return t
+
+
+class _ConvBiasNHWCFn(torch.autograd.Function):
+    """xh: the module's input view (Conv2dNHWCBias._input of x), made by the caller, where x still carries its padding tag."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, mod, xh):
+        out = mod._run_biased(xh)
+        ctx.mod = mod
+        ctx.in_shape = tuple(x.shape)
+        ctx.save_for_backward(xh if weight.requires_grad else None)
+        return out.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, gy):
+        mod = ctx.mod
+        (xh,) = ctx.saved_tensors
+        co, cop = mod.out_channels, mod.cout_pad
+        g = _nhwc(gy) if co == cop else _nhwc_padded(gy, cop)
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = mod._dgrad(g, ctx.in_shape).permute(0, 3, 1, 2)
+        if ctx.needs_input_grad[1]:
+            dw = mod._wgrad(xh, g)
+        if ctx.needs_input_grad[2]:       # the bias gradient is a channel sum, taken only when somebody wants it
+            db = ops.channel_sums(g)[0][:co]
+        return dx, dw, db, None, None
+
+
+class Conv2dNHWCBias(Conv2dNHWC):
+    """Conv2dNHWC with an optional bias and any number of output channels (the OCR heads of HRNet: conv3x3_ocr.0, aux_head.0 / .3,
+    cls_head).  The bias is the conv epilogue's per-channel shift (scale 1, no ReLU), the way the cheap-conv block carries its
+    pointwise bias; run_folded() puts an eval-mode BN (+ ReLU) into the same epilogue.  An output channel count that is no
+    multiple of 16 (the 19 classes) is computed with the packed weight zero-padded to 32 rows and returned as a channel view of
+    that buffer.  In the backward the output gradient is the K operand of the input-gradient conv, so there any count that is
+    no multiple of 32 (HRNet's 48-channel branch) is zero-padded to the granule, with weights packed to match.  With bias=False
+    this is the conv of every HRNet layer.  An input whose storage is
+    already zero-padded to the input granule (attribute set by its producer: HRNet's 720-channel concatenation in a 736-channel
+    buffer; a 48-channel output of another Conv2dNHWCBias or of the fuse sum, which new_padded() / mark_padded() allocate and
+    tag) is read in place instead of being copied."""
+
+    def _check(self):
+        k, s, p = self.kernel_size, self.stride, self.padding
+        if self.padding_mode != "zeros" or isinstance(p, str) or k[0] != k[1] or k[0] not in (1, 3) or s[0] != s[1] or p[0] != p[1] \
+                or self.dilation != (1, 1) or self.groups != 1:
+            raise NotImplementedError("Conv2dNHWCBias: 1x1 / 3x3, square stride and padding, no dilation or groups")
+
+    @property
+    def cout_pad(self):
+        """Channels of the (padded) output gradient the backward works on."""
+        return -(-self.out_channels // _CIN_GRANULE) * _CIN_GRANULE
+
+    @property
+    def cout_fwd(self):
+        """Output rows of the forward's packed weight."""
+        return self.out_channels if self.out_channels % 16 == 0 else self.cout_pad
+
+    def _padded_rows(self, t, rows=None):
+        """Parameter (Cout, ...) -> (rows, ...) with zero rows behind (rows = cout_fwd unless given)."""
+        rows = self.cout_fwd if rows is None else rows
+        if self.out_channels == rows:
+            return t.detach()
+        out = torch.zeros((rows,) + tuple(t.shape[1:]), dtype=torch.float32, device=t.device)
+        out[:self.out_channels].copy_(t.detach())
+        return out
+
+    def _pack(self, mode):
+        from ._lib import KD_PACK_FWD
+        w = self.weight
+        key = (mode, w._version, w.data_ptr())
+        hit = self._packs.get(mode)
+        if hit is None or hit[0] != key:
+            if mode == KD_PACK_FWD:
+                hit = (key, ops.pack_conv_weight(self._padded_rows(w), torch.float32, mode, cin_pad=self.cin_pad))
+            else:
+                hit = (key, ops.pack_conv_weight(self._padded_rows(w, self.cout_pad), torch.float32, mode))
+            self._packs[mode] = hit
+        return hit[1]
+
+    def _shift(self):
+        b = self.bias
+        if b is None:
+            return None
+        key = ("bias", b._version, b.data_ptr())
+        hit = self._packs.get("bias")
+        if hit is None or hit[0] != key:
+            hit = (key, self._padded_rows(b).float().contiguous())
+            self._packs["bias"] = hit
+        return hit[1]
+
+    def _prepadded(self, x):
+        """The (N,H,W,cin_pad) view of an input whose producer left zero channels behind it, or None."""
+        if self.in_channels != self.cin_pad and getattr(x, _PADDED, 0) == self.cin_pad:
+            v = x.detach().permute(0, 2, 3, 1)
+            if v.stride(3) == 1 and v.stride(2) == self.cin_pad:
+                N, H, W, _ = v.shape
+                return v.as_strided((N, H, W, self.cin_pad), v.stride())
+        return None
+
+    def _input(self, x):
+        pre = self._prepadded(x)
+        return pre if pre is not None else super()._input(x.detach())
+
+    def _run_biased(self, xh, scale=None, shift=None, relu=False):
+        """act(scale * (conv(xh) + bias) + shift) -> (N,Ho,Wo,Cout) view; scale / shift are (Cout,) vectors of a folded BN."""
+        from ._lib import KD_PACK_FWD
+        N, H, W, _ = xh.shape
+        k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
+        Ho, Wo = ops.conv_out_size(H, k, s, p, 1), ops.conv_out_size(W, k, s, p, 1)
+        co, cop = self.out_channels, self.cout_fwd
+        out = new_padded((N, Ho, Wo, cop), xh.device)
+        b = self._shift()
+        if scale is not None:
+            b = shift if b is None else shift + scale * b[:co]
+        if scale is not None and co != cop:
+            scale, b = self._padded_rows(scale), self._padded_rows(b)
+        if b is None and scale is None:
+            ops.conv2d(xh, self._pack(KD_PACK_FWD), s, p, out_raw=out)
+        else:
+            ops.conv2d(xh, self._pack(KD_PACK_FWD), s, p, out_act=out, act_scale=None if scale is None else scale.contiguous(),
+                       act_shift=b.contiguous(), act_relu=relu)
+        return out if co == cop else out[..., :co]
+
+    def run_folded(self, x, bn, relu):
+        """relu?(bn(conv(x) + bias)) for an eval-mode BatchNorm2dNHWC in ONE launch (no autograd: frozen layers only)."""
+        self._check()
+        s, b = bn.folded()
+        return mark_padded(self._run_biased(self._input(x), s, b, relu).permute(0, 3, 1, 2))
+
+    def _wgrad(self, xh, g):
+        k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
+        dw = torch.empty((self.cout_pad, xh.shape[3], k, k), dtype=torch.float32, device=g.device)
+        if k == 1 and s == 1:
+            ops.pw_wgrad(xh, g, dw)
+        else:
+            ops.conv2d_wgrad(xh, g, dw, s, p, 1)
+        if dw.shape[0] == self.out_channels and dw.shape[1] == self.in_channels:
+            return dw
+        return dw[:self.out_channels, :self.in_channels].contiguous()
+
+    def forward(self, x, residual=None, out=None):
+        if residual is not None or out is not None:
+            raise ValueError("Conv2dNHWCBias: no residual / out operands")
+        if _host(x):
+            return nn.Conv2d.forward(self, x)
+        self._check()
+        if x.dtype != torch.float32:
+            raise TypeError("Conv2dNHWCBias is fp32")
+        return mark_padded(_ConvBiasNHWCFn.apply(x, self.weight, self.bias, self, self._input(x)))
+
+
+def _copy_into(src, dst):
+    """dst = src for two (N,H,W,C) views (dst a channel slice of a wider buffer): one kd_copy_cast."""
+    s, d = src.permute(0, 3, 1, 2), dst.permute(0, 3, 1, 2)
+    try:
+        ops.copy_cast(s, d)
+    except ValueError:              # (rows that are not one plane: make them so first)
+        ops.copy_cast(s.contiguous(), d)

@@ -1806,3 +1806,136 @@ def radam_step(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay):
     # the kernel wrote through raw pointers: tell autograd / version-keyed caches (engine weight packs) about it
     for t in (p, m, v):
         torch.autograd.graph.increment_version(t)
+
+
+# ------------------------------------------------------------------------- HRNetV2 + OCR (csrc/hrnet_ops.hip)
+def _f32_views(name, *ts):
+    for t in ts:
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32):
+            raise (_lib.KdccError if not t.is_cuda else TypeError)(f"{name}: fp32 device tensors only (there is no CPU fallback)")
+
+
+def _pixel_ld(t):
+    """nhwc_ld() that also takes extents of 1, whose strides torch leaves arbitrary (a 1x1 source of the fuse sum)."""
+    if t.dim() != 4 or (t.shape[3] > 1 and t.stride(3) != 1):
+        raise ValueError(f"expected an (N,H,W,C) tensor with dense channels, got shape {tuple(t.shape)} stride {t.stride()}")
+    N, H, W, Cc = t.shape
+    ld = t.stride(2) if W > 1 else t.stride(1) if H > 1 else t.stride(0) if N > 1 else Cc
+    if ld < Cc or (H > 1 and t.stride(1) != W * ld) or (N > 1 and t.stride(0) != H * W * ld):
+        raise ValueError(f"not a pixel-strided NHWC view: shape {tuple(t.shape)} stride {t.stride()}")
+    return ld
+
+
+def _hr_views(ts, shape_nc, name):
+    arr = (_lib.HrView * len(ts))()
+    for i, t in enumerate(ts):
+        if t is None:
+            arr[i].ptr, arr[i].H, arr[i].W, arr[i].ld = None, 0, 0, 0
+            continue
+        if t.dim() != 4 or (t.shape[0], t.shape[3]) != shape_nc:
+            raise ValueError(f"{name}: source {i} has shape {tuple(t.shape)}, expected (N,H,W,C) with (N, C) = {shape_nc}")
+        arr[i].ptr, arr[i].H, arr[i].W, arr[i].ld = t.data_ptr(), t.shape[1], t.shape[2], _pixel_ld(t)
+    return arr
+
+
+def hr_fuse(srcs, size=None, out=None):
+    """y = relu(sum_s sample(srcs[s])): 1..4 (N,H_s,W_s,C) fp32 views; a source of the output size (Ho, Wo) -- srcs[0]'s unless
+    `size` / `out` says otherwise -- is read directly, a coarser one sampled bilinearly (align_corners=True)."""
+    _f32_views("hr_fuse", *srcs, out)
+    N, Cc = srcs[0].shape[0], srcs[0].shape[3]
+    Ho, Wo = (out.shape[1], out.shape[2]) if out is not None else (size or srcs[0].shape[1:3])
+    if out is None:
+        out = torch.empty((N, Ho, Wo, Cc), dtype=torch.float32, device=srcs[0].device)
+    if tuple(out.shape) != (N, Ho, Wo, Cc):
+        raise ValueError("hr_fuse: bad output view")
+    arr = _hr_views(srcs, (N, Cc), "hr_fuse")
+    check(_lib.lib().kd_hr_fuse_fwd(arr, len(srcs), _ptr(out), _pixel_ld(out), N, Ho, Wo, Cc, stream_ptr()), "kd_hr_fuse_fwd")
+    return out
+
+
+def hr_fuse_bwd(gy, y, sizes, need=None):
+    """Gradients of hr_fuse's sources from gy and the forward's y: sizes = [(H_s, W_s)], need[s] False skips that source (None)."""
+    _f32_views("hr_fuse_bwd", gy, y)
+    N, Ho, Wo, Cc = y.shape
+    if tuple(gy.shape) != (N, Ho, Wo, Cc):
+        raise ValueError("hr_fuse_bwd: gy must have y's shape")
+    need = [True] * len(sizes) if need is None else list(need)
+    outs = [torch.empty((N, h, w, Cc), dtype=torch.float32, device=y.device) if nd else None for (h, w), nd in zip(sizes, need)]
+    arr = _hr_views(outs, (N, Cc), "hr_fuse_bwd")
+    check(_lib.lib().kd_hr_fuse_bwd(_ptr(gy), _pixel_ld(gy), _ptr(y), _pixel_ld(y), arr, len(outs), N, Ho, Wo, Cc, stream_ptr()), "kd_hr_fuse_bwd")
+    return outs
+
+
+def _rows3(t, name):
+    """(N, HW, C) view with dense channels and one pixel stride -> that stride."""
+    if t.dim() != 3 or t.stride(2) != 1 or (t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.stride(1)) or t.stride(1) < t.shape[2]:
+        raise ValueError(f"{name}: expected an (N,HW,C) view with dense channels, got shape {tuple(t.shape)} stride {t.stride()}")
+    return t.stride(1)
+
+
+def ocr_gather(logits, feats):
+    """logits (N,HW,K), feats (N,HW,C) -> ctx (N,K,C) = softmax_HW(logits)^T . feats, and (mx, lse) (N,K) for the backward."""
+    _f32_views("ocr_gather", logits, feats)
+    N, HW, K = logits.shape
+    Cc = feats.shape[2]
+    if tuple(feats.shape[:2]) != (N, HW):
+        raise ValueError("ocr_gather: logits and feats must share (N, HW)")
+    ctx = torch.empty((N, K, Cc), dtype=torch.float32, device=feats.device)
+    mx, lse = torch.empty((N, K), dtype=torch.float32, device=feats.device), torch.empty((N, K), dtype=torch.float32, device=feats.device)
+    need = _lib.lib().kd_ocr_gather_workspace(N, HW, K, Cc)
+    ws = _ws(need, feats.device)
+    check(_lib.lib().kd_ocr_gather_fwd(_ptr(logits), _rows3(logits, "ocr_gather"), _ptr(feats), _rows3(feats, "ocr_gather"), _ptr(ctx), _ptr(mx),
+                                       _ptr(lse), N, HW, K, Cc, _ptr(ws), need, stream_ptr()), "kd_ocr_gather_fwd")
+    return ctx, mx, lse
+
+
+def ocr_gather_bwd(gctx, ctx, logits, feats, lse):
+    """-> (d_feats (N,HW,C), d_logits (N,HW,K)); the probabilities are recomputed from logits and lse."""
+    _f32_views("ocr_gather_bwd", gctx, ctx, logits, feats, lse)
+    N, HW, K = logits.shape
+    Cc = feats.shape[2]
+    gctx, ctx, lse = gctx.contiguous(), ctx.contiguous(), lse.contiguous()
+    if tuple(gctx.shape) != (N, K, Cc) or tuple(ctx.shape) != (N, K, Cc) or tuple(lse.shape) != (N, K):
+        raise ValueError("ocr_gather_bwd: operand mismatch")
+    d_feats = torch.empty((N, HW, Cc), dtype=torch.float32, device=feats.device)
+    d_logits = torch.empty((N, HW, K), dtype=torch.float32, device=feats.device)
+    need = _lib.lib().kd_ocr_gather_workspace(N, HW, K, Cc)
+    ws = _ws(need, feats.device)
+    check(_lib.lib().kd_ocr_gather_bwd(_ptr(gctx), _ptr(ctx), _ptr(logits), _rows3(logits, "ocr_gather_bwd"), _ptr(feats),
+                                       _rows3(feats, "ocr_gather_bwd"), _ptr(lse), _ptr(d_feats), Cc, _ptr(d_logits), K, N, HW, K, Cc, _ptr(ws),
+                                       need, stream_ptr()), "kd_ocr_gather_bwd")
+    return d_feats, d_logits
+
+
+def ocr_attend(query, key, value, scale=None):
+    """query (N,HW,Ck), key / value (N,K,Ck) -> ctx (N,HW,Ck) = softmax_K(scale * query . key^T) . value; scale defaults to Ck^-0.5."""
+    _f32_views("ocr_attend", query, key, value)
+    N, HW, Ck = query.shape
+    K = key.shape[1]
+    key, value = key.contiguous(), value.contiguous()
+    if tuple(key.shape) != (N, K, Ck) or tuple(value.shape) != (N, K, Ck):
+        raise ValueError("ocr_attend: key / value must be (N,K,Ck)")
+    scale = float(Ck) ** -0.5 if scale is None else float(scale)
+    ctx = torch.empty((N, HW, Ck), dtype=torch.float32, device=query.device)
+    check(_lib.lib().kd_ocr_attend_fwd(_ptr(query), _rows3(query, "ocr_attend"), _ptr(key), _ptr(value), _ptr(ctx), Ck, N, HW, K, Ck,
+                                       C.c_float(scale), stream_ptr()), "kd_ocr_attend_fwd")
+    return ctx
+
+
+def ocr_attend_bwd(g, query, key, value, scale=None):
+    """-> (d_query, d_key, d_value) of ocr_attend from g = d ctx (N,HW,Ck)."""
+    _f32_views("ocr_attend_bwd", g, query, key, value)
+    N, HW, Ck = query.shape
+    K = key.shape[1]
+    key, value = key.contiguous(), value.contiguous()
+    if tuple(g.shape) != (N, HW, Ck) or tuple(key.shape) != (N, K, Ck) or tuple(value.shape) != (N, K, Ck):
+        raise ValueError("ocr_attend_bwd: operand mismatch")
+    scale = float(Ck) ** -0.5 if scale is None else float(scale)
+    dq = torch.empty((N, HW, Ck), dtype=torch.float32, device=query.device)
+    dk, dv = torch.empty_like(key), torch.empty_like(value)
+    need = _lib.lib().kd_ocr_attend_workspace(N, HW, K, Ck)
+    ws = _ws(need, query.device)
+    check(_lib.lib().kd_ocr_attend_bwd(_ptr(g), _rows3(g, "ocr_attend_bwd"), _ptr(query), _rows3(query, "ocr_attend_bwd"), _ptr(key), _ptr(value),
+                                       _ptr(dq), Ck, _ptr(dk), _ptr(dv), N, HW, K, Ck, C.c_float(scale), _ptr(ws), need, stream_ptr()),
+          "kd_ocr_attend_bwd")
+    return dq, dk, dv

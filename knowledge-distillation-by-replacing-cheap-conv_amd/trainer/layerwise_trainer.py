@@ -139,7 +139,7 @@ class LayerwiseTrainer(BaseTrainer):
             return
         from ..parallel import GradReducer, broadcast_module
         broadcast_module(self.model.student)   # replicas start from rank 0's weights (new blocks come from each rank's RNG)
-        if getattr(self.model, "fused", False):
+        if getattr(self.model, "engine_plan", False):
             eng = self.model._student_engine()
             self._reducer = GradReducer(eng.grad_production_order())
             eng.reducer = self._reducer
@@ -148,8 +148,8 @@ class LayerwiseTrainer(BaseTrainer):
             self._reducer = GradReducer(params)
 
     def _reduce_unfused_grads(self):
-        """Non-fused students (plain module graphs): all-reduce after backward."""
-        if self.world_size == 1 or getattr(self.model, "fused", False):
+        """Students without an engine plan (module graphs, HRNet included): all-reduce after backward."""
+        if self.world_size == 1 or getattr(self.model, "engine_plan", False):
             return
         for p in self._reducer.params:
             self._reducer.grad_buffer(p).copy_(p.grad)

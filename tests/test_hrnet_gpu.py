@@ -1,0 +1,455 @@
+"""HRNetV2 + OCR on the GPU: the fuse-sum and OCR kernels against fp64 host compositions, the biased conv subclass, the cheap-conv
+block at the shipped plan's 9x9 / dilation 5 / padding 20 geometry on maps smaller than the padding, the whole narrow network
+against the reference's own results (tests/golden/hrnet.npz, tools/make_golden_hrnet.py) and one LayerwiseTrainer step.
+
+Bounds.  Kernel tests compare fp32 results with an fp64 composition of the same fp32 inputs: 1e-5 rel-L2 for the fuse sum (a
+handful of fp32 products and sums per element), 1e-4 for the OCR contractions (exponentials of arguments up to 60 in magnitude
+carry 60 * 2^-23 = 7e-6 each, summed over 77 pixels or 19 classes), 1e-3 -- the project's parity bar -- where a convolution is
+involved.  Whole-network tests use the goldens' rule: max(1e-3, 3 x the reference's own fp32-vs-fp64 deviation)."""
+import copy
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+
+from _hrnetref import seeded_target  # noqa: E402
+from _hrnetref import HINT_CLASSES, INPUT_SHAPE, NARROW, PLAN, PLAN_ARGS, TAG, bound, project, rel_l2, seeded_fill_, seeded_input  # noqa: E402
+from _seeded import sample_idx  # noqa: E402
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+CFG = os.path.join(GOLDEN, "cfg", "cityscapes", "10M_hrnet_all.json")
+FUSE_SIZES = [(9, 13), (5, 7), (3, 4), (1, 1)]     # odd extents, a non-integer ratio, the zero-scale case
+
+
+def _nhwc(t):
+    """NCHW host tensor -> (N,H,W,C) fp32 device tensor."""
+    return t.float().permute(0, 2, 3, 1).contiguous().cuda()
+
+
+def _nchw(t):
+    return t.detach().cpu().permute(0, 3, 1, 2).double()
+
+
+def _close(got, ref, tol, what=""):
+    err = rel_l2(got, ref)
+    print(f"{what}: rel-L2 {err:.3e} (bound {tol:.1e})")
+    assert err <= tol, f"{what}: {err:.3e} > {tol:.1e}"
+
+
+# ------------------------------------------------------------------------------------------------ fuse sum
+def _fuse_ref(srcs, gy, need):
+    xs = [s.double().requires_grad_(nd) for s, nd in zip(srcs, need)]
+    size = xs[0].shape[-2:]
+    y = None
+    for x in xs:
+        v = x if x.shape[-2:] == size else F.interpolate(x, size=size, mode="bilinear", align_corners=True)
+        y = v if y is None else y + v
+    y = F.relu(y)
+    y.backward(gy.double())
+    return y.detach(), [x.grad for x in xs]
+
+
+@pytest.mark.parametrize("C", [16, 48])
+@pytest.mark.parametrize("nsrc,skip", [(4, None), (3, None), (2, None), (4, 1), (4, 0)])
+def test_fuse_sum_forward_and_backward(C, nsrc, skip):
+    from kdcc_amd import ops
+    srcs = [seeded_input(f"fuse{C}.{i}", (2, C, h, w)) for i, (h, w) in enumerate(FUSE_SIZES[:nsrc])]
+    gy = seeded_input(f"fuse{C}.gy", (2, C, 9, 13))
+    need = [i != skip for i in range(nsrc)]
+    y_ref, g_ref = _fuse_ref(srcs, gy, need)
+    dev = [_nhwc(s) for s in srcs]
+    y = ops.hr_fuse(dev)
+    _close(_nchw(y), y_ref, 1e-5, "y")
+    gs = ops.hr_fuse_bwd(_nhwc(gy), y, FUSE_SIZES[:nsrc], need)
+    again = ops.hr_fuse_bwd(_nhwc(gy), y, FUSE_SIZES[:nsrc], need)
+    for i, (g, g2, r) in enumerate(zip(gs, again, g_ref)):
+        if not need[i]:
+            assert g is None
+            continue
+        _close(_nchw(g), r, 1e-5, f"d src{i}")
+        assert torch.equal(g, g2)                      # fixed-order gather: bit-identical
+    assert torch.equal(ops.hr_fuse(dev), y)
+
+
+def test_fuse_sum_reads_and_writes_channel_slices():
+    """Sources and output as channel slices of wider buffers (ld > C), the output sized by an explicit `size`."""
+    from kdcc_amd import ops
+    a, b = seeded_input("fuse.sl.a", (2, 16, 5, 7)), seeded_input("fuse.sl.b", (2, 16, 9, 13))
+    wide_a, wide_b = torch.zeros(2, 5, 7, 32, device="cuda"), torch.zeros(2, 9, 13, 48, device="cuda")
+    wide_a[..., 16:] = _nhwc(a)
+    wide_b[..., 32:] = _nhwc(b)
+    out = torch.full((2, 9, 13, 64), 7.0, device="cuda")
+    ops.hr_fuse([wide_a[..., 16:], wide_b[..., 32:]], out=out[..., 4:20])
+    ref = F.relu(F.interpolate(a.double(), size=(9, 13), mode="bilinear", align_corners=True) + b.double())
+    _close(_nchw(out[..., 4:20]), ref, 1e-5, "y")
+    assert bool((out[..., :4] == 7).all()) and bool((out[..., 20:] == 7).all())
+
+
+def test_fuse_module_function_differentiates():
+    from kdcc_amd.models.hrnet_ocr import fuse_sum
+    srcs = [seeded_input(f"fusefn.{i}", (2, 48, h, w)) for i, (h, w) in enumerate(FUSE_SIZES[:3])]
+    gy = seeded_input("fusefn.gy", (2, 48, 5, 7))
+    order = [srcs[1], srcs[0][:, :, :5, :7].contiguous(), srcs[2]]          # two 5x7 sources and a 3x4 one; the output takes order[1]'s size
+    xs = [s.double().requires_grad_(True) for s in order]
+    ref = F.relu(xs[0] + xs[1] + F.interpolate(xs[2], size=(5, 7), mode="bilinear", align_corners=True))
+    ref.backward(gy.double())
+    dev = [s.cuda().contiguous(memory_format=torch.channels_last).requires_grad_(i != 1) for i, s in enumerate(order)]
+    y = fuse_sum(dev, at=1)
+    y.backward(gy.cuda())
+    _close(y.detach().cpu(), ref.detach(), 1e-5, "y")
+    assert dev[1].grad is None
+    _close(dev[0].grad.cpu(), xs[0].grad, 1e-5, "d src0")
+    _close(dev[2].grad.cpu(), xs[2].grad, 1e-5, "d src2")
+
+
+# ------------------------------------------------------------------------------------------------ OCR
+@pytest.mark.parametrize("spread,C", [(1.0, 40), (30.0, 40), (1.0, 512)])
+def test_ocr_gather_forward_and_backward(spread, C):
+    """C = 512 (the shipped mid channels): two channel steps per lane in the backward, two channel blocks in the contraction."""
+    from kdcc_amd import ops
+    N, HW, K = 2, 77, 19
+    logits = seeded_input("gather.l", (N, HW, K))
+    if spread != 1.0:
+        logits = logits / logits.abs().max() * spread                  # spread over +-30: needs the max subtraction
+    feats, gctx = seeded_input("gather.f", (N, HW, C)), seeded_input("gather.g", (N, K, C))
+    l64, f64 = logits.double().requires_grad_(True), feats.double().requires_grad_(True)
+    ref = torch.matmul(F.softmax(l64, dim=1).transpose(1, 2), f64)
+    ref.backward(gctx.double())
+    ld, fd = logits.cuda(), feats.cuda()
+    ctx, mx, lse = ops.ocr_gather(ld, fd)
+    _close(ctx.cpu(), ref.detach(), 1e-4, "ctx")
+    _close(mx.cpu(), logits.double().max(dim=1).values, 1e-6, "max")
+    _close(lse.cpu(), torch.logsumexp(logits.double(), dim=1), 1e-5, "lse")
+    df, dl = ops.ocr_gather_bwd(gctx.cuda(), ctx, ld, fd, lse)
+    _close(df.cpu(), f64.grad, 1e-4, "d feats")
+    _close(dl.cpu(), l64.grad, 1e-4, "d logits")
+    df2, dl2 = ops.ocr_gather_bwd(gctx.cuda(), ctx, ld, fd, lse)
+    assert torch.equal(df, df2) and torch.equal(dl, dl2) and torch.equal(ops.ocr_gather(ld, fd)[0], ctx)
+
+
+def test_ocr_gather_takes_strided_views():
+    """logits as a 19-channel view of a 32-channel buffer (what the padded class head produces), feats as a slice."""
+    from kdcc_amd import ops
+    N, HW, K, C = 2, 77, 19, 40
+    logits, feats = seeded_input("gather.l", (N, HW, K)), seeded_input("gather.f", (N, HW, C))
+    lw, fw = torch.zeros(N, HW, 32, device="cuda"), torch.zeros(N, HW, 64, device="cuda")
+    lw[..., :K] = logits.cuda()
+    fw[..., 8:48] = feats.cuda()
+    a = ops.ocr_gather(lw[..., :K], fw[..., 8:48])
+    b = ops.ocr_gather(logits.cuda(), feats.cuda())
+    assert all(torch.equal(u, v) for u, v in zip(a, b))
+
+
+@pytest.mark.parametrize("spread,Ck", [(1.0, 32), (30.0, 32), (1.0, 256), (1.0, 320)])
+def test_ocr_attend_forward_and_backward(spread, Ck):
+    """Ck = 256 (the shipped key channels): every lane of the wave owns channels; Ck = 320: a second channel step per lane and a
+    second channel block of the key / value gradient contraction."""
+    from kdcc_amd import ops
+    N, HW, K = 2, 77, 19
+    q, k, v = (seeded_input("attend." + n, s) for n, s in (("q", (N, HW, Ck)), ("k", (N, K, Ck)), ("v", (N, K, Ck))))
+    if spread != 1.0:                                                      # scores spread over about +-30
+        sc = torch.matmul(q, k.transpose(1, 2)) * Ck ** -0.5
+        q = q * (spread / sc.abs().max())
+    g = seeded_input("attend.g", (N, HW, Ck))
+    q64, k64, v64 = (t.double().requires_grad_(True) for t in (q, k, v))
+    ref = torch.matmul(F.softmax(torch.matmul(q64, k64.transpose(1, 2)) * Ck ** -0.5, dim=-1), v64)
+    ref.backward(g.double())
+    qd, kd, vd, gd = q.cuda(), k.cuda(), v.cuda(), g.cuda()
+    ctx = ops.ocr_attend(qd, kd, vd)
+    _close(ctx.cpu(), ref.detach(), 1e-4, "ctx")
+    dq, dk, dv = ops.ocr_attend_bwd(gd, qd, kd, vd)
+    _close(dq.cpu(), q64.grad, 1e-4, "d query")
+    _close(dk.cpu(), k64.grad, 1e-4, "d key")
+    _close(dv.cpu(), v64.grad, 1e-4, "d value")
+    again = ops.ocr_attend_bwd(gd, qd, kd, vd)
+    assert all(torch.equal(a, b) for a, b in zip((dq, dk, dv), again)) and torch.equal(ops.ocr_attend(qd, kd, vd), ctx)
+
+
+def test_ocr_kernels_refuse_what_they_do_not_implement():
+    from kdcc_amd import ops
+    from kdcc_amd._lib import KdccError
+    z = lambda *s: torch.zeros(*s, device="cuda")
+    with pytest.raises(KdccError):
+        ops.ocr_gather(z(1, 8, 33), z(1, 8, 8))                # K > 32
+    with pytest.raises(KdccError):
+        ops.ocr_attend(z(1, 8, 6), z(1, 4, 6), z(1, 4, 6))     # Ck % 4
+    with pytest.raises(KdccError):
+        ops.ocr_gather(torch.zeros(1, 8, 4), torch.zeros(1, 8, 8))   # host tensors
+
+
+# ------------------------------------------------------------------------------------------------ cheap-conv block, small maps
+@pytest.mark.parametrize("hw", [(2, 3), (4, 4)])
+def test_depthwise_block_with_padding_beyond_the_map(hw):
+    """9x9 / dilation 5 / padding 20 on 2x3 and 4x4 maps: most taps fall outside.  Forward and all three gradients."""
+    from kdcc_amd.models.students.transform_blocks import DepthwiseSeparableBlock
+    C = 64
+    blk = seeded_fill_(DepthwiseSeparableBlock(C, C, 9, 20, 5, C, None), "dwsmall.")
+    x, gy = seeded_input("dwsmall.x", (2, C, *hw)), seeded_input("dwsmall.gy", (2, C, *hw))
+    x64 = x.double().requires_grad_(True)
+    wd, wp = blk.separable_conv.weight.detach().double().requires_grad_(True), blk.pointwise_conv.weight.detach().double().requires_grad_(True)
+    ref = F.conv2d(F.conv2d(x64, wd, padding=20, dilation=5, groups=C), wp)
+    ref.backward(gy.double())
+    blk = blk.cuda()
+    xd = x.cuda().contiguous(memory_format=torch.channels_last).requires_grad_(True)
+    y = blk(xd)
+    y.backward(gy.cuda())
+    _close(y.detach().cpu(), ref.detach(), 1e-3, "y")
+    _close(xd.grad.cpu(), x64.grad, 1e-3, "dx")
+    _close(blk.separable_conv.weight.grad.cpu(), wd.grad, 1e-3, "d depthwise weight")
+    _close(blk.pointwise_conv.weight.grad.cpu(), wp.grad, 1e-3, "d pointwise weight")
+
+
+# ------------------------------------------------------------------------------------------------ biased conv
+@pytest.mark.parametrize("k", [1, 3])
+def test_biased_conv(k):
+    from kdcc_amd.nn_hip import Conv2dNHWCBias
+    conv = seeded_fill_(Conv2dNHWCBias(48, 19, kernel_size=k, padding=k // 2), f"cb{k}.")
+    x, gy = seeded_input(f"cb{k}.x", (2, 48, 5, 7)), seeded_input(f"cb{k}.gy", (2, 19, 5, 7))
+    x64 = x.double().requires_grad_(True)
+    w64, b64 = conv.weight.detach().double().requires_grad_(True), conv.bias.detach().double().requires_grad_(True)
+    ref = F.conv2d(x64, w64, b64, padding=k // 2)
+    ref.backward(gy.double())
+    conv = conv.cuda()
+    xd = x.cuda().contiguous(memory_format=torch.channels_last).requires_grad_(True)
+    y = conv(xd)
+    assert tuple(y.shape) == (2, 19, 5, 7)
+    y.backward(gy.cuda())
+    _close(y.detach().cpu(), ref.detach(), 1e-3, "y")
+    _close(xd.grad.cpu(), x64.grad, 1e-3, "dx")
+    _close(conv.weight.grad.cpu(), w64.grad, 1e-3, "dw")
+    _close(conv.bias.grad.cpu(), b64.grad, 1e-3, "db")
+    conv.bias.requires_grad_(False)                    # the channel sum is taken only when the bias wants it
+    conv.zero_grad()
+    conv(xd).backward(gy.cuda())
+    assert conv.bias.grad is None and conv.weight.grad is not None
+
+
+def test_biased_conv_folds_an_eval_bn():
+    from kdcc_amd.nn_hip import BatchNorm2dNHWC, Conv2dNHWCBias
+    from kdcc_amd.models.hrnet_ocr import conv_bn
+    conv, bn = seeded_fill_(Conv2dNHWCBias(48, 64, kernel_size=3, padding=1), "cbf.c."), seeded_fill_(BatchNorm2dNHWC(64), "cbf.b.").eval()
+    x = seeded_input("cbf.x", (2, 48, 5, 7))
+    ref = F.relu(F.batch_norm(F.conv2d(x.double(), conv.weight.double(), conv.bias.double(), padding=1), bn.running_mean.double(),
+                              bn.running_var.double(), bn.weight.double(), bn.bias.double(), False, 0.1, bn.eps))
+    conv, bn = conv.cuda(), bn.cuda()
+    with torch.no_grad():
+        y = conv_bn(conv, bn, x.cuda().contiguous(memory_format=torch.channels_last), True)
+    _close(y.cpu(), ref.detach(), 1e-3, "y")
+
+
+# ------------------------------------------------------------------------------------------------ padded concatenation
+@pytest.mark.parametrize("k", [1, 3])
+def test_padded_concatenation_is_read_in_place(k, monkeypatch):
+    """Branches 16 / 48 / 64 / 80 = 208 channels, no multiple of 32 (the W48 model's 720): concat_upsampled() writes them into a
+    224-stride buffer with a zero tail and the biased conv reads that buffer in place -- the same pointer, no padded copy --
+    forward, dx of every branch, dw and db against the fp64 host composition."""
+    from kdcc_amd import nn_hip
+    from kdcc_amd.models.hrnet_ocr import concat_upsampled
+    chans, sizes = [16, 48, 64, 80], [(6, 10), (3, 5), (2, 3), (1, 2)]
+    conv = seeded_fill_(nn_hip.Conv2dNHWCBias(208, 64, kernel_size=k, padding=k // 2), f"cat{k}.")
+    xs = [seeded_input(f"cat{k}.x{i}", (2, c, h, w)) for i, (c, (h, w)) in enumerate(zip(chans, sizes))]
+    gy = seeded_input(f"cat{k}.gy", (2, 64, 6, 10))
+    x64 = [x.double().requires_grad_(True) for x in xs]
+    w64, b64 = conv.weight.detach().double().requires_grad_(True), conv.bias.detach().double().requires_grad_(True)
+    cat64 = torch.cat([x64[0]] + [F.interpolate(x, size=(6, 10), mode="bilinear", align_corners=True) for x in x64[1:]], 1)
+    ref = F.conv2d(cat64, w64, b64, padding=k // 2)
+    ref.backward(gy.double())
+    conv = conv.cuda()
+    xd = [x.cuda().contiguous(memory_format=torch.channels_last).requires_grad_(True) for x in xs]
+    feats = concat_upsampled(xd)
+    assert tuple(feats.shape) == (2, 208, 6, 10) and feats.permute(0, 2, 3, 1).stride() == (6 * 10 * 224, 10 * 224, 224, 1)
+    view = conv._input(feats)                                   # what the conv's kernels are handed
+    assert view.data_ptr() == feats.data_ptr() and tuple(view.shape) == (2, 6, 10, 224) and view.stride() == (6 * 10 * 224, 10 * 224, 224, 1)
+    assert bool((view[..., 208:] == 0).all())
+    _close(feats.detach().cpu(), cat64.detach(), 1e-5, "concatenation")
+
+    def no_copy(*a, **kw):
+        raise AssertionError("the padded concatenation was copied")
+    monkeypatch.setattr(nn_hip, "_nhwc_padded", no_copy)
+    y = conv(feats)
+    y.backward(gy.cuda())
+    _close(y.detach().cpu(), ref.detach(), 1e-3, "y")
+    for i, (a, b) in enumerate(zip(xd, x64)):
+        _close(a.grad.cpu(), b.grad, 1e-3, f"d branch {i}")
+    _close(conv.weight.grad.cpu(), w64.grad, 1e-3, "dw")
+    _close(conv.bias.grad.cpu(), b64.grad, 1e-3, "db")
+
+
+def test_network_with_a_padded_concatenation(monkeypatch):
+    """The narrow network with branches 16 / 48 / 64 / 80: aux_head.0 and conv3x3_ocr.0 read the 208-channel concatenation in
+    place (no padded copy of a 208-channel tensor is made), and the logits equal the fp64 host graph."""
+    from kdcc_amd import models, nn_hip
+    cfg = copy.deepcopy(NARROW)
+    cfg["extra"]["STAGE4"]["NUM_CHANNELS"] = [16, 48, 64, 80]
+    net = seeded_fill_(models.HighResolutionNet(cfg), TAG + "80.").eval()
+    x = seeded_input(TAG + "x", INPUT_SHAPE)
+    host = copy.deepcopy(net).double()
+    nn_hip.allow_host_tensors(True)
+    try:
+        with torch.no_grad():
+            ref = host(x.double())
+    finally:
+        nn_hip.allow_host_tensors(False)
+    copied, orig = [], nn_hip._nhwc_padded
+    monkeypatch.setattr(nn_hip, "_nhwc_padded", lambda t, cpad: (copied.append(t.shape[1]), orig(t, cpad))[1])
+    net = net.cuda()
+    with torch.no_grad():
+        y = net(x.cuda())
+    _close(y.cpu(), ref, 1e-3, "logits")
+    # only the 3-channel image is padded by a copy: the 16- / 48- / 80-channel maps and the concatenation live in padded buffers
+    assert copied == [3], copied
+
+
+# ------------------------------------------------------------------------------------------------ the narrow network
+@pytest.fixture(scope="module")
+def g():
+    return np.load(os.path.join(GOLDEN, "hrnet.npz"))
+
+
+@pytest.fixture(scope="module")
+def teacher():
+    from kdcc_amd import models
+    return seeded_fill_(models.HighResolutionNet(copy.deepcopy(NARROW)), TAG).eval().cuda()
+
+
+def _sampled(y):
+    f = y.detach().float().cpu().contiguous().reshape(-1)
+    return f[sample_idx(f.numel())]
+
+
+def _x():
+    return seeded_input(TAG + "x", INPUT_SHAPE).cuda()
+
+
+def test_network_eval_logits(g, teacher):
+    with torch.no_grad():
+        y = teacher(_x())
+    assert tuple(y.shape) == (2, 19, 64, 96)
+    _close(_sampled(y), g["eval_logits"], bound(g, "eval_logits"), "eval logits")
+
+
+def test_network_train_logits(g, teacher):
+    net = copy.deepcopy(teacher).train()
+    for m in net.modules():
+        if isinstance(m, torch.nn.Dropout2d):
+            m.p = 0.0
+    with torch.no_grad():
+        y = net(_x())
+    _close(_sampled(y), g["train_logits"], bound(g, "train_logits"), "train logits")
+
+
+def test_network_with_the_plan_hints_loss_and_gradients(g, teacher):
+    from kdcc_amd import losses
+    from kdcc_amd.models.students import DepthwiseStudent
+    model = DepthwiseStudent(teacher, None)
+    model.replace([{"name": n, "epoch": 1} for n in PLAN], **PLAN_ARGS)
+    for n in PLAN:
+        seeded_fill_(model.get_block(n, model.student), f"{TAG}student.{n}.")
+    model.register_hint_layers(PLAN)
+    model.unfreeze(PLAN)
+    assert model.fused and not model.engine_plan
+    s, t = model(_x())
+    _close(_sampled(s), g["student_logits"], bound(g, "student_logits"), "student logits")
+    _close(_sampled(t), g["teacher_logits"], bound(g, "teacher_logits"), "teacher logits")
+    crit = losses.MSELoss(reduction="mean", num_classes=HINT_CLASSES)
+    assert len(model.student_hidden_outputs) == len(model.teacher_hidden_outputs) == len(PLAN)
+    loss = sum(crit(a, b) for a, b in zip(model.student_hidden_outputs, model.teacher_hidden_outputs))
+    loss.backward()
+    for i, (a, b) in enumerate(zip(model.student_hidden_outputs, model.teacher_hidden_outputs)):
+        _close(a.detach().cpu().contiguous().reshape(-1), g[f"hint_s{i}"], bound(g, f"hint_s{i}"), f"student hint {i}")
+        _close(b.detach().cpu().contiguous().reshape(-1), g[f"hint_t{i}"], bound(g, f"hint_t{i}"), f"teacher hint {i}")
+    _close(loss.detach().cpu().reshape(1), g["hint_loss"].reshape(1), bound(g, "hint_loss"), "hint loss")
+    target = seeded_target().cuda()
+    ce, kd = losses.CrossEntropyLoss2d(ignore_index=255), losses.MSELoss(reduction="mean", num_classes=1)
+    with torch.no_grad():
+        terms = {"supervised_loss": ce(s, target), "kd_loss": kd(s, t), "teacher_loss": ce(t, target)}
+    for k, v in terms.items():
+        _close(v.detach().cpu().reshape(1), g[k].reshape(1), bound(g, k), k)
+    trainable = sorted(n for n, p in model.student.named_parameters() if p.requires_grad)
+    assert trainable == [str(n) for n in g["trainable"]]
+    for n, p in model.student.named_parameters():
+        if p.requires_grad:
+            _close(project(p.grad, n), g["grad:" + n], bound(g, "grad:" + n), "grad " + n)
+        else:
+            assert p.grad is None
+
+
+def test_network_differentiates_through_the_head(teacher):
+    """Every layer trainable, loss on the logits: the fuse, gather, attention, concat and biased-conv backwards all run, and the
+    result equals the host graph (torch base classes, autograd) in fp64.  Bound per tensor, by the goldens' rule: the 1e-3 parity
+    bar or three times the deviation of the SAME host graph run in fp32 from its fp64 run, whichever is larger (the softmax
+    Jacobians of the OCR head cancel leading terms, so some of these gradients are ill-conditioned in fp32 for anybody)."""
+    from kdcc_amd import nn_hip
+    net = copy.deepcopy(teacher).eval()
+    x, gy = _x(), seeded_input(TAG + "gy", (2, 19, 64, 96))
+    for p in net.parameters():
+        p.requires_grad_(True)
+    net(x).backward(gy.cuda())
+    hosts = {}
+    nn_hip.allow_host_tensors(True)
+    try:
+        for dt in (torch.float64, torch.float32):
+            host = copy.deepcopy(net).cpu().to(dt)
+            host.zero_grad()
+            host(x.cpu().to(dt)).backward(gy.to(dt))
+            hosts[dt] = {n: p.grad for n, p in host.named_parameters()}
+    finally:
+        nn_hip.allow_host_tensors(False)
+    mine = {n: p.grad for n, p in net.named_parameters()}
+    bad = []
+    for n in ("conv1.weight", "stage2.0.branches.0.0.conv1.weight", "stage3.0.fuse_layers.0.2.0.weight", "stage4.0.fuse_layers.3.0.2.0.weight",
+              "stage4.0.branches.3.0.conv2.weight", "aux_head.0.weight", "aux_head.0.bias", "aux_head.3.weight", "conv3x3_ocr.0.weight",
+              "ocr_distri_head.object_context_block.f_pixel.0.weight", "ocr_distri_head.object_context_block.f_object.2.weight",
+              "ocr_distri_head.object_context_block.f_down.0.weight", "ocr_distri_head.object_context_block.f_up.0.weight",
+              "ocr_distri_head.conv_bn_dropout.0.weight", "cls_head.weight", "cls_head.bias"):
+        ref = hosts[torch.float64][n]
+        own = rel_l2(hosts[torch.float32][n], ref)
+        err, tol = rel_l2(mine[n].cpu(), ref), max(1e-3, 3.0 * own)
+        print(f"grad {n}: rel-L2 {err:.3e} (host fp32 {own:.3e}, bound {tol:.1e})")
+        if err > tol:
+            bad.append((n, err, tol))
+    assert not bad, bad
+    # (aux_head.3.bias shifts every pixel's logit of a class alike, which the softmax over the pixels cancels: its gradient is
+    # zero up to rounding, so it is bounded against the weight gradient's scale instead of against itself)
+    assert float(mine["aux_head.3.bias"].norm()) <= 1e-4 * float(mine["aux_head.3.weight"].norm())
+
+
+def test_one_layerwise_trainer_step(tmp_path):
+    """The stored config, shrunk to the narrow model and a 64x96 crop: one step runs, the losses are finite and only the
+    trainable weights change."""
+    from kdcc_amd import ConfigParser, losses, models
+    from kdcc_amd.models.students import DepthwiseStudent
+    from kdcc_amd.trainer import LayerwiseTrainer
+    from kdcc_amd.utils import WeightScheduler
+    from kdcc_amd.utils import optim as optim_module
+    cfg = json.load(open(CFG))
+    cfg["teacher"] = {"type": "HighResolutionNet", "args": {"config": copy.deepcopy(NARROW), "num_classes": 19}}
+    for k in ("pruning_plan", "hint", "unfreeze"):
+        cfg["pruning"][k] = [e for e in cfg["pruning"][k] if e["name"] in PLAN]
+        assert len(cfg["pruning"][k]) == len(PLAN)
+    cfg["trainer"].update(save_dir=str(tmp_path), tensorboard=False, verbosity=0, monitor="off", len_epoch=1, epochs=1, dtype="fp32")
+    cfg["metrics"] = []
+    config = ConfigParser(cfg, run_id="hr")
+    teacher = seeded_fill_(config.init_obj("teacher", models), TAG).eval()
+    model = DepthwiseStudent(teacher, config)
+    assert model.dtype == torch.float32
+    crit = [config.init_obj(k, losses) for k in ("supervised_loss", "kd_loss", "hint_loss")]
+    opt = config.init_obj("optimizer", optim_module, model.student.parameters())
+    sched = config.init_obj("lr_scheduler", optim_module.lr_scheduler, opt)
+    target = torch.randint(0, 19, (2, 64, 96), generator=torch.Generator().manual_seed(5))
+    tr = LayerwiseTrainer(model, crit, [], opt, config, [(seeded_input(TAG + "x", INPUT_SHAPE), target)], None, sched,
+                          WeightScheduler(config["weight_scheduler"]))
+    tr.prepare_train_epoch(1)
+    before = {n: p.detach().clone() for n, p in model.student.named_parameters()}
+    tr.prepare_train_epoch = lambda epoch: None               # (already prepared above, so that `before` holds the new blocks)
+    log = tr._train_epoch(1)
+    for k in ("loss", "supervised_loss", "kd_loss", "hint_loss", "teacher_loss"):
+        assert np.isfinite(float(log[k])), k
+    assert float(log["hint_loss"]) > 0
+    changed = sorted(n for n, p in model.student.named_parameters() if not torch.equal(p.detach(), before[n]))
+    assert changed == sorted(f"{n}.{c}.weight" for n in PLAN for c in ("separable_conv", "pointwise_conv"))

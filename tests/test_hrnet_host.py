@@ -1,0 +1,115 @@
+"""HRNetV2 + OCR, host side (no GPU): the module tree equals the reference's, the narrow test config builds, the shipped plan
+applies, hint names are validated at registration, and the `fused` / `engine_plan` predicates of DepthwiseStudent."""
+import copy
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import kdcc_amd  # noqa: F401
+from kdcc_amd import models, nn_hip
+from kdcc_amd.engine import EngineError
+from kdcc_amd.models import cifar_models
+from kdcc_amd.models.students import DepthwiseStudent, TaylorPruneStudent
+
+from _hrnetref import INPUT_SHAPE, NARROW, PLAN, PLAN_ARGS, TAG, bound, rel_l2, seeded_fill_, seeded_input
+from _seeded import sample_idx
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+CFG = os.path.join(GOLDEN, "cfg", "cityscapes", "10M_hrnet_all.json")
+
+
+def test_default_state_dict_equals_the_reference():
+    ref = json.load(open(os.path.join(GOLDEN, "hrnet_keys.json")))
+    with torch.device("meta"):
+        m = models.HighResolutionNet(num_classes=19)          # (extra kwargs are accepted and ignored, as in the reference)
+    mine = {k: list(v.shape) for k, v in m.state_dict().items()}
+    assert list(mine) == list(ref["keys"])                    # same keys in the same order
+    assert mine == ref["keys"]
+    assert sum(p.numel() for p in m.parameters()) == ref["num_params"]
+
+
+def test_default_config_is_a_module_level_dict_and_is_not_modified():
+    from kdcc_amd.models import hrnet_ocr
+    before = copy.deepcopy(hrnet_ocr.DEFAULT_CONFIG)
+    assert before["extra"]["STAGE4"]["NUM_CHANNELS"] == [48, 96, 192, 384] and before["ocr.mid_channels"] == 512
+    assert before["ocr.key_channels"] == 256 and before["num_classes"] == 19 and before["align_corners"] is True
+    assert [before["extra"]["STAGE%d" % i]["NUM_MODULES"] for i in (2, 3, 4)] == [1, 4, 3]
+    with torch.device("meta"):
+        models.HighResolutionNet()
+    assert hrnet_ocr.DEFAULT_CONFIG == before
+
+
+def test_narrow_config_builds_and_matches_the_reference_on_the_host():
+    """The narrow config builds; in host plumbing mode (torch base classes) its eval logits equal the reference's."""
+    g = np.load(os.path.join(GOLDEN, "hrnet.npz"))
+    m = seeded_fill_(models.HighResolutionNet(copy.deepcopy(NARROW)), TAG).eval()
+    assert m.aux_head[0].in_channels == 16 + 48 + 64 + 96
+    nn_hip.allow_host_tensors(True)
+    try:
+        with torch.no_grad():
+            y = m(seeded_input(TAG + "x", INPUT_SHAPE))
+    finally:
+        nn_hip.allow_host_tensors(False)
+    assert tuple(y.shape) == (2, 19, 64, 96)
+    got = y.contiguous().reshape(-1)[sample_idx(y.numel())]
+    assert rel_l2(got, g["eval_logits"]) <= bound(g, "eval_logits")
+
+
+def _apply_shipped_plan(student_cls=DepthwiseStudent):
+    cfg = json.load(open(CFG))
+    with torch.device("meta"):
+        teacher = getattr(models, cfg["teacher"]["type"])(**cfg["teacher"]["args"])
+        model = student_cls(teacher, None)
+        pr = cfg["pruning"]
+        model.replace(pr["pruning_plan"], **pr["args"])
+    model.register_hint_layers([e["name"] for e in pr["hint"]])
+    model.unfreeze([e["name"] for e in pr["unfreeze"]])
+    return model, cfg
+
+
+def test_shipped_plan_leaves_exactly_the_cheap_conv_weights_trainable():
+    model, cfg = _apply_shipped_plan()
+    names = [e["name"] for e in cfg["pruning"]["pruning_plan"]]
+    assert len(names) == 8
+    trainable = sorted(n for n, p in model.student.named_parameters() if p.requires_grad)
+    assert trainable == sorted(f"{n}.{c}.weight" for n in names for c in ("separable_conv", "pointwise_conv")) and len(trainable) == 16
+    blk = model.get_block(names[0], model.student)
+    assert blk.geometry == (9, 20, 5) and blk.in_channels == blk.out_channels == 384
+    assert model.dtype == torch.float32
+
+
+def test_unresolvable_hint_name_raises_at_registration():
+    model, _ = _apply_shipped_plan()
+    for bad in (["stage4.0.branches.9.0.conv1"], ["stage4.0.nothing"], ["stage4.0.branches.3.0.bn1"], ["relu"],
+                ["ocr_distri_head.object_context_block.f_pixel.1"]):     # a BN + ReLU pair that forward never calls as a module
+        with pytest.raises(EngineError):
+            model.register_hint_layers(bad)
+    model.register_hint_layers(["stage4.0.branches.3.0", "stage4.0.branches.3", "stage4.0.branches.3.1.conv2",      # block, branch, conv
+                                "ocr_distri_head.object_context_block.f_pixel", "stage4.0.fuse_layers.0.1", "aux_head"])
+
+
+def test_predicates():
+    model, _ = _apply_shipped_plan()
+    assert model.fused and not model.engine_plan
+    with torch.device("meta"):
+        for teacher, both in ((models.DeepWV3Plus(num_classes=19), True), (models.GSCNN(num_classes=19), True),
+                              (cifar_models.wrn(depth=10, num_classes=10, widen_factor=1), False),
+                              (cifar_models.DenseNet(block_config=(1, 1), num_classes=10), False)):
+            for cls in (DepthwiseStudent, TaylorPruneStudent):
+                s = cls(teacher, None)
+                assert s.fused is both and s.engine_plan is both, type(teacher).__name__
+
+
+def test_host_tensor_and_bf16_are_refused():
+    with torch.device("meta"):
+        teacher = models.HighResolutionNet(copy.deepcopy(NARROW))
+    with pytest.raises(TypeError):
+        DepthwiseStudent(teacher, None, dtype=torch.bfloat16)
+    model = DepthwiseStudent(seeded_fill_(models.HighResolutionNet(copy.deepcopy(NARROW)), TAG), None)
+    with pytest.raises(RuntimeError):
+        model(torch.zeros(1, 3, 64, 96))
+    with pytest.raises(RuntimeError):
+        model.inference(torch.zeros(1, 3, 64, 96))
