@@ -33,7 +33,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ... import nn_hip, ops
-from ...nn_hip import AvgPool2x2NHWC, BatchNorm2dNHWC, Conv2dNHWC, GradChain, MaxPool3x3s2NHWC
+from ...nn_hip import AvgPool2x2NHWC, BatchNorm2dNHWC, Conv2dNHWC, GradChain, MaxPool3x3s2NHWC, _copy_cast, _hooked
 
 __all__ = ["DenseNet", "densenet121", "densenet169", "densenet201", "densenet161"]
 
@@ -49,17 +49,6 @@ def _take_stats(x, bn):
     if not bn.training or st[0] != bn.eps or st[1].numel() != bn.num_features:
         return None
     return st[1:]
-
-
-def _hooked(*mods):
-    return any(m._forward_hooks or m._forward_pre_hooks for m in mods)
-
-
-def _copy_in(src, dst):
-    try:
-        ops.copy_cast(src, dst)
-    except ValueError:              # (rows that are not one plane: make them so first)
-        ops.copy_cast(src.contiguous(), dst)
 
 
 class _BlockState:
@@ -92,7 +81,7 @@ class _EnterFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, st):
         c0 = x.shape[1]
-        _copy_in(x, st.view(0, c0))
+        _copy_cast(x, st.view(0, c0))
         return st.view(0, c0)
 
     @staticmethod
@@ -109,7 +98,7 @@ class _AppendFn(torch.autograd.Function):
         ctx.c_in = c_in
         c1 = c_in + new.shape[1]
         if copy:
-            _copy_in(new, st.view(c_in, c1))
+            _copy_cast(new, st.view(c_in, c1))
         return st.view(0, c1)
 
     @staticmethod

@@ -19,7 +19,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ... import nn_hip
-from ...nn_hip import BatchNorm2dNHWC, Conv2dNHWC
+from ...nn_hip import BatchNorm2dNHWC, Conv2dNHWC, _nhwc
 
 __all__ = ["wrn", "WideResNet"]
 
@@ -58,7 +58,6 @@ class BasicBlock(nn.Module):
                 and (self.convShortcut is None or type(self.convShortcut) is nn_hip.Conv2dNHWC))
 
     def _forward_fused(self, x):
-        from ...nn_hip import _nhwc
         a = _take_act(x, self.bn1)
         if a is None:
             a = self.bn1(x, relu=True)

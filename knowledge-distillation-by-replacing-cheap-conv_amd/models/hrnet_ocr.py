@@ -6,7 +6,8 @@ loads through forgiving_state_restore and the plan names of the shipped config (
 Same constructor: HighResolutionNet(config=DEFAULT_CONFIG, **kwargs), extra kwargs (num_classes=19) accepted and ignored.
 
 Channels-last fp32 throughout, as in cifar_models/wrn.py and densenet.py: convolutions are nn_hip.Conv2dNHWCBias (Conv2dNHWC
-with an optional bias and any output channel count), BatchNorm nn_hip.BatchNorm2dNHWC following the module's training flag.  What is specific to this network:
+with pad_channels on: any output channel count, outputs in granule-padded buffers), BatchNorm nn_hip.BatchNorm2dNHWC following
+the module's training flag.  What is specific to this network:
 
   * the exchange unit of a HighResolutionModule -- upsample every coarser branch, add, ReLU -- is one kd_hr_fuse_fwd pass per
     output branch (backward kd_hr_fuse_bwd); the 1x1 conv + BN of a coarser branch and the strided 3x3 chains of a finer one stay
@@ -32,7 +33,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import nn_hip, ops
-from ..nn_hip import BatchNorm2dNHWC, Conv2dNHWCBias
+from ..nn_hip import BatchNorm2dNHWC, Conv2dNHWCBias, _hooked
 
 __all__ = ["HighResolutionNet", "DEFAULT_CONFIG"]
 
@@ -54,8 +55,6 @@ DEFAULT_CONFIG = {
     "ocr.key_channels": 256,
     "num_classes": 19,
 }
-
-_GRANULE = nn_hip._CIN_GRANULE
 
 
 # ------------------------------------------------------------------------------------------------ autograd wrappers
@@ -165,11 +164,7 @@ class _ConcatUpFn(torch.autograd.Function):
     def forward(ctx, *xs):
         hs = [nn_hip._nhwc(x) for x in xs]
         N, H, W, _ = hs[0].shape
-        total = sum(h.shape[3] for h in hs)
-        cpad = -(-total // _GRANULE) * _GRANULE
-        buf = torch.empty((N, H, W, cpad), dtype=torch.float32, device=hs[0].device)
-        if cpad != total:
-            buf[..., total:].zero_()
+        buf = nn_hip.new_padded((N, H, W, sum(h.shape[3] for h in hs)), hs[0].device)
         c0 = 0
         for h in hs:
             c1 = c0 + h.shape[3]
@@ -179,8 +174,7 @@ class _ConcatUpFn(torch.autograd.Function):
                 ops.upsample_bilinear_ac(h, (H, W), out=buf[..., c0:c1])
             c0 = c1
         ctx.sizes = [tuple(h.shape[1:]) for h in hs]
-        out = buf[..., :total].permute(0, 3, 1, 2)
-        return out
+        return buf.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, gy):
@@ -202,10 +196,7 @@ def concat_upsampled(xs):
     if nn_hip._host(xs[0]):
         size = xs[0].shape[-2:]
         return torch.cat([xs[0]] + [F.interpolate(x, size=size, mode="bilinear", align_corners=True) for x in xs[1:]], 1)
-    out = _ConcatUpFn.apply(*xs)
-    total = out.shape[1]
-    setattr(out, nn_hip._PADDED, -(-total // _GRANULE) * _GRANULE)
-    return out
+    return nn_hip.mark_padded(_ConcatUpFn.apply(*xs))
 
 
 class _Concat2Fn(torch.autograd.Function):
@@ -233,10 +224,6 @@ def concat2(a, b):
 
 
 # ------------------------------------------------------------------------------------------------ conv + BN (+ ReLU)
-def _hooked(*mods):
-    return any(m._forward_hooks or m._forward_pre_hooks for m in mods)
-
-
 def _needs_graph(x, *mods):
     return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for m in mods for p in m.parameters()))
 
@@ -254,15 +241,11 @@ def conv_bn(conv, bn, x, relu):
     return F.relu(y) if relu else y
 
 
-def _bn_relu():
-    return nn.ReLU(inplace=True)
-
-
 class _ConvBN(nn.Sequential):
     """Sequential(conv, bn[, relu]) with the reference's child indices, run through conv_bn()."""
 
     def __init__(self, conv, bn, relu):
-        super().__init__(conv, bn, *([_bn_relu()] if relu else []))
+        super().__init__(conv, bn, *([nn.ReLU(inplace=True)] if relu else []))
 
     def forward(self, x):
         return conv_bn(self[0], self[1], x, len(self) > 2)
@@ -291,8 +274,8 @@ class _ConvBNReLUChain(nn.Sequential):
         return x
 
 
-# (Conv2dNHWCBias also without a bias: its backward takes output channel counts that are no multiple of 32 -- 48, and the
-# narrow test configs' 16 -- which Conv2dNHWC's input gradient does not)
+# (the pad_channels flavour for every layer: its backward takes output channel counts that are no multiple of 32 -- 48, and
+# the narrow test configs' 16 -- which the dense flavour's input gradient does not)
 def _conv3x3(cin, cout, stride=1):
     return Conv2dNHWCBias(cin, cout, kernel_size=3, stride=stride, padding=1, bias=False)
 

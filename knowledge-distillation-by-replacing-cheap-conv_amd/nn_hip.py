@@ -8,12 +8,14 @@ host plumbing mode was switched on explicitly (`allow_host_tensors(True)`: BaseT
 reference's CPU plumbing case, BASELINE config 1 -- and the CPU-only host-logic tests do it themselves).  In that mode the
 modules behave exactly like their torch base classes; it is never the measured or parity-tested path.
 """
+import copy
+
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from . import ops
-from ._lib import KdccError
+from ._lib import KD_PACK_DGRAD, KD_PACK_FWD, KdccError
 
 _HOST_OK = False
 
@@ -31,6 +33,25 @@ def _host(x):
         raise KdccError("kdcc nn_hip modules got a host tensor: the HIP kernels need device tensors and there is no silent CPU "
                         "fallback (host plumbing runs, `n_gpu: 0`, call nn_hip.allow_host_tensors(True) -- BaseTrainer does)")
     return True
+
+
+def _one(v):
+    """A square geometry argument (an int, or a pair of equal ints) as one int; anything else comes back as given."""
+    return v[0] if isinstance(v, (tuple, list)) and len({*v}) == 1 else v
+
+
+def _hooked(*mods):
+    return any(m._forward_hooks or m._forward_pre_hooks for m in mods)
+
+
+def _deepcopy_without(mod, memo, **fresh):
+    """copy.deepcopy(mod) that does not carry the cached device tensors over: the attributes named in `fresh` start from the
+    values given there."""
+    new = mod.__class__.__new__(mod.__class__)
+    memo[id(mod)] = new
+    new.__dict__.update({k: copy.deepcopy(v, memo) for k, v in mod.__dict__.items() if k not in fresh})
+    new.__dict__.update(fresh)
+    return new
 
 
 class _DirectConv(torch.autograd.Function):
@@ -60,8 +81,7 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, dilation=1, groups=1):
         return F.conv2d(x, weight, bias, stride, padding, dilation, groups)
     if x.dtype != torch.float32:
         raise TypeError("the small-shape conv kernels are fp32 (the CIFAR path of the reference is fp32)")
-    one = lambda v: v[0] if isinstance(v, (tuple, list)) else v
-    return _DirectConv.apply(x, weight, bias, one(stride), one(padding), one(dilation), groups)
+    return _DirectConv.apply(x, weight, bias, _one(stride), _one(padding), _one(dilation), groups)
 
 
 class _BatchNorm(torch.autograd.Function):
@@ -108,10 +128,28 @@ class BatchNorm2d(nn.BatchNorm2d):
                                 float(self.eps), bool(relu))
 
 
-# ------------------------------------------------------------------ channels-last modules (Wide-ResNet CIFAR path)
+# ------------------------------------------------------------------ channels-last modules (Wide-ResNet, DenseNet, HRNet-OCR)
 # NCHW-logical tensors with NHWC strides (torch.channels_last): the MFMA implicit-GEMM convolutions (kd_conv2d_fwd /
 # kd_conv2d_wgrad / kd_pw_wgrad, fp32) and BatchNorm on NHWC views (kd_bn_nhwc_*) read and write them without a layout copy.
 _CIN_GRANULE = 32      # fp32 K granule of kd_conv2d_fwd: fewer input channels are zero-padded up to it (the 3->16 stem, 16->160)
+_PADDED = "_nhwc_pad"  # tensor attribute: its NHWC storage continues with zero channels up to this pixel stride
+
+
+def _granule_up(c):
+    return -(-c // _CIN_GRANULE) * _CIN_GRANULE
+
+
+def _copy_cast(src, dst):
+    """dst = src for two (N,C,H,W)-logical tensors of any dense-plane layout: one kd_copy_cast."""
+    try:
+        ops.copy_cast(src, dst)
+    except ValueError:              # (rows that are not one plane: make them so first)
+        ops.copy_cast(src.contiguous(), dst)
+
+
+def _copy_into(src, dst):
+    """dst = src for two (N,H,W,C) views (dst a channel slice of a wider buffer)."""
+    _copy_cast(src.permute(0, 3, 1, 2), dst.permute(0, 3, 1, 2))
 
 
 def _nhwc(t):
@@ -125,10 +163,7 @@ def _nhwc(t):
         pass
     N, Cc, H, W = t.shape
     out = torch.empty((N, H, W, Cc), dtype=t.dtype, device=t.device)
-    try:
-        ops.copy_cast(t, out.permute(0, 3, 1, 2))
-    except ValueError:              # (rows that are not one plane: make them so first)
-        ops.copy_cast(t.contiguous(), out.permute(0, 3, 1, 2))
+    _copy_cast(t, out.permute(0, 3, 1, 2))
     return out
 
 
@@ -136,99 +171,183 @@ def _nhwc_padded(t, cpad):
     """(N,C,H,W)-logical tensor -> (N,H,W,cpad) fp32 buffer, channels >= C zero (the conv's K granule)."""
     N, Cc, H, W = t.shape
     out = torch.zeros((N, H, W, cpad), dtype=t.dtype, device=t.device)
-    src = t if t.dim() == 4 else t.reshape(N, Cc, H, W)
-    try:
-        ops.copy_cast(src, out[..., :Cc].permute(0, 3, 1, 2))
-    except ValueError:
-        ops.copy_cast(src.contiguous(), out[..., :Cc].permute(0, 3, 1, 2))
+    _copy_cast(t, out[..., :Cc].permute(0, 3, 1, 2))
     return out
 
 
+def new_padded(shape, device):
+    """(N,H,W,C) fp32 view for a kernel to fill.  When C is no multiple of the conv granule the view is the channel prefix of a
+    buffer whose pixel stride is the granule above C, with a zero tail: tagged with mark_padded(), a conv reads it in place."""
+    N, H, W, Cc = shape
+    buf = torch.empty((N, H, W, _granule_up(Cc)), dtype=torch.float32, device=device)
+    if buf.shape[3] != Cc:
+        buf[..., Cc:].zero_()
+    return buf[..., :Cc]
+
+
+def mark_padded(t):
+    """Tag an NCHW-logical tensor whose storage came from new_padded() (and was written through its view only)."""
+    v = t.permute(0, 2, 3, 1)
+    cpad = _granule_up(v.shape[3])
+    if cpad != v.shape[3] and v.stride(3) == 1 and v.stride(2) == cpad:
+        setattr(t, _PADDED, cpad)
+    return t
+
+
 class _ConvNHWCFn(torch.autograd.Function):
+    """xh: the module's input view (Conv2dNHWC._input of x), made by the caller, where x still carries its padding tag."""
+
     @staticmethod
-    def forward(ctx, x, weight, res, mod, out=None):
-        xh = mod._input(x)
-        out = mod._run(xh, res_pre=None if res is None else _nhwc(res), raw_into=out)
+    def forward(ctx, x, weight, bias, res, mod, xh, out):
+        y = mod._run(xh, res_pre=None if res is None else _nhwc(res), raw_into=out)
         ctx.mod = mod
         ctx.in_shape = tuple(x.shape)
         ctx.save_for_backward(xh if weight.requires_grad else None)
-        return out.permute(0, 3, 1, 2)
+        return y.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, gy):
         mod = ctx.mod
         (xh,) = ctx.saved_tensors
-        g = _nhwc(gy)
-        dx = dw = None
+        co, cop = mod.out_channels, mod.cout_pad
+        g = _nhwc(gy) if co == cop else _nhwc_padded(gy, cop)
+        dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = mod._dgrad(g, ctx.in_shape).permute(0, 3, 1, 2)
         if ctx.needs_input_grad[1]:
             dw = mod._wgrad(xh, g)
-        return dx, dw, gy if ctx.needs_input_grad[2] else None, None, None
+        if ctx.needs_input_grad[2]:       # the bias gradient is a channel sum, taken only when somebody wants it
+            db = ops.channel_sums(g)[0][:co]
+        return dx, dw, db, gy if ctx.needs_input_grad[3] else None, None, None, None
 
 
 class Conv2dNHWC(nn.Conv2d):
-    """nn.Conv2d (3x3 or 1x1, square stride / padding, no groups, no bias) on channels-last fp32 device tensors:
+    """nn.Conv2d (3x3 or 1x1, square stride / padding, no groups, optional bias) on channels-last fp32 device tensors:
     forward kd_conv2d_fwd; input gradient kd_conv2d_fwd on KD_PACK_DGRAD weights (zero-inserted first for stride 2);
-    weight gradient kd_conv2d_wgrad / kd_pw_wgrad, computed only for a weight that requires grad.  Packed weights are cached
-    per parameter version: a frozen weight is packed once, a trained one once per optimizer step.  Fewer than 32 input
-    channels are zero-padded to 32 (weights packed with cin_pad, the input copied into a zeroed 32-channel buffer).
+    weight gradient kd_conv2d_wgrad / kd_pw_wgrad, computed only for a weight that requires grad; the bias is the forward
+    epilogue's per-channel shift (scale 1, no ReLU), its gradient a channel sum taken only when it requires grad.  Packed
+    weights (and the shift vector) are cached per parameter version: a frozen one is packed once, a trained one once per
+    optimizer step.  Fewer than 32 input channels are zero-padded to 32 (weights packed with cin_pad, the input copied into a
+    zeroed 32-channel buffer); an input whose storage is already zero-padded to that granule (tagged by its producer, see
+    new_padded() / mark_padded()) is read in place instead.
     forward(x, residual=None, out=None): residual (the block's shortcut) is added in the conv's epilogue; out, an (N,Ho,Wo,Cout)
-    fp32 NHWC view (a channel slice of a wider buffer: a dense block's), receives the result instead of a fresh tensor."""
+    fp32 NHWC view (a channel slice of a wider buffer: a dense block's), receives the result instead of a fresh tensor.
+    run_folded() puts an eval-mode BN (+ ReLU) into the epilogue as well.
+
+    pad_channels says what happens to an output channel count that is no multiple of the granule.  Off (this class): outputs
+    are dense tensors (or the caller's `out`), the output gradient is used as it arrives, so Cout is what the kernels take.
+    On (Conv2dNHWCBias): see there."""
+
+    pad_channels = False
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
         self._packs = {}
 
     def __deepcopy__(self, memo):
-        import copy
-        new = self.__class__.__new__(self.__class__)      # (the cached device packs are not carried over)
-        memo[id(self)] = new
-        new.__dict__.update({k: copy.deepcopy(v, memo) for k, v in self.__dict__.items() if k != "_packs"})
-        new._packs = {}
-        return new
+        return _deepcopy_without(self, memo, _packs={})
 
     def _check(self):
         k, s, p = self.kernel_size, self.stride, self.padding
         if self.padding_mode != "zeros" or isinstance(p, str) or k[0] != k[1] or k[0] not in (1, 3) or s[0] != s[1] or p[0] != p[1] \
-                or self.dilation != (1, 1) or self.groups != 1 or self.bias is not None:
-            raise NotImplementedError("Conv2dNHWC: 1x1 / 3x3, square stride and padding, no dilation, groups or bias")
+                or self.dilation != (1, 1) or self.groups != 1:
+            raise NotImplementedError(f"{type(self).__name__}: 1x1 / 3x3, square stride and padding, no dilation or groups")
 
     @property
     def cin_pad(self):
-        return -(-self.in_channels // _CIN_GRANULE) * _CIN_GRANULE
+        return _granule_up(self.in_channels)
 
-    def _pack(self, mode):
-        from ._lib import KD_PACK_FWD
-        w = self.weight
-        key = (mode, w._version, w.data_ptr())
-        hit = self._packs.get(mode)
+    @property
+    def cout_pad(self):
+        """Channels of the output gradient the backward works on (and rows of the weights packed for it)."""
+        return _granule_up(self.out_channels) if self.pad_channels else self.out_channels
+
+    @property
+    def cout_fwd(self):
+        """Output rows of the forward's packed weight."""
+        return self.out_channels if self.out_channels % 16 == 0 else self.cout_pad
+
+    def _padded_rows(self, t, rows=None):
+        """Parameter (Cout, ...) -> (rows, ...) with zero rows behind (rows = cout_fwd unless given)."""
+        rows = self.cout_fwd if rows is None else rows
+        if self.out_channels == rows:
+            return t.detach()
+        out = torch.zeros((rows,) + tuple(t.shape[1:]), dtype=torch.float32, device=t.device)
+        out[:self.out_channels].copy_(t.detach())
+        return out
+
+    def _cached(self, what, t, make):
+        key = (what, t._version, t.data_ptr())
+        hit = self._packs.get(what)
         if hit is None or hit[0] != key:
-            cin_pad = self.cin_pad if mode == KD_PACK_FWD else None
-            hit = (key, ops.pack_conv_weight(w, torch.float32, mode, cin_pad=cin_pad))
-            self._packs[mode] = hit
+            hit = self._packs[what] = (key, make())
         return hit[1]
 
+    def _pack(self, mode):
+        w = self.weight
+        rows, cin_pad = (self.cout_fwd, self.cin_pad) if mode == KD_PACK_FWD else (self.cout_pad, None)
+        return self._cached(mode, w, lambda: ops.pack_conv_weight(self._padded_rows(w, rows), torch.float32, mode, cin_pad=cin_pad))
+
+    def _shift(self):
+        """The bias as the epilogue's shift vector (cout_fwd long), or None."""
+        b = self.bias
+        return None if b is None else self._cached("bias", b, lambda: self._padded_rows(b).float().contiguous())
+
+    def _prepadded(self, x):
+        """The (N,H,W,cin_pad) view of an input whose producer left zero channels behind it, or None."""
+        if self.in_channels != self.cin_pad and getattr(x, _PADDED, 0) == self.cin_pad:
+            v = x.detach().permute(0, 2, 3, 1)
+            if v.stride(3) == 1 and v.stride(2) == self.cin_pad:
+                N, H, W, _ = v.shape
+                return v.as_strided((N, H, W, self.cin_pad), v.stride())
+        return None
+
     def _input(self, x):
+        """The (N,H,W,cin_pad) view the kernels read; called where x still carries its padding tag (not inside a Function)."""
+        pre = self._prepadded(x)
+        if pre is not None:
+            return pre
         if self.in_channels != self.cin_pad:
-            return _nhwc_padded(x, self.cin_pad)
-        return _nhwc(x)
+            return _nhwc_padded(x.detach(), self.cin_pad)
+        return _nhwc(x.detach())
 
     def _run(self, xh, res_pre=None, out_act=False, act_scale=None, act_shift=None, act_relu=False, want_raw=True, raw_into=None):
-        """Forward on an (N,H,W,cin_pad) view -> out_raw [, out_act] (N,Ho,Wo,Cout) fp32 buffers (out_raw is raw_into when given)."""
-        from ._lib import KD_PACK_FWD
+        """Forward on an (N,H,W,cin_pad) view: raw = conv(xh) + bias [+ res_pre] and, with out_act, act = relu?(act_scale * raw +
+        act_shift) -> raw [, act], (N,Ho,Wo,Cout) fp32 views (raw is raw_into when given, None without want_raw).  The bias
+        rides in the epilogue's shift, so a biased conv gives raw or act, not both."""
         N, H, W, _ = xh.shape
         k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
         Ho, Wo = ops.conv_out_size(H, k, s, p, 1), ops.conv_out_size(W, k, s, p, 1)
-        new = lambda: torch.empty((N, Ho, Wo, self.out_channels), dtype=torch.float32, device=xh.device)
+        co, rows = self.out_channels, self.cout_fwd
+        if self.pad_channels:
+            new = lambda: new_padded((N, Ho, Wo, rows), xh.device)
+        else:
+            new = lambda: torch.empty((N, Ho, Wo, co), dtype=torch.float32, device=xh.device)
         raw = raw_into if raw_into is not None else (new() if want_raw else None)
         act = new() if out_act else None
-        ops.conv2d(xh, self._pack(KD_PACK_FWD), s, p, res_pre=res_pre, out_raw=raw, out_act=act, act_scale=act_scale,
-                   act_shift=act_shift, act_relu=act_relu)
-        return (raw, act) if out_act else raw
+        k_raw, k_act, b = raw, act, self._shift()
+        if b is not None and out_act:
+            if raw is not None:
+                raise NotImplementedError(f"{type(self).__name__}: a biased conv gives the raw or the activated output, not both")
+            act_shift = act_shift + act_scale * b[:co]
+        elif b is not None:                  # the bias alone is the epilogue: the kernel's activated output is conv + bias
+            k_raw, k_act, act_shift = None, raw, b
+        if act_scale is not None and co != rows:
+            act_scale, act_shift = self._padded_rows(act_scale), self._padded_rows(act_shift)
+        vec = lambda v: None if v is None else v.contiguous()
+        ops.conv2d(xh, self._pack(KD_PACK_FWD), s, p, res_pre=res_pre, out_raw=k_raw, out_act=k_act, act_scale=vec(act_scale),
+                   act_shift=vec(act_shift), act_relu=act_relu)
+        view = lambda t: t if t is None or co == rows else t[..., :co]
+        return (view(raw), view(act)) if out_act else view(raw)
+
+    def run_folded(self, x, bn, relu):
+        """relu?(bn(conv(x) + bias)) for an eval-mode BatchNorm2dNHWC in ONE launch (no autograd: frozen layers only)."""
+        self._check()
+        s, b = bn.folded()
+        y = self._run(self._input(x), out_act=True, act_scale=s, act_shift=b, act_relu=relu, want_raw=False)[1].permute(0, 3, 1, 2)
+        return mark_padded(y) if self.pad_channels else y
 
     def _dgrad(self, g, in_shape):
-        from ._lib import KD_PACK_DGRAD
         N, Cin, H, W = in_shape
         k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
         if s != 1:
@@ -239,23 +358,40 @@ class Conv2dNHWC(nn.Conv2d):
 
     def _wgrad(self, xh, g):
         k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
-        dw = torch.empty((self.out_channels, xh.shape[3], k, k), dtype=torch.float32, device=g.device)
+        dw = torch.empty((self.cout_pad, xh.shape[3], k, k), dtype=torch.float32, device=g.device)
         if k == 1 and s == 1:
             ops.pw_wgrad(xh, g, dw)
         else:
             ops.conv2d_wgrad(xh, g, dw, s, p, 1)
-        return dw if xh.shape[3] == self.in_channels else dw[:, :self.in_channels].contiguous()
+        if dw.shape[0] == self.out_channels and dw.shape[1] == self.in_channels:
+            return dw
+        return dw[:self.out_channels, :self.in_channels].contiguous()
 
     def forward(self, x, residual=None, out=None):
+        name = type(self).__name__
+        if self.pad_channels and (residual is not None or out is not None):
+            raise ValueError(f"{name}: no residual / out operands")
         if _host(x):
             if out is not None:
-                raise ValueError("Conv2dNHWC: out= is a device view")
+                raise ValueError(f"{name}: out= is a device view")
             y = super().forward(x)
             return y if residual is None else y + residual
         self._check()
         if x.dtype != torch.float32:
-            raise TypeError("Conv2dNHWC is fp32 (the CIFAR path of the reference is fp32)")
-        return _ConvNHWCFn.apply(x, self.weight, residual, self, out)
+            raise TypeError(f"{name} is fp32")
+        y = _ConvNHWCFn.apply(x, self.weight, self.bias, residual, self, self._input(x), out)
+        return mark_padded(y) if self.pad_channels else y
+
+
+class Conv2dNHWCBias(Conv2dNHWC):
+    """Conv2dNHWC for any number of output channels (every HRNet layer: the 48-channel branch, the 19 classes of the OCR
+    heads).  An output channel count that is no multiple of 16 is computed with the packed weight and bias zero-padded to the
+    granule (32 rows for the 19 classes); the output is allocated by new_padded(), returned as a channel view of that buffer and
+    tagged by mark_padded(), so that the next conv reads it in place.  In the backward the output gradient is the K operand
+    of the input-gradient conv, so there any count that is no multiple of 32 (48) is zero-padded to the granule, with weights
+    packed to match; the weight gradient is computed at that many rows and sliced.  No residual / out operands."""
+
+    pad_channels = True
 
 
 class _BatchNormNHWCFn(torch.autograd.Function):
@@ -330,12 +466,7 @@ class BatchNorm2dNHWC(nn.BatchNorm2d):
         self._fold = None
 
     def __deepcopy__(self, memo):
-        import copy
-        new = self.__class__.__new__(self.__class__)      # (the cached folded vectors are not carried over)
-        memo[id(self)] = new
-        new.__dict__.update({k: copy.deepcopy(v, memo) for k, v in self.__dict__.items() if k != "_fold"})
-        new._fold = None
-        return new
+        return _deepcopy_without(self, memo, _fold=None)
 
     def _check(self, x):
         if not (self.affine and self.track_running_stats) or self.momentum is None:
@@ -401,8 +532,7 @@ class MaxPool3x3s2NHWC(nn.MaxPool2d):
     def forward(self, x):
         if _host(x):
             return super().forward(x)
-        one = lambda v: v[0] if isinstance(v, (tuple, list)) and len({*v}) == 1 else v
-        if (one(self.kernel_size), one(self.stride), one(self.padding), one(self.dilation)) != (3, 2, 1, 1) or self.ceil_mode \
+        if (_one(self.kernel_size), _one(self.stride), _one(self.padding), _one(self.dilation)) != (3, 2, 1, 1) or self.ceil_mode \
                 or self.return_indices:
             raise NotImplementedError("MaxPool3x3s2NHWC: kernel 3, stride 2, padding 1 only")
         if x.dtype != torch.float32:
@@ -427,192 +557,8 @@ class AvgPool2x2NHWC(nn.AvgPool2d):
     def forward(self, x):
         if _host(x):
             return super().forward(x)
-        one = lambda v: v[0] if isinstance(v, (tuple, list)) and len({*v}) == 1 else v
-        if (one(self.kernel_size), one(self.stride), one(self.padding)) != (2, 2, 0) or self.ceil_mode or self.divisor_override:
+        if (_one(self.kernel_size), _one(self.stride), _one(self.padding)) != (2, 2, 0) or self.ceil_mode or self.divisor_override:
             raise NotImplementedError("AvgPool2x2NHWC: kernel 2, stride 2, no padding only")
         if x.dtype != torch.float32:
             raise TypeError("AvgPool2x2NHWC is fp32")
         return _AvgPool2x2Fn.apply(x)
-
-
-# ------------------------------------------------------------------ biased channels-last conv (HRNet-OCR heads)
-_PADDED = "_nhwc_pad"     # tensor attribute: its NHWC storage continues with zero channels up to this pixel stride
-
-
-def new_padded(shape, device):
-    """(N,H,W,C) fp32 view for a kernel to fill.  When C is no multiple of the conv granule the view is the channel prefix of a
-    buffer whose pixel stride is the granule above C, with a zero tail: tagged with mark_padded(), a conv reads it in place."""
-    N, H, W, Cc = shape
-    cpad = -(-Cc // _CIN_GRANULE) * _CIN_GRANULE
-    if cpad == Cc:
-        return torch.empty(shape, dtype=torch.float32, device=device)
-    buf = torch.empty((N, H, W, cpad), dtype=torch.float32, device=device)
-    buf[..., Cc:].zero_()
-    return buf[..., :Cc]
-
-
-def mark_padded(t):
-    """Tag an NCHW-logical tensor whose storage came from new_padded() (and was written through its view only)."""
-    v = t.permute(0, 2, 3, 1)
-    cpad = -(-v.shape[3] // _CIN_GRANULE) * _CIN_GRANULE
-    if cpad != v.shape[3] and v.stride(3) == 1 and v.stride(2) == cpad:
-        setattr(t, _PADDED, cpad)
-    return t
-
-
-class _ConvBiasNHWCFn(torch.autograd.Function):
-    """xh: the module's input view (Conv2dNHWCBias._input of x), made by the caller, where x still carries its padding tag."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, mod, xh):
-        out = mod._run_biased(xh)
-        ctx.mod = mod
-        ctx.in_shape = tuple(x.shape)
-        ctx.save_for_backward(xh if weight.requires_grad else None)
-        return out.permute(0, 3, 1, 2)
-
-    @staticmethod
-    def backward(ctx, gy):
-        mod = ctx.mod
-        (xh,) = ctx.saved_tensors
-        co, cop = mod.out_channels, mod.cout_pad
-        g = _nhwc(gy) if co == cop else _nhwc_padded(gy, cop)
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            dx = mod._dgrad(g, ctx.in_shape).permute(0, 3, 1, 2)
-        if ctx.needs_input_grad[1]:
-            dw = mod._wgrad(xh, g)
-        if ctx.needs_input_grad[2]:       # the bias gradient is a channel sum, taken only when somebody wants it
-            db = ops.channel_sums(g)[0][:co]
-        return dx, dw, db, None, None
-
-
-class Conv2dNHWCBias(Conv2dNHWC):
-    """Conv2dNHWC with an optional bias and any number of output channels (the OCR heads of HRNet: conv3x3_ocr.0, aux_head.0 / .3,
-    cls_head).  The bias is the conv epilogue's per-channel shift (scale 1, no ReLU), the way the cheap-conv block carries its
-    pointwise bias; run_folded() puts an eval-mode BN (+ ReLU) into the same epilogue.  An output channel count that is no
-    multiple of 16 (the 19 classes) is computed with the packed weight zero-padded to 32 rows and returned as a channel view of
-    that buffer.  In the backward the output gradient is the K operand of the input-gradient conv, so there any count that is
-    no multiple of 32 (HRNet's 48-channel branch) is zero-padded to the granule, with weights packed to match.  With bias=False
-    this is the conv of every HRNet layer.  An input whose storage is
-    already zero-padded to the input granule (attribute set by its producer: HRNet's 720-channel concatenation in a 736-channel
-    buffer; a 48-channel output of another Conv2dNHWCBias or of the fuse sum, which new_padded() / mark_padded() allocate and
-    tag) is read in place instead of being copied."""
-
-    def _check(self):
-        k, s, p = self.kernel_size, self.stride, self.padding
-        if self.padding_mode != "zeros" or isinstance(p, str) or k[0] != k[1] or k[0] not in (1, 3) or s[0] != s[1] or p[0] != p[1] \
-                or self.dilation != (1, 1) or self.groups != 1:
-            raise NotImplementedError("Conv2dNHWCBias: 1x1 / 3x3, square stride and padding, no dilation or groups")
-
-    @property
-    def cout_pad(self):
-        """Channels of the (padded) output gradient the backward works on."""
-        return -(-self.out_channels // _CIN_GRANULE) * _CIN_GRANULE
-
-    @property
-    def cout_fwd(self):
-        """Output rows of the forward's packed weight."""
-        return self.out_channels if self.out_channels % 16 == 0 else self.cout_pad
-
-    def _padded_rows(self, t, rows=None):
-        """Parameter (Cout, ...) -> (rows, ...) with zero rows behind (rows = cout_fwd unless given)."""
-        rows = self.cout_fwd if rows is None else rows
-        if self.out_channels == rows:
-            return t.detach()
-        out = torch.zeros((rows,) + tuple(t.shape[1:]), dtype=torch.float32, device=t.device)
-        out[:self.out_channels].copy_(t.detach())
-        return out
-
-    def _pack(self, mode):
-        from ._lib import KD_PACK_FWD
-        w = self.weight
-        key = (mode, w._version, w.data_ptr())
-        hit = self._packs.get(mode)
-        if hit is None or hit[0] != key:
-            if mode == KD_PACK_FWD:
-                hit = (key, ops.pack_conv_weight(self._padded_rows(w), torch.float32, mode, cin_pad=self.cin_pad))
-            else:
-                hit = (key, ops.pack_conv_weight(self._padded_rows(w, self.cout_pad), torch.float32, mode))
-            self._packs[mode] = hit
-        return hit[1]
-
-    def _shift(self):
-        b = self.bias
-        if b is None:
-            return None
-        key = ("bias", b._version, b.data_ptr())
-        hit = self._packs.get("bias")
-        if hit is None or hit[0] != key:
-            hit = (key, self._padded_rows(b).float().contiguous())
-            self._packs["bias"] = hit
-        return hit[1]
-
-    def _prepadded(self, x):
-        """The (N,H,W,cin_pad) view of an input whose producer left zero channels behind it, or None."""
-        if self.in_channels != self.cin_pad and getattr(x, _PADDED, 0) == self.cin_pad:
-            v = x.detach().permute(0, 2, 3, 1)
-            if v.stride(3) == 1 and v.stride(2) == self.cin_pad:
-                N, H, W, _ = v.shape
-                return v.as_strided((N, H, W, self.cin_pad), v.stride())
-        return None
-
-    def _input(self, x):
-        pre = self._prepadded(x)
-        return pre if pre is not None else super()._input(x.detach())
-
-    def _run_biased(self, xh, scale=None, shift=None, relu=False):
-        """act(scale * (conv(xh) + bias) + shift) -> (N,Ho,Wo,Cout) view; scale / shift are (Cout,) vectors of a folded BN."""
-        from ._lib import KD_PACK_FWD
-        N, H, W, _ = xh.shape
-        k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
-        Ho, Wo = ops.conv_out_size(H, k, s, p, 1), ops.conv_out_size(W, k, s, p, 1)
-        co, cop = self.out_channels, self.cout_fwd
-        out = new_padded((N, Ho, Wo, cop), xh.device)
-        b = self._shift()
-        if scale is not None:
-            b = shift if b is None else shift + scale * b[:co]
-        if scale is not None and co != cop:
-            scale, b = self._padded_rows(scale), self._padded_rows(b)
-        if b is None and scale is None:
-            ops.conv2d(xh, self._pack(KD_PACK_FWD), s, p, out_raw=out)
-        else:
-            ops.conv2d(xh, self._pack(KD_PACK_FWD), s, p, out_act=out, act_scale=None if scale is None else scale.contiguous(),
-                       act_shift=b.contiguous(), act_relu=relu)
-        return out if co == cop else out[..., :co]
-
-    def run_folded(self, x, bn, relu):
-        """relu?(bn(conv(x) + bias)) for an eval-mode BatchNorm2dNHWC in ONE launch (no autograd: frozen layers only)."""
-        self._check()
-        s, b = bn.folded()
-        return mark_padded(self._run_biased(self._input(x), s, b, relu).permute(0, 3, 1, 2))
-
-    def _wgrad(self, xh, g):
-        k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
-        dw = torch.empty((self.cout_pad, xh.shape[3], k, k), dtype=torch.float32, device=g.device)
-        if k == 1 and s == 1:
-            ops.pw_wgrad(xh, g, dw)
-        else:
-            ops.conv2d_wgrad(xh, g, dw, s, p, 1)
-        if dw.shape[0] == self.out_channels and dw.shape[1] == self.in_channels:
-            return dw
-        return dw[:self.out_channels, :self.in_channels].contiguous()
-
-    def forward(self, x, residual=None, out=None):
-        if residual is not None or out is not None:
-            raise ValueError("Conv2dNHWCBias: no residual / out operands")
-        if _host(x):
-            return nn.Conv2d.forward(self, x)
-        self._check()
-        if x.dtype != torch.float32:
-            raise TypeError("Conv2dNHWCBias is fp32")
-        return mark_padded(_ConvBiasNHWCFn.apply(x, self.weight, self.bias, self, self._input(x)))
-
-
-def _copy_into(src, dst):
-    """dst = src for two (N,H,W,C) views (dst a channel slice of a wider buffer): one kd_copy_cast."""
-    s, d = src.permute(0, 3, 1, 2), dst.permute(0, 3, 1, 2)
-    try:
-        ops.copy_cast(s, d)
-    except ValueError:              # (rows that are not one plane: make them so first)
-        ops.copy_cast(s.contiguous(), d)

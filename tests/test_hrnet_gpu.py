@@ -242,6 +242,51 @@ def test_biased_conv_folds_an_eval_bn():
     _close(y.cpu(), ref.detach(), 1e-3, "y")
 
 
+@pytest.mark.parametrize("k", [1, 3])
+def test_dense_flavour_conv_with_a_bias(k):
+    """Conv2dNHWC (pad_channels off) with a bias: the same epilogue shift and channel-sum gradient as the padded flavour."""
+    from kdcc_amd.nn_hip import Conv2dNHWC
+    conv = seeded_fill_(Conv2dNHWC(32, 32, kernel_size=k, padding=k // 2, bias=True), f"cd{k}.")
+    x, gy = seeded_input(f"cd{k}.x", (2, 32, 5, 7)), seeded_input(f"cd{k}.gy", (2, 32, 5, 7))
+    x64 = x.double().requires_grad_(True)
+    w64, b64 = conv.weight.detach().double().requires_grad_(True), conv.bias.detach().double().requires_grad_(True)
+    ref = F.conv2d(x64, w64, b64, padding=k // 2)
+    ref.backward(gy.double())
+    conv = conv.cuda()
+    xd = x.cuda().contiguous(memory_format=torch.channels_last).requires_grad_(True)
+    y = conv(xd)
+    assert tuple(y.shape) == (2, 32, 5, 7)
+    y.backward(gy.cuda())
+    _close(y.detach().cpu(), ref.detach(), 1e-3, "y")
+    _close(xd.grad.cpu(), x64.grad, 1e-3, "dx")
+    _close(conv.weight.grad.cpu(), w64.grad, 1e-3, "dw")
+    _close(conv.bias.grad.cpu(), b64.grad, 1e-3, "db")
+    conv.bias.requires_grad_(False)
+    conv.zero_grad()
+    conv(xd).backward(gy.cuda())
+    assert conv.bias.grad is None and conv.weight.grad is not None
+
+
+def test_output_layout_of_the_two_flavours():
+    """32 -> 16 channels: Conv2dNHWC returns a dense, untagged tensor; Conv2dNHWCBias the 16-channel view of a 32-stride
+    buffer with a zero tail, tagged for the next conv to read in place."""
+    from kdcc_amd import nn_hip
+    x = seeded_input("lay.x", (2, 32, 5, 7)).cuda().contiguous(memory_format=torch.channels_last)
+    for cls, ld in ((nn_hip.Conv2dNHWC, 16), (nn_hip.Conv2dNHWCBias, 32)):
+        conv = seeded_fill_(cls(32, 16, 3, padding=1), "lay.").cuda()
+        with torch.no_grad():
+            y = conv(x)
+        v = y.permute(0, 2, 3, 1)
+        assert tuple(v.shape) == (2, 5, 7, 16) and v.stride() == (5 * 7 * ld, 7 * ld, ld, 1), (cls.__name__, v.stride())
+        if ld == 16:
+            assert not hasattr(y, nn_hip._PADDED)
+        else:
+            assert getattr(y, nn_hip._PADDED) == 32
+            assert bool((v.as_strided((2, 5, 7, 32), v.stride())[..., 16:] == 0).all())
+        _close(y.cpu(), F.conv2d(x.cpu().double(), conv.weight.detach().cpu().double(), conv.bias.detach().cpu().double(), padding=1),
+               1e-3, cls.__name__)
+
+
 # ------------------------------------------------------------------------------------------------ padded concatenation
 @pytest.mark.parametrize("k", [1, 3])
 def test_padded_concatenation_is_read_in_place(k, monkeypatch):

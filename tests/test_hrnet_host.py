@@ -113,3 +113,23 @@ def test_host_tensor_and_bf16_are_refused():
         model(torch.zeros(1, 3, 64, 96))
     with pytest.raises(RuntimeError):
         model.inference(torch.zeros(1, 3, 64, 96))
+
+
+def test_deepcopy_drops_the_device_caches_and_keeps_the_parameters():
+    """The conv's packed weights and the BN's folded vectors are caches of device tensors: a deep copy starts with none."""
+    for m, attr, filled, empty in ((nn_hip.Conv2dNHWC(32, 16, 3, padding=1), "_packs", {0: (("k",), torch.ones(3))}, {}),
+                                   (nn_hip.Conv2dNHWCBias(48, 19, 1), "_packs", {"bias": (("k",), torch.ones(3))}, {}),
+                                   (nn_hip.BatchNorm2dNHWC(16), "_fold", (("k",), (torch.ones(16), torch.zeros(16))), None)):
+        seeded_fill_(m, "dc.")
+        setattr(m, attr, filled)
+        c = copy.deepcopy(m)
+        assert type(c) is type(m) and getattr(c, attr) == empty and getattr(m, attr) is filled
+        sd, sc = m.state_dict(), c.state_dict()
+        assert list(sd) == list(sc) and all(torch.equal(sd[k], sc[k]) and sd[k].data_ptr() != sc[k].data_ptr() for k in sd)
+
+
+def test_the_padded_conv_flavour_is_an_attribute_not_an_implementation():
+    import types
+    assert issubclass(nn_hip.Conv2dNHWCBias, nn_hip.Conv2dNHWC)
+    assert nn_hip.Conv2dNHWCBias.pad_channels is True and nn_hip.Conv2dNHWC.pad_channels is False
+    assert not [k for k, v in vars(nn_hip.Conv2dNHWCBias).items() if isinstance(v, (types.FunctionType, property, staticmethod, classmethod))]
