@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include "conv_common.h"
+#include "conv_select.h"
 
 namespace {
 
@@ -1432,94 +1433,52 @@ __global__ void pack_conv_weight_kernel(const float *__restrict__ src, T *__rest
 
 }  // namespace
 
-// conv_row_lw_kernel (conv_lw.hip: one wave per SIMD, hand-scheduled loop) instead of conv_row_persist_kernel<pp>; A/B: KDCC_CONV_LW=0
-static bool lw_row()
+// the tile table of conv_select.h against the Cfg types the kernels are compiled for
+template <typename CF> constexpr bool tile_is(ConvTile t) { return CF::BM == 256 && CF::BN == t.bn && CF::RB == t.rb; }
+static_assert(tile_is<CfgNarrow>(CONV_TILE_128) && tile_is<CfgWide>(CONV_TILE_256) && tile_is<CfgWideF>(CONV_TILE_256) && tile_is<CfgDeep>(CONV_TILE_256_K64) &&
+                  tile_is<CfgHalf>(CONV_TILE_128_K64) && tile_is<CfgNarrow2>(CONV_TILE_128_K64) && tile_is<CfgRow>(CONV_TILE_256) && tile_is<CfgRowX>(CONV_TILE_256) &&
+                  tile_is<CfgRowF>(CONV_TILE_256) && tile_is<CfgRowXF>(CONV_TILE_256) && tile_is<CfgRowH>(CONV_TILE_128_K64) && tile_is<CfgRowHX>(CONV_TILE_128_K64) &&
+                  tile_is<CfgRowN>(CONV_TILE_128_K64) && CfgRow::MAXDIL == CONV_ROW_MAXDIL && CfgRowX::MAXDIL == CONV_ROWX_MAXDIL && CfgRowN::MAXDIL == CONV_ROWN_MAXDIL,
+              "conv_select.h restates a tile configuration wrongly");
+
+// Every KDCC_* switch this file reads, read once per process.
+static const ConvSwitches &conv_switches()
 {
-    static int lw = -1;
-    if (lw < 0) { const char *v = getenv("KDCC_CONV_LW"); lw = !(v && v[0] == '0'); }
-    return lw != 0;
+    static const ConvSwitches sw = [] {
+        auto on = [](const char *name) { const char *v = getenv(name); return !(v && v[0] == '0') ? 1 : 0; };   // A/B: NAME=0 turns it off
+        auto num = [](const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; };
+        ConvSwitches s;
+        s.lw = on("KDCC_CONV_LW"); s.pp = on("KDCC_CONV_PP"); s.persist = on("KDCC_CONV_PERSIST");
+        s.dual = on("KDCC_CONV_DUAL"); s.epi_batch = on("KDCC_EPI_BATCH");
+        s.duo = num("KDCC_CONV_DUO", 0); s.tngroup = num("KDCC_CONV_TNGROUP", 4); s.persist_cus = num("KDCC_PERSIST_CUS", 0);
+        if (const char *v = getenv("KDCC_CONV_LW_PW")) s.lw_pw = v[0] == '1';   // opt-in
+        if (const char *e = getenv("KDCC_CONV_CFG"))                            // tuning hook
+            s.cfg = !strcmp(e, "narrow") ? CONV_CFG_NARROW : !strcmp(e, "norow") ? CONV_CFG_NOROW : !strcmp(e, "half") ? CONV_CFG_HALF
+                  : !strcmp(e, "deep") ? CONV_CFG_DEEP : !strcmp(e, "narrow1") ? CONV_CFG_NARROW1 : CONV_CFG_DEFAULT;
+        s.tune = KD_TUNING_ENV_INT("KDCC_CONV_TUNE");   // timing ablations / timestamps: tuning build only (kd_common.h)
+        s.stagger_us = KD_TUNING_ENV_INT("KDCC_CONV_STAGGER");
+        return s;
+    }();
+    return sw;
 }
 
-static bool pp_row()
+// CUs of the device current at the first call (256 when it cannot be asked)
+static int conv_ncu()
 {
-    static int pp = -1;
-    if (pp < 0) { const char *v = getenv("KDCC_CONV_PP"); pp = !(v && v[0] == '0'); }   // A/B: KDCC_CONV_PP=0 = lock-step waves
-    return pp != 0;
+    static const int ncu = [] {
+        int dev = 0, n = 0;
+        return hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
+    }();
+    return ncu;
 }
-
-// Which kernel kd_conv2d_fwd runs for a problem (shared with kd_conv2d_bn_sums_rows, which must predict it).
-struct ConvSel {
-    int cfg;   // 0 narrow2, 1 wide, 2 deep, 3 narrow (one workgroup per CU)
-    bool norow, half, row_wide, row_x, row_narrow, vec_ok;
-    int nops, ncu;
-    bool use_row_persist, use_igemm_persist, use_pp128;
-};
-static ConvSel conv_select(const kd_conv_desc *d, const kd_conv_epilogue *ep, int tune)
-{
-    ConvSel c;
-    const int es = kd_elem_size(d->dtype);
-    const int M = d->N * d->Ho * d->Wo;
-    auto ok = [&](const void *ptr, int ld, int esz) { return !ptr || (kd_aligned16(ptr) && (ld * esz) % 16 == 0); };
-    c.vec_ok = ok(ep->res_pre, ep->ld_res_pre, es) && ok(ep->mask, ep->ld_mask, es) &&
-               ok(ep->res_post, ep->ld_res_post, es) && ok(ep->out_raw, ep->ld_raw, ep->raw_f32 ? 4 : es) &&
-               ok(ep->out_act, ep->ld_act, es);
-    // wide tiles only when they still fill the chip (one workgroup per CU, 256 CUs); e.g. the ASPP 4096->256 1x1 at
-    // 128x256 pixels would give 128 wide tiles, so it runs on the narrow config (256 tiles)
-    const long long wide_tiles = (long long)((M + CfgWide::BM - 1) / CfgWide::BM) * ((d->Cout + CfgWide::BN - 1) / CfgWide::BN);
-    c.norow = false; c.half = false;
-    c.cfg = (d->Cout > 128 && wide_tiles >= 224) ? 1 : 0;
-    if (const char *e = getenv("KDCC_CONV_CFG")) {              // tuning hook
-        if (!strcmp(e, "narrow")) c.cfg = 0;
-        else if (!strcmp(e, "norow")) c.norow = true;
-        else if (!strcmp(e, "half")) c.half = true;
-        else if (!strcmp(e, "deep") && c.cfg == 1) c.cfg = 2;
-        else if (!strcmp(e, "narrow1") && c.cfg == 0) c.cfg = 3;
-    }
-    // 256-pixel tiles that are segments of one image row, 3x3 / stride 1 / 'same': row-buffer kernels (the narrow one is
-    // compiled for <= 128 VGPRs, which the fp32 parity path's blocked accumulation does not fit)
-    const bool row_geom = !c.norow && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == d->dil && d->W % 256 == 0;
-    c.row_wide = row_geom && c.cfg == 1 && d->dil <= CfgRowX::MAXDIL;
-    c.row_x = c.row_wide && d->dil > CfgRow::MAXDIL;
-    c.row_narrow = row_geom && c.cfg == 0 && d->dtype == KD_BF16 && d->dil <= CfgRowN::MAXDIL;
-    // persistent kernels (bf16 wide tiles, whole tiles, vector-friendly epilogue): one workgroup per CU walks the tiles
-    static int persist = -1, ncu = 0;
-    if (persist < 0) {
-        const char *v = getenv("KDCC_CONV_PERSIST");
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-            ncu = 256;
-        persist = !(v && v[0] == '0');
-    }
-    c.ncu = ncu;
-    c.nops = (ep->res_pre ? 1 : 0) + (ep->mask ? 1 : 0) + (ep->res_post ? 1 : 0);
-    const bool persist_ok = persist && !c.half && d->dtype == KD_BF16 && c.cfg == 1 && c.vec_ok && !ep->raw_f32 && M % 256 == 0 && d->Cout % 256 == 0 &&
-                            (c.nops <= 2 || (pp_row() && !(tune & 512)));   // three operands: the default (ping-pong) instantiations only
-    c.use_row_persist = persist_ok && c.row_wide && !c.row_x;
-    c.use_igemm_persist = !c.use_row_persist && persist_ok && d->kh == 1 && d->stride == 1 && d->pad == 0;
-    c.use_pp128 = !c.use_row_persist && !c.use_igemm_persist && !(c.row_wide && c.half && d->dtype == KD_BF16) && c.row_narrow && pp_row() && persist &&
-                  c.vec_ok && !ep->raw_f32 && c.nops <= 2 && d->Cout % 128 == 0 && d->W % 512 == 0 && d->dil <= 16 && d->Cin % 32 == 0;
-    return c;
-}
+static ConvSel conv_select_here(const kd_conv_desc *d, const kd_conv_epilogue *ep, int cin1) { return conv_select(d, ep, cin1, conv_ncu(), conv_switches()); }
 
 /* Rows of per-channel partial sums the kernel selected for (d, ep) writes to ep->bn_sums (one per 128 output pixels), or 0 when
  * that kernel does not produce them (the caller then runs kd_channel_sums on the result). */
 extern "C" int32_t kd_conv2d_bn_sums_rows(const kd_conv_desc *d, const kd_conv_epilogue *ep)
 {
     if (!d || !ep || d->dtype != KD_BF16 || d->N <= 0 || d->Ho <= 0 || d->Wo <= 0) return 0;
-    static int tn = -1;
-    if (tn < 0) tn = KD_TUNING_ENV_INT("KDCC_CONV_TUNE");
-    const ConvSel c = conv_select(d, ep, tn);
-    if (!ep->mask) {
-        // no mask: the sums of the OUTPUT (S1 = sum of the stored values, S2 = 0), which only the ping-pong 1x1 kernel without
-        // epilogue operands and with the raw output alone takes (the tensor the ASPP image pooling averages)
-        static int lw_pw = -1;
-        if (lw_pw < 0) { const char *v = getenv("KDCC_CONV_LW_PW"); lw_pw = (v && v[0] == '1') ? 1 : 0; }
-        if (!c.use_igemm_persist || c.nops != 0 || !ep->out_raw || ep->out_act || ep->raw_f32 || (tn & 512) || !pp_row() || lw_pw) return 0;
-        return (int32_t)((long long)d->N * d->Ho * d->Wo / 128);
-    }
-    // (the ping-pong instantiations with one or two epilogue operands; with three the sums' registers spill 150 values)
-    if (!(c.use_row_persist || c.use_igemm_persist || c.use_pp128) || (tn & 512) || !pp_row() || (c.use_row_persist && d->dil > 32) || c.nops > 2) return 0;
-    return (int32_t)((long long)d->N * d->Ho * d->Wo / 128);
+    return conv_select_here(d, ep, 0).sums_rows;
 }
 
 /* The classifier epilogue (kd_conv_epilogue.cls_w): conv_row_lw_kernel only, one N tile (Cout == 256), nothing else in the epilogue. */
@@ -1528,33 +1487,14 @@ extern "C" int32_t kd_conv2d_cls_supported(const kd_conv_desc *d, const kd_conv_
     if (!d || !ep || !ep->cls_w || !ep->cls_out || d->dtype != KD_BF16 || d->N <= 0 || d->Ho <= 0 || d->Wo <= 0) return 0;
     if (d->Cout != 256 || ep->ncls < 1 || ep->ncls > 32 || ep->ld_cls < ep->ncls || !kd_aligned16(ep->cls_w)) return 0;
     if (ep->out_raw || ep->out_act || ep->bn_sums || ep->raw_f32) return 0;
-    static int tn = -1;
-    if (tn < 0) tn = KD_TUNING_ENV_INT("KDCC_CONV_TUNE");
-    static int duo = -1;
-    if (duo < 0) { const char *v = getenv("KDCC_CONV_DUO"); duo = v ? atoi(v) : 0; }
-    const ConvSel c = conv_select(d, ep, tn);
-    return c.use_row_persist && c.nops == 0 && duo < 2 && lw_row() && pp_row() && d->dil <= 32 && d->H >= 2 * d->dil && !(tn & 512);
+    return conv_select_here(d, ep, 0).cls_ok;
 }
 
 // Workgroups of the persistent conv grids: one per CU, or fewer (a multiple of 8, one XCD round) when KDCC_PERSIST_CUS / kd_conv_set_persist_cus
 // says so -- that leaves CUs to a kernel on another stream (the RCCL all-reduce the reducer launches from inside backward, which
 // otherwise only gets a CU between two conv launches).  Results do not depend on it: a tile's arithmetic is the same whichever
 // workgroup computes it (tests/test_ddp_gpu.py).
-static std::atomic<int> g_persist_cus{-1};   // -1: not read yet; 0: every CU (process-wide; launches on any thread / device read it)
-static int persist_cus_value(int ncu)
-{
-    int n = g_persist_cus.load(std::memory_order_relaxed);
-    if (n < 0) {
-        const char *v = getenv("KDCC_PERSIST_CUS");
-        n = v ? atoi(v) : 0;
-        if (n < 0) n = 0;
-        int expect = -1;
-        if (!g_persist_cus.compare_exchange_strong(expect, n)) n = expect;   // (a concurrent kd_conv_set_persist_cus wins)
-    }
-    if (n == 0 || n > ncu) n = ncu;        // 0 = every CU; a cap above the CU count is the full chip
-    if (n < 8) n = 8;                      // a cap below one XCD round is one XCD round (never "the full chip")
-    return n - n % 8;
-}
+static std::atomic<int> g_persist_cus{-1};   // -1: kd_conv_set_persist_cus not called yet, KDCC_PERSIST_CUS holds (process-wide; launches on any thread / device read it)
 extern "C" int kd_conv_set_persist_cus(int32_t n)
 {
     KD_REQUIRE(n >= 0, KD_ERR_INVALID, "kd_conv_set_persist_cus: n must be >= 0 (0 = one workgroup per CU)");
@@ -1592,6 +1532,7 @@ static int conv2d_fwd_impl(const kd_conv_desc *d, const void *x, const void *w_p
                "kd_conv2d_fwd: the classifier epilogue needs conv_row_lw_kernel with one N tile and nothing else in the epilogue (ask kd_conv2d_cls_supported first)");
     KD_REQUIRE(cls || ep->out_raw || ep->out_act, KD_ERR_INVALID, "kd_conv2d_fwd: no output requested");
 
+    const ConvSwitches &sw = conv_switches();
     ConvParams p;
     p.x = x; p.w = w_packed;
     p.M = d->N * d->Ho * d->Wo;
@@ -1599,189 +1540,94 @@ static int conv2d_fwd_impl(const kd_conv_desc *d, const void *x, const void *w_p
     p.kh = d->kh; p.kw = d->kw; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil; p.ldx = d->ldx;
     p.HoWo = d->Ho * d->Wo;
     p.Ktot = d->kh * d->kw * d->Cin;
-    p.x2 = x2; p.ldx2 = ldx2; p.nk1 = 0x7fffffff;
+    p.x2 = x2; p.ldx2 = ldx2;
     p.ep = *ep;
-    {
-        static int eb = -1;
-        if (eb < 0) { const char *v = getenv("KDCC_EPI_BATCH"); eb = !(v && v[0] == '0'); }
-        p.epi_batch = eb;
-        static int tn = -1;
-        if (tn < 0) tn = KD_TUNING_ENV_INT("KDCC_CONV_TUNE");   // timing ablations / timestamps: tuning build only (kd_common.h)
-        p.tune = tn;
-        static int sg = -1;
-        if (sg < 0) sg = KD_TUNING_ENV_INT("KDCC_CONV_STAGGER");
-        p.stagger_us = sg;
-    }
-    const ConvSel sel = conv_select(d, ep, p.tune);
+    p.epi_batch = sw.epi_batch; p.tune = sw.tune; p.stagger_us = sw.stagger_us;
+    const ConvSel sel = conv_select_here(d, ep, x2 ? cin1 : 0);
     p.vec_ok = sel.vec_ok;
-    const int cfg = sel.cfg, nops = sel.nops, ncu = sel.ncu;
-    const bool half = sel.half, row_wide = sel.row_wide, row_x = sel.row_x, row_narrow = sel.row_narrow;
+    p.nkc = sel.nkc; p.nk = sel.nk; p.nk1 = sel.nk1;
+    p.tiles_m = sel.tiles_m; p.tiles_n = sel.tiles_n; p.ntiles = sel.ntiles; p.tn_group = sel.tn_group;
     KD_REQUIRE(!ep->bn_sums || kd_conv2d_bn_sums_rows(d, ep) > 0, KD_ERR_UNSUPPORTED,
                "kd_conv2d_fwd: bn_sums is not produced by the kernel this problem selects (ask kd_conv2d_bn_sums_rows first)");
     if (ep->bn_sums) KD_NOTE_KERNEL(ep->mask ? "bn_sums_epilogue" : "out_sums_epilogue");   // (kernel-selection log: counted next to the kernel that carries it)
     if (cls) KD_NOTE_KERNEL("cls_epilogue");
-    hipStream_t s = (hipStream_t)stream;
-    // Workgroups of the persistent kernels (one per CU, each walks tiles for 1-6 ms).  KDCC_PERSIST_CUS=n (a multiple of 8,
-    // e.g. 248) leaves CUs free for a concurrent kernel -- the RCCL all-reduce the gradient reducer launches on its side stream
-    // from inside backward -- which otherwise only gets a CU between two conv launches.  Results do not depend on it: a tile's
-    // arithmetic is the same whichever workgroup computes it (tests/test_ddp_gpu.py).
-    auto persist_cus = [&]() { return persist_cus_value(ncu); };
-    auto launch = [&](auto cf, auto tag) {
-        using CF = decltype(cf);
-        using T = decltype(tag);
-        const int bkk = CF::RB / (int)sizeof(T);
-        p.nkc = d->Cin / bkk;
-        p.nk = d->kh * d->kw * p.nkc;
-        p.tiles_n = (d->Cout + CF::BN - 1) / CF::BN;
-        const int tiles_m = (p.M + CF::BM - 1) / CF::BM;
-        hipLaunchKernelGGL((conv_igemm_kernel<T, CF>), dim3((unsigned)(tiles_m * p.tiles_n)), dim3(64 * CF::NW), 0, s, p);
-    };
-    const bool f32 = d->dtype == KD_F32;
-    auto persist_grid = [&]() {
-        p.tiles_n = d->Cout / 256;
-        p.tiles_m = p.M / 256;
-        p.ntiles = p.tiles_m * p.tiles_n;
-        static int tng = -1;
-        // N tiles walked four at a time over all M tiles (Cout >= 2048): an XCD then keeps 4 weight slabs (K x 256) in its L2 for
-        // the whole launch instead of cycling all 8-16 of them per round of tiles; +3-4 % on the 4096-wide 1x1 layers
-        if (tng < 0) { const char *v = getenv("KDCC_CONV_TNGROUP"); tng = v ? atoi(v) : 4; }
-        p.tn_group = (tng > 0 && p.tiles_n > tng && p.tiles_n % tng == 0) ? tng : 0;
-        const int nwg = p.ntiles < persist_cus() ? p.ntiles : persist_cus();
-        return dim3((unsigned)((nwg + 7) / 8 * 8));
-    };
-    // conv_row_duo_kernel (conv_lw.hip): 256 x 128 tiles, two workgroups per CU -- one's epilogue under the other's main loop.
-    // KDCC_CONV_DUO: 0 off, 1 the Cout = 128 layers (instead of the 512 x 128 ping-pong kernel), 2 every row-buffer layer it fits
-    static int duo = -1;
-    if (duo < 0) { const char *v = getenv("KDCC_CONV_DUO"); duo = v ? atoi(v) : 0; }
-    const bool duo_ok = duo > 0 && lw_row() && d->dtype == KD_BF16 && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == d->dil && d->dil <= 32 &&
-                        d->W % 256 == 0 && p.M % 256 == 0 && d->H >= 2 * d->dil && d->Cout % 128 == 0 && d->Cin % 64 == 0 && sel.vec_ok && !ep->raw_f32 && nops <= 1 &&
-                        !ep->bn_sums && !(p.tune & 512) && (long long)(p.M / 256) * (d->Cout / 128) >= 2 * ncu &&
-                        (duo >= 2 || d->Cout == 128);
     if (x2)   // two A sources: the persistent ping-pong 1x1 kernel only (kd_conv1x1_dual_supported)
-        KD_REQUIRE(!duo_ok && !sel.use_row_persist && sel.use_igemm_persist && pp_row() && cin1 % (CfgWide::RB / es) == 0, KD_ERR_UNSUPPORTED,
+        KD_REQUIRE(sel.dual_ok, KD_ERR_UNSUPPORTED,
                    "kd_conv1x1_dual_fwd: this shape does not select conv_igemm_persist_kernel<pp> (ask kd_conv1x1_dual_supported first)");
-    if (duo_ok) {
-        p.tiles_n = d->Cout / 128;
-        p.tiles_m = p.M / 256;
-        p.ntiles = p.tiles_m * p.tiles_n;
-        {   // N tiles walked in groups over all M tiles for wide layers (see persist_grid): 8 tiles of 128 channels = 4 of 256
-            static int tng = -1;
-            if (tng < 0) { const char *v = getenv("KDCC_CONV_TNGROUP"); tng = v ? atoi(v) : 4; }
-            p.tn_group = (tng > 0 && p.tiles_n > 2 * tng && p.tiles_n % (2 * tng) == 0) ? 2 * tng : 0;
-        }
-        p.nkc = d->Cin / 32;
-        p.nk = 9 * p.nkc;
-        const int cap = 2 * persist_cus();
-        const int nwg = p.ntiles < cap ? p.ntiles : cap;
-        KD_NOTE_KERNEL("conv_row_duo_kernel");
-        KD_REQUIRE(kd_launch_conv_row_duo(p, nops, (unsigned)((nwg + 7) / 8 * 8), s), KD_ERR_UNSUPPORTED, "kd_conv2d_fwd: no conv_row_duo_kernel instantiation");
-    } else if (sel.use_row_persist) {
-        p.nkc = d->Cin / (CfgRow::RB / es);
-        p.nk = 9 * p.nkc;
-        const dim3 grid = persist_grid();
-        // H >= 2 dil: every output row has >= 2 kernel rows inside the image, which the loop's period hand-over assumes (with dil < H < 2 dil the
-        // rows H - dil <= ho < dil have one; they go to the ping-pong kernel, which counts kernel rows per tile)
-        const bool lw = lw_row() && pp_row() && d->dil <= 32 && d->H >= 2 * d->dil && !(p.tune & 512);
-        KD_NOTE_KERNEL((p.tune & 512) ? "conv_row_persist_kernel<dbg>" : lw ? "conv_row_lw_kernel" : (pp_row() && d->dil <= 32) ? "conv_row_persist_kernel<pp>" : "conv_row_persist_kernel<lockstep>");
-        if (lw) {
-            KD_REQUIRE(kd_launch_conv_row_lw(p, cls ? 16 : (nops | (ep->bn_sums ? 4 : 0)), grid.x, s), KD_ERR_UNSUPPORTED, "kd_conv2d_fwd: no conv_row_lw_kernel instantiation for %d epilogue operands", nops);
-        } else if (p.tune & 512) {   // phase clocks (tools/conv_timeline.py)
-            if (nops == 0) hipLaunchKernelGGL((conv_row_persist_kernel<CfgRow, 0, true, true>), grid, dim3(512), 0, s, p);
-            else if (nops == 1) hipLaunchKernelGGL((conv_row_persist_kernel<CfgRow, 1, true, true>), grid, dim3(512), 0, s, p);
-            else hipLaunchKernelGGL((conv_row_persist_kernel<CfgRow, 2, true, true>), grid, dim3(512), 0, s, p);
-        } else if (pp_row() && d->dil <= 32) {
-            if (nops == 0) hipLaunchKernelGGL((conv_row_persist_kernel<CfgRow, 0, false, true>), grid, dim3(512), 0, s, p);
-            else if (ep->bn_sums && nops == 1) hipLaunchKernelGGL((conv_row_persist_kernel<CfgRow, 5, false, true>), grid, dim3(512), 0, s, p);
-            else if (ep->bn_sums && nops == 2) hipLaunchKernelGGL((conv_row_persist_kernel<CfgRow, 6, false, true>), grid, dim3(512), 0, s, p);
-            else if (nops == 1) hipLaunchKernelGGL((conv_row_persist_kernel<CfgRow, 1, false, true>), grid, dim3(512), 0, s, p);
-            else if (nops == 2) hipLaunchKernelGGL((conv_row_persist_kernel<CfgRow, 2, false, true>), grid, dim3(512), 0, s, p);
-            else hipLaunchKernelGGL((conv_row_persist_kernel<CfgRow, 3, false, true>), grid, dim3(512), 0, s, p);
-        } else if (nops == 0) hipLaunchKernelGGL((conv_row_persist_kernel<CfgRow, 0>), grid, dim3(512), 0, s, p);
-        else if (nops == 1) hipLaunchKernelGGL((conv_row_persist_kernel<CfgRow, 1>), grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((conv_row_persist_kernel<CfgRow, 2>), grid, dim3(512), 0, s, p);
-    } else if (sel.use_igemm_persist) {
-        p.nkc = d->Cin / (CfgWide::RB / es);
-        p.nk = d->kh * d->kw * p.nkc;
-        const dim3 grid = persist_grid();
-        // conv_pw_lw_kernel (the lone-wave loop for 1x1 layers) is bit-identical but NOT faster here: its main loop ties the
-        // ping-pong kernel's (8 DMA pieces per k-step keep both near the staging rate) and its serial epilogue -- four waves with
-        // twice the instructions each, nothing to overlap them -- costs 10-60 % more on these short-K layers (tools/lw_ablate.sh).
-        // Opt-in for A/B: KDCC_CONV_LW_PW=1.
-        static int lw_pw = -1;
-        if (lw_pw < 0) { const char *v = getenv("KDCC_CONV_LW_PW"); lw_pw = (v && v[0] == '1') ? 1 : 0; }
-        if (x2) p.nk1 = cin1 / (CfgWide::RB / es);
-        const bool lw = lw_pw && lw_row() && pp_row() && d->Cin % 128 == 0 && !(p.tune & 512) && !x2;
-        KD_NOTE_KERNEL(lw ? "conv_pw_lw_kernel" : x2 ? "conv_igemm_persist_kernel<pp,dual>" : pp_row() ? "conv_igemm_persist_kernel<pp>" : "conv_igemm_persist_kernel<lockstep>");
-        if (lw) {
-            KD_REQUIRE(kd_launch_conv_pw_lw(p, nops | (ep->bn_sums ? 4 : 0), grid.x, s), KD_ERR_UNSUPPORTED, "kd_conv2d_fwd: no conv_pw_lw_kernel instantiation for %d epilogue operands", nops);
-        } else if (pp_row()) {
-            if (nops == 0 && ep->bn_sums) hipLaunchKernelGGL((conv_igemm_persist_kernel<CfgWide, 8, true>), grid, dim3(512), 0, s, p);
-            else if (nops == 0) hipLaunchKernelGGL((conv_igemm_persist_kernel<CfgWide, 0, true>), grid, dim3(512), 0, s, p);
-            else if (ep->bn_sums && nops == 1) hipLaunchKernelGGL((conv_igemm_persist_kernel<CfgWide, 5, true>), grid, dim3(512), 0, s, p);
-            else if (ep->bn_sums && nops == 2) hipLaunchKernelGGL((conv_igemm_persist_kernel<CfgWide, 6, true>), grid, dim3(512), 0, s, p);
-            else if (nops == 1) hipLaunchKernelGGL((conv_igemm_persist_kernel<CfgWide, 1, true>), grid, dim3(512), 0, s, p);
-            else if (nops == 2) hipLaunchKernelGGL((conv_igemm_persist_kernel<CfgWide, 2, true>), grid, dim3(512), 0, s, p);
-            else hipLaunchKernelGGL((conv_igemm_persist_kernel<CfgWide, 3, true>), grid, dim3(512), 0, s, p);
-        } else if (nops == 0) hipLaunchKernelGGL((conv_igemm_persist_kernel<CfgWide, 0>), grid, dim3(512), 0, s, p);
-        else if (nops == 1) hipLaunchKernelGGL((conv_igemm_persist_kernel<CfgWide, 1>), grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((conv_igemm_persist_kernel<CfgWide, 2>), grid, dim3(512), 0, s, p);
-    } else if (row_wide && half && d->dtype == KD_BF16) {
-        p.nkc = d->Cin / (CfgRowH::RB / es);
-        p.nk = 9 * p.nkc;
-        p.tiles_n = (d->Cout + CfgRowH::BN - 1) / CfgRowH::BN;
-        const dim3 grid((unsigned)((p.M / 256) * p.tiles_n));
-        KD_NOTE_KERNEL("conv_igemm_row_kernel<half>");
-        if (row_x) hipLaunchKernelGGL((conv_igemm_row_kernel<bf16_t, CfgRowHX>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((conv_igemm_row_kernel<bf16_t, CfgRowH>), grid, dim3(256), 0, s, p);
-    } else if (sel.use_pp128) {
-        // Cout = 128 layers: 512 x 128 ping-pong tiles
-        p.nkc = d->Cin / 32;
-        p.nk = 9 * p.nkc;
-        p.tiles_n = d->Cout / 128;
-        p.tiles_m = p.M / 512;
-        p.ntiles = p.tiles_m * p.tiles_n;
-        p.tn_group = 0;
-        const int nwg = p.ntiles < persist_cus() ? p.ntiles : persist_cus();
-        const dim3 grid((unsigned)((nwg + 7) / 8 * 8));
-        // conv_row_tall_kernel (conv_lw.hip): the same tiles with one wave per SIMD and the hand-scheduled loop; A/B: KDCC_CONV_LW=0
-        const bool tall = lw_row() && d->Cin % 64 == 0 && d->H > d->dil && !(p.tune & 512) && !(ep->bn_sums && nops == 0);
-        KD_NOTE_KERNEL(tall ? "conv_row_tall_kernel" : "conv_row_pp128_kernel");
-        if (tall) {
-            KD_REQUIRE(kd_launch_conv_row_tall(p, nops | (ep->bn_sums ? 4 : 0), grid.x, s), KD_ERR_UNSUPPORTED, "kd_conv2d_fwd: no conv_row_tall_kernel instantiation for %d epilogue operands", nops);
-        } else
-        if (p.tune & 512) hipLaunchKernelGGL((conv_row_pp128_kernel<0, true>), grid, dim3(512), 0, s, p);   // phase clocks (no-operand form only)
-        else if (nops == 0) hipLaunchKernelGGL((conv_row_pp128_kernel<0>), grid, dim3(512), 0, s, p);
-        else if (ep->bn_sums && nops == 1) hipLaunchKernelGGL((conv_row_pp128_kernel<5>), grid, dim3(512), 0, s, p);
-        else if (ep->bn_sums) hipLaunchKernelGGL((conv_row_pp128_kernel<6>), grid, dim3(512), 0, s, p);
-        else if (nops == 1) hipLaunchKernelGGL((conv_row_pp128_kernel<1>), grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((conv_row_pp128_kernel<2>), grid, dim3(512), 0, s, p);
-    } else if (row_wide || row_narrow) {
-        p.nkc = d->Cin / ((row_wide ? CfgRow::RB : CfgRowN::RB) / es);
-        p.nk = 9 * p.nkc;
-        p.tiles_n = (d->Cout + (row_wide ? CfgRow::BN : CfgRowN::BN) - 1) / (row_wide ? CfgRow::BN : CfgRowN::BN);
-        const dim3 grid((unsigned)((p.M / 256) * p.tiles_n));
-        KD_NOTE_KERNEL(row_narrow ? "conv_igemm_row_kernel<narrow>" : row_x ? (f32 ? "conv_igemm_row_kernel<f32,x>" : "conv_igemm_row_kernel<x>")
-                                  : (f32 ? "conv_igemm_row_kernel<f32,wide>" : "conv_igemm_row_kernel<wide>"));
-        if (row_narrow) hipLaunchKernelGGL((conv_igemm_row_kernel<bf16_t, CfgRowN>), grid, dim3(512), 0, s, p);
-        else if (d->dtype == KD_BF16 && row_x) hipLaunchKernelGGL((conv_igemm_row_kernel<bf16_t, CfgRowX>), grid, dim3(512), 0, s, p);
-        else if (d->dtype == KD_BF16) hipLaunchKernelGGL((conv_igemm_row_kernel<bf16_t, CfgRow>), grid, dim3(512), 0, s, p);
-        else if (row_x) hipLaunchKernelGGL((conv_igemm_row_kernel<float, CfgRowXF>), grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((conv_igemm_row_kernel<float, CfgRowF>), grid, dim3(512), 0, s, p);
-    } else if (d->dtype == KD_BF16) {
-        KD_NOTE_KERNEL(cfg == 1 ? (half ? "conv_igemm_kernel<half>" : "conv_igemm_kernel<wide>") : cfg == 2 ? "conv_igemm_kernel<deep>"
-                                : cfg == 3 ? "conv_igemm_kernel<narrow>" : "conv_igemm_kernel<narrow2>");
-        if (cfg == 1 && (p.tune & 8)) launch(CfgWideF{}, bf16_t{});   // A/B: plain main loop
-        else if (cfg == 1 && half) launch(CfgHalf{}, bf16_t{});
-        else if (cfg == 1) launch(CfgWide{}, bf16_t{});
-        else if (cfg == 2) launch(CfgDeep{}, bf16_t{});
-        else if (cfg == 3) launch(CfgNarrow{}, bf16_t{});
-        else launch(CfgNarrow2{}, bf16_t{});
-    } else {
-        KD_NOTE_KERNEL(cfg == 1 ? "conv_igemm_kernel<f32,wide>" : cfg == 2 ? "conv_igemm_kernel<f32,deep>" : "conv_igemm_kernel<f32,narrow>");
-        if (cfg == 1) launch(CfgWideF{}, float{});
-        else if (cfg == 2) launch(CfgDeep{}, float{});
-        else launch(CfgNarrow{}, float{});   // fp32 parity path: its blocked accumulation does not fit 128 VGPRs
+    hipStream_t s = (hipStream_t)stream;
+    const int nops = sel.nops, gpc = g_persist_cus.load(std::memory_order_relaxed);
+    const dim3 grid(conv_grid(sel, conv_persist_cus(gpc < 0 ? sw.persist_cus : gpc, conv_ncu())));
+#define KD_LAUNCH(threads, ...) hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(threads), 0, s, p)
+#define KD_CASE(epi, ...) case epi: KD_LAUNCH(512, __VA_ARGS__); break;
+    switch (sel.kernel) {
+    case CONV_ROW_DUO: KD_NOTE_KERNEL("conv_row_duo_kernel");
+        KD_REQUIRE(kd_launch_conv_row_duo(p, sel.epi, grid.x, s), KD_ERR_UNSUPPORTED, "kd_conv2d_fwd: no conv_row_duo_kernel instantiation"); break;
+    case CONV_ROW_PERSIST_DBG: KD_NOTE_KERNEL("conv_row_persist_kernel<dbg>");   // phase clocks (tools/conv_timeline.py)
+        switch (sel.epi) {
+        KD_CASE(0, conv_row_persist_kernel<CfgRow, 0, true, true>) KD_CASE(1, conv_row_persist_kernel<CfgRow, 1, true, true>)
+        default: KD_LAUNCH(512, conv_row_persist_kernel<CfgRow, 2, true, true>);
+        } break;
+    case CONV_ROW_LW: KD_NOTE_KERNEL("conv_row_lw_kernel");
+        KD_REQUIRE(kd_launch_conv_row_lw(p, sel.epi, grid.x, s), KD_ERR_UNSUPPORTED, "kd_conv2d_fwd: no conv_row_lw_kernel instantiation for %d epilogue operands", nops); break;
+    case CONV_ROW_PERSIST_PP: KD_NOTE_KERNEL("conv_row_persist_kernel<pp>");
+        switch (sel.epi) {
+        KD_CASE(0, conv_row_persist_kernel<CfgRow, 0, false, true>) KD_CASE(5, conv_row_persist_kernel<CfgRow, 5, false, true>)
+        KD_CASE(6, conv_row_persist_kernel<CfgRow, 6, false, true>) KD_CASE(1, conv_row_persist_kernel<CfgRow, 1, false, true>)
+        KD_CASE(2, conv_row_persist_kernel<CfgRow, 2, false, true>) default: KD_LAUNCH(512, conv_row_persist_kernel<CfgRow, 3, false, true>);
+        } break;
+    case CONV_ROW_PERSIST_LOCKSTEP: KD_NOTE_KERNEL("conv_row_persist_kernel<lockstep>");
+        switch (sel.epi) {
+        KD_CASE(0, conv_row_persist_kernel<CfgRow, 0>) KD_CASE(1, conv_row_persist_kernel<CfgRow, 1>) default: KD_LAUNCH(512, conv_row_persist_kernel<CfgRow, 2>);
+        } break;
+    case CONV_PW_LW: KD_NOTE_KERNEL("conv_pw_lw_kernel");   // opt-in for A/B: KDCC_CONV_LW_PW=1
+        KD_REQUIRE(kd_launch_conv_pw_lw(p, sel.epi, grid.x, s), KD_ERR_UNSUPPORTED, "kd_conv2d_fwd: no conv_pw_lw_kernel instantiation for %d epilogue operands", nops); break;
+    case CONV_IGEMM_PERSIST_PP_DUAL:
+    case CONV_IGEMM_PERSIST_PP:
+        if (sel.kernel == CONV_IGEMM_PERSIST_PP_DUAL) KD_NOTE_KERNEL("conv_igemm_persist_kernel<pp,dual>");
+        else KD_NOTE_KERNEL("conv_igemm_persist_kernel<pp>");
+        switch (sel.epi) {
+        KD_CASE(8, conv_igemm_persist_kernel<CfgWide, 8, true>) KD_CASE(0, conv_igemm_persist_kernel<CfgWide, 0, true>) KD_CASE(5, conv_igemm_persist_kernel<CfgWide, 5, true>)
+        KD_CASE(6, conv_igemm_persist_kernel<CfgWide, 6, true>) KD_CASE(1, conv_igemm_persist_kernel<CfgWide, 1, true>) KD_CASE(2, conv_igemm_persist_kernel<CfgWide, 2, true>)
+        default: KD_LAUNCH(512, conv_igemm_persist_kernel<CfgWide, 3, true>);
+        } break;
+    case CONV_IGEMM_PERSIST_LOCKSTEP: KD_NOTE_KERNEL("conv_igemm_persist_kernel<lockstep>");
+        switch (sel.epi) {
+        KD_CASE(0, conv_igemm_persist_kernel<CfgWide, 0>) KD_CASE(1, conv_igemm_persist_kernel<CfgWide, 1>) default: KD_LAUNCH(512, conv_igemm_persist_kernel<CfgWide, 2>);
+        } break;
+    case CONV_ROW_HALF: KD_NOTE_KERNEL("conv_igemm_row_kernel<half>");
+        if (sel.row_x) KD_LAUNCH(256, conv_igemm_row_kernel<bf16_t, CfgRowHX>);
+        else KD_LAUNCH(256, conv_igemm_row_kernel<bf16_t, CfgRowH>);
+        break;
+    case CONV_ROW_TALL: KD_NOTE_KERNEL("conv_row_tall_kernel");   // A/B: KDCC_CONV_LW=0
+        KD_REQUIRE(kd_launch_conv_row_tall(p, sel.epi, grid.x, s), KD_ERR_UNSUPPORTED, "kd_conv2d_fwd: no conv_row_tall_kernel instantiation for %d epilogue operands", nops); break;
+    case CONV_ROW_PP128: KD_NOTE_KERNEL("conv_row_pp128_kernel");
+        switch (sel.epi) {
+        KD_CASE(-1, conv_row_pp128_kernel<0, true>)   // phase clocks (no-operand form only)
+        KD_CASE(0, conv_row_pp128_kernel<0>) KD_CASE(5, conv_row_pp128_kernel<5>) KD_CASE(6, conv_row_pp128_kernel<6>) KD_CASE(1, conv_row_pp128_kernel<1>)
+        default: KD_LAUNCH(512, conv_row_pp128_kernel<2>);
+        } break;
+    case CONV_ROW_NARROW: KD_NOTE_KERNEL("conv_igemm_row_kernel<narrow>"); KD_LAUNCH(512, conv_igemm_row_kernel<bf16_t, CfgRowN>); break;
+    case CONV_ROW_X: KD_NOTE_KERNEL("conv_igemm_row_kernel<x>"); KD_LAUNCH(512, conv_igemm_row_kernel<bf16_t, CfgRowX>); break;
+    case CONV_ROW_WIDE: KD_NOTE_KERNEL("conv_igemm_row_kernel<wide>"); KD_LAUNCH(512, conv_igemm_row_kernel<bf16_t, CfgRow>); break;
+    case CONV_ROW_F32_X: KD_NOTE_KERNEL("conv_igemm_row_kernel<f32,x>"); KD_LAUNCH(512, conv_igemm_row_kernel<float, CfgRowXF>); break;
+    case CONV_ROW_F32_WIDE: KD_NOTE_KERNEL("conv_igemm_row_kernel<f32,wide>"); KD_LAUNCH(512, conv_igemm_row_kernel<float, CfgRowF>); break;
+    case CONV_IGEMM_HALF: KD_NOTE_KERNEL("conv_igemm_kernel<half>");
+        if (sel.plain) KD_LAUNCH(64 * CfgWideF::NW, conv_igemm_kernel<bf16_t, CfgWideF>);   // A/B: plain main loop
+        else KD_LAUNCH(64 * CfgHalf::NW, conv_igemm_kernel<bf16_t, CfgHalf>);
+        break;
+    case CONV_IGEMM_WIDE: KD_NOTE_KERNEL("conv_igemm_kernel<wide>");
+        if (sel.plain) KD_LAUNCH(64 * CfgWideF::NW, conv_igemm_kernel<bf16_t, CfgWideF>);
+        else KD_LAUNCH(64 * CfgWide::NW, conv_igemm_kernel<bf16_t, CfgWide>);
+        break;
+    case CONV_IGEMM_DEEP: KD_NOTE_KERNEL("conv_igemm_kernel<deep>"); KD_LAUNCH(64 * CfgDeep::NW, conv_igemm_kernel<bf16_t, CfgDeep>); break;
+    case CONV_IGEMM_NARROW: KD_NOTE_KERNEL("conv_igemm_kernel<narrow>"); KD_LAUNCH(64 * CfgNarrow::NW, conv_igemm_kernel<bf16_t, CfgNarrow>); break;
+    case CONV_IGEMM_NARROW2: KD_NOTE_KERNEL("conv_igemm_kernel<narrow2>"); KD_LAUNCH(64 * CfgNarrow2::NW, conv_igemm_kernel<bf16_t, CfgNarrow2>); break;
+    case CONV_IGEMM_F32_WIDE: KD_NOTE_KERNEL("conv_igemm_kernel<f32,wide>"); KD_LAUNCH(64 * CfgWideF::NW, conv_igemm_kernel<float, CfgWideF>); break;
+    case CONV_IGEMM_F32_DEEP: KD_NOTE_KERNEL("conv_igemm_kernel<f32,deep>"); KD_LAUNCH(64 * CfgDeep::NW, conv_igemm_kernel<float, CfgDeep>); break;
+    case CONV_IGEMM_F32_NARROW: KD_NOTE_KERNEL("conv_igemm_kernel<f32,narrow>"); KD_LAUNCH(64 * CfgNarrow::NW, conv_igemm_kernel<float, CfgNarrow>); break;
     }
+#undef KD_CASE
+#undef KD_LAUNCH
     KD_CHECK_LAUNCH("kd_conv2d_fwd");
     return KD_OK;
 }
@@ -1803,12 +1649,7 @@ static bool dual_shape_ok(const kd_conv_desc *d, int Cin2, int ldx2, const kd_co
     if (Cin2 <= 0 || d->Cin % 64 != 0 || Cin2 % 64 != 0 || ldx2 < Cin2 || (ldx2 * 2) % 16 != 0) return false;
     *tot = *d;
     tot->Cin = d->Cin + Cin2;
-    static int tn = -1;
-    if (tn < 0) tn = KD_TUNING_ENV_INT("KDCC_CONV_TUNE");
-    const ConvSel c = conv_select(tot, ep, tn);
-    static int dual = -1;
-    if (dual < 0) { const char *v = getenv("KDCC_CONV_DUAL"); dual = !(v && v[0] == '0'); }   // A/B: 0 = two launches (engine falls back)
-    return dual && c.use_igemm_persist && !c.use_row_persist && pp_row();
+    return conv_select_here(tot, ep, d->Cin).dual_ok;
 }
 
 extern "C" int32_t kd_conv1x1_dual_supported(const kd_conv_desc *d, int32_t Cin2, int32_t ldx2, const kd_conv_epilogue *ep)
@@ -1831,7 +1672,7 @@ extern "C" int kd_conv1x1_dual_fwd(const kd_conv_desc *d, const void *x, const v
 
 extern "C" int kd_debug_conv_tlog(unsigned long long *dst, size_t bytes)
 {
-    if (KD_TUNING_ENV_INT("KDCC_CONV_TUNE") & 1024) return kd_lw_tlog_copy(dst, bytes) == 0 ? KD_OK : KD_ERR_HIP;   // conv_lw.hip's log
+    if (conv_switches().tune & 1024) return kd_lw_tlog_copy(dst, bytes) == 0 ? KD_OK : KD_ERR_HIP;   // conv_lw.hip's log
     return hipMemcpyFromSymbol(dst, HIP_SYMBOL(kd_conv_tlog), bytes < sizeof(kd_conv_tlog) ? bytes : sizeof(kd_conv_tlog), 0,
                                hipMemcpyDeviceToHost) == hipSuccess ? KD_OK : KD_ERR_HIP;
 }

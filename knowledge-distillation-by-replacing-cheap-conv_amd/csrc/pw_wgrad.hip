@@ -8,6 +8,7 @@
 // fixed-order reduction (deterministic, unlike float atomics).
 #include <stdlib.h>
 
+#include "conv_select.h"
 #include "igemm_core.h"
 #include "wgrad_lw_body.inc"
 #include "wgrad_pw_lw_body.inc"
@@ -472,7 +473,6 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_pw_lw_kernel(const WgradPar
 // four-stage ring of 40 KiB stages (160 KiB, one workgroup per CU): three stages in flight behind a counted vmcnt.
 // s_waitcnt immediate (gfx9 layout): vmcnt(vm) lgkmcnt(0), expcnt untouched
 constexpr int waitcnt_vm_lgkm0(int vm) { return (vm & 15) | (7 << 4) | ((vm >> 4) << 14); }
-constexpr int WR_XROWS = 96;                        // row-buffer rows: 64 + 2 * dil <= 96
 constexpr int WR_STAGE = 16384 + WR_XROWS * 256;    // dy image + row buffer
 constexpr int WR_NST = 4;
 __device__ unsigned long long kd_wgrad_tlog[256 * 8 * 8];   // KDCC_WGRAD_DBG=1: per-wave phase clocks of conv_wgrad_row_kernel (debug)
@@ -928,27 +928,6 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_pw_lw_kernel(const WgradPar
 #undef WGPW_ACC_RW
 }
 
-// plan of the row-buffer kernel: ~2.5 one-per-CU workgroups per CU, >= 8 stages per split
-int fill_splits(int per, int max_splits);   // below, next to wide_plan
-void row_plan(long long M, int Cin, int Cout, int &tiles, int &tiles_ci, int &splits, int &rps)
-{
-    tiles_ci = (Cin + 127) / 128;
-    tiles = tiles_ci * ((Cout + 127) / 128);
-    const int stages = (int)(M / 64);
-    static int target = -1;
-    if (target < 0) { const char *e = getenv("KDCC_WGRAD_TARGET"); target = e ? atoi(e) : 0; }   // A/B: floor(n / workgroups per split)
-    const int per = tiles * 3, max_splits = (stages + 7) / 8;
-    splits = target > 0 ? target / per : fill_splits(per, max_splits);
-    splits = splits < 1 ? 1 : (splits > max_splits ? max_splits : splits);
-    rps = ((stages + splits - 1) / splits) * 64;
-    splits = (int)((M + rps - 1) / rps);
-}
-bool row_eligible(const kd_conv_desc *d)
-{
-    return d->dtype == KD_BF16 && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == d->dil && 2 * d->dil + 64 <= WR_XROWS &&
-           d->W % 64 == 0 && d->Cin % 8 == 0 && d->Cout % 8 == 0;
-}
-
 __global__ void slab_reduce_kernel(const float *__restrict__ part, float *__restrict__ dw, size_t n, int splits,
                                    int accumulate)
 {
@@ -986,101 +965,123 @@ void launch_slab_reduce(const float *part, float *dw, size_t n, int splits, int 
     }
 }
 
-void launch_tr(dim3 grid, hipStream_t s, const WgradParams &p)
+void fastdiv_magic(uint32_t d, uint32_t &magic, uint32_t &shift)
 {
-    static int nst = -1;
-    if (nst < 0) { const char *e = getenv("KDCC_WGRAD_NST"); nst = e ? atoi(e) : 2; }   // A/B hook: 2 | 3 | 4 (measured: 128->128 3x3 at 512x1024 1.70 ms with 2, 2.44 with 3 or 4: occupancy beats depth)
-    KD_NOTE_KERNEL("pw_wgrad_tr_kernel");
-    if (nst == 2) hipLaunchKernelGGL(pw_wgrad_tr_kernel<2>, grid, dim3(256), 0, s, p);
-    else if (nst == 3) hipLaunchKernelGGL(pw_wgrad_tr_kernel<3>, grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(pw_wgrad_tr_kernel<4>, grid, dim3(256), 0, s, p);
-}
-
-void plan(int dtype, int M, int Cin, int Cout, int &tiles, int &tiles_ci, int &splits, int &rows_per_split, int taps = 1)
-{
-    const int krows = IG_ROWB / kd_elem_size(dtype);
-    tiles_ci = (Cin + TN - 1) / TN;
-    tiles = tiles_ci * ((Cout + TM - 1) / TM);
-    const int stages = (M + krows - 1) / krows;
-    int want = (1024 + tiles * taps - 1) / (tiles * taps);   // aim for ~1024 workgroups (4 per CU)
-    const int max_splits = (stages + 3) / 4;        // keep >= 4 stages per split
-    splits = want < 1 ? 1 : (want > max_splits ? max_splits : want);
-    if (splits < 1) splits = 1;
-    const int st_per = (stages + splits - 1) / splits;
-    rows_per_split = st_per * krows;
-    splits = (M + rows_per_split - 1) / rows_per_split;
-}
-
-// plan of the 256 x 256 tile (bf16 LDS-DMA path): ~3 waves of one-per-CU workgroups, >= 8 stages per split
-bool wide_tile_pays(int dtype, int Cin, int Cout)
-{
-    const long long pad256 = (long long)((Cout + 255) / 256) * ((Cin + 255) / 256) * 65536;
-    const long long pad128 = (long long)((Cout + 127) / 128) * ((Cin + 127) / 128) * 16384;
-    bool wide = dtype == KD_BF16 && Cin % 8 == 0 && Cout % 8 == 0 && Cout >= 256 && Cin >= 256 &&
-                pad256 * 100 <= pad128 * 135;   // (the decoder's 304-channel conv: 2 x 256 vs 3 x 128 columns)
-    if (const char *e = getenv("KDCC_WGRAD_WIDE")) wide = wide && e[0] != '0';
-    return wide;
-}
-// Split-K factor for kernels that run ONE workgroup per CU, all of equal length (the 256 x 256 and the row-buffer weight-gradient
-// tiles): the launch takes ceil(W / 256) rounds of the 256 CUs with W = splits * per workgroups, so W should sit just BELOW a
-// multiple of 256, and the fewest rounds that fill the chip win (fewer partial slabs to write and reduce, fewer pipeline fills).
-// Returns the first floor(256 k / per), k = 1..4, that fills >= 95 % of its k rounds, else the best fill.  Round 2 aimed at "about
-// 640 / 768 workgroups" rounded UP: 2.5 rounds with the last half empty, or one workgroup into a fourth round.  Measured
-// (tools/bench_wgrad.py, 4 images): 3x3 128->128 at 512x1024 1.01 -> 0.85 ms, 256->256 at 512x1024 2.99 -> 2.50, 512->512 0.78 -> 0.73,
-// 1024->512 1.44 -> 1.27, 304->256 4.45 -> 3.87; 1x1 512->512 0.220 -> 0.114, 4096->256 0.371 -> 0.313; mode B 24.5 -> 25.8 img/s.
-int fill_splits(int per, int max_splits)
-{
-    int splits = 1;
-    double best = -1.0;
-    for (int k = 1; k <= 4; ++k) {
-        int sp = (256 * k) / per;
-        sp = sp < 1 ? 1 : (sp > max_splits ? max_splits : sp);
-        const long long w = (long long)sp * per;
-        const double fill = (double)w / (double)(((w + 255) / 256) * 256);
-        if (fill >= 0.95) return sp;
-        if (fill > best) { best = fill; splits = sp; }
-    }
-    return splits;
-}
-
-// conv_wgrad_pw_lw_kernel instead of conv_wgrad_wide_kernel<true>: whole 256 x 256 tiles and whole 32-pixel stages.  Measured at 8 images
-// (tools/wgrad_lw_check.py, ms incl. the reduce): 2048->4096 4.49 -> 3.28, 1024->2048 1.19 -> 0.80, 2048->1024 1.17 -> 0.78, 4096->256 0.85 -> 0.66,
-// 512->1024 0.34 -> 0.22, 1280->256 0.24 -> 0.18, 512->512 0.20 -> 0.15.  (With the workgroups dealt round-robin over the XCDs, as the 8-wave
-// kernel's 2-D grid is, the short splits were SLOWER than the 8-wave kernel, x 0.90-0.92: the tiles of a split fetched their shared rows into
-// eight L2s.)  mode: KDCC_WGRAD_PW_LW, 0 = never.
-bool pw_lw_pays(long long M, int Cin, int Cout, int rps, int mode)
-{
-    return mode && Cin % 256 == 0 && Cout % 256 == 0 && M % 64 == 0 && rps % 32 == 0;
-}
-
-void wide_plan(long long M, int Cin, int Cout, int taps, int &tiles, int &tiles_ci, int &splits, int &rps)
-{
-    tiles_ci = (Cin + 255) / 256;
-    tiles = tiles_ci * ((Cout + 255) / 256);
-    const int stages = (int)((M + 63) / 64);
-    static int target = -1;
-    if (target < 0) { const char *e = getenv("KDCC_WGRAD_WIDE_TARGET"); target = e ? atoi(e) : 0; }   // A/B: floor(n / workgroups per split)
-    const int max_splits = (stages + 7) / 8;
-    const int want = target > 0 ? target / (tiles * taps) : fill_splits(tiles * taps, max_splits);
-    splits = want < 1 ? 1 : (want > max_splits ? max_splits : want);
-    if (splits < 1) splits = 1;
-    rps = ((stages + splits - 1) / splits) * 64;
-    splits = (int)((M + rps - 1) / rps);
+    // n / d == (umulhi(n, magic) + n) >> shift for 0 <= n < 2^31 (round-up method, 33-bit magic with the top bit implicit)
+    shift = 0;
+    while ((1ull << shift) < d) ++shift;
+    magic = (uint32_t)(((1ull << 32) * ((1ull << shift) - d)) / d + 1);
 }
 
 }  // namespace
 
+// Every KDCC_* switch this file reads, read once per process.
+static const WgradSwitches &wgrad_switches()
+{
+    static const WgradSwitches sw = [] {
+        auto num = [](const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; };
+        auto on = [](const char *name) { const char *e = getenv(name); return (e && e[0] == '0') ? 0 : 1; };   // A/B: NAME=0 turns it off
+        WgradSwitches s;
+        s.row = num("KDCC_WGRAD_ROW", 2); s.lw = on("KDCC_WGRAD_LW"); s.wide = on("KDCC_WGRAD_WIDE");
+        if (const char *e = getenv("KDCC_WGRAD_WIDE_GENERAL")) s.wide_general = e[0] == '1';
+        s.pw_lw = num("KDCC_WGRAD_PW_LW", 1); s.nst = num("KDCC_WGRAD_NST", 2);
+        s.target = num("KDCC_WGRAD_TARGET", 0); s.wide_target = num("KDCC_WGRAD_WIDE_TARGET", 0);
+#ifdef KDCC_TUNING
+        s.il = num("KDCC_WGRAD_IL", 1);
+#endif
+        s.dbg = KD_TUNING_ENV_INT("KDCC_WGRAD_DBG");   // phase clocks: tuning build only
+        return s;
+    }();
+    return sw;
+}
+
+extern "C" int kd_debug_wgrad_tlog(unsigned long long *dst, size_t bytes)
+{
+    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(kd_wgrad_tlog), bytes < sizeof(kd_wgrad_tlog) ? bytes : sizeof(kd_wgrad_tlog), 0,
+                               hipMemcpyDeviceToHost) == hipSuccess ? KD_OK : KD_ERR_HIP;
+}
+
 extern "C" size_t kd_pw_wgrad_workspace(int32_t M, int32_t Cin, int32_t Cout)
 {
-    // dtype-independent upper bound: plan with the smaller K stage (f32: 32 rows) gives the larger split count
-    int tiles, tiles_ci, s0, s1, rps;
-    plan(KD_F32, M, Cin, Cout, tiles, tiles_ci, s0, rps);
-    plan(KD_BF16, M, Cin, Cout, tiles, tiles_ci, s1, rps);
-    int splits = s0 > s1 ? s0 : s1;
-    const int stages = (M + 63) / 64;
-    const int wsplits = (stages + 7) / 8 < 768 ? (stages + 7) / 8 : 768;   // the wide-tile plan never splits finer
-    if (wsplits > splits) splits = wsplits;
-    return (size_t)splits * Cout * Cin * sizeof(float);
+    return (size_t)wgrad_workspace_splits(M, Cin, Cout, 1, nullptr, wgrad_switches()) * Cout * Cin * sizeof(float);
+}
+
+extern "C" size_t kd_conv2d_wgrad_workspace(const kd_conv_desc *d)
+{
+    if (!d) return 0;
+    const int taps = d->kh * d->kw;
+    return (size_t)wgrad_workspace_splits(d->N * d->Ho * d->Wo, d->Cin, d->Cout, taps, d, wgrad_switches()) * taps * d->Cout * d->Cin * sizeof(float);
+}
+
+// The weight gradient behind both entry points, arguments validated: the same TN GEMM per tap over pixel splits, partial slabs in
+// the workspace, fixed-order reduction.  d: the conv (A rows gathered through its pixel map: stride, padding, dilation; zeros
+// outside the image), or nullptr for kd_pw_wgrad (one tap, GEMM row m = pixel m).
+static int wgrad_impl(const char *who, int dtype, long long M, int Cin, int Cout, int taps, const kd_conv_desc *d, const void *a, int lda,
+                      const void *dy, int ldy, float *dw, int accumulate, void *workspace, size_t workspace_bytes, kd_stream_t stream)
+{
+    const WgradSwitches &sw = wgrad_switches();
+    const WgradSel sel = wgrad_select(dtype, M, Cin, Cout, taps, d, sw);
+    const int splits = sel.splits;
+    const size_t plane = (size_t)Cout * Cin, need = (size_t)splits * taps * plane * sizeof(float);
+    KD_REQUIRE(workspace_bytes >= need, KD_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
+    WgradParams p;
+    p.a = a; p.dy = dy; p.part = (float *)workspace;
+    p.M = (int)M; p.Cin = Cin; p.Cout = Cout; p.lda = lda; p.ldy = ldy;
+    p.tiles_ci = sel.tiles_ci; p.rows_per_split = sel.rps; p.splits = splits; p.tiles = sel.tiles;
+    p.dbg = sw.dbg;
+    p.geom = 0; p.kw = 1; p.H = p.W = p.Ho = p.Wo = 0; p.stride = 1; p.pad = 0; p.dil = 1;
+    p.mg_howo = p.sh_howo = p.mg_wo = p.sh_wo = 0;
+    if (d) {
+        const bool row = sel.kernel == WGRAD_LW || sel.kernel == WGRAD_ROW;   // (the row kernels walk input pixels: Ho = H, Wo = W)
+        p.geom = !(taps == 1 && d->stride == 1 && d->pad == 0);
+        p.H = d->H; p.W = d->W; p.Ho = d->Ho; p.Wo = d->Wo; p.kw = d->kw; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
+        fastdiv_magic((uint32_t)(row ? d->H * d->W : d->Ho * d->Wo), p.mg_howo, p.sh_howo);
+        fastdiv_magic((uint32_t)(row ? d->W : d->Wo), p.mg_wo, p.sh_wo);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(sel.grid[0], sel.grid[1], sel.grid[2]);
+    switch (sel.kernel) {   // (cases in the order the code object has always held the kernels)
+    case WGRAD_TR:
+        KD_NOTE_KERNEL("pw_wgrad_tr_kernel");
+        if (sw.nst == 2) hipLaunchKernelGGL(pw_wgrad_tr_kernel<2>, grid, dim3(256), 0, s, p);
+        else if (sw.nst == 3) hipLaunchKernelGGL(pw_wgrad_tr_kernel<3>, grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL(pw_wgrad_tr_kernel<4>, grid, dim3(256), 0, s, p);
+        break;
+    case WGRAD_WIDE: KD_NOTE_KERNEL("conv_wgrad_wide_kernel"); hipLaunchKernelGGL(conv_wgrad_wide_kernel<true>, grid, dim3(512), 0, s, p); break;
+    case WGRAD_BF16: KD_NOTE_KERNEL("pw_wgrad_kernel<bf16>"); hipLaunchKernelGGL(pw_wgrad_kernel<bf16_t>, grid, dim3(256), 0, s, p); break;
+    case WGRAD_F32: KD_NOTE_KERNEL("pw_wgrad_kernel<f32>"); hipLaunchKernelGGL(pw_wgrad_kernel<float>, grid, dim3(256), 0, s, p); break;
+    case WGRAD_LW: KD_NOTE_KERNEL("conv_wgrad_lw_kernel"); hipLaunchKernelGGL(conv_wgrad_lw_kernel, grid, dim3(256), 0, s, p); break;
+    case WGRAD_ROW:
+        KD_NOTE_KERNEL("conv_wgrad_row_kernel");
+#ifdef KDCC_TUNING
+        if (p.dbg && sw.il == 2) hipLaunchKernelGGL((conv_wgrad_row_kernel<true, 2>), grid, dim3(512), 0, s, p);
+        else if (p.dbg && sw.il == 1) hipLaunchKernelGGL((conv_wgrad_row_kernel<true, 1>), grid, dim3(512), 0, s, p);
+        else if (p.dbg) hipLaunchKernelGGL((conv_wgrad_row_kernel<true, 0>), grid, dim3(512), 0, s, p);
+        else if (sw.il == 2) hipLaunchKernelGGL((conv_wgrad_row_kernel<false, 2>), grid, dim3(512), 0, s, p);
+        else if (sw.il == 0) hipLaunchKernelGGL((conv_wgrad_row_kernel<false, 0>), grid, dim3(512), 0, s, p);
+        else
+#endif
+        hipLaunchKernelGGL((conv_wgrad_row_kernel<false, 1>), grid, dim3(512), 0, s, p);
+        break;
+    case WGRAD_WIDE_GENERAL: KD_NOTE_KERNEL("conv_wgrad_wide_kernel"); hipLaunchKernelGGL(conv_wgrad_wide_kernel<false>, grid, dim3(512), 0, s, p); break;
+    case WGRAD_PW_LW: KD_NOTE_KERNEL("conv_wgrad_pw_lw_kernel"); hipLaunchKernelGGL(conv_wgrad_pw_lw_kernel, grid, dim3(256), 0, s, p); break;
+    }
+    KD_CHECK_LAUNCH(who);
+    const float *part = (const float *)workspace;
+    if (taps == 1) {
+        launch_slab_reduce(part, dw, plane, splits, accumulate, s);
+    } else if (taps == 9) {
+        const int rb9 = (int)((plane + 255) / 256 > 4096 ? 4096 : (plane + 255) / 256);
+        hipLaunchKernelGGL(slab_reduce_taps_cc_kernel<9>, dim3(rb9), dim3(256), 0, s, part, dw, plane, splits, accumulate);
+    } else {
+        const size_t n = plane * taps;
+        const int rb = (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
+        hipLaunchKernelGGL(slab_reduce_taps_kernel, dim3(rb), dim3(256), 0, s, part, dw, Cout, Cin, taps, splits, accumulate);
+    }
+    char reduce[48];
+    snprintf(reduce, sizeof(reduce), "%s(reduce)", who);
+    KD_CHECK_LAUNCH(reduce);
+    return KD_OK;
 }
 
 extern "C" int kd_pw_wgrad(int32_t dtype, int32_t M, int32_t Cin, int32_t Cout, const void *a, int32_t lda,
@@ -1094,74 +1095,10 @@ extern "C" int kd_pw_wgrad(int32_t dtype, int32_t M, int32_t Cin, int32_t Cout, 
     KD_REQUIRE(lda >= Cin && ldy >= Cout && (lda * es) % 16 == 0 && (ldy * es) % 16 == 0 && kd_aligned16(a) &&
                    kd_aligned16(dy),
                KD_ERR_INVALID, "kd_pw_wgrad: operands must be 16-B aligned with 16-B multiple row strides");
-    int tiles, tiles_ci, splits, rps;
-    plan(dtype, M, Cin, Cout, tiles, tiles_ci, splits, rps);
-    const bool wide = wide_tile_pays(dtype, Cin, Cout);   // the 256 x 256 tile of kd_conv2d_wgrad (444 -> 624 TFLOP/s on large layers)
-    if (wide) wide_plan(M, Cin, Cout, 1, tiles, tiles_ci, splits, rps);
-    KD_REQUIRE(workspace_bytes >= (size_t)splits * Cout * Cin * sizeof(float), KD_ERR_WORKSPACE,
-               "kd_pw_wgrad: workspace %zu < %zu", workspace_bytes, (size_t)splits * Cout * Cin * sizeof(float));
-    WgradParams p;
-    p.a = a; p.dy = dy; p.part = (float *)workspace;
-    p.M = M; p.Cin = Cin; p.Cout = Cout; p.lda = lda; p.ldy = ldy;
-    p.tiles_ci = tiles_ci; p.rows_per_split = rps; p.splits = splits; p.tiles = tiles;
-    { static int wd = -1; if (wd < 0) wd = KD_TUNING_ENV_INT("KDCC_WGRAD_DBG"); p.dbg = wd; }   // phase clocks: tuning build only
-    p.geom = 0; p.kw = 1; p.H = p.W = p.Ho = p.Wo = 0; p.stride = 1; p.pad = 0; p.dil = 1;
-    p.mg_howo = p.sh_howo = p.mg_wo = p.sh_wo = 0;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)tiles, (unsigned)splits);
-    static int pwlw = -1;
-    if (pwlw < 0) { const char *e = getenv("KDCC_WGRAD_PW_LW"); pwlw = e ? atoi(e) : 1; }   // A/B: 0 = conv_wgrad_wide_kernel (8 waves); bit-identical
-    if (wide && !p.dbg && pw_lw_pays(M, Cin, Cout, rps, pwlw)) {
-        KD_NOTE_KERNEL("conv_wgrad_pw_lw_kernel");
-        hipLaunchKernelGGL(conv_wgrad_pw_lw_kernel, dim3((unsigned)(tiles * splits)), dim3(256), 0, s, p);
-    }
-    else if (wide) { KD_NOTE_KERNEL("conv_wgrad_wide_kernel"); hipLaunchKernelGGL(conv_wgrad_wide_kernel<true>, grid, dim3(512), 0, s, p); }
-    else if (dtype == KD_BF16 && Cin % 8 == 0 && Cout % 8 == 0) launch_tr(grid, s, p);
-    else if (dtype == KD_BF16) { KD_NOTE_KERNEL("pw_wgrad_kernel<bf16>"); hipLaunchKernelGGL(pw_wgrad_kernel<bf16_t>, grid, dim3(256), 0, s, p); }
-    else { KD_NOTE_KERNEL("pw_wgrad_kernel<f32>"); hipLaunchKernelGGL(pw_wgrad_kernel<float>, grid, dim3(256), 0, s, p); }
-    KD_CHECK_LAUNCH("kd_pw_wgrad");
-    launch_slab_reduce((const float *)workspace, dw, (size_t)Cout * Cin, splits, accumulate, s);
-    KD_CHECK_LAUNCH("kd_pw_wgrad(reduce)");
-    return KD_OK;
+    return wgrad_impl("kd_pw_wgrad", dtype, M, Cin, Cout, 1, nullptr, a, lda, dy, ldy, dw, accumulate, workspace, workspace_bytes, stream);
 }
 
-// ---- general convolution weight gradient (kd_conv2d_wgrad): the same TN GEMM per tap, A rows gathered through the conv's
-// pixel map (stride, padding, dilation; zeros outside the image).  grid = (Cout x Cin tiles, pixel splits, taps).
-namespace {
-void fastdiv_magic(uint32_t d, uint32_t &magic, uint32_t &shift)
-{
-    // n / d == (umulhi(n, magic) + n) >> shift for 0 <= n < 2^31 (round-up method, 33-bit magic with the top bit implicit)
-    shift = 0;
-    while ((1ull << shift) < d) ++shift;
-    magic = (uint32_t)(((1ull << 32) * ((1ull << shift) - d)) / d + 1);
-}
-}  // namespace
-
-extern "C" int kd_debug_wgrad_tlog(unsigned long long *dst, size_t bytes)
-{
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(kd_wgrad_tlog), bytes < sizeof(kd_wgrad_tlog) ? bytes : sizeof(kd_wgrad_tlog), 0,
-                               hipMemcpyDeviceToHost) == hipSuccess ? KD_OK : KD_ERR_HIP;
-}
-
-extern "C" size_t kd_conv2d_wgrad_workspace(const kd_conv_desc *d)
-{
-    if (!d) return 0;
-    const int M = d->N * d->Ho * d->Wo, taps = d->kh * d->kw;
-    int tiles, tiles_ci, s0, s1, rps;
-    plan(KD_F32, M, d->Cin, d->Cout, tiles, tiles_ci, s0, rps, taps);
-    plan(KD_BF16, M, d->Cin, d->Cout, tiles, tiles_ci, s1, rps, taps);
-    int splits = s0 > s1 ? s0 : s1;
-    const int stages = (M + 63) / 64;
-    const int wsplits = (stages + 7) / 8 < 768 ? (stages + 7) / 8 : 768;   // the wide-tile plan never splits finer
-    if (wsplits > splits) splits = wsplits;
-    if (row_eligible(d)) {
-        int rt, rtc, rs, rr;
-        row_plan(M, d->Cin, d->Cout, rt, rtc, rs, rr);
-        if (rs > splits) splits = rs;
-    }
-    return (size_t)splits * taps * d->Cout * d->Cin * sizeof(float);
-}
-
+// ---- general convolution weight gradient (kd_conv2d_wgrad): grid = (Cout x Cin tiles, pixel splits, taps).
 extern "C" int kd_conv2d_wgrad(const kd_conv_desc *d, const void *x, const void *dy, int32_t ld_dy, float *dw,
                                int32_t accumulate, void *workspace, size_t workspace_bytes, kd_stream_t stream)
 {
@@ -1180,90 +1117,7 @@ extern "C" int kd_conv2d_wgrad(const kd_conv_desc *d, const void *x, const void 
                KD_ERR_INVALID, "kd_conv2d_wgrad: operands must be 16-B aligned with 16-B multiple pixel strides");
     const long long M = (long long)d->N * d->Ho * d->Wo;
     KD_REQUIRE(M < (1ll << 31) && (long long)d->N * d->H * d->W < (1ll << 31), KD_ERR_UNSUPPORTED, "kd_conv2d_wgrad: too many pixels");
-    const int taps = d->kh * d->kw;
-    KD_REQUIRE(taps <= 65535, KD_ERR_UNSUPPORTED, "kd_conv2d_wgrad: kernel too large");
-    int tiles, tiles_ci, splits, rps;
-    plan(d->dtype, (int)M, d->Cin, d->Cout, tiles, tiles_ci, splits, rps, taps);
-    bool wide = wide_tile_pays(d->dtype, d->Cin, d->Cout);
-    // A/B hook KDCC_WGRAD_ROW: 0 = never, 1 = only where the 256 x 256 tile is not chosen, 2 = wherever eligible (default: it is
-    // faster on every 3x3 layer of the net, tools/bench_wgrad.py at 4 images: 128->128 1.70 -> 1.06 ms, 304->256 7.25 -> 4.69,
-    // 256->256 1.04 -> 0.88, 512->512 0.87 -> 0.78, 512->1024 dil 2 1.60 -> 1.43, 64->128 1.51 -> 0.83)
-    static int rowmode = -1;
-    if (rowmode < 0) { const char *e = getenv("KDCC_WGRAD_ROW"); rowmode = e ? atoi(e) : 2; }
-    const bool row = row_eligible(d) && (rowmode == 2 || (rowmode == 1 && !wide));
-    if (row) {
-        wide = false;
-        row_plan(M, d->Cin, d->Cout, tiles, tiles_ci, splits, rps);
-    } else if (wide) {
-        wide_plan(M, d->Cin, d->Cout, taps, tiles, tiles_ci, splits, rps);
-    }
-    const size_t need = (size_t)splits * taps * d->Cout * d->Cin * sizeof(float);
-    KD_REQUIRE(workspace_bytes >= need, KD_ERR_WORKSPACE, "kd_conv2d_wgrad: workspace %zu < %zu", workspace_bytes, need);
-    WgradParams p;
-    p.a = x; p.dy = dy; p.part = (float *)workspace;
-    p.M = (int)M; p.Cin = d->Cin; p.Cout = d->Cout; p.lda = d->ldx; p.ldy = ld_dy;
-    p.tiles_ci = tiles_ci; p.rows_per_split = rps; p.splits = splits; p.tiles = tiles;
-    { static int wd = -1; if (wd < 0) wd = KD_TUNING_ENV_INT("KDCC_WGRAD_DBG"); p.dbg = wd; }   // phase clocks: tuning build only
-    p.geom = !(taps == 1 && d->stride == 1 && d->pad == 0);
-    static int wide_general = -1;
-    if (wide_general < 0) { const char *e = getenv("KDCC_WGRAD_WIDE_GENERAL"); wide_general = e && e[0] == '1'; }   // A/B: the general staging on 1x1 too
-    p.H = d->H; p.W = d->W; p.Ho = d->Ho; p.Wo = d->Wo; p.kw = d->kw; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
-    fastdiv_magic((uint32_t)(d->Ho * d->Wo), p.mg_howo, p.sh_howo);
-    fastdiv_magic((uint32_t)d->Wo, p.mg_wo, p.sh_wo);
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)tiles, (unsigned)splits, (unsigned)taps);
-    if (row) {
-        fastdiv_magic((uint32_t)(d->H * d->W), p.mg_howo, p.sh_howo);
-        fastdiv_magic((uint32_t)d->W, p.mg_wo, p.sh_wo);
-        p.tiles = tiles;
-        static int lwmode = -1;
-        if (lwmode < 0) { const char *e = getenv("KDCC_WGRAD_LW"); lwmode = (e && e[0] == '0') ? 0 : 1; }   // A/B: 0 = conv_wgrad_row_kernel (8 waves); bit-identical
-        if (lwmode && !p.dbg && d->Cout % 128 == 0 && d->dil <= 8) {   // (Cin % 8 == 0: row_eligible; a ragged last Cin tile is masked)
-            KD_NOTE_KERNEL("conv_wgrad_lw_kernel");
-            hipLaunchKernelGGL(conv_wgrad_lw_kernel, dim3((unsigned)(tiles * splits * 3)), dim3(256), 0, s, p);
-        } else {
-        KD_NOTE_KERNEL("conv_wgrad_row_kernel");
-#ifdef KDCC_TUNING
-        static int il = -1;
-        if (il < 0) { const char *e = getenv("KDCC_WGRAD_IL"); il = e ? atoi(e) : 1; }   // A/B: 0 = reads in front of the MFMAs, 1 = interleaved (shipped), 2 = ping-pong
-        const dim3 grid((unsigned)(tiles * splits * 3));
-        if (p.dbg && il == 2) hipLaunchKernelGGL((conv_wgrad_row_kernel<true, 2>), grid, dim3(512), 0, s, p);
-        else if (p.dbg && il == 1) hipLaunchKernelGGL((conv_wgrad_row_kernel<true, 1>), grid, dim3(512), 0, s, p);
-        else if (p.dbg) hipLaunchKernelGGL((conv_wgrad_row_kernel<true, 0>), grid, dim3(512), 0, s, p);
-        else if (il == 2) hipLaunchKernelGGL((conv_wgrad_row_kernel<false, 2>), grid, dim3(512), 0, s, p);
-        else if (il == 0) hipLaunchKernelGGL((conv_wgrad_row_kernel<false, 0>), grid, dim3(512), 0, s, p);
-        else
-#endif
-        hipLaunchKernelGGL((conv_wgrad_row_kernel<false, 1>), dim3((unsigned)(tiles * splits * 3)), dim3(512), 0, s, p);
-        }
-    } else if (wide) {
-        static int pwlw = -1;
-        if (pwlw < 0) { const char *e = getenv("KDCC_WGRAD_PW_LW"); pwlw = e ? atoi(e) : 1; }   // A/B: 0 = conv_wgrad_wide_kernel (8 waves); bit-identical
-        if (!p.dbg && !p.geom && !wide_general && taps == 1 && pw_lw_pays(M, d->Cin, d->Cout, rps, pwlw)) {
-            KD_NOTE_KERNEL("conv_wgrad_pw_lw_kernel");
-            hipLaunchKernelGGL(conv_wgrad_pw_lw_kernel, dim3((unsigned)(tiles * splits)), dim3(256), 0, s, p);
-        } else {
-        KD_NOTE_KERNEL("conv_wgrad_wide_kernel");
-        if (!p.geom && !wide_general) hipLaunchKernelGGL(conv_wgrad_wide_kernel<true>, grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL(conv_wgrad_wide_kernel<false>, grid, dim3(512), 0, s, p);
-        }
-    }
-    else if (d->dtype == KD_BF16 && d->Cin % 8 == 0 && d->Cout % 8 == 0) launch_tr(grid, s, p);
-    else if (d->dtype == KD_BF16) { KD_NOTE_KERNEL("pw_wgrad_kernel<bf16>"); hipLaunchKernelGGL(pw_wgrad_kernel<bf16_t>, grid, dim3(256), 0, s, p); }
-    else { KD_NOTE_KERNEL("pw_wgrad_kernel<f32>"); hipLaunchKernelGGL(pw_wgrad_kernel<float>, grid, dim3(256), 0, s, p); }
-    KD_CHECK_LAUNCH("kd_conv2d_wgrad");
-    const size_t n = (size_t)d->Cout * d->Cin * taps;
-    const int rb = (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
-    if (taps == 1) {
-        launch_slab_reduce((const float *)workspace, dw, (size_t)d->Cout * d->Cin, splits, accumulate, s);
-    } else if (taps == 9) {
-        const size_t plane = (size_t)d->Cout * d->Cin;
-        const int rb9 = (int)((plane + 255) / 256 > 4096 ? 4096 : (plane + 255) / 256);
-        hipLaunchKernelGGL(slab_reduce_taps_cc_kernel<9>, dim3(rb9), dim3(256), 0, s, (const float *)workspace, dw, plane, splits,
-                           accumulate);
-    } else
-        hipLaunchKernelGGL(slab_reduce_taps_kernel, dim3(rb), dim3(256), 0, s, (const float *)workspace, dw, d->Cout, d->Cin, taps,
-                           splits, accumulate);
-    KD_CHECK_LAUNCH("kd_conv2d_wgrad(reduce)");
-    return KD_OK;
+    KD_REQUIRE(d->kh * d->kw <= 65535, KD_ERR_UNSUPPORTED, "kd_conv2d_wgrad: kernel too large");
+    return wgrad_impl("kd_conv2d_wgrad", d->dtype, M, d->Cin, d->Cout, d->kh * d->kw, d, x, d->ldx, dy, ld_dy, dw, accumulate, workspace,
+                      workspace_bytes, stream);
 }

@@ -1,17 +1,18 @@
 """Case table of tests/test_conv_dispatch_gpu.py: one row per branch, and per side of each gate, of the two dispatchers that carry
-almost all of the project's FLOPs -- kd_conv2d_fwd (csrc/conv_igemm.hip: conv_select + the branch order of conv2d_fwd_impl) and
-kd_conv2d_wgrad / kd_pw_wgrad (csrc/pw_wgrad.hip) -- together with a pure-Python restatement of both selections for the default
-environment (no KDCC_* switch set).  tests/test_conv_dispatch_host.py evaluates the restatement on every row without a GPU; on the
-GPU the same name is compared with the dispatcher's own log.  Nothing here imports torch or touches the device.
+almost all of the project's FLOPs -- kd_conv2d_fwd (csrc/conv_igemm.hip) and kd_conv2d_wgrad / kd_pw_wgrad (csrc/pw_wgrad.hip), whose
+selections are conv_select / wgrad_select of csrc/conv_select.h -- together with a pure-Python restatement of both selections for
+the default environment (no KDCC_* switch set).  tests/test_conv_dispatch_host.py evaluates the restatement on every row without a
+GPU and tests/test_conv_select_host.py holds it against the C selection; on the GPU the same name is compared with the dispatcher's
+own log.  Nothing here imports torch or touches the device.
 
 Every limit is read off the source:
   conv_igemm.hip  CfgRowT::MAXDIL = (AROWS - BM) / 2: CfgRow (320 rows) 32, CfgRowX (384) 64, CfgRowN (384) 64;
-                  conv_select: cfg = wide iff Cout > 128 and ceil(M / 256) * ceil(Cout / 256) >= 224; row geometry = 3x3, stride 1,
+  conv_select.h   conv_select: cfg = wide iff Cout > 128 and ceil(M / 256) * ceil(Cout / 256) >= 224; row geometry = 3x3, stride 1,
                   pad == dil, W % 256 == 0; persist_ok = bf16, wide, vec_ok, !raw_f32, M % 256 == 0, Cout % 256 == 0;
                   use_pp128 = narrow row geometry, vec_ok, !raw_f32, <= 2 operands, Cout % 128 == 0, W % 512 == 0, dil <= 16;
-                  conv2d_fwd_impl: conv_row_lw_kernel iff H >= 2 dil, conv_row_tall_kernel iff Cin % 64 == 0 and H > dil;
-                  persist_grid: tn_group = 4 iff Cout / 256 > 4 and (Cout / 256) % 4 == 0
-  pw_wgrad.hip    WR_XROWS = 96 (row_eligible: 2 dil + 64 <= 96, i.e. dil <= 16), conv_wgrad_lw_kernel iff Cout % 128 == 0 and
+                  conv_row_lw_kernel iff H >= 2 dil, conv_row_tall_kernel iff Cin % 64 == 0 and H > dil;
+                  tn_group = 4 iff Cout / 256 > 4 and (Cout / 256) % 4 == 0;
+                  WR_XROWS = 96 (row_eligible: 2 dil + 64 <= 96, i.e. dil <= 16), conv_wgrad_lw_kernel iff Cout % 128 == 0 and
                   dil <= 8, wide_tile_pays (>= 256 channels on both sides, padding of 256-tiles <= 135 % of 128-tiles),
                   pw_lw_pays (Cin % 256, Cout % 256, M % 64, rps % 32), plan / wide_plan / row_plan / fill_splits.
 

@@ -115,22 +115,31 @@ def test_the_restated_selection_predicts_the_row(c, ncu):
 
 
 def test_the_constants_the_restatement_uses_are_the_sources():
+    """The tile types stay in conv_igemm.hip, which asserts conv_select.h's table against them; every gate expression is in
+    conv_select.h, and in the whole library exactly once."""
     with open(os.path.join(CSRC, "conv_igemm.hip")) as f:
         conv = f.read()
     with open(os.path.join(CSRC, "pw_wgrad.hip")) as f:
         wg = f.read()
+    with open(os.path.join(CSRC, "conv_select.h")) as f:
+        sel = f.read()
     rows = dict(re.findall(r"typedef CfgRowT<8, 2, 4, 128, (\d+), 2, 2, 4, 1> (CfgRowX?);", conv))
     rows = {v: int(k) for k, v in rows.items()}
     assert (rows["CfgRow"] - 256) // 2 == T.ROW_MAXDIL and (rows["CfgRowX"] - 256) // 2 == T.ROWX_MAXDIL
     assert int(re.search(r"typedef CfgRowT<4, 4, 2, 64, (\d+), 3, 4> CfgRowN;", conv).group(1)) == 256 + 2 * T.ROWN_MAXDIL
     assert "MAXDIL = (AROWS - BM) / 2" in conv
-    assert f"wide_tiles >= {T.WIDE_TILES_MIN}" in conv and "d->Cout > 128 &&" in conv
-    assert "d->W % 512 == 0 && d->dil <= 16 && d->Cin % 32 == 0" in conv
-    assert "d->H >= 2 * d->dil" in conv and "d->Cin % 64 == 0 && d->H > d->dil" in conv
+    assert f"CONV_ROW_MAXDIL = {T.ROW_MAXDIL}, CONV_ROWX_MAXDIL = {T.ROWX_MAXDIL}, CONV_ROWN_MAXDIL = {T.ROWN_MAXDIL};" in sel
+    assert "CfgRow::MAXDIL == CONV_ROW_MAXDIL && CfgRowX::MAXDIL == CONV_ROWX_MAXDIL && CfgRowN::MAXDIL == CONV_ROWN_MAXDIL" in conv
     assert "KD_REQUIRE(d->Cin % bk == 0" in conv and "const int bk = 128 / es;" in conv       # what makes REFUSED_CIN unreachable
-    assert f"constexpr int WR_XROWS = {T.WR_XROWS};" in wg and "2 * d->dil + 64 <= WR_XROWS" in wg
-    assert "d->Cout % 128 == 0 && d->dil <= 8" in wg and "pad256 * 100 <= pad128 * 135" in wg
-    assert f"< {T.WS_SPLIT_CAP} ? (stages + 7) / 8 : {T.WS_SPLIT_CAP}" in wg
+    library = ""
+    for name in sorted(n for n in os.listdir(CSRC) if n.endswith((".hip", ".h", ".inc"))):
+        with open(os.path.join(CSRC, name)) as f:
+            library += f.read()
+    for gate in (f"wide_tiles >= {T.WIDE_TILES_MIN}", "d->Cout > 128 &&", "d->W % 512 == 0 && d->dil <= 16 && d->Cin % 32 == 0", "d->H >= 2 * d->dil",
+                 "d->Cin % 64 == 0 && d->H > d->dil", f"constexpr int WR_XROWS = {T.WR_XROWS};", "2 * d->dil + 64 <= WR_XROWS",
+                 "d->Cout % 128 == 0 && d->dil <= 8", "pad256 * 100 <= pad128 * 135", f"< {T.WS_SPLIT_CAP} ? (stages + 7) / 8 : {T.WS_SPLIT_CAP}"):
+        assert gate in sel and library.count(gate) == 1, gate
+    assert "WR_XROWS" in wg                                                                    # the kernels' row buffer is the gate's constant
 
 
 def test_grid_rows_walk_what_they_claim():
