@@ -13,14 +13,21 @@ namespace {
 
 constexpr int MAX_BLOCKS = 2048;
 
-__device__ __forceinline__ void block_partial(double v, double *partial)
+// K per-thread sums -> out[q][blockIdx.x], q < K: a wave reduction, then the four waves added in a fixed order
+template <int K> __device__ __forceinline__ void block_partials(const double (&v)[K], double *const (&out)[K])
 {
-    __shared__ double wsum[4];
-    v = wave_sum_d(v);
+    __shared__ double w[K][4];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) wsum[wv] = v;
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+        const double s = wave_sum_d(v[q]);
+        if (lane == 0) w[q][wv] = s;
+    }
     __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 0; q < K; ++q) out[q][blockIdx.x] = w[q][0] + w[q][1] + w[q][2] + w[q][3];
+    }
 }
 
 // loss = scale * sum(partial[0..n)) / (denom_ptr ? sum(partial2) : 1)
@@ -108,39 +115,7 @@ __global__ __launch_bounds__(256) void confusion_kernel(V3 x, const int64_t *__r
         if (hist[i]) atomicAdd(&conf[i], (unsigned long long)hist[i]);
 }
 
-// ---- KLDiv: one thread per pixel ----------------------------------------------------------
-__global__ __launch_bounds__(256) void kldiv_kernel(V3 s, V3 t, M3 g, float invT, float gscale, int N, int C, long long P,
-                                                    double *partial)
-{
-    double acc = 0.0;
-    const long long total = (long long)N * P;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const long long n = i / P, p = i - n * P;
-        const long long bs = n * s.sN + p * s.sP, bt = n * t.sN + p * t.sP;
-        float ms = -INFINITY, mt = -INFINITY;
-        for (int c = 0; c < C; ++c) {
-            ms = fmaxf(ms, kd_ld(s.p, s.dt, bs + c * s.sC) * invT);
-            mt = fmaxf(mt, kd_ld(t.p, t.dt, bt + c * t.sC) * invT);
-        }
-        float zs = 0.f, zt = 0.f;
-        for (int c = 0; c < C; ++c) {
-            zs += __expf(kd_ld(s.p, s.dt, bs + c * s.sC) * invT - ms);
-            zt += __expf(kd_ld(t.p, t.dt, bt + c * t.sC) * invT - mt);
-        }
-        const float lzs = __logf(zs) + ms, lzt = __logf(zt) + mt;
-        float kl = 0.f;
-        for (int c = 0; c < C; ++c) {
-            const float lps = kd_ld(s.p, s.dt, bs + c * s.sC) * invT - lzs;
-            const float lpt = kd_ld(t.p, t.dt, bt + c * t.sC) * invT - lzt;
-            const float pt = __expf(lpt);
-            kl += pt > 0.f ? pt * (lpt - lps) : 0.f;
-            if (g.p) kd_st(g.p, g.dt, n * g.sN + p * g.sP + c * g.sC, gscale * (__expf(lps) - pt));
-        }
-        acc += (double)kl;
-    }
-    block_partial(acc, partial);
-}
-
+// ---- global <-> LDS staging of the NHWC-dense fast paths ------------------------------------------------------------
 // global -> LDS staging of `nel` consecutive elements (scaled): 16-B vectors when the operand is fp32, the chunk is whole and
 // 16-B aligned (19 scalar loads per thread and operand otherwise: the 19-class logit kernels ran at 2.5 TB/s)
 template <typename T> __device__ __forceinline__ void stage_scaled(float *dst, const T *src, int nel, float mul)
@@ -166,49 +141,6 @@ template <typename T> __device__ __forceinline__ void unstage(T *dst, const floa
     } else {
         for (int i = threadIdx.x; i < nel; i += 256) Elem<T>::st(dst + i, src[i]);
     }
-}
-
-// NHWC-dense fast path (the engine's logits layout): a block stages 256 pixels x C channels of both operands in LDS
-// with fully coalesced loads, each thread then owns one pixel (row stride C words: conflict-free for odd C), and
-// the gradient goes back out through the same LDS rows, coalesced.
-template <typename TS, typename TT, typename TG>
-__global__ __launch_bounds__(256) void kldiv_nhwc_kernel(const TS *__restrict__ s, const TT *__restrict__ t, TG *__restrict__ g,
-                                                         int C, long long npix, float invT, float gscale, double *partial)
-{
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float *ss = sm, *st = sm + 256 * C;   // 256 * C * 4 B: a multiple of 16
-    double acc = 0.0;
-    for (long long base = (long long)blockIdx.x * 256; base < npix; base += (long long)gridDim.x * 256) {
-        const int np = (int)min((long long)256, npix - base);
-        const int nel = np * C;
-        const TS *sp = s + base * C;
-        const TT *tp = t + base * C;
-        stage_scaled(ss, sp, nel, invT);
-        stage_scaled(st, tp, nel, invT);
-        __syncthreads();
-        if ((int)threadIdx.x < np) {
-            float *a = ss + threadIdx.x * C, *b = st + threadIdx.x * C;
-            float ms = -INFINITY, mt = -INFINITY;
-            for (int c = 0; c < C; ++c) { ms = fmaxf(ms, a[c]); mt = fmaxf(mt, b[c]); }
-            float zs = 0.f, zt = 0.f;
-            for (int c = 0; c < C; ++c) { zs += __expf(a[c] - ms); zt += __expf(b[c] - mt); }
-            const float lzs = __logf(zs) + ms, lzt = __logf(zt) + mt;
-            float kl = 0.f;
-            for (int c = 0; c < C; ++c) {
-                const float lps = a[c] - lzs, lpt = b[c] - lzt;
-                const float pt = __expf(lpt);
-                kl += pt > 0.f ? pt * (lpt - lps) : 0.f;
-                a[c] = gscale * (__expf(lps) - pt);
-            }
-            acc += (double)kl;
-        }
-        __syncthreads();
-        if (g) {
-            unstage(g + base * C, ss, nel);
-        }
-        __syncthreads();
-    }
-    block_partial(acc, partial);
 }
 
 template <typename TX>
@@ -303,13 +235,54 @@ __device__ __forceinline__ UpChunk up_chunk(const UpGeom &g, long long chunk, in
     k.wlo = a; k.nw = b - a + 1;
     return k;
 }
+// output column wo of a chunk: its horizontal blend weight, the offsets of its two source columns in a staged row, the row length
+struct UpCol { float aw; int o0, o1, nr; };
+__device__ __forceinline__ UpCol up_col(const UpGeom &g, const UpChunk &k, int wo)
+{
+    const float fw = fmaxf(wo * g.sw + g.ow, 0.f);
+    int w0 = (int)fw; w0 = w0 > g.w - 1 ? g.w - 1 : w0;
+    const int w1 = w0 + 1 < g.w ? w0 + 1 : g.w - 1;
+    return UpCol{fw - w0, (w0 - k.wlo) * g.C, (w1 - k.wlo) * g.C, k.nw * g.C};
+}
+// One interpolated pixel of a staged patch, channel c through operator().  CT: the class count at compile time (19: the logits
+// are interpolated ONCE into registers) or 0 (any C: re-interpolated at every read).  mul: the 1/T of the two-distribution losses.
+template <int CT> struct UpPix {
+    const float *sm;
+    UpCol col;
+    float ah, mul, v[CT > 0 ? CT : 1];
+    __device__ __forceinline__ UpPix(const float *sm_, const UpCol &col_, float ah_, float mul_ = 1.f) : sm(sm_), col(col_), ah(ah_), mul(mul_)
+    {
+        if constexpr (CT > 0) {
+#pragma unroll
+            for (int c = 0; c < CT; ++c) v[c] = up_val(sm, col.nr, col.o0, col.o1, c, col.aw, ah) * mul;
+        }
+    }
+    __device__ __forceinline__ float operator()(int c) const
+    {
+        if constexpr (CT > 0) return v[c];
+        else return up_val(sm, col.nr, col.o0, col.o1, c, col.aw, ah) * mul;
+    }
+    // channel y, known at run time only (a select per register, never an indexed register array)
+    __device__ __forceinline__ float at(int y) const
+    {
+        if constexpr (CT > 0) {
+            float r = 0.f;
+#pragma unroll
+            for (int c = 0; c < CT; ++c) r = c == y ? v[c] : r;
+            return r;
+        } else {
+            return (*this)(y);
+        }
+    }
+};
 
-// CT: the class count at compile time (19: a pixel's logits are interpolated ONCE into registers) or 0 (any C: re-interpolated per pass)
 template <int CT>
 __global__ __launch_bounds__(256) void ce2d_up_kernel(const float *__restrict__ x, const int64_t *__restrict__ target, int ignore_index,
                                                       UpGeom g, long long nchunks, int cpr, double *partial, double *count)
 {
     extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int C = CT > 0 ? CT : g.C;
+    constexpr int UR = CT > 0 ? CT : 8;   // (fully unrolled at a compile-time class count, 8-way at any other)
     double acc = 0.0, cnt = 0.0;
     for (long long chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
         const UpChunk k = up_chunk(g, chunk, cpr);
@@ -319,93 +292,19 @@ __global__ __launch_bounds__(256) void ce2d_up_kernel(const float *__restrict__ 
         if (wo < g.W) {
             const int64_t y = target[((size_t)k.n * g.H + k.ho) * g.W + wo];
             if (!(y == ignore_index || y < 0 || y >= g.C)) {
-                const float fw = fmaxf(wo * g.sw + g.ow, 0.f);
-                int w0 = (int)fw; w0 = w0 > g.w - 1 ? g.w - 1 : w0;
-                const int w1 = w0 + 1 < g.w ? w0 + 1 : g.w - 1;
-                const float aw = fw - w0;
-                const int o0 = (w0 - k.wlo) * g.C, o1 = (w1 - k.wlo) * g.C, nr = k.nw * g.C;
-                float m = -INFINITY, z = 0.f, vy = 0.f;
-                if constexpr (CT > 0) {
-                    float v[CT];
-#pragma unroll
-                    for (int c = 0; c < CT; ++c) { v[c] = up_val(sm, nr, o0, o1, c, aw, k.ah); m = fmaxf(m, v[c]); }
-#pragma unroll
-                    for (int c = 0; c < CT; ++c) { z += __expf(v[c] - m); vy = c == (int)y ? v[c] : vy; }
-                } else {
-                    for (int c = 0; c < g.C; ++c) m = fmaxf(m, up_val(sm, nr, o0, o1, c, aw, k.ah));
-                    for (int c = 0; c < g.C; ++c) z += __expf(up_val(sm, nr, o0, o1, c, aw, k.ah) - m);
-                    vy = up_val(sm, nr, o0, o1, (int)y, aw, k.ah);
-                }
-                acc += (double)(-(vy - m - __logf(z)));
+                const UpPix<CT> v(sm, up_col(g, k, wo), k.ah);
+                float m = -INFINITY, z = 0.f;
+                // (no count on the max pass: a compile-time C unrolls fully by itself, a run-time C as the compiler chooses)
+                for (int c = 0; c < C; ++c) m = fmaxf(m, v(c));
+#pragma unroll UR
+                for (int c = 0; c < C; ++c) z += __expf(v(c) - m);
+                acc += (double)(-(v.at((int)y) - m - __logf(z)));
                 cnt += 1.0;
             }
         }
         __syncthreads();
     }
-    __shared__ double w1s[4], w2s[4];
-    acc = wave_sum_d(acc); cnt = wave_sum_d(cnt);
-    if ((threadIdx.x & 63) == 0) { w1s[threadIdx.x >> 6] = acc; w2s[threadIdx.x >> 6] = cnt; }
-    __syncthreads();
-    if (threadIdx.x == 0) { partial[blockIdx.x] = w1s[0] + w1s[1] + w1s[2] + w1s[3]; count[blockIdx.x] = w2s[0] + w2s[1] + w2s[2] + w2s[3]; }
-}
-
-template <int CT>
-__global__ __launch_bounds__(256) void kldiv_up_kernel(const float *__restrict__ s, const float *__restrict__ t, UpGeom g, float invT,
-                                                       long long nchunks, int cpr, double *partial)
-{
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float *ss = sm, *st = sm + 2 * UP_NW * g.C;
-    double acc = 0.0;
-    for (long long chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-        const UpChunk k = up_chunk(g, chunk, cpr);
-        up_stage(ss, s, g, k.n, k.h0, k.h1, k.wlo, k.nw);
-        up_stage(st, t, g, k.n, k.h0, k.h1, k.wlo, k.nw);
-        __syncthreads();
-        const int wo = k.wo0 + threadIdx.x;
-        if (wo < g.W) {
-            const float fw = fmaxf(wo * g.sw + g.ow, 0.f);
-            int w0 = (int)fw; w0 = w0 > g.w - 1 ? g.w - 1 : w0;
-            const int w1 = w0 + 1 < g.w ? w0 + 1 : g.w - 1;
-            const float aw = fw - w0;
-            const int o0 = (w0 - k.wlo) * g.C, o1 = (w1 - k.wlo) * g.C, nr = k.nw * g.C;
-            float ms = -INFINITY, mt = -INFINITY, zs = 0.f, zt = 0.f, kl = 0.f;
-            if constexpr (CT > 0) {
-                float a[CT], b[CT];
-#pragma unroll
-                for (int c = 0; c < CT; ++c) {
-                    a[c] = up_val(ss, nr, o0, o1, c, aw, k.ah) * invT;
-                    b[c] = up_val(st, nr, o0, o1, c, aw, k.ah) * invT;
-                    ms = fmaxf(ms, a[c]); mt = fmaxf(mt, b[c]);
-                }
-#pragma unroll
-                for (int c = 0; c < CT; ++c) { zs += __expf(a[c] - ms); zt += __expf(b[c] - mt); }
-                const float lzs = __logf(zs) + ms, lzt = __logf(zt) + mt;
-#pragma unroll
-                for (int c = 0; c < CT; ++c) {
-                    const float lps = a[c] - lzs, lpt = b[c] - lzt, pt = __expf(lpt);
-                    kl += pt > 0.f ? pt * (lpt - lps) : 0.f;
-                }
-            } else {
-                for (int c = 0; c < g.C; ++c) {
-                    ms = fmaxf(ms, up_val(ss, nr, o0, o1, c, aw, k.ah) * invT);
-                    mt = fmaxf(mt, up_val(st, nr, o0, o1, c, aw, k.ah) * invT);
-                }
-                for (int c = 0; c < g.C; ++c) {
-                    zs += __expf(up_val(ss, nr, o0, o1, c, aw, k.ah) * invT - ms);
-                    zt += __expf(up_val(st, nr, o0, o1, c, aw, k.ah) * invT - mt);
-                }
-                const float lzs = __logf(zs) + ms, lzt = __logf(zt) + mt;
-                for (int c = 0; c < g.C; ++c) {
-                    const float lps = up_val(ss, nr, o0, o1, c, aw, k.ah) * invT - lzs, lpt = up_val(st, nr, o0, o1, c, aw, k.ah) * invT - lzt;
-                    const float pt = __expf(lpt);
-                    kl += pt > 0.f ? pt * (lpt - lps) : 0.f;
-                }
-            }
-            acc += (double)kl;
-        }
-        __syncthreads();
-    }
-    block_partial(acc, partial);
+    block_partials<2>({acc, cnt}, {partial, count});
 }
 
 // ---- the analysis step's logged metrics from both low-resolution logit tensors (trainer/analysis_trainer.py:55-81) ---------------------
@@ -424,6 +323,8 @@ __global__ __launch_bounds__(256) void logit_metrics_up_kernel(const float *__re
     float *ss = sm, *st = sm + 2 * UP_NW * g.C;
     unsigned int *hs = (unsigned int *)(sm + 4 * UP_NW * g.C), *ht = hs + g.C * g.C;
     for (int i = threadIdx.x; i < 2 * g.C * g.C; i += 256) hs[i] = 0u;
+    const int C = CT > 0 ? CT : g.C;
+    constexpr int UR = CT > 0 ? CT : 2;   // (two operands and two histograms a pixel: 2-way at a run-time class count)
     double ces = 0.0, cet = 0.0, cnt = 0.0, sq = 0.0;
     for (long long chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
         const UpChunk k = up_chunk(g, chunk, cpr);
@@ -436,45 +337,21 @@ __global__ __launch_bounds__(256) void logit_metrics_up_kernel(const float *__re
             const bool lab = y >= 0 && y < g.C;                    // counted by the confusion matrices (kd_confusion)
             const bool valid = lab && y != ignore_index;           // counted by the cross entropies (kd_ce2d)
             const int yc = lab ? (int)y : 0;
-            const float fw = fmaxf(wo * g.sw + g.ow, 0.f);
-            int w0 = (int)fw; w0 = w0 > g.w - 1 ? g.w - 1 : w0;
-            const int w1 = w0 + 1 < g.w ? w0 + 1 : g.w - 1;
-            const float aw = fw - w0;
-            const int o0 = (w0 - k.wlo) * g.C, o1 = (w1 - k.wlo) * g.C, nr = k.nw * g.C;
-            float ms, mt, zs = 0.f, zt = 0.f, vs = 0.f, vt = 0.f, d2 = 0.f;
+            const UpCol col = up_col(g, k, wo);
+            const UpPix<CT> a(ss, col, k.ah), b(st, col, k.ah);
+            float ms = a(0), mt = b(0), zs = 0.f, zt = 0.f, d2 = 0.f;
             int as = 0, at = 0;
-            if constexpr (CT > 0) {
-                float a[CT], b[CT];
-#pragma unroll
-                for (int c = 0; c < CT; ++c) { a[c] = up_val(ss, nr, o0, o1, c, aw, k.ah); b[c] = up_val(st, nr, o0, o1, c, aw, k.ah); }
-                ms = a[0]; mt = b[0];
-#pragma unroll
-                for (int c = 0; c < CT; ++c) {
-                    if (c > 0 && arg_better(a[c], ms)) { ms = a[c]; as = c; }
-                    if (c > 0 && arg_better(b[c], mt)) { mt = b[c]; at = c; }
-                    const float d = a[c] - b[c];
-                    d2 += d * d;
-                }
-#pragma unroll
-                for (int c = 0; c < CT; ++c) {
-                    zs += __expf(a[c] - ms); zt += __expf(b[c] - mt);
-                    vs = c == yc ? a[c] : vs; vt = c == yc ? b[c] : vt;
-                }
-            } else {
-                ms = up_val(ss, nr, o0, o1, 0, aw, k.ah); mt = up_val(st, nr, o0, o1, 0, aw, k.ah);
-                for (int c = 0; c < g.C; ++c) {
-                    const float a = up_val(ss, nr, o0, o1, c, aw, k.ah), b = up_val(st, nr, o0, o1, c, aw, k.ah);
-                    if (c > 0 && arg_better(a, ms)) { ms = a; as = c; }
-                    if (c > 0 && arg_better(b, mt)) { mt = b; at = c; }
-                    const float d = a - b;
-                    d2 += d * d;
-                }
-                for (int c = 0; c < g.C; ++c) {
-                    zs += __expf(up_val(ss, nr, o0, o1, c, aw, k.ah) - ms);
-                    zt += __expf(up_val(st, nr, o0, o1, c, aw, k.ah) - mt);
-                }
-                vs = up_val(ss, nr, o0, o1, yc, aw, k.ah); vt = up_val(st, nr, o0, o1, yc, aw, k.ah);
+#pragma unroll UR
+            for (int c = 0; c < C; ++c) {
+                const float av = a(c), bv = b(c);
+                if (c > 0 && arg_better(av, ms)) { ms = av; as = c; }
+                if (c > 0 && arg_better(bv, mt)) { mt = bv; at = c; }
+                const float d = av - bv;
+                d2 += d * d;
             }
+#pragma unroll UR
+            for (int c = 0; c < C; ++c) { zs += __expf(a(c) - ms); zt += __expf(b(c) - mt); }
+            const float vs = a.at(yc), vt = b.at(yc);
             sq += (double)d2;
             if (valid) {
                 ces += (double)(-(vs - ms - __logf(zs)));
@@ -548,7 +425,7 @@ __global__ __launch_bounds__(256) void mse_vec_kernel(const T *__restrict__ s, c
         if (++cnt == 16) { dacc += (double)acc; acc = 0.f; cnt = 0; }  // bound fp32 accumulation length
     }
     dacc += (double)acc;
-    block_partial(dacc, partial);
+    block_partials<1>({dacc}, {partial});
 }
 __global__ __launch_bounds__(256) void mse_strided_kernel(V3 s, V3 t, M3 g, float gscale, int N, int C, long long P,
                                                           int c_fast, double *partial)
@@ -563,7 +440,7 @@ __global__ __launch_bounds__(256) void mse_strided_kernel(V3 s, V3 t, M3 g, floa
         acc += (double)d * d;
         if (g.p) kd_st(g.p, g.dt, n * g.sN + c * g.sC + p * g.sP, gscale * d);
     }
-    block_partial(acc, partial);
+    block_partials<1>({acc}, {partial});
 }
 
 // ---- weighted hint MSE ---------------------------------------------------------------------
@@ -788,15 +665,16 @@ __global__ __launch_bounds__(256) void scale_by_device_scalar_kernel(T *x, long 
     }
 }
 
-// ---- JSD / ensemble KL: the two-distribution criteria beside KLDiv -----------------------------------------------------------
+// ---- KLDiv / JSD / ensemble KL: the two-distribution criteria -----------------------------------------------------------------
 // One pixel's C-vector through an accessor (LDS row, register array, strided global or in-register interpolation): ls(c) / lt(c)
 // return the student / target value at channel c (already divided by T), sg(c, v) stores the gradient.  CT > 0: the class count
 // at compile time (loops unrolled, register arrays stay registers).
+//   PAIR_KLD (losses/KLDiv.py): value sum_c pt (lpt - lps); grad gscale * (ps - pt), stored in the value's own pass
 //   PAIR_JSD (losses/JSDiv.py:19-26): value sum_c ps (lps - lq) + pt (lpt - lq), lq = log 1/2 + logaddexp(lps, lpt)
 //                                      grad  gscale * ps * (a - <ps, a>), a = lps - lq
 //   PAIR_EKL (losses/EnsembleKLDiv.py:17-21): t holds probabilities; value sum_c xlogy(t, t) - t lps
 //                                      grad  gscale * (ps * sum_c t - t)
-enum { PAIR_JSD = 1, PAIR_EKL = 2 };
+enum { PAIR_KLD = 0, PAIR_JSD = 1, PAIR_EKL = 2 };
 
 __device__ __forceinline__ float log_half_sum(float x, float y)
 {
@@ -813,27 +691,38 @@ __device__ __forceinline__ float jsd_log_q(float lps, float lpt, float ps, float
 
 // STASH: the caller's rows are writable (LDS): the forward pass parks ps and a in them (put), the gradient pass reads them back
 // (get) instead of recomputing two exponentials and a logarithm per element
-template <int KIND, int CT, bool STASH, typename LS, typename LT, typename SG, typename PUT, typename GET>
+// UR0: the unrolling of the loops at a run-time class count (CT == 0), the caller's choice: 8 where a read is an LDS access and the
+// body short (the KL kernels over LDS), 1 (rolled) where it is a strided global load or the body long (JSD / EKL)
+template <int KIND, int CT, bool STASH, int UR0, typename LS, typename LT, typename SG, typename PUT, typename GET>
 __device__ __forceinline__ float pair_pixel(int C_, LS ls, LT lt, SG sg, PUT put, GET get, bool want_grad, float gscale)
 {
     const int C = CT > 0 ? CT : C_;
-    constexpr int UR = CT > 0 ? CT : 1;   // (fully unrolled at a compile-time class count only)
-    float ms = -INFINITY;
+    constexpr int UR = CT > 0 ? CT : UR0;
+    constexpr bool TLOGITS = KIND != PAIR_EKL;   // the target holds logits too: its softmax statistics ride in the student's passes
+    float ms = -INFINITY, mt = -INFINITY;
 #pragma unroll UR
-    for (int c = 0; c < C; ++c) ms = fmaxf(ms, ls(c));
-    float zs = 0.f;
+    for (int c = 0; c < C; ++c) {
+        ms = fmaxf(ms, ls(c));
+        if constexpr (TLOGITS) mt = fmaxf(mt, lt(c));
+    }
+    float zs = 0.f, zt = 0.f;
 #pragma unroll UR
-    for (int c = 0; c < C; ++c) zs += __expf(ls(c) - ms);
+    for (int c = 0; c < C; ++c) {
+        zs += __expf(ls(c) - ms);
+        if constexpr (TLOGITS) zt += __expf(lt(c) - mt);
+    }
     const float lzs = __logf(zs) + ms;
+    [[maybe_unused]] const float lzt = __logf(zt) + mt;
     float val = 0.f;
-    if constexpr (KIND == PAIR_JSD) {
-        float mt = -INFINITY;
-#pragma unroll UR
-        for (int c = 0; c < C; ++c) mt = fmaxf(mt, lt(c));
-        float zt = 0.f;
-#pragma unroll UR
-        for (int c = 0; c < C; ++c) zt += __expf(lt(c) - mt);
-        const float lzt = __logf(zt) + mt;
+    if constexpr (KIND == PAIR_KLD) {
+        constexpr int URG = CT > 0 ? CT : (UR0 > 4 ? 4 : UR0);   // (this pass stores as well: at most 4-way at a run-time class count)
+#pragma unroll URG
+        for (int c = 0; c < C; ++c) {
+            const float lps = ls(c) - lzs, lpt = lt(c) - lzt, pt = __expf(lpt);
+            val += pt > 0.f ? pt * (lpt - lps) : 0.f;
+            if (want_grad) sg(c, gscale * (__expf(lps) - pt));
+        }
+    } else if constexpr (KIND == PAIR_JSD) {
         float dot = 0.f;
 #pragma unroll UR
         for (int c = 0; c < C; ++c) {
@@ -887,17 +776,18 @@ __global__ __launch_bounds__(256) void pair_kernel(V3 s, V3 t, M3 g, float invT,
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const long long n = i / P, p = i - n * P;
         const long long bs = n * s.sN + p * s.sP, bt = n * t.sN + p * t.sP, bg = n * g.sN + p * g.sP;
-        const float tmul = KIND == PAIR_JSD ? invT : 1.f;
-        acc += (double)pair_pixel<KIND, 0, false>(
+        const float tmul = KIND == PAIR_EKL ? 1.f : invT;
+        acc += (double)pair_pixel<KIND, 0, false, 1>(
             C, [&](int c) { return kd_ld(s.p, s.dt, bs + c * s.sC) * invT; },
             [&](int c) { return kd_ld(t.p, t.dt, bt + c * t.sC) * tmul; },
             [&](int c, float v) { kd_st(g.p, g.dt, bg + c * g.sC, v); }, pair_noput, pair_noget, g.p != nullptr, gscale);
     }
-    block_partial(acc, partial);
+    block_partials<1>({acc}, {partial});
 }
 
-// NHWC-dense fast path: the staging of kldiv_nhwc_kernel (256 pixels x C channels of both operands in LDS, one pixel per thread,
-// the gradient back out through the student's LDS rows)
+// NHWC-dense fast path (the engine's logits layout): a block stages 256 pixels x C channels of both operands in LDS with fully
+// coalesced loads, each thread then owns one pixel (row stride C words: conflict-free for odd C), and the gradient goes back out
+// through the student's LDS rows, coalesced.
 template <int KIND, typename TS, typename TT, typename TG>
 __global__ __launch_bounds__(256) void pair_nhwc_kernel(const TS *__restrict__ s, const TT *__restrict__ t, TG *__restrict__ g, int C,
                                                         long long npix, float invT, float gscale, double *partial)
@@ -909,11 +799,11 @@ __global__ __launch_bounds__(256) void pair_nhwc_kernel(const TS *__restrict__ s
         const int np = (int)min((long long)256, npix - base);
         const int nel = np * C;
         stage_scaled(ss, s + base * C, nel, invT);
-        stage_scaled(st, t + base * C, nel, KIND == PAIR_JSD ? invT : 1.f);
+        stage_scaled(st, t + base * C, nel, KIND == PAIR_EKL ? 1.f : invT);
         __syncthreads();
         if ((int)threadIdx.x < np) {
             float *a = ss + threadIdx.x * C, *b = st + threadIdx.x * C;
-            acc += (double)pair_pixel<KIND, 0, true>(
+            acc += (double)pair_pixel<KIND, 0, true, KIND == PAIR_KLD ? 8 : 1>(
                 C, [&](int c) { return a[c]; }, [&](int c) { return b[c]; }, [&](int c, float v) { a[c] = v; },
                 [&](int c, float ps, float av) { a[c] = ps; b[c] = av; }, [&](int c, float &ps, float &av) { ps = a[c]; av = b[c]; },
                 g != nullptr, gscale);
@@ -922,13 +812,13 @@ __global__ __launch_bounds__(256) void pair_nhwc_kernel(const TS *__restrict__ s
         if (g) unstage(g + base * C, ss, nel);
         __syncthreads();
     }
-    block_partial(acc, partial);
+    block_partials<1>({acc}, {partial});
 }
 
-// JSD from the two low-resolution logit tensors: kldiv_up_kernel's staging and interpolation, pair_pixel's arithmetic
-template <int CT>
-__global__ __launch_bounds__(256) void jsdiv_up_kernel(const float *__restrict__ s, const float *__restrict__ t, UpGeom g, float invT,
-                                                       long long nchunks, int cpr, double *partial)
+// KLDiv / JSD from the two low-resolution logit tensors: ce2d_up_kernel's staging and interpolation, pair_pixel's arithmetic
+template <int KIND, int CT>
+__global__ __launch_bounds__(256) void pair_up_kernel(const float *__restrict__ s, const float *__restrict__ t, UpGeom g, float invT,
+                                                      long long nchunks, int cpr, double *partial)
 {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float *ss = sm, *st = sm + 2 * UP_NW * g.C;
@@ -941,29 +831,13 @@ __global__ __launch_bounds__(256) void jsdiv_up_kernel(const float *__restrict__
         __syncthreads();
         const int wo = k.wo0 + threadIdx.x;
         if (wo < g.W) {
-            const float fw = fmaxf(wo * g.sw + g.ow, 0.f);
-            int w0 = (int)fw; w0 = w0 > g.w - 1 ? g.w - 1 : w0;
-            const int w1 = w0 + 1 < g.w ? w0 + 1 : g.w - 1;
-            const float aw = fw - w0;
-            const int o0 = (w0 - k.wlo) * g.C, o1 = (w1 - k.wlo) * g.C, nr = k.nw * g.C;
-            if constexpr (CT > 0) {
-                float a[CT], b[CT];
-#pragma unroll
-                for (int c = 0; c < CT; ++c) {
-                    a[c] = up_val(ss, nr, o0, o1, c, aw, k.ah) * invT;
-                    b[c] = up_val(st, nr, o0, o1, c, aw, k.ah) * invT;
-                }
-                acc += (double)pair_pixel<PAIR_JSD, CT, false>(CT, [&](int c) { return a[c]; }, [&](int c) { return b[c]; }, nostore,
-                                                               pair_noput, pair_noget, false, 0.f);
-            } else {
-                acc += (double)pair_pixel<PAIR_JSD, 0, false>(
-                    g.C, [&](int c) { return up_val(ss, nr, o0, o1, c, aw, k.ah) * invT; },
-                    [&](int c) { return up_val(st, nr, o0, o1, c, aw, k.ah) * invT; }, nostore, pair_noput, pair_noget, false, 0.f);
-            }
+            const UpCol col = up_col(g, k, wo);
+            acc += (double)pair_pixel<KIND, CT, false, KIND == PAIR_KLD ? 4 : 1>(g.C, UpPix<CT>(ss, col, k.ah, invT), UpPix<CT>(st, col, k.ah, invT), nostore,
+                                                       pair_noput, pair_noget, false, 0.f);
         }
         __syncthreads();
     }
-    block_partial(acc, partial);
+    block_partials<1>({acc}, {partial});
 }
 
 // ---- focal loss (losses/FocalLoss.py:15-28) ------------------------------------------------------------------------------------
@@ -1002,20 +876,6 @@ __device__ __forceinline__ void focal_pixel(int C_, LX lx, int y, bool valid, fl
     ce = valid ? wy * -(vy - m - __logf(z)) : 0.f;
 }
 
-__device__ __forceinline__ void block_partial3(double a, double b, double c, double *pa, double *pb, double *pc)
-{
-    __shared__ double w[3][4];
-    a = wave_sum_d(a); b = wave_sum_d(b); c = wave_sum_d(c);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) { w[0][wv] = a; w[1][wv] = b; w[2][wv] = c; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        pa[blockIdx.x] = w[0][0] + w[0][1] + w[0][2] + w[0][3];
-        pb[blockIdx.x] = w[1][0] + w[1][1] + w[1][2] + w[1][3];
-        pc[blockIdx.x] = w[2][0] + w[2][1] + w[2][2] + w[2][3];
-    }
-}
-
 __device__ __forceinline__ bool focal_valid(int64_t y, int ignore_index, int C) { return !(y == ignore_index || y < 0 || y >= C); }
 
 __global__ __launch_bounds__(256) void focal_kernel(V3 x, const int64_t *__restrict__ target, const float *__restrict__ cw, float gamma,
@@ -1034,7 +894,7 @@ __global__ __launch_bounds__(256) void focal_kernel(V3 x, const int64_t *__restr
         if (amap) { amap[i] = a; cemap[i] = ce; }
         sa += (double)a; sc += (double)ce; sw += (double)wy;
     }
-    block_partial3(sa, sc, sw, partial, partial + FOCAL_MAX_BLOCKS, partial + 2 * FOCAL_MAX_BLOCKS);
+    block_partials<3>({sa, sc, sw}, {partial, partial + FOCAL_MAX_BLOCKS, partial + 2 * FOCAL_MAX_BLOCKS});
 }
 
 template <int CT>
@@ -1052,25 +912,13 @@ __global__ __launch_bounds__(256) void focal_up_kernel(const float *__restrict__
             const int64_t y = target[((size_t)k.n * g.H + k.ho) * g.W + wo];
             const bool valid = focal_valid(y, ignore_index, g.C);
             const float wy = valid ? (cw ? cw[y] : 1.f) : 0.f;
-            const float fw = fmaxf(wo * g.sw + g.ow, 0.f);
-            int w0 = (int)fw; w0 = w0 > g.w - 1 ? g.w - 1 : w0;
-            const int w1 = w0 + 1 < g.w ? w0 + 1 : g.w - 1;
-            const float aw = fw - w0;
-            const int o0 = (w0 - k.wlo) * g.C, o1 = (w1 - k.wlo) * g.C, nr = k.nw * g.C;
             float a, ce;
-            if constexpr (CT > 0) {
-                float v[CT];
-#pragma unroll
-                for (int c = 0; c < CT; ++c) v[c] = up_val(sm, nr, o0, o1, c, aw, k.ah);
-                focal_pixel<CT>(CT, [&](int c) { return v[c]; }, valid ? (int)y : 0, valid, wy, gamma, a, ce);
-            } else {
-                focal_pixel<0>(g.C, [&](int c) { return up_val(sm, nr, o0, o1, c, aw, k.ah); }, valid ? (int)y : 0, valid, wy, gamma, a, ce);
-            }
+            focal_pixel<CT>(g.C, UpPix<CT>(sm, up_col(g, k, wo), k.ah), valid ? (int)y : 0, valid, wy, gamma, a, ce);
             sa += (double)a; sc += (double)ce; sw += (double)wy;
         }
         __syncthreads();
     }
-    block_partial3(sa, sc, sw, partial, partial + FOCAL_MAX_BLOCKS, partial + 2 * FOCAL_MAX_BLOCKS);
+    block_partials<3>({sa, sc, sw}, {partial, partial + FOCAL_MAX_BLOCKS, partial + 2 * FOCAL_MAX_BLOCKS});
 }
 
 // stats = (sum a, sum ce, sum w) in fixed order; loss: 'mean' mean(a) * (sum ce / sum w), 'sum' sum a * sum ce ('none': none)
@@ -1270,7 +1118,7 @@ __global__ __launch_bounds__(256) void topk_grad_kernel(V3 s, V3 t, M3 g, const 
 // gradient is written once.  The target views travel by value in the kernel argument (w already divided by W).  Three shapes:
 //   mt_wave_kernel   class stride 1, a row of C <= 1024 classes held in one wave's registers, reductions by lane shuffles;
 //   kldm_nhwc_kernel dense NHWC with few classes and many pixels: 256 pixels per block staged through LDS, one pixel per thread;
-//   kldm_kernel      any strides / any C: one pixel per thread, the operands re-read from cache as kldiv_kernel does.
+//   kldm_kernel      any strides / any C: one pixel per thread, the operands re-read from cache as pair_kernel does.
 struct MT { V3 t[KD_MULTI_MAX]; float w[KD_MULTI_MAX]; int n; };
 constexpr int MT_MAX_BLOCKS = 2 * MAX_BLOCKS / 3;      // kd / ce / count partials inside kd_loss_workspace's 2 * MAX_BLOCKS doubles
 
@@ -1288,15 +1136,6 @@ __device__ __forceinline__ float mt_sup_scale(const double *count, int ncount, f
     for (int i = threadIdx.x & 63; i < ncount; i += 64) c += count[i];
     c = wave_sum_d(c);
     return c > 0.0 ? sup_scale / (float)c : 0.f;
-}
-
-__device__ __forceinline__ void block_partial2(double a, double b, double *pa, double *pb)
-{
-    __shared__ double w1[4], w2[4];
-    a = wave_sum_d(a); b = wave_sum_d(b);
-    if ((threadIdx.x & 63) == 0) { w1[threadIdx.x >> 6] = a; w2[threadIdx.x >> 6] = b; }
-    __syncthreads();
-    if (threadIdx.x == 0) { pa[blockIdx.x] = w1[0] + w1[1] + w1[2] + w1[3]; pb[blockIdx.x] = w2[0] + w2[1] + w2[2] + w2[3]; }
 }
 
 // A row of C classes in one wave: lane l holds 4 * NCH elements.  VEC: element (j, q) is class (j * 64 + l) * 4 + q, one 16-B (fp32)
@@ -1446,7 +1285,7 @@ __global__ __launch_bounds__(256) void mt_wave_kernel(V3 s, const MT tg, M3 g, c
             row_store<NCH, VEC>(g.p, g.dt, n * g.sN + p * g.sP, C, lane, q);
         }
     }
-    if (!SMEAN) block_partial2(akd, ace, pkd, pce);
+    if (!SMEAN) block_partials<2>({akd, ace}, {pkd, pce});
 }
 
 // global <-> LDS staging of `nel` consecutive elements of either storage type: 16-B accesses when the chunk is whole and aligned
@@ -1561,7 +1400,7 @@ __global__ __launch_bounds__(256) void kldm_nhwc_kernel(V3 s, const MT tg, M3 g,
         }
         __syncthreads();
     }
-    block_partial2(akd, ace, pkd, pce);
+    block_partials<2>({akd, ace}, {pkd, pce});
 }
 
 // any strides, any C: one pixel per thread; log Z of every target parked in LDS ([target][thread]: conflict-free)
@@ -1633,7 +1472,7 @@ __global__ __launch_bounds__(256) void kldm_kernel(V3 s, const MT tg, M3 g, cons
         }
         akd += (double)kl;
     }
-    if (!SMEAN) block_partial2(akd, ace, pkd, pce);
+    if (!SMEAN) block_partials<2>({akd, ace}, {pkd, pce});
 }
 
 // out[0] = kd, out[1] = sup, out[2] = kd_scale * kd + sup_scale * sup
@@ -1677,47 +1516,57 @@ extern "C" size_t kd_loss_workspace(int32_t N, int32_t C, int64_t P)
     KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, P), KD_ERR_WORKSPACE, who ": workspace too small");        \
     KD_REQUIRE(((uintptr_t)workspace & 7) == 0, KD_ERR_INVALID, who ": workspace must be 8-B aligned")
 
+// ---- kd_kldiv / kd_jsdiv / kd_ensemble_kldiv: the entry point sets the scales, this picks the kernel -------------------------------
+static int pair_impl(const char *who, int kind, const kd_view3 *s, const kd_view3 *t, float invT, int32_t N, int32_t C, int64_t P,
+                     float *loss, const kd_mview3 *grad, float gscale, double loss_scale, void *workspace, kd_stream_t stream)
+{
+    double *partial = (double *)workspace;
+    const int nb = blocks_for((long long)N * P);
+    hipStream_t st = (hipStream_t)stream;
+    auto nhwc = [&](long long sN, long long sC, long long sP) { return sC == 1 && sP == C && (sN == (long long)C * P || N == 1); };
+    // (the fast path stages 2 x 256 x C floats in dynamic LDS; it stays inside the 64-KiB default limit, larger class
+    // counts -- e.g. the 100-class CIFAR heads -- take the strided kernel)
+    const size_t lds = (size_t)2 * 256 * C * sizeof(float);
+    const bool fast = lds <= 65536 && nhwc(s->sN, s->sC, s->sP) && nhwc(t->sN, t->sC, t->sP) && (!grad || nhwc(grad->sN, grad->sC, grad->sP));
+    if (fast) {
+        const long long npix = (long long)N * P;
+        void *gp = grad ? grad->ptr : nullptr;
+        const int gdt = grad ? grad->dtype : s->dtype;
+#define KD_PAIR(K, TS, TT, TG) hipLaunchKernelGGL((pair_nhwc_kernel<K, TS, TT, TG>), dim3(nb), dim3(256), lds, st, (const TS *)s->ptr, \
+                                                  (const TT *)t->ptr, (TG *)gp, C, npix, invT, gscale, partial)
+#define KD_PAIR_DT(K)                                                                                       \
+        if (s->dtype == KD_F32 && t->dtype == KD_F32 && gdt == KD_F32) KD_PAIR(K, float, float, float);       \
+        else if (s->dtype == KD_F32 && t->dtype == KD_BF16 && gdt == KD_F32) KD_PAIR(K, float, bf16_t, float); \
+        else if (s->dtype == KD_BF16 && t->dtype == KD_BF16 && gdt == KD_BF16) KD_PAIR(K, bf16_t, bf16_t, bf16_t); \
+        else if (s->dtype == KD_BF16 && t->dtype == KD_F32 && gdt == KD_BF16) KD_PAIR(K, bf16_t, float, bf16_t); \
+        else if (s->dtype == KD_F32 && t->dtype == KD_F32) KD_PAIR(K, float, float, bf16_t);                  \
+        else if (s->dtype == KD_F32 && t->dtype == KD_BF16) KD_PAIR(K, float, bf16_t, bf16_t);                \
+        else if (s->dtype == KD_BF16 && t->dtype == KD_BF16) KD_PAIR(K, bf16_t, bf16_t, float);               \
+        else KD_PAIR(K, bf16_t, float, float)
+        if (kind == PAIR_KLD) { KD_PAIR_DT(PAIR_KLD); }
+        else if (kind == PAIR_JSD) { KD_PAIR_DT(PAIR_JSD); }
+        else { KD_PAIR_DT(PAIR_EKL); }
+#undef KD_PAIR_DT
+#undef KD_PAIR
+    } else {
+        auto fn = kind == PAIR_KLD ? pair_kernel<PAIR_KLD> : kind == PAIR_JSD ? pair_kernel<PAIR_JSD> : pair_kernel<PAIR_EKL>;
+        hipLaunchKernelGGL(fn, dim3(nb), dim3(256), 0, st, v3(s), v3(t), m3(grad), invT, gscale, N, C, (long long)P, partial);
+    }
+    KD_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, nb, loss_scale, (const double *)nullptr, loss);
+    KD_CHECK_LAUNCH(who);
+    return KD_OK;
+}
+
 extern "C" int kd_kldiv(const kd_view3 *s, const kd_view3 *t, float temperature, int32_t N, int32_t C, int64_t P, float *loss,
                         const kd_mview3 *grad, float grad_scale, void *workspace, size_t workspace_bytes, kd_stream_t stream)
 {
     KD_LOSS_COMMON("kd_kldiv");
     KD_REQUIRE(temperature > 0.f, KD_ERR_INVALID, "kd_kldiv: temperature must be positive");
-    double *partial = (double *)workspace;
-    const int nb = blocks_for((long long)N * P);
-    hipStream_t st = (hipStream_t)stream;
     const float gscale = grad_scale * temperature / ((float)N * (float)P);
-    auto nhwc = [&](long long sN, long long sC, long long sP) { return sC == 1 && sP == C && (sN == (long long)C * P || N == 1); };
-    // (the fast path stages 2 x 256 x C floats in dynamic LDS; it stays inside the 64-KiB default limit, larger class
-    // counts -- e.g. the 100-class CIFAR heads -- take the strided kernel)
-    const bool fast = (size_t)2 * 256 * C * sizeof(float) <= 65536 && nhwc(s->sN, s->sC, s->sP) && nhwc(t->sN, t->sC, t->sP) &&
-                      (!grad || nhwc(grad->sN, grad->sC, grad->sP));
-    if (fast) {
-        const long long npix = (long long)N * P;
-        const size_t lds = (size_t)2 * 256 * C * sizeof(float);
-        const float invT = 1.f / temperature;
-        void *gp = grad ? grad->ptr : nullptr;
-        const int gdt = grad ? grad->dtype : s->dtype;
-#define KD_KLD(TS, TT, TG) hipLaunchKernelGGL((kldiv_nhwc_kernel<TS, TT, TG>), dim3(nb), dim3(256), lds, st, (const TS *)s->ptr, \
-                                              (const TT *)t->ptr, (TG *)gp, C, npix, invT, gscale, partial)
-        if (s->dtype == KD_F32 && t->dtype == KD_F32 && gdt == KD_F32) KD_KLD(float, float, float);
-        else if (s->dtype == KD_F32 && t->dtype == KD_BF16 && gdt == KD_F32) KD_KLD(float, bf16_t, float);
-        else if (s->dtype == KD_BF16 && t->dtype == KD_BF16 && gdt == KD_BF16) KD_KLD(bf16_t, bf16_t, bf16_t);
-        else if (s->dtype == KD_BF16 && t->dtype == KD_F32 && gdt == KD_BF16) KD_KLD(bf16_t, float, bf16_t);
-        else if (s->dtype == KD_F32 && t->dtype == KD_F32) KD_KLD(float, float, bf16_t);
-        else if (s->dtype == KD_F32 && t->dtype == KD_BF16) KD_KLD(float, bf16_t, bf16_t);
-        else if (s->dtype == KD_BF16 && t->dtype == KD_BF16) KD_KLD(bf16_t, bf16_t, float);
-        else KD_KLD(bf16_t, float, float);
-#undef KD_KLD
-    } else {
-        hipLaunchKernelGGL(kldiv_kernel, dim3(nb), dim3(256), 0, st, v3(s), v3(t), m3(grad), 1.f / temperature, gscale, N, C,
-                           (long long)P, partial);
-    }
-    KD_CHECK_LAUNCH("kd_kldiv");
     // 'mean' over N*C*P elements, then * T^2 * C  ==  T^2 / (N*P) * sum
     const double scale = (double)temperature * temperature / ((double)N * (double)P);
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, nb, scale, (const double *)nullptr, loss);
-    KD_CHECK_LAUNCH("kd_kldiv(finish)");
-    return KD_OK;
+    return pair_impl("kd_kldiv", PAIR_KLD, s, t, 1.f / temperature, N, C, P, loss, grad, gscale, scale, workspace, stream);
 }
 
 extern "C" int kd_hint_mse(const kd_view3 *s, const kd_view3 *t, float num_classes, int32_t N, int32_t C, int64_t P,
@@ -1811,7 +1660,7 @@ extern "C" int kd_ce2d_weighted(const kd_view3 *x, const int64_t *target, const 
     return ce2d_impl("kd_ce2d_weighted", x, target, class_weight, sum_reduction, ignore_index, N, C, P, loss, workspace, workspace_bytes, stream);
 }
 
-// ---- kd_ce2d_up / kd_kldiv_up: the logged logit losses from the low-resolution logits (see ce2d_up_kernel) ---------------------------
+// ---- kd_ce2d_up / kd_kldiv_up / kd_jsdiv_up / kd_focal_up / kd_logit_metrics_up: from the low-resolution logits (see ce2d_up_kernel) ----
 static bool up_geom(UpGeom &g, int32_t N, int32_t h, int32_t w, int32_t C, int32_t H, int32_t W, int32_t align_corners)
 {
     g.N = N; g.h = h; g.w = w; g.C = C; g.H = H; g.W = W;
@@ -1826,26 +1675,43 @@ static bool up_geom(UpGeom &g, int32_t N, int32_t h, int32_t w, int32_t C, int32
     return (int)(255.f * g.sw) + 3 <= UP_NW;
 }
 
+// What the five entry points share after their own argument checks: the workspace and resampling-ratio checks, the geometry, the
+// chunking (cpr chunks of 256 output pixels per output row) and the block count.  An entry point describes itself in an UpEntry:
+// its name for the messages, how many partials its finishing kernel's layout holds, whether its ratio message names the scale.
+struct UpEntry { const char *who; int max_blocks; bool say_scale; };
+struct UpPlan { UpGeom g; int cpr, nb; long long nchunks; };
+static int up_plan(UpPlan &u, const UpEntry &e, int32_t N, int32_t h, int32_t w, int32_t C, int32_t H, int32_t W, int32_t align_corners,
+                   size_t workspace_bytes)
+{
+    KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, (int64_t)H * W), KD_ERR_WORKSPACE, "%s: workspace too small", e.who);
+    if (!up_geom(u.g, N, h, w, C, H, W, align_corners)) {
+        if (e.say_scale)
+            kd_set_error("%s: a 256-pixel chunk spans more than %d source columns (scale %dx%d -> %dx%d): materialise the logits", e.who, UP_NW, h, w, H, W);
+        else
+            kd_set_error("%s: a 256-pixel chunk spans more than %d source columns: materialise the logits", e.who, UP_NW);
+        return KD_ERR_UNSUPPORTED;
+    }
+    u.cpr = (W + 255) / 256;
+    u.nchunks = (long long)N * H * u.cpr;
+    u.nb = (int)(u.nchunks < e.max_blocks ? u.nchunks : e.max_blocks);
+    return KD_OK;
+}
+
 extern "C" int kd_ce2d_up(const float *x_lo, const int64_t *target, int32_t ignore_index, int32_t N, int32_t h, int32_t w, int32_t C,
                           int32_t H, int32_t W, int32_t align_corners, float *loss, void *workspace, size_t workspace_bytes,
                           kd_stream_t stream)
 {
     KD_REQUIRE(x_lo && target && loss && workspace, KD_ERR_INVALID, "kd_ce2d_up: null argument");
     KD_REQUIRE(N > 0 && h > 0 && w > 0 && C > 0 && C <= 48 && H > 0 && W > 0, KD_ERR_INVALID, "kd_ce2d_up: bad argument (C <= 48: the staged patch fits 64 KiB of LDS)");
-    KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, (int64_t)H * W), KD_ERR_WORKSPACE, "kd_ce2d_up: workspace too small");
-    UpGeom g;
-    KD_REQUIRE(up_geom(g, N, h, w, C, H, W, align_corners), KD_ERR_UNSUPPORTED,
-               "kd_ce2d_up: a 256-pixel chunk spans more than %d source columns (scale %dx%d -> %dx%d): materialise the logits", UP_NW, h, w, H, W);
+    UpPlan u;
+    if (const int rc = up_plan(u, UpEntry{"kd_ce2d_up", MAX_BLOCKS, true}, N, h, w, C, H, W, align_corners, workspace_bytes)) return rc;
     double *partial = (double *)workspace, *count = partial + MAX_BLOCKS;
-    const int cpr = (W + 255) / 256;
-    const long long nchunks = (long long)N * H * cpr;
-    const int nb = (int)(nchunks < MAX_BLOCKS ? nchunks : MAX_BLOCKS);
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)2 * UP_NW * C * sizeof(float);
-    if (C == 19) hipLaunchKernelGGL(ce2d_up_kernel<19>, dim3(nb), dim3(256), lds, st, x_lo, target, ignore_index, g, nchunks, cpr, partial, count);
-    else hipLaunchKernelGGL(ce2d_up_kernel<0>, dim3(nb), dim3(256), lds, st, x_lo, target, ignore_index, g, nchunks, cpr, partial, count);
+    hipLaunchKernelGGL(C == 19 ? ce2d_up_kernel<19> : ce2d_up_kernel<0>, dim3(u.nb), dim3(256), lds, st, x_lo, target, ignore_index, u.g, u.nchunks,
+                       u.cpr, partial, count);
     KD_CHECK_LAUNCH("kd_ce2d_up");
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, nb, 1.0, (const double *)count, loss);
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, u.nb, 1.0, (const double *)count, loss);
     KD_CHECK_LAUNCH("kd_ce2d_up(finish)");
     return KD_OK;
 }
@@ -1855,23 +1721,38 @@ extern "C" int kd_kldiv_up(const float *s_lo, const float *t_lo, float temperatu
 {
     KD_REQUIRE(s_lo && t_lo && loss && workspace, KD_ERR_INVALID, "kd_kldiv_up: null argument");
     KD_REQUIRE(N > 0 && h > 0 && w > 0 && C > 0 && C <= 24 && H > 0 && W > 0 && temperature > 0.f, KD_ERR_INVALID, "kd_kldiv_up: bad argument (C <= 24: two staged patches fit 64 KiB of LDS)");
-    KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, (int64_t)H * W), KD_ERR_WORKSPACE, "kd_kldiv_up: workspace too small");
-    UpGeom g;
-    KD_REQUIRE(up_geom(g, N, h, w, C, H, W, align_corners), KD_ERR_UNSUPPORTED,
-               "kd_kldiv_up: a 256-pixel chunk spans more than %d source columns: materialise the logits", UP_NW);
+    UpPlan u;
+    if (const int rc = up_plan(u, UpEntry{"kd_kldiv_up", MAX_BLOCKS, false}, N, h, w, C, H, W, align_corners, workspace_bytes)) return rc;
     double *partial = (double *)workspace;
-    const int cpr = (W + 255) / 256;
-    const long long nchunks = (long long)N * H * cpr;
-    const int nb = (int)(nchunks < MAX_BLOCKS ? nchunks : MAX_BLOCKS);
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)4 * UP_NW * C * sizeof(float);
-    if (C == 19) hipLaunchKernelGGL(kldiv_up_kernel<19>, dim3(nb), dim3(256), lds, st, s_lo, t_lo, g, 1.f / temperature, nchunks, cpr, partial);
-    else hipLaunchKernelGGL(kldiv_up_kernel<0>, dim3(nb), dim3(256), lds, st, s_lo, t_lo, g, 1.f / temperature, nchunks, cpr, partial);
+    hipLaunchKernelGGL((C == 19 ? pair_up_kernel<PAIR_KLD, 19> : pair_up_kernel<PAIR_KLD, 0>), dim3(u.nb), dim3(256), lds, st, s_lo, t_lo, u.g,
+                       1.f / temperature, u.nchunks, u.cpr, partial);
     KD_CHECK_LAUNCH("kd_kldiv_up");
     // 'mean' over N*C*P elements, then * T^2 * C  ==  T^2 / (N*P) * sum  (kd_kldiv)
     const double scale = (double)temperature * temperature / ((double)N * (double)H * (double)W);
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, nb, scale, (const double *)nullptr, loss);
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, u.nb, scale, (const double *)nullptr, loss);
     KD_CHECK_LAUNCH("kd_kldiv_up(finish)");
+    return KD_OK;
+}
+
+extern "C" int kd_jsdiv_up(const float *s_lo, const float *t_lo, float temperature, int32_t N, int32_t h, int32_t w, int32_t C, int32_t H,
+                           int32_t W, int32_t align_corners, float *loss, void *workspace, size_t workspace_bytes, kd_stream_t stream)
+{
+    KD_REQUIRE(s_lo && t_lo && loss && workspace, KD_ERR_INVALID, "kd_jsdiv_up: null argument");
+    KD_REQUIRE(N > 0 && h > 0 && w > 0 && C > 0 && C <= 24 && H > 0 && W > 0 && temperature > 0.f, KD_ERR_INVALID, "kd_jsdiv_up: bad argument (C <= 24: two staged patches fit 64 KiB of LDS)");
+    UpPlan u;
+    if (const int rc = up_plan(u, UpEntry{"kd_jsdiv_up", MAX_BLOCKS, false}, N, h, w, C, H, W, align_corners, workspace_bytes)) return rc;
+    double *partial = (double *)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t lds = (size_t)4 * UP_NW * C * sizeof(float);
+    hipLaunchKernelGGL((C == 19 ? pair_up_kernel<PAIR_JSD, 19> : pair_up_kernel<PAIR_JSD, 0>), dim3(u.nb), dim3(256), lds, st, s_lo, t_lo, u.g,
+                       1.f / temperature, u.nchunks, u.cpr, partial);
+    KD_CHECK_LAUNCH("kd_jsdiv_up");
+    // T^2 / (2N) * sum  (kd_jsdiv)
+    const double scale = (double)temperature * temperature / (2.0 * (double)N);
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, u.nb, scale, (const double *)nullptr, loss);
+    KD_CHECK_LAUNCH("kd_jsdiv_up(finish)");
     return KD_OK;
 }
 
@@ -1884,10 +1765,8 @@ extern "C" int kd_logit_metrics_up(const float *s_lo, const float *t_lo, const i
     KD_REQUIRE(conf_s != conf_t && (((uintptr_t)conf_s | (uintptr_t)conf_t | (uintptr_t)workspace) & 7) == 0, KD_ERR_INVALID,
                "kd_logit_metrics_up: conf_s / conf_t must be two 8-B aligned matrices, the workspace 8-B aligned");
     KD_REQUIRE(C <= 48, KD_ERR_UNSUPPORTED, "kd_logit_metrics_up: C <= 48 (got %d): materialise the logits", C);
-    KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, (int64_t)H * W), KD_ERR_WORKSPACE, "kd_logit_metrics_up: workspace too small");
-    UpGeom g;
-    KD_REQUIRE(up_geom(g, N, h, w, C, H, W, align_corners), KD_ERR_UNSUPPORTED,
-               "kd_logit_metrics_up: a 256-pixel chunk spans more than %d source columns (scale %dx%d -> %dx%d): materialise the logits", UP_NW, h, w, H, W);
+    UpPlan u;
+    if (const int rc = up_plan(u, UpEntry{"kd_logit_metrics_up", MET_MAX_BLOCKS, true}, N, h, w, C, H, W, align_corners, workspace_bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (!accumulate) {
         if (hipMemsetAsync(conf_s, 0, (size_t)C * C * sizeof(int64_t), st) != hipSuccess ||
@@ -1897,9 +1776,6 @@ extern "C" int kd_logit_metrics_up(const float *s_lo, const float *t_lo, const i
         }
     }
     double *partial = (double *)workspace;
-    const int cpr = (W + 255) / 256;
-    const long long nchunks = (long long)N * H * cpr;
-    const int nb = (int)(nchunks < MET_MAX_BLOCKS ? nchunks : MET_MAX_BLOCKS);
     // two staged patches + two C x C histograms: 50.3 KiB at 19 classes, 138 KiB at 48 (of the CU's 160 KiB)
     const size_t lds = (size_t)4 * UP_NW * C * sizeof(float) + (size_t)2 * C * C * sizeof(unsigned int);
     auto fn = C == 19 ? logit_metrics_up_kernel<19> : logit_metrics_up_kernel<0>;
@@ -1910,56 +1786,16 @@ extern "C" int kd_logit_metrics_up(const float *s_lo, const float *t_lo, const i
             return KD_ERR_UNSUPPORTED;
         }
     }
-    hipLaunchKernelGGL(fn, dim3(nb), dim3(256), lds, st, s_lo, t_lo, target, ignore_index, g, nchunks, cpr, partial,
+    hipLaunchKernelGGL(fn, dim3(u.nb), dim3(256), lds, st, s_lo, t_lo, target, ignore_index, u.g, u.nchunks, u.cpr, partial,
                        (unsigned long long *)conf_s, (unsigned long long *)conf_t);
     KD_CHECK_LAUNCH("kd_logit_metrics_up");
-    hipLaunchKernelGGL(logit_metrics_finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, nb,
+    hipLaunchKernelGGL(logit_metrics_finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, u.nb,
                        1.0 / ((double)N * (double)C * (double)H * (double)W), out);
     KD_CHECK_LAUNCH("kd_logit_metrics_up(finish)");
     return KD_OK;
 }
 
-// ---- kd_jsdiv / kd_ensemble_kldiv / kd_jsdiv_up -----------------------------------------------------------------------------------
-static int pair_impl(const char *who, int kind, const kd_view3 *s, const kd_view3 *t, float invT, int32_t N, int32_t C, int64_t P,
-                     float *loss, const kd_mview3 *grad, float gscale, double loss_scale, void *workspace, kd_stream_t stream)
-{
-    double *partial = (double *)workspace;
-    const int nb = blocks_for((long long)N * P);
-    hipStream_t st = (hipStream_t)stream;
-    auto nhwc = [&](long long sN, long long sC, long long sP) { return sC == 1 && sP == C && (sN == (long long)C * P || N == 1); };
-    const bool fast = (size_t)2 * 256 * C * sizeof(float) <= 65536 && nhwc(s->sN, s->sC, s->sP) && nhwc(t->sN, t->sC, t->sP) &&
-                      (!grad || nhwc(grad->sN, grad->sC, grad->sP));
-    if (fast) {
-        const long long npix = (long long)N * P;
-        const size_t lds = (size_t)2 * 256 * C * sizeof(float);
-        void *gp = grad ? grad->ptr : nullptr;
-        const int gdt = grad ? grad->dtype : s->dtype;
-#define KD_PAIR(K, TS, TT, TG) hipLaunchKernelGGL((pair_nhwc_kernel<K, TS, TT, TG>), dim3(nb), dim3(256), lds, st, (const TS *)s->ptr, \
-                                                  (const TT *)t->ptr, (TG *)gp, C, npix, invT, gscale, partial)
-#define KD_PAIR_DT(K)                                                                                       \
-        if (s->dtype == KD_F32 && t->dtype == KD_F32 && gdt == KD_F32) KD_PAIR(K, float, float, float);       \
-        else if (s->dtype == KD_F32 && t->dtype == KD_BF16 && gdt == KD_F32) KD_PAIR(K, float, bf16_t, float); \
-        else if (s->dtype == KD_BF16 && t->dtype == KD_BF16 && gdt == KD_BF16) KD_PAIR(K, bf16_t, bf16_t, bf16_t); \
-        else if (s->dtype == KD_BF16 && t->dtype == KD_F32 && gdt == KD_BF16) KD_PAIR(K, bf16_t, float, bf16_t); \
-        else if (s->dtype == KD_F32 && t->dtype == KD_F32) KD_PAIR(K, float, float, bf16_t);                  \
-        else if (s->dtype == KD_F32 && t->dtype == KD_BF16) KD_PAIR(K, float, bf16_t, bf16_t);                \
-        else if (s->dtype == KD_BF16 && t->dtype == KD_BF16) KD_PAIR(K, bf16_t, bf16_t, float);               \
-        else KD_PAIR(K, bf16_t, float, float)
-        if (kind == PAIR_JSD) { KD_PAIR_DT(PAIR_JSD); }
-        else { KD_PAIR_DT(PAIR_EKL); }
-#undef KD_PAIR_DT
-#undef KD_PAIR
-    } else if (kind == PAIR_JSD) {
-        hipLaunchKernelGGL(pair_kernel<PAIR_JSD>, dim3(nb), dim3(256), 0, st, v3(s), v3(t), m3(grad), invT, gscale, N, C, (long long)P, partial);
-    } else {
-        hipLaunchKernelGGL(pair_kernel<PAIR_EKL>, dim3(nb), dim3(256), 0, st, v3(s), v3(t), m3(grad), invT, gscale, N, C, (long long)P, partial);
-    }
-    KD_CHECK_LAUNCH(who);
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, nb, loss_scale, (const double *)nullptr, loss);
-    KD_CHECK_LAUNCH(who);
-    return KD_OK;
-}
-
+// ---- kd_jsdiv / kd_ensemble_kldiv -------------------------------------------------------------------------------------------
 extern "C" int kd_jsdiv(const kd_view3 *s, const kd_view3 *t, float temperature, int32_t N, int32_t C, int64_t P, float *loss,
                         const kd_mview3 *grad, float grad_scale, void *workspace, size_t workspace_bytes, kd_stream_t stream)
 {
@@ -2120,30 +1956,6 @@ extern "C" int kd_softmax_mean(const kd_multi_targets *logits, float temperature
     return KD_OK;
 }
 
-extern "C" int kd_jsdiv_up(const float *s_lo, const float *t_lo, float temperature, int32_t N, int32_t h, int32_t w, int32_t C, int32_t H,
-                           int32_t W, int32_t align_corners, float *loss, void *workspace, size_t workspace_bytes, kd_stream_t stream)
-{
-    KD_REQUIRE(s_lo && t_lo && loss && workspace, KD_ERR_INVALID, "kd_jsdiv_up: null argument");
-    KD_REQUIRE(N > 0 && h > 0 && w > 0 && C > 0 && C <= 24 && H > 0 && W > 0 && temperature > 0.f, KD_ERR_INVALID, "kd_jsdiv_up: bad argument (C <= 24: two staged patches fit 64 KiB of LDS)");
-    KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, (int64_t)H * W), KD_ERR_WORKSPACE, "kd_jsdiv_up: workspace too small");
-    UpGeom g;
-    KD_REQUIRE(up_geom(g, N, h, w, C, H, W, align_corners), KD_ERR_UNSUPPORTED,
-               "kd_jsdiv_up: a 256-pixel chunk spans more than %d source columns: materialise the logits", UP_NW);
-    double *partial = (double *)workspace;
-    const int cpr = (W + 255) / 256;
-    const long long nchunks = (long long)N * H * cpr;
-    const int nb = (int)(nchunks < MAX_BLOCKS ? nchunks : MAX_BLOCKS);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t lds = (size_t)4 * UP_NW * C * sizeof(float);
-    if (C == 19) hipLaunchKernelGGL(jsdiv_up_kernel<19>, dim3(nb), dim3(256), lds, st, s_lo, t_lo, g, 1.f / temperature, nchunks, cpr, partial);
-    else hipLaunchKernelGGL(jsdiv_up_kernel<0>, dim3(nb), dim3(256), lds, st, s_lo, t_lo, g, 1.f / temperature, nchunks, cpr, partial);
-    KD_CHECK_LAUNCH("kd_jsdiv_up");
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, nb, (double)temperature * temperature / (2.0 * (double)N),
-                       (const double *)nullptr, loss);
-    KD_CHECK_LAUNCH("kd_jsdiv_up(finish)");
-    return KD_OK;
-}
-
 // ---- kd_focal / kd_focal_grad / kd_focal_up -----------------------------------------------------------------------------------------
 extern "C" int kd_focal(const kd_view3 *x, const int64_t *target, const float *alpha, float gamma, int32_t ignore_index, int32_t reduction,
                         int32_t N, int32_t C, int64_t P, float *loss, double *stats, float *a_map, float *ce_map, void *workspace,
@@ -2192,23 +2004,18 @@ extern "C" int kd_focal_up(const float *x_lo, const int64_t *target, const float
     KD_REQUIRE(N > 0 && h > 0 && w > 0 && C > 0 && C <= 48 && H > 0 && W > 0 && gamma >= 0.f, KD_ERR_INVALID,
                "kd_focal_up: bad argument (C <= 48: the staged patch fits 64 KiB of LDS)");
     KD_REQUIRE(reduction == 1 || reduction == 2, KD_ERR_INVALID, "kd_focal_up: reduction is 1 (mean) or 2 (sum)");
+    // (the size before the alignment, as this entry point always reported them; up_plan repeats the size check)
     KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, (int64_t)H * W), KD_ERR_WORKSPACE, "kd_focal_up: workspace too small");
     KD_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)stats & 7) == 0, KD_ERR_INVALID, "kd_focal_up: workspace / stats must be 8-B aligned");
-    UpGeom g;
-    KD_REQUIRE(up_geom(g, N, h, w, C, H, W, align_corners), KD_ERR_UNSUPPORTED,
-               "kd_focal_up: a 256-pixel chunk spans more than %d source columns: materialise the logits", UP_NW);
+    UpPlan u;
+    if (const int rc = up_plan(u, UpEntry{"kd_focal_up", FOCAL_MAX_BLOCKS, false}, N, h, w, C, H, W, align_corners, workspace_bytes)) return rc;
     double *partial = (double *)workspace;
-    const int cpr = (W + 255) / 256;
-    const long long nchunks = (long long)N * H * cpr;
-    const int nb = (int)(nchunks < FOCAL_MAX_BLOCKS ? nchunks : FOCAL_MAX_BLOCKS);
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)2 * UP_NW * C * sizeof(float);
-    if (C == 19)
-        hipLaunchKernelGGL(focal_up_kernel<19>, dim3(nb), dim3(256), lds, st, x_lo, target, alpha, gamma, ignore_index, g, nchunks, cpr, partial);
-    else
-        hipLaunchKernelGGL(focal_up_kernel<0>, dim3(nb), dim3(256), lds, st, x_lo, target, alpha, gamma, ignore_index, g, nchunks, cpr, partial);
+    hipLaunchKernelGGL(C == 19 ? focal_up_kernel<19> : focal_up_kernel<0>, dim3(u.nb), dim3(256), lds, st, x_lo, target, alpha, gamma, ignore_index,
+                       u.g, u.nchunks, u.cpr, partial);
     KD_CHECK_LAUNCH("kd_focal_up");
-    hipLaunchKernelGGL(focal_finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, nb, (int)reduction, (double)N * H * W, stats, loss);
+    hipLaunchKernelGGL(focal_finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, u.nb, (int)reduction, (double)N * H * W, stats, loss);
     KD_CHECK_LAUNCH("kd_focal_up(finish)");
     return KD_OK;
 }

@@ -1369,50 +1369,63 @@ def _loss_common(s, t):
     return vs, vt, dims
 
 
-def kldiv(s, t, temperature=1.0, want_grad=True, grad_scale=1.0):
+# The profiler's `kernel` field of every loss entry point: the kernel family that runs (csrc/losses.hip picks the member by layout,
+# dtype and class count).
+_LOSS_KERNELS = {
+    "kd_kldiv": "pair_kernel<kld> / pair_nhwc_kernel<kld>",
+    "kd_jsdiv": "pair_kernel<jsd> / pair_nhwc_kernel<jsd>",
+    "kd_ensemble_kldiv": "pair_kernel<ekl> / pair_nhwc_kernel<ekl>",
+    "kd_hint_mse": "mse_vec_kernel / mse_strided_kernel",
+    "kd_weighted_hint_mse": "whmse_kernel",
+    "kd_topk_hint_mse": "topk_sums_kernel + topk_select_kernel + topk_grad_kernel",
+    "kd_ce2d": "ce2d_kernel / ce2d_nhwc_kernel",
+    "kd_ce2d_up": "ce2d_up_kernel",
+    "kd_kldiv_up": "pair_up_kernel<kld>",
+    "kd_jsdiv_up": "pair_up_kernel<jsd>",
+    "kd_focal_up": "focal_up_kernel",
+    "kd_logit_metrics_up": "logit_metrics_up_kernel",
+    "kd_kldiv_multi": "kd_kldiv_multi",
+    "kd_softmax_mean": "kd_softmax_mean",
+    "kd_focal": "focal_kernel",
+    "kd_focal_grad": "focal_grad_kernel",
+}
+
+
+def _pair_loss(fn, label, s, t, extra, want_grad, grad_scale):
+    """The two-operand criteria share one call shape: fn(s, t, *extra, N, C, P, loss, grad or NULL, grad_scale, workspace, bytes,
+    stream) -> (loss, grad or None).  extra: the criterion's own operands, or a function of (N, C, P) that checks and returns them
+    (after the checks of s and t)."""
     vs, vt, (N, Cc, P) = _loss_common(s, t)
+    if callable(extra):
+        extra = extra(N, Cc, P)
     loss = torch.empty((), dtype=torch.float32, device=s.device)
     grad = torch.empty_like(s) if want_grad else None
     vg = view3(grad)[0] if want_grad else None
     ws, need = loss_workspace(N, Cc, P, s.device)
     e0 = _prof_start()
-    check(_lib.lib().kd_kldiv(C.byref(vs), C.byref(vt), C.c_float(temperature), N, Cc, P, _ptr(loss),
-                              C.byref(vg) if vg is not None else None, C.c_float(grad_scale), _ptr(ws), need, stream_ptr()),
-          "kd_kldiv")
-    _prof_stop(e0, "loss", _nbytes(s, t, grad), f"kldiv {N}x{Cc}x{P}", "kldiv_kernel")
+    own = [_ptr(e) if torch.is_tensor(e) else e for e in extra]      # (`extra` keeps a tensor operand alive over the call)
+    check(getattr(_lib.lib(), fn)(C.byref(vs), C.byref(vt), *own, N, Cc, P, _ptr(loss), C.byref(vg) if vg is not None else None,
+                                  C.c_float(grad_scale), _ptr(ws), need, stream_ptr()), fn)
+    _prof_stop(e0, "loss", _nbytes(s, t, grad), f"{label} {N}x{Cc}x{P}", _LOSS_KERNELS[fn])
     return loss, grad
+
+
+def kldiv(s, t, temperature=1.0, want_grad=True, grad_scale=1.0):
+    return _pair_loss("kd_kldiv", "kldiv", s, t, (C.c_float(temperature),), want_grad, grad_scale)
 
 
 def hint_mse(s, t, num_classes=19, want_grad=True, grad_scale=1.0):
-    vs, vt, (N, Cc, P) = _loss_common(s, t)
-    loss = torch.empty((), dtype=torch.float32, device=s.device)
-    grad = torch.empty_like(s) if want_grad else None
-    vg = view3(grad)[0] if want_grad else None
-    ws, need = loss_workspace(N, Cc, P, s.device)
-    e0 = _prof_start()
-    check(_lib.lib().kd_hint_mse(C.byref(vs), C.byref(vt), C.c_float(num_classes), N, Cc, P, _ptr(loss),
-                                 C.byref(vg) if vg is not None else None, C.c_float(grad_scale), _ptr(ws), need, stream_ptr()),
-          "kd_hint_mse")
-    _prof_stop(e0, "loss", _nbytes(s, t, grad), f"hint mse {N}x{Cc}x{P}", "mse_vec_kernel")
-    return loss, grad
+    return _pair_loss("kd_hint_mse", "hint mse", s, t, (C.c_float(num_classes),), want_grad, grad_scale)
 
 
 def weighted_hint_mse(s, t, w, want_grad=True, grad_scale=1.0):
-    vs, vt, (N, Cc, P) = _loss_common(s, t)
-    _need_cuda(w)
-    w = w.detach().float().contiguous()
-    if tuple(w.shape) not in ((Cc,), (N, Cc)):
-        raise ValueError(f"weighted_hint_mse: filter_weight must be (C,) or (N,C), got {tuple(w.shape)}")
-    loss = torch.empty((), dtype=torch.float32, device=s.device)
-    grad = torch.empty_like(s) if want_grad else None
-    vg = view3(grad)[0] if want_grad else None
-    ws, need = loss_workspace(N, Cc, P, s.device)
-    e0 = _prof_start()
-    check(_lib.lib().kd_weighted_hint_mse(C.byref(vs), C.byref(vt), _ptr(w), int(w.dim() == 2), N, Cc, P, _ptr(loss),
-                                          C.byref(vg) if vg is not None else None, C.c_float(grad_scale), _ptr(ws), need,
-                                          stream_ptr()), "kd_weighted_hint_mse")
-    _prof_stop(e0, "loss", _nbytes(s, t, grad), f"weighted hint mse {N}x{Cc}x{P}", "whmse_kernel")
-    return loss, grad
+    def weights(N, Cc, P):
+        _need_cuda(w)
+        wf = w.detach().float().contiguous()
+        if tuple(wf.shape) not in ((Cc,), (N, Cc)):
+            raise ValueError(f"weighted_hint_mse: filter_weight must be (C,) or (N,C), got {tuple(wf.shape)}")
+        return wf, int(wf.dim() == 2)
+    return _pair_loss("kd_weighted_hint_mse", "weighted hint mse", s, t, weights, want_grad, grad_scale)
 
 
 def _class_weight(weight, Cc, device):
@@ -1437,7 +1450,7 @@ def ce2d(x, target, ignore_index=255, weight=None, size_average=True):
                                           _ptr(loss), _ptr(ws), need, stream_ptr()), "kd_ce2d_weighted")
     else:
         check(_lib.lib().kd_ce2d(C.byref(vx), _ptr(tgt), ignore_index, N, Cc, P, _ptr(loss), _ptr(ws), need, stream_ptr()), "kd_ce2d")
-    _prof_stop(e0, "loss", _nbytes(x, tgt), f"ce2d {N}x{Cc}x{P}", "ce2d_kernel")
+    _prof_stop(e0, "loss", _nbytes(x, tgt), f"ce2d {N}x{Cc}x{P}", _LOSS_KERNELS["kd_ce2d"])
     return loss
 
 
@@ -1447,38 +1460,53 @@ def _lowres_ok(*lows):
             raise ValueError("low-resolution logits must be dense fp32 (N,h,w,C)")
 
 
+def _up_prologue(who, lows, size, target=None):
+    """What the *_up wrappers check and allocate alike -> ((N, h, w, C, H, W), target or None, workspace, bytes)."""
+    _need_cuda(*lows, target)
+    _lowres_ok(*lows)
+    if any(t.shape != lows[0].shape for t in lows[1:]):
+        raise ValueError(f"{who}: shape mismatch")
+    N, h, w, Cc = lows[0].shape
+    H, W = size
+    tgt = None
+    if target is not None:
+        tgt = target.contiguous()
+        if tgt.dtype != torch.int64 or tgt.numel() != N * H * W:
+            raise ValueError(f"{who}: target must be int64 (N,H,W)")
+    ws, need = loss_workspace(N, Cc, H * W, lows[0].device)
+    return (N, h, w, Cc, H, W), tgt, ws, need
+
+
 def ce2d_up(x_lo, target, size, ignore_index=255, align_corners=True):
     """ce2d(upsample_bilinear(x_lo, size), target) without the full-resolution tensor (kd_ce2d_up)."""
-    _need_cuda(x_lo, target)
-    _lowres_ok(x_lo)
-    N, h, w, Cc = x_lo.shape
-    H, W = size
-    tgt = target.contiguous()
-    if tgt.dtype != torch.int64 or tgt.numel() != N * H * W:
-        raise ValueError("ce2d_up: target must be int64 (N,H,W)")
+    (N, h, w, Cc, H, W), tgt, ws, need = _up_prologue("ce2d_up", (x_lo,), size, target)
     loss = torch.empty((), dtype=torch.float32, device=x_lo.device)
-    ws, need = loss_workspace(N, Cc, H * W, x_lo.device)
     e0 = _prof_start()
     check(_lib.lib().kd_ce2d_up(_ptr(x_lo), _ptr(tgt), ignore_index, N, h, w, Cc, H, W, int(bool(align_corners)), _ptr(loss), _ptr(ws),
                                 need, stream_ptr()), "kd_ce2d_up")
-    _prof_stop(e0, "loss", _nbytes(x_lo, tgt), f"ce2d from {h}x{w} logits at {H}x{W}", "ce2d_up_kernel")
+    _prof_stop(e0, "loss", _nbytes(x_lo, tgt), f"ce2d from {h}x{w} logits at {H}x{W}", _LOSS_KERNELS["kd_ce2d_up"])
     return loss
 
 
 def kldiv_up(s_lo, t_lo, size, temperature=1.0, align_corners=True):
     """kldiv(upsample_bilinear(s_lo, size), upsample_bilinear(t_lo, size)) forward, without the full-resolution tensors."""
-    _need_cuda(s_lo, t_lo)
-    _lowres_ok(s_lo, t_lo)
-    if s_lo.shape != t_lo.shape:
-        raise ValueError("kldiv_up: shape mismatch")
-    N, h, w, Cc = s_lo.shape
-    H, W = size
+    (N, h, w, Cc, H, W), _, ws, need = _up_prologue("kldiv_up", (s_lo, t_lo), size)
     loss = torch.empty((), dtype=torch.float32, device=s_lo.device)
-    ws, need = loss_workspace(N, Cc, H * W, s_lo.device)
     e0 = _prof_start()
     check(_lib.lib().kd_kldiv_up(_ptr(s_lo), _ptr(t_lo), C.c_float(temperature), N, h, w, Cc, H, W, int(bool(align_corners)), _ptr(loss),
                                  _ptr(ws), need, stream_ptr()), "kd_kldiv_up")
-    _prof_stop(e0, "loss", _nbytes(s_lo, t_lo), f"kldiv from {h}x{w} logits at {H}x{W}", "kldiv_up_kernel")
+    _prof_stop(e0, "loss", _nbytes(s_lo, t_lo), f"kldiv from {h}x{w} logits at {H}x{W}", _LOSS_KERNELS["kd_kldiv_up"])
+    return loss
+
+
+def jsdiv_up(s_lo, t_lo, size, temperature=1.0, align_corners=True):
+    """jsdiv(upsample_bilinear(s_lo, size), upsample_bilinear(t_lo, size)) forward, without the full-resolution tensors."""
+    (N, h, w, Cc, H, W), _, ws, need = _up_prologue("jsdiv_up", (s_lo, t_lo), size)
+    loss = torch.empty((), dtype=torch.float32, device=s_lo.device)
+    e0 = _prof_start()
+    check(_lib.lib().kd_jsdiv_up(_ptr(s_lo), _ptr(t_lo), C.c_float(temperature), N, h, w, Cc, H, W, int(bool(align_corners)), _ptr(loss),
+                                 _ptr(ws), need, stream_ptr()), "kd_jsdiv_up")
+    _prof_stop(e0, "loss", _nbytes(s_lo, t_lo), f"jsdiv from {h}x{w} logits at {H}x{W}", _LOSS_KERNELS["kd_jsdiv_up"])
     return loss
 
 
@@ -1491,15 +1519,7 @@ def logit_metrics_up(s_lo, t_lo, target, size, ignore_index=255, align_corners=T
     Returns (out, conf_s, conf_t): out fp32 (3,) = [ce2d(up(s), target), ce2d(up(t), target), mean (up(s) - up(t))^2]; conf_*
     int64 (C,C) [label][prediction] as confusion() of each up-sampled tensor (added to the given matrices when accumulate).
     Raises MetricsUnsupported (nothing launched) outside the kernel's limits."""
-    _need_cuda(s_lo, t_lo, target)
-    _lowres_ok(s_lo, t_lo)
-    if s_lo.shape != t_lo.shape:
-        raise ValueError("logit_metrics_up: shape mismatch")
-    N, h, w, Cc = s_lo.shape
-    H, W = size
-    tgt = target.contiguous()
-    if tgt.dtype != torch.int64 or tgt.numel() != N * H * W:
-        raise ValueError("logit_metrics_up: target must be int64 (N,H,W)")
+    (N, h, w, Cc, H, W), tgt, ws, need = _up_prologue("logit_metrics_up", (s_lo, t_lo), size, target)
     if conf_s is None or conf_t is None:
         if accumulate:
             raise ValueError("logit_metrics_up: accumulate needs both confusion matrices")
@@ -1510,7 +1530,6 @@ def logit_metrics_up(s_lo, t_lo, target, size, ignore_index=255, align_corners=T
         if cf.dtype != torch.int64 or tuple(cf.shape) != (Cc, Cc) or not cf.is_contiguous():
             raise ValueError("logit_metrics_up: conf must be a contiguous int64 (C, C) tensor")
     out = torch.empty(3, dtype=torch.float32, device=s_lo.device)
-    ws, need = loss_workspace(N, Cc, H * W, s_lo.device)
     e0 = _prof_start()
     rc = _lib.lib().kd_logit_metrics_up(_ptr(s_lo), _ptr(t_lo), _ptr(tgt), ignore_index, N, h, w, Cc, H, W, int(bool(align_corners)), _ptr(out),
                                         _ptr(conf_s), _ptr(conf_t), int(bool(accumulate)), _ptr(ws), need, stream_ptr())
@@ -1518,7 +1537,7 @@ def logit_metrics_up(s_lo, t_lo, target, size, ignore_index=255, align_corners=T
         msg = _lib.lib().kd_last_error()
         raise MetricsUnsupported(f"kd_logit_metrics_up: {msg.decode() if msg else ''}")
     check(rc, "kd_logit_metrics_up")
-    _prof_stop(e0, "loss", _nbytes(s_lo, t_lo, tgt), f"logit metrics from {h}x{w} logits at {H}x{W}", "logit_metrics_up_kernel")
+    _prof_stop(e0, "loss", _nbytes(s_lo, t_lo, tgt), f"logit metrics from {h}x{w} logits at {H}x{W}", _LOSS_KERNELS["kd_logit_metrics_up"])
     return out, conf_s, conf_t
 
 
@@ -1559,47 +1578,12 @@ def confusion(x, target, conf=None, accumulate=False):
 
 def jsdiv(s, t, temperature=1.0, want_grad=True, grad_scale=1.0):
     """JSDivergenceLoss (losses/JSDiv.py:19-26) and its gradient w.r.t. s (t constant), one pass (kd_jsdiv)."""
-    vs, vt, (N, Cc, P) = _loss_common(s, t)
-    loss = torch.empty((), dtype=torch.float32, device=s.device)
-    grad = torch.empty_like(s) if want_grad else None
-    vg = view3(grad)[0] if want_grad else None
-    ws, need = loss_workspace(N, Cc, P, s.device)
-    e0 = _prof_start()
-    check(_lib.lib().kd_jsdiv(C.byref(vs), C.byref(vt), C.c_float(temperature), N, Cc, P, _ptr(loss),
-                              C.byref(vg) if vg is not None else None, C.c_float(grad_scale), _ptr(ws), need, stream_ptr()), "kd_jsdiv")
-    _prof_stop(e0, "loss", _nbytes(s, t, grad), f"jsdiv {N}x{Cc}x{P}", "pair_kernel<jsd>")
-    return loss, grad
-
-
-def jsdiv_up(s_lo, t_lo, size, temperature=1.0, align_corners=True):
-    """jsdiv(upsample_bilinear(s_lo, size), upsample_bilinear(t_lo, size)) forward, without the full-resolution tensors."""
-    _need_cuda(s_lo, t_lo)
-    _lowres_ok(s_lo, t_lo)
-    if s_lo.shape != t_lo.shape:
-        raise ValueError("jsdiv_up: shape mismatch")
-    N, h, w, Cc = s_lo.shape
-    H, W = size
-    loss = torch.empty((), dtype=torch.float32, device=s_lo.device)
-    ws, need = loss_workspace(N, Cc, H * W, s_lo.device)
-    e0 = _prof_start()
-    check(_lib.lib().kd_jsdiv_up(_ptr(s_lo), _ptr(t_lo), C.c_float(temperature), N, h, w, Cc, H, W, int(bool(align_corners)), _ptr(loss),
-                                 _ptr(ws), need, stream_ptr()), "kd_jsdiv_up")
-    _prof_stop(e0, "loss", _nbytes(s_lo, t_lo), f"jsdiv from {h}x{w} logits at {H}x{W}", "jsdiv_up_kernel")
-    return loss
+    return _pair_loss("kd_jsdiv", "jsdiv", s, t, (C.c_float(temperature),), want_grad, grad_scale)
 
 
 def ensemble_kldiv(s, t, want_grad=True, grad_scale=1.0):
     """EnsembleKLDivergenceLoss (losses/EnsembleKLDiv.py:17-21): t are probabilities (kd_ensemble_kldiv)."""
-    vs, vt, (N, Cc, P) = _loss_common(s, t)
-    loss = torch.empty((), dtype=torch.float32, device=s.device)
-    grad = torch.empty_like(s) if want_grad else None
-    vg = view3(grad)[0] if want_grad else None
-    ws, need = loss_workspace(N, Cc, P, s.device)
-    e0 = _prof_start()
-    check(_lib.lib().kd_ensemble_kldiv(C.byref(vs), C.byref(vt), N, Cc, P, _ptr(loss), C.byref(vg) if vg is not None else None,
-                                       C.c_float(grad_scale), _ptr(ws), need, stream_ptr()), "kd_ensemble_kldiv")
-    _prof_stop(e0, "loss", _nbytes(s, t, grad), f"ensemble kldiv {N}x{Cc}x{P}", "pair_kernel<ekl>")
-    return loss, grad
+    return _pair_loss("kd_ensemble_kldiv", "ensemble kldiv", s, t, (), want_grad, grad_scale)
 
 
 def _multi_views(ts, weights, dims, what):
@@ -1641,7 +1625,7 @@ def kldiv_multi(s, targets, weights, temperature=1.0, labels=None, ignore_index=
     check(_lib.lib().kd_kldiv_multi(C.byref(vs), C.byref(mt), C.c_float(temperature), _ptr(tgt), int(ignore_index), C.c_float(kd_scale),
                                     C.c_float(sup_scale), N, Cc, P, _ptr(losses), C.byref(vg) if vg is not None else None, _ptr(ws), need,
                                     stream_ptr()), "kd_kldiv_multi")
-    _prof_stop(e0, "loss", _nbytes(s, grad, tgt, *targets), f"kldiv multi x{len(targets)} {N}x{Cc}x{P}", "kd_kldiv_multi")
+    _prof_stop(e0, "loss", _nbytes(s, grad, tgt, *targets), f"kldiv multi x{len(targets)} {N}x{Cc}x{P}", _LOSS_KERNELS["kd_kldiv_multi"])
     return losses[0], losses[1], losses[2], grad
 
 
@@ -1661,7 +1645,7 @@ def softmax_mean(logits, weights, temperature=1.0):
     vo, _ = view3(out)
     e0 = _prof_start()
     check(_lib.lib().kd_softmax_mean(C.byref(mt), C.c_float(temperature), N, Cc, P, C.byref(vo), stream_ptr()), "kd_softmax_mean")
-    _prof_stop(e0, "loss", _nbytes(out, *logits), f"softmax mean x{len(logits)} {N}x{Cc}x{P}", "kd_softmax_mean")
+    _prof_stop(e0, "loss", _nbytes(out, *logits), f"softmax mean x{len(logits)} {N}x{Cc}x{P}", _LOSS_KERNELS["kd_softmax_mean"])
     return out
 
 
@@ -1700,7 +1684,7 @@ def focal(x, target, gamma, alpha=None, ignore_index=-100, reduction="mean", wan
     e0 = _prof_start()
     check(_lib.lib().kd_focal(C.byref(vx), _ptr(tgt), _ptr(w), C.c_float(gamma), int(ignore_index), red, N, Cc, P, _ptr(loss), _ptr(stats),
                               _ptr(amap), _ptr(cemap), _ptr(ws), need, stream_ptr()), "kd_focal")
-    _prof_stop(e0, "loss", _nbytes(x, tgt, amap, cemap), f"focal {N}x{Cc}x{P}", "focal_kernel")
+    _prof_stop(e0, "loss", _nbytes(x, tgt, amap, cemap), f"focal {N}x{Cc}x{P}", _LOSS_KERNELS["kd_focal"])
     return loss, stats, amap, cemap
 
 
@@ -1722,7 +1706,7 @@ def focal_grad(x, target, gamma, alpha, ignore_index, reduction, upstream, stats
     e0 = _prof_start()
     check(_lib.lib().kd_focal_grad(C.byref(vx), _ptr(tgt), _ptr(w), C.c_float(gamma), int(ignore_index), red, N, Cc, P, _ptr(stats), _ptr(up),
                                    _ptr(a_map), _ptr(ce_map), C.byref(vg), stream_ptr()), "kd_focal_grad")
-    _prof_stop(e0, "loss", _nbytes(x, tgt, grad), f"focal grad {N}x{Cc}x{P}", "focal_grad_kernel")
+    _prof_stop(e0, "loss", _nbytes(x, tgt, grad), f"focal grad {N}x{Cc}x{P}", _LOSS_KERNELS["kd_focal_grad"])
     return grad
 
 
@@ -1731,18 +1715,16 @@ def focal_up(x_lo, target, size, gamma, alpha=None, ignore_index=-100, reduction
     -> (loss, stats)."""
     _need_cuda(x_lo, target)
     _lowres_ok(x_lo)
-    red = _focal_red(reduction, ("mean", "sum"))
-    N, h, w, Cc = x_lo.shape
-    H, W = size
+    red = _focal_red(reduction, ("mean", "sum"))      # (checked between the operands and the labels, whose message is focal's own)
+    (N, h, w, Cc, H, W), _, ws, need = _up_prologue("focal_up", (x_lo,), size)
     tgt = _focal_target((N, H * W), target)
     wt = _class_weight(alpha, Cc, x_lo.device) if alpha is not None else None
     loss = torch.empty((), dtype=torch.float32, device=x_lo.device)
     stats = torch.empty(3, dtype=torch.float64, device=x_lo.device)
-    ws, need = loss_workspace(N, Cc, H * W, x_lo.device)
     e0 = _prof_start()
     check(_lib.lib().kd_focal_up(_ptr(x_lo), _ptr(tgt), _ptr(wt), C.c_float(gamma), int(ignore_index), red, N, h, w, Cc, H, W,
                                  int(bool(align_corners)), _ptr(loss), _ptr(stats), _ptr(ws), need, stream_ptr()), "kd_focal_up")
-    _prof_stop(e0, "loss", _nbytes(x_lo, tgt), f"focal from {h}x{w} logits at {H}x{W}", "focal_up_kernel")
+    _prof_stop(e0, "loss", _nbytes(x_lo, tgt), f"focal from {h}x{w} logits at {H}x{W}", _LOSS_KERNELS["kd_focal_up"])
     return loss, stats
 
 
@@ -1770,7 +1752,7 @@ def topk_hint_mse(s, t, k, want_grad=True, grad_scale=1.0, want_mask=False):
     e0 = _prof_start()
     check(_lib.lib().kd_topk_hint_mse(C.byref(vs), C.byref(vt), k, N, Cc, P, _ptr(loss), C.byref(vg) if vg is not None else None,
                                       C.c_float(grad_scale), _ptr(mask), _ptr(ws), need, stream_ptr()), "kd_topk_hint_mse")
-    _prof_stop(e0, "loss", _nbytes(s, t, grad), f"top-{k} hint mse {N}x{Cc}x{P}", "topk_sums_kernel")
+    _prof_stop(e0, "loss", _nbytes(s, t, grad), f"top-{k} hint mse {N}x{Cc}x{P}", _LOSS_KERNELS["kd_topk_hint_mse"])
     return loss, grad, mask
 
 

@@ -1,4 +1,4 @@
-"""The logged logit losses from the half-resolution logits (kd_ce2d_up / kd_kldiv_up) and the lazily materialised
+"""The logit losses from the half-resolution logits (kd_ce2d_up / kd_kldiv_up / kd_jsdiv_up / kd_focal_up) and the lazily materialised
 full-resolution tensor behind `model(data) -> (output_st, output_tc)` (lazy.LazyLogits).  Reference semantics:
 models/deeplabv3/deeplabv3.py:160-162 (bilinear up-sampling, align_corners=True; the Gated-SCNN uses the default False,
 models/gscnn/gscnn.py:323) followed by losses/CrossEntropy.py:10-14 and losses/KLDiv.py:19-23."""
@@ -44,6 +44,63 @@ def test_losses_from_low_resolution_logits_match_the_upsampled_reference(h, w, H
     # ... and the materialised path of this library gives the same numbers
     full = ops.upsample_bilinear_ac(cu(s_lo), (H, W), out_dtype=torch.float32, align_corners=align).permute(0, 3, 1, 2)
     np.testing.assert_allclose(ops.ce2d(full, cu(tgt), 255).item(), ce.item(), rtol=1e-6)
+
+
+def _low_res_case(C, h, w, H, W, N, seed):
+    gen = torch.Generator(device="cuda").manual_seed(seed)
+    s_lo = torch.randn((N, h, w, C), device="cuda", generator=gen) * 3
+    t_lo = torch.randn((N, h, w, C), device="cuda", generator=gen) * 3
+    tgt = torch.randint(0, C, (N, H, W), device="cuda", generator=gen)
+    tgt[:, : max(1, H // 8)] = 255                           # an ignore band
+    tgt[0, -1, -1] = 255
+    alpha = torch.rand(C, device="cuda", generator=gen) + 0.5
+    return s_lo, t_lo, tgt, alpha
+
+
+def _check_up_against_materialised(ops, which, s_lo, t_lo, tgt, alpha, size, align):
+    """Each *_up entry point in `which` against the same op of this library on upsample_bilinear_ac(...), at the tolerances the
+    19-class tests hold them to (above, and test_criteria_gpu.py: test_low_resolution_forms_match_the_materialised_ones)."""
+    up = lambda lo: ops.upsample_bilinear_ac(lo, size, out_dtype=torch.float32, align_corners=align).permute(0, 3, 1, 2)
+    s_full, t_full = up(s_lo), up(t_lo)
+    if "ce2d" in which:
+        np.testing.assert_allclose(ops.ce2d_up(s_lo, tgt, size, 255, align).item(), ops.ce2d(s_full, tgt, 255).item(), rtol=1e-6)
+    for name in ("kldiv", "jsdiv"):
+        if name not in which:
+            continue
+        for T in (1.0, 4.0):
+            ref, _ = getattr(ops, name)(s_full, t_full, T, want_grad=False)
+            got = getattr(ops, name + "_up")(s_lo, t_lo, size, T, align)
+            np.testing.assert_allclose(got.item(), ref.item(), rtol=2e-5, atol=1e-7, err_msg=f"{name} T={T}")
+    if "focal" in which:
+        for gamma, red, a in ((2.0, "mean", None), (0.5, "sum", alpha), (0.0, "mean", alpha)):
+            ref = ops.focal(s_full, tgt, gamma, a, 255, red)[0]
+            got = ops.focal_up(s_lo, tgt, size, gamma, a, 255, red, align)[0]
+            np.testing.assert_allclose(got.item(), ref.item(), rtol=2e-5, err_msg=f"focal {gamma} {red}")
+
+
+@pytest.mark.parametrize("C", [7, 19])
+@pytest.mark.parametrize("h,w,H,W,align", [(12, 20, 24, 40, True), (14, 22, 25, 40, False), (5, 150, 9, 300, True)])
+def test_low_resolution_losses_at_a_generic_class_count(C, h, w, H, W, align):
+    """The kernels keep two bodies per entry point: 19 classes at compile time (interpolated once into registers) and any other
+    count (re-interpolated per pass).  Both, on an odd size, a non-aligned one and a row of two chunks (W > 256)."""
+    from kdcc_amd import ops
+    s_lo, t_lo, tgt, alpha = _low_res_case(C, h, w, H, W, 2, C * 100000 + h * 1000 + w)
+    _check_up_against_materialised(ops, ("ce2d", "kldiv", "jsdiv", "focal"), s_lo, t_lo, tgt, alpha, (H, W), align)
+
+
+def test_low_resolution_class_count_limits():
+    """The staged patches fit 64 KiB of LDS up to 24 classes with two operands and 48 with one: the last accepted count gives the
+    materialised numbers, the next one is refused."""
+    from kdcc_amd import _lib, ops
+    for which, last in ((("kldiv", "jsdiv"), 24), (("ce2d", "focal"), 48)):
+        s_lo, t_lo, tgt, alpha = _low_res_case(last, 4, 6, 8, 12, 1, last)
+        _check_up_against_materialised(ops, which, s_lo, t_lo, tgt, alpha, (8, 12), True)
+        s_lo, t_lo, tgt, alpha = _low_res_case(last + 1, 4, 6, 8, 12, 1, last + 1)
+        calls = {"kldiv": lambda: ops.kldiv_up(s_lo, t_lo, (8, 12), 2.0), "jsdiv": lambda: ops.jsdiv_up(s_lo, t_lo, (8, 12), 2.0),
+                 "ce2d": lambda: ops.ce2d_up(s_lo, tgt, (8, 12), 255), "focal": lambda: ops.focal_up(s_lo, tgt, (8, 12), 2.0, None, 255, "mean")}
+        for name in which:
+            with pytest.raises(_lib.KdccError):
+                calls[name]()
 
 
 def test_unsupported_ratio_is_refused_loudly():

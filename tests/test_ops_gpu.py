@@ -1041,6 +1041,49 @@ def test_logit_losses_channels_last_any_class_count(K, Cc):
     if Cc <= 64:
         conf = K.confusion(sd, torch.from_numpy(tgt).cuda()).cpu().numpy()
         assert np.array_equal(conf, orc.confusion(s, tgt)), f"confusion C={Cc}"
+    # the other two criteria behind the same gate, against the float64 restatement
+    import _criteria_ref as R
+    pd = torch.softmax(td, 1).contiguous(memory_format=torch.channels_last)
+    for what, (loss, grad), (rl, rg) in (("jsd", K.jsdiv(sd, td, 2.0), R.jsd(sd, td, 2.0)),
+                                         ("ekl", K.ensemble_kldiv(sd, pd), R.ensemble_kl(sd, pd))):
+        np.testing.assert_allclose(loss.item(), rl.item(), rtol=1e-4, err_msg=f"{what} C={Cc}")
+        assert_close(grad.cpu().numpy(), rg.cpu().numpy(), "f32", f"{what} grad C={Cc}")
+
+
+@pytest.mark.parametrize("sdt", ["f32", "bf16"])
+@pytest.mark.parametrize("tdt", ["f32", "bf16"])
+def test_pair_losses_channels_last_every_operand_dtype(K, sdt, tdt):
+    """KLDiv / JSD / ensemble KL through the NHWC kernels on 558 pixels (two whole 256-pixel blocks and a tail, an element count
+    that is no multiple of 4) for every (student, target) dtype pair: against the oracle / the float64 restatement on the rounded
+    operands at the bars of each gradient dtype (test_losses_bf16_large_vs_oracle, test_criteria_gpu.py); a batch of one; and
+    want_grad=False, whose loss is bit-equal to the loss computed with the gradient, channels-last and NCHW."""
+    import _criteria_ref as R
+    N, Cc, H, W = 2, 19, 9, 31
+    s, t = q(rnd(N, Cc, H, W, scale=3.0), sdt), q(rnd(N, Cc, H, W, scale=3.0), tdt)
+    e = np.exp(t - t.max(1, keepdims=True))
+    p = q(e / e.sum(1, keepdims=True), tdt)
+    sd, td, pd = (dev_nhwc(a, dt).permute(0, 3, 1, 2) for a, dt in ((s, sdt), (t, tdt), (p, tdt)))
+    kl_ref = lambda a, b: orc.kldiv(a.float().cpu().numpy(), b.float().cpu().numpy(), 2.0)
+    cases = (("kld", lambda a, b, **k: K.kldiv(a, b, 2.0, **k), td, kl_ref),
+             ("jsd", lambda a, b, **k: K.jsdiv(a, b, 2.0, **k), td, lambda a, b: R.jsd(a, b, 2.0)),
+             ("ekl", lambda a, b, **k: K.ensemble_kldiv(a, b, **k), pd, R.ensemble_kl))
+    for what, op, tgt, ref in cases:
+        for n in (N, 1):
+            a, b = sd[:n], tgt[:n]
+            loss, grad = op(a, b)
+            rl, rg = ref(a, b)
+            rg = rg.cpu().numpy() if torch.is_tensor(rg) else rg
+            tag = f"{what} s={sdt} t={tdt} N={n}"
+            np.testing.assert_allclose(loss.item(), float(rl), rtol=1e-4, err_msg=tag)
+            assert grad.dtype == DT[sdt] and grad.shape == a.shape
+            assert_close(grad.float().cpu().numpy(), rg, sdt, tag)
+            if sdt == "f32":
+                got = grad.double().cpu().numpy()
+                assert np.sqrt(((got - rg) ** 2).sum() / (rg.astype(np.float64) ** 2).sum()) <= 1e-4, tag
+        for a, b in ((sd, tgt), (sd.contiguous(), tgt.contiguous())):
+            loss, _ = op(a, b)
+            bare, none = op(a, b, want_grad=False)
+            assert none is None and torch.equal(bare, loss), f"{what} s={sdt} t={tdt} {a.stride()}: the loss changes without the gradient"
 
 
 def test_radam_golden(K, golden):
