@@ -16,11 +16,13 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "dw_select.h"
 #include "kd_common.h"
 
 namespace {
 
 constexpr int CB = 64;    // channels per block
+static_assert(CB == DW_REG_CB, "dw_select.h plans the register kernels' grids");
 constexpr int CQ = 16;    // channel quads per block (threads along channels)
 constexpr int WTR = 8;    // lattice cols per thread in the weight-gradient kernel
 
@@ -394,18 +396,48 @@ int check_desc(const kd_dw_desc *d, const char *who)
 
 }  // namespace
 
-// dwconv_mfma.hip: matrix-core path for bf16 / 9x9 (1 = launched, 0 = not eligible, < 0 = error)
-int kd_internal_dw_mfma_fwd(const kd_dw_desc *d, const void *x, const float *w_taps, const float *bias,
-                            const kd_dw_epilogue *ep, void *y, hipStream_t s);
+// Every KDCC_DW_* switch of the three depthwise files, read once per process (NAME=0 turns an A/B switch off).
+const DwSwitches &dw_switches()
+{
+    static const DwSwitches sw = [] {
+        auto on = [](const char *name) { const char *v = getenv(name); return !(v && v[0] == '0') ? 1 : 0; };
+        DwSwitches s;
+        s.mfma = on("KDCC_DW_MFMA"); s.lattice = on("KDCC_DW_LATTICE"); s.lw = on("KDCC_DW_LW"); s.lw_order = on("KDCC_DW_LW_ORDER");
+        int ts = 0, tr = 0;
+        if (const char *e = getenv("KDCC_DW_TILE")) sscanf(e, "%dx%d", &ts, &tr);   // tuning hook (2x8 | 2x4 | 4x4)
+        if ((ts == 2 || ts == 4) && tr == 4) { s.tile_s = ts; s.tile_r = tr; }
+        s.dbg = KD_TUNING_ENV_INT("KDCC_DW_DBG");          // timing ablations: tuning build only (kd_common.h)
+        s.lw_dbg = KD_TUNING_ENV_INT("KDCC_DW_LW_DBG");
+        return s;
+    }();
+    return sw;
+}
 
-long long kd_internal_lattice_rows(int N, int H, int W, int dil);
-int kd_internal_dw_lattice_ok(const kd_dw_desc *d, int nb);
-int kd_internal_dw_mfma_fwd_n(const kd_dw_desc *d, int nb, int fan, const void *const *xs, const float *const *ws, void *const *ys,
-                              const float *bias, const kd_dw_epilogue *ep, hipStream_t s, int lp = 0);
-int kd_internal_dw_mfma_wgrad_slabs(const kd_dw_desc *d);
-int kd_internal_dw_mfma_wgrad(const kd_dw_desc *d, const void *x, const void *dy, int ld_dy, float *part, hipStream_t s);
-int kd_internal_dw_mfma_wgrad_multi_slabs(const kd_dw_desc *d, int n);
-int kd_internal_dw_mfma_wgrad_multi(const kd_dw_desc *d, int n, const void *x, const void *const *dys, int ld_dy, float *part, hipStream_t s, int lp = 0);
+// The launchers of dwconv_mfma.hip / dwconv_lw.hip: they fill the params of the kernel `c` names and launch it (KD_OK or an error).
+int kd_internal_dw_mfma_fwd_n(const DwSel &c, const kd_dw_desc *d, const void *const *xs, const float *const *ws, void *const *ys, hipStream_t s);
+int kd_internal_dw_mfma_wgrad(const DwSel &c, const kd_dw_desc *d, const void *x, const void *dy, int ld_dy, float *part, hipStream_t s);
+int kd_internal_dw_mfma_wgrad_multi(const DwSel &c, const kd_dw_desc *d, const void *x, const void *const *dys, int ld_dy, float *part, hipStream_t s);
+// ... or KD_DW_LW_NO_TABLE
+int kd_internal_dw_lw_fanout(const DwSel &c, const kd_dw_desc *d, const void *x, const float *const *ws, void *const *ys, hipStream_t s);
+
+static bool all_aligned16(const void *a, const void *const *v, int n)
+{
+    bool ok = kd_aligned16(a);
+    for (int i = 0; i < n; ++i) ok = ok && kd_aligned16(v[i]);
+    return ok;
+}
+
+// dws[i] (+)= the sum of branch i's slabs of partial sums ([branch][slab][k*k][C] fp32 in `part`)
+static int dw_reduce_slabs(const char *who, const kd_dw_desc *d, const float *part, int slabs, int n, float *const *dws, int accumulate, hipStream_t s)
+{
+    const int total = d->k * d->k * d->C;
+    for (int i = 0; i < n; ++i) {
+        hipLaunchKernelGGL(dw_slab_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, s, part + (size_t)i * slabs * total, dws[i], slabs,
+                           d->k * d->k, d->C, accumulate);
+        KD_CHECK_LAUNCH(who);
+    }
+    return KD_OK;
+}
 
 extern "C" int kd_pack_dw_weight(const float *src, float *dst, int32_t C, int32_t k, int32_t flip, kd_stream_t stream)
 {
@@ -427,11 +459,6 @@ extern "C" int kd_dwconv_fwd(const kd_dw_desc *d, const void *x, const float *w_
     KD_REQUIRE(d->ldy >= d->C && d->ldy % 4 == 0 && d->ldx % 4 == 0, KD_ERR_INVALID, "kd_dwconv_fwd: ld must be a multiple of 4");
     KD_REQUIRE(((uintptr_t)x % (4 * es)) == 0 && ((uintptr_t)y % (4 * es)) == 0, KD_ERR_INVALID,
                "kd_dwconv_fwd: x/y must be aligned to 4 elements");
-    {
-        const int took = kd_internal_dw_mfma_fwd(d, x, w_taps, bias, ep, y, (hipStream_t)stream);
-        if (took < 0) return took;
-        if (took) return KD_OK;
-    }
     DwParams p;
     memset(&p.ep, 0, sizeof(p.ep));
     if (ep) {
@@ -440,28 +467,26 @@ extern "C" int kd_dwconv_fwd(const kd_dw_desc *d, const void *x, const float *w_
         KD_REQUIRE(okp(ep->res_pre, ep->ld_res_pre) && okp(ep->mask, ep->ld_mask) && okp(ep->res_post, ep->ld_res_post),
                    KD_ERR_INVALID, "kd_dwconv_fwd: epilogue operands must be aligned to 4 elements");
     }
+    hipStream_t s = (hipStream_t)stream;
+    const DwFacts f{kd_aligned16(x) && kd_aligned16(y), 0, bias || (ep && (ep->res_pre || ep->mask || ep->res_post)), false};
+    const DwSel c = dw_select(DW_FWD, d, 1, false, f, dw_switches());
+    if (c.kernel == DW_MFMA_FWD_1) return kd_internal_dw_mfma_fwd_n(c, d, &x, &w_taps, &y, s);
     p.x = x; p.w = w_taps; p.bias = bias; p.y = y;
     p.N = d->N; p.H = d->H; p.W = d->W; p.C = d->C; p.pad = d->pad; p.dil = d->dil; p.ldx = d->ldx; p.ldy = d->ldy;
     p.LH = (d->H + d->dil - 1) / d->dil;
     p.LW = (d->W + d->dil - 1) / d->dil;
-    // thread tile (lattice rows x cols per thread): 2x8 measured fastest at the student's shapes
-    int ts = 2, tr = 8;
-    if (const char *e = getenv("KDCC_DW_TILE")) sscanf(e, "%dx%d", &ts, &tr);   // tuning hook (2x8 | 2x4 | 4x4)
-    p.tiles_h = (p.LH + ts - 1) / ts;
-    p.tiles_w = (p.LW + tr - 1) / tr;
-    p.gx = (p.tiles_h * p.tiles_w + 15) / 16;
-    p.gz = d->N * d->dil * d->dil;
-    const dim3 grid((unsigned)(p.gx * p.gz * ((d->C + CB - 1) / CB)));
-    hipStream_t s = (hipStream_t)stream;
+    p.tiles_h = c.nty; p.tiles_w = c.ntx;
+    p.gx = c.nitems; p.gz = c.nseg;
+    const dim3 grid((unsigned)c.blocks);
 #define KD_DW_LAUNCH(TT, KK, A, B) hipLaunchKernelGGL((dwconv_fwd_kernel<TT, KK, A, B>), grid, dim3(256), 0, s, p)
 #define KD_DW_TILES(TT, KK)                                   \
     do {                                                      \
-        if (ts == 2 && tr == 4) KD_DW_LAUNCH(TT, KK, 2, 4);   \
-        else if (ts == 4 && tr == 4) KD_DW_LAUNCH(TT, KK, 4, 4); \
+        if (c.tile_s == 2 && c.tile_r == 4) KD_DW_LAUNCH(TT, KK, 2, 4);   \
+        else if (c.tile_s == 4 && c.tile_r == 4) KD_DW_LAUNCH(TT, KK, 4, 4); \
         else KD_DW_LAUNCH(TT, KK, 2, 8);                      \
     } while (0)
-    KD_NOTE_KERNEL(d->dtype == KD_BF16 ? "dwconv_fwd_kernel<bf16>" : "dwconv_fwd_kernel<f32>");
-    if (d->dtype == KD_BF16) {
+    KD_NOTE_KERNEL(dw_kernel_name(c.kernel));
+    if (c.kernel == DW_REG_FWD_BF16) {
         if (d->k == 9) KD_DW_TILES(bf16_t, 9);
         else KD_DW_TILES(bf16_t, 3);
     } else {
@@ -482,19 +507,15 @@ extern "C" int kd_dwconv_fwd_sum(const kd_dw_desc *d, int32_t n, const void *con
         KD_REQUIRE(xs[i] && w_taps[i], KD_ERR_INVALID, "kd_dwconv_fwd_sum: null input / tap table %d", i);
         KD_REQUIRE(xs[i] != y, KD_ERR_INVALID, "kd_dwconv_fwd_sum: y must not alias an input");
     }
-    // up to three inputs per launch on the matrix cores; longer lists and every other shape chain through res_post
-    int done = 0;
-    if (n <= 3) {
-        const int took = kd_internal_dw_mfma_fwd_n(d, n, 0, xs, w_taps, &y, nullptr, nullptr, (hipStream_t)stream);
-        if (took < 0) return took;
-        if (took) return KD_OK;
-    }
-    for (; done < n; ++done) {
+    // up to three inputs in one launch on the matrix cores; longer lists and every other shape chain through res_post
+    const DwSel c = dw_select(DW_SUM, d, n, false, DwFacts{all_aligned16(y, xs, n), 0, false, false}, dw_switches());
+    if (c.kernel != DW_EACH) return kd_internal_dw_mfma_fwd_n(c, d, xs, w_taps, &y, (hipStream_t)stream);
+    for (int i = 0; i < n; ++i) {
         kd_dw_epilogue ep;
         memset(&ep, 0, sizeof(ep));
         ep.res_post = y;
         ep.ld_res_post = d->ldy;
-        rc = kd_dwconv_fwd(d, xs[done], w_taps[done], nullptr, done ? &ep : nullptr, y, stream);
+        rc = kd_dwconv_fwd(d, xs[i], w_taps[i], nullptr, i ? &ep : nullptr, y, stream);
         if (rc) return rc;
     }
     return KD_OK;
@@ -511,33 +532,43 @@ extern "C" int kd_dwconv_fwd_fanout(const kd_dw_desc *d, int32_t n, const void *
         KD_REQUIRE(ys[i] != x, KD_ERR_INVALID, "kd_dwconv_fwd_fanout: an output must not alias the input");
         for (int j = 0; j < i; ++j) KD_REQUIRE(ys[i] != ys[j], KD_ERR_INVALID, "kd_dwconv_fwd_fanout: outputs %d and %d alias", j, i);
     }
+    hipStream_t s = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const bool capturing = hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
     // up to three outputs per launch on the matrix cores (the tile of x staged once); everything else one launch per output
-    for (int done = 0; done < n;) {
-        const int m = n - done < 3 ? n - done : 3;
-        const int took = kd_internal_dw_mfma_fwd_n(d, m, 1, &x, w_taps + done, ys + done, nullptr, nullptr, (hipStream_t)stream);
-        if (took < 0) return took;
-        if (took) { done += m; continue; }
+    for (int done = 0, m; done < n; done += m) {
+        m = dw_chunk(n, done);
+        const DwFacts f{all_aligned16(x, ys + done, m), 0, false, capturing};
+        DwSel c = dw_select(DW_FANOUT, d, m, false, f, dw_switches());
+        if (c.kernel == DW_LW_FAN3) {
+            rc = kd_internal_dw_lw_fanout(c, d, x, w_taps + done, ys + done, s);
+            if (rc <= 0) {
+                if (rc) return rc;
+                continue;
+            }
+            // The one choice that can fail at run time: the item table of a new geometry did not fit on the device or did not get
+            // there.  Nothing was launched; what the selection says without the lone-wave kernel runs instead.
+            DwSwitches no_lw = dw_switches();
+            no_lw.lw = 0;
+            c = dw_select(DW_FANOUT, d, m, false, f, no_lw);
+        }
+        if (c.kernel != DW_EACH) {
+            rc = kd_internal_dw_mfma_fwd_n(c, d, &x, w_taps + done, ys + done, s);
+            if (rc) return rc;
+            continue;
+        }
         for (int i = 0; i < m; ++i) {
             rc = kd_dwconv_fwd(d, x, w_taps[done + i], nullptr, nullptr, ys[done + i], stream);
             if (rc) return rc;
         }
-        done += m;
     }
     return KD_OK;
-}
-
-static int wgrad_slabs(const kd_dw_desc *d)
-{
-    const int LH = (d->H + d->dil - 1) / d->dil;
-    const int nstrips = d->N * d->dil * d->dil * LH;
-    return (nstrips + 15) / 16;
 }
 
 extern "C" size_t kd_dwconv_wgrad_workspace(const kd_dw_desc *d)
 {
     if (!d || d->dil < 1) return 0;
-    const int slabs = wgrad_slabs(d), mslabs = kd_internal_dw_mfma_wgrad_slabs(d);
-    return (size_t)(slabs > mslabs ? slabs : mslabs) * d->k * d->k * d->C * sizeof(float);
+    return dw_wgrad_workspace(d, dw_switches());
 }
 
 extern "C" int kd_dwconv_wgrad(const kd_dw_desc *d, const void *x, const void *dy, int32_t ld_dy, float *dw,
@@ -552,40 +583,30 @@ extern "C" int kd_dwconv_wgrad(const kd_dw_desc *d, const void *x, const void *d
                "kd_dwconv_wgrad: x/dy must be aligned to 4 elements");
     KD_REQUIRE(workspace_bytes >= kd_dwconv_wgrad_workspace(d), KD_ERR_WORKSPACE, "kd_dwconv_wgrad: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    {
-        const int took = kd_internal_dw_mfma_wgrad(d, x, dy, ld_dy, (float *)workspace, s);
-        if (took < 0) return took;
-        if (took) {
-            const int total = d->k * d->k * d->C;
-            hipLaunchKernelGGL(dw_slab_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, s, (const float *)workspace, dw,
-                               kd_internal_dw_mfma_wgrad_slabs(d), d->k * d->k, d->C, accumulate);
-            KD_CHECK_LAUNCH("kd_dwconv_wgrad(reduce)");
-            return KD_OK;
-        }
-    }
-    DwWgradParams p;
-    p.x = x; p.dy = dy; p.part = (float *)workspace;
-    p.N = d->N; p.H = d->H; p.W = d->W; p.C = d->C; p.pad = d->pad; p.dil = d->dil; p.ldx = d->ldx; p.ld_dy = ld_dy;
-    p.LH = (d->H + d->dil - 1) / d->dil;
-    p.LW = (d->W + d->dil - 1) / d->dil;
-    p.nstrips = d->N * d->dil * d->dil * p.LH;
-    const int slabs = wgrad_slabs(d);
-    p.nslabs = slabs;
-    const dim3 grid((unsigned)(slabs * ((d->C + CB - 1) / CB) * d->k));
-    KD_NOTE_KERNEL(d->dtype == KD_BF16 ? "dwconv_wgrad_kernel<bf16>" : "dwconv_wgrad_kernel<f32>");
-    if (d->dtype == KD_BF16) {
-        if (d->k == 9) hipLaunchKernelGGL((dwconv_wgrad_kernel<bf16_t, 9>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((dwconv_wgrad_kernel<bf16_t, 3>), grid, dim3(256), 0, s, p);
+    const DwSel c = dw_select(DW_WGRAD, d, 1, false, DwFacts{kd_aligned16(x) && kd_aligned16(dy), ld_dy, false, false}, dw_switches());
+    if (c.kernel == DW_MFMA_WGRAD) {
+        rc = kd_internal_dw_mfma_wgrad(c, d, x, dy, ld_dy, (float *)workspace, s);
+        if (rc) return rc;
     } else {
-        if (d->k == 9) hipLaunchKernelGGL((dwconv_wgrad_kernel<float, 9>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((dwconv_wgrad_kernel<float, 3>), grid, dim3(256), 0, s, p);
+        DwWgradParams p;
+        p.x = x; p.dy = dy; p.part = (float *)workspace;
+        p.N = d->N; p.H = d->H; p.W = d->W; p.C = d->C; p.pad = d->pad; p.dil = d->dil; p.ldx = d->ldx; p.ld_dy = ld_dy;
+        p.LH = (d->H + d->dil - 1) / d->dil;
+        p.LW = (d->W + d->dil - 1) / d->dil;
+        p.nstrips = c.nitems;
+        p.nslabs = c.slabs;
+        const dim3 grid((unsigned)c.blocks);
+        KD_NOTE_KERNEL(dw_kernel_name(c.kernel));
+        if (c.kernel == DW_REG_WGRAD_BF16) {
+            if (d->k == 9) hipLaunchKernelGGL((dwconv_wgrad_kernel<bf16_t, 9>), grid, dim3(256), 0, s, p);
+            else hipLaunchKernelGGL((dwconv_wgrad_kernel<bf16_t, 3>), grid, dim3(256), 0, s, p);
+        } else {
+            if (d->k == 9) hipLaunchKernelGGL((dwconv_wgrad_kernel<float, 9>), grid, dim3(256), 0, s, p);
+            else hipLaunchKernelGGL((dwconv_wgrad_kernel<float, 3>), grid, dim3(256), 0, s, p);
+        }
+        KD_CHECK_LAUNCH("kd_dwconv_wgrad");
     }
-    KD_CHECK_LAUNCH("kd_dwconv_wgrad");
-    const int total = d->k * d->k * d->C;
-    hipLaunchKernelGGL(dw_slab_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, s, (const float *)workspace, dw,
-                       slabs, d->k * d->k, d->C, accumulate);
-    KD_CHECK_LAUNCH("kd_dwconv_wgrad(reduce)");
-    return KD_OK;
+    return dw_reduce_slabs("kd_dwconv_wgrad(reduce)", d, (const float *)workspace, c.slabs, 1, &dw, accumulate, s);
 }
 
 // Weight gradients of n depthwise convs of one geometry that read ONE input (the replaced ASPP branches): fused on the matrix
@@ -593,11 +614,7 @@ extern "C" int kd_dwconv_wgrad(const kd_dw_desc *d, const void *x, const void *d
 extern "C" size_t kd_dwconv_wgrad_multi_workspace(const kd_dw_desc *d, int32_t n)
 {
     if (!d || d->dil < 1 || n < 1) return 0;
-    const size_t single = kd_dwconv_wgrad_workspace(d);
-    // branches are fused three (or two) at a time; the largest chunk sets the size (slabs per branch do not depend on the count)
-    const int m = n < 3 ? n : 3;
-    const size_t multi = m >= 2 ? (size_t)kd_internal_dw_mfma_wgrad_multi_slabs(d, m) * m * d->k * d->k * d->C * sizeof(float) : 0;
-    return single > multi ? single : multi;
+    return dw_wgrad_multi_workspace(d, n, dw_switches());
 }
 
 extern "C" int kd_dwconv_wgrad_multi(const kd_dw_desc *d, int32_t n, const void *x, const void *const *dys, int32_t ld_dy,
@@ -610,31 +627,19 @@ extern "C" int kd_dwconv_wgrad_multi(const kd_dw_desc *d, int32_t n, const void 
     for (int i = 0; i < n; ++i) KD_REQUIRE(dys[i] && dws[i], KD_ERR_INVALID, "kd_dwconv_wgrad_multi: null gradient %d", i);
     KD_REQUIRE(workspace_bytes >= kd_dwconv_wgrad_multi_workspace(d, n), KD_ERR_WORKSPACE, "kd_dwconv_wgrad_multi: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    for (int done = 0; done < n;) {
-        const int m = n - done < 3 ? n - done : 3;
-        const int slabs = kd_internal_dw_mfma_wgrad_multi_slabs(d, m);
-        int took = 0;
-        if (slabs > 0) {
-            const int es = kd_elem_size(d->dtype);
-            bool ok = ld_dy >= d->C && ld_dy % 4 == 0 && d->ldx % 4 == 0 && ((uintptr_t)x % (4 * es)) == 0;
-            for (int i = 0; i < m; ++i) ok = ok && ((uintptr_t)dys[done + i] % (4 * es)) == 0;
-            if (ok) took = kd_internal_dw_mfma_wgrad_multi(d, m, x, dys + done, ld_dy, (float *)workspace, s);
-            if (took < 0) return took;
+    for (int done = 0, m; done < n; done += m) {
+        m = dw_chunk(n, done);
+        const DwSel c = dw_select(DW_WGRAD_MULTI, d, m, false, DwFacts{all_aligned16(x, dys + done, m), ld_dy, false, false}, dw_switches());
+        if (c.kernel != DW_EACH) {
+            rc = kd_internal_dw_mfma_wgrad_multi(c, d, x, dys + done, ld_dy, (float *)workspace, s);
+            if (!rc) rc = dw_reduce_slabs("kd_dwconv_wgrad_multi(reduce)", d, (const float *)workspace, c.slabs, m, dws + done, accumulate, s);
+            if (rc) return rc;
+            continue;
         }
-        if (took) {
-            const int total = d->k * d->k * d->C;
-            for (int i = 0; i < m; ++i) {
-                hipLaunchKernelGGL(dw_slab_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, s,
-                                   (const float *)workspace + (size_t)i * slabs * total, dws[done + i], slabs, d->k * d->k, d->C, accumulate);
-                KD_CHECK_LAUNCH("kd_dwconv_wgrad_multi(reduce)");
-            }
-        } else {
-            for (int i = 0; i < m; ++i) {
-                rc = kd_dwconv_wgrad(d, x, dys[done + i], ld_dy, dws[done + i], accumulate, workspace, workspace_bytes, stream);
-                if (rc) return rc;
-            }
+        for (int i = 0; i < m; ++i) {
+            rc = kd_dwconv_wgrad(d, x, dys[done + i], ld_dy, dws[done + i], accumulate, workspace, workspace_bytes, stream);
+            if (rc) return rc;
         }
-        done += m;
     }
     return KD_OK;
 }
@@ -667,13 +672,13 @@ __global__ void lattice_rows_kernel(uint4 *img, uint4 *rows, long long nrows, in
 
 extern "C" int64_t kd_lattice_rows(int32_t N, int32_t H, int32_t W, int32_t dil)
 {
-    return (int64_t)kd_internal_lattice_rows(N, H, W, dil);
+    return (int64_t)dw_lattice_rows(N, H, W, dil);
 }
 
 extern "C" int32_t kd_dwconv_lattice_ok(const kd_dw_desc *d, int32_t n)
 {
     if (!d || check_desc(d, "kd_dwconv_lattice_ok")) return 0;
-    return kd_internal_dw_lattice_ok(d, n);
+    return dw_lattice_ok(d, n, dw_switches());
 }
 
 extern "C" int kd_lattice_rows_move(int32_t dtype, int32_t N, int32_t H, int32_t W, int32_t C, int32_t dil, void *img, int32_t ld_img,
@@ -684,7 +689,7 @@ extern "C" int kd_lattice_rows_move(int32_t dtype, int32_t N, int32_t H, int32_t
     const int es = kd_elem_size(dtype), v = 16 / es;
     KD_REQUIRE(C % v == 0 && ld_img % v == 0 && ld_rows % v == 0 && ld_img >= C && ld_rows >= C && kd_aligned16(img) && kd_aligned16(rows),
                KD_ERR_INVALID, "kd_lattice_rows_move: channels / strides must be multiples of 16 B and the tensors 16-B aligned");
-    const long long nrows = kd_internal_lattice_rows(N, H, W, dil);
+    const long long nrows = dw_lattice_rows(N, H, W, dil);
     const int Ly = (H + dil - 1) / dil, Lx = (W + dil - 1) / dil;
     const long long total = nrows * (C / v);
     const unsigned grid = (unsigned)((total + 255) / 256 > 65536 ? 65536 : (total + 255) / 256);
@@ -708,13 +713,10 @@ extern "C" int kd_dwconv_fwd_fanout_lattice(const kd_dw_desc *d, int32_t n, cons
         KD_REQUIRE(ys[i] && w_taps[i] && ys[i] != x, KD_ERR_INVALID, "kd_dwconv_fwd_fanout_lattice: null / aliasing output %d", i);
         for (int j = 0; j < i; ++j) KD_REQUIRE(ys[i] != ys[j], KD_ERR_INVALID, "kd_dwconv_fwd_fanout_lattice: outputs %d and %d alias", j, i);
     }
-    KD_REQUIRE(kd_internal_dw_lattice_ok(d, n), KD_ERR_UNSUPPORTED, "kd_dwconv_fwd_fanout_lattice: shape not eligible (kd_dwconv_lattice_ok)");
-    kd_dw_desc dd = *d;
-    dd.ldy = d->C;   // (unused by the lattice kernels; the eligibility test of the shared launcher reads it)
-    const int took = kd_internal_dw_mfma_fwd_n(&dd, n, 1, &x, w_taps, ys, nullptr, nullptr, (hipStream_t)stream, 1);
-    if (took < 0) return took;
-    KD_REQUIRE(took, KD_ERR_UNSUPPORTED, "kd_dwconv_fwd_fanout_lattice: the matrix-core kernel refused the call");
-    return KD_OK;
+    KD_REQUIRE(dw_lattice_ok(d, n, dw_switches()), KD_ERR_UNSUPPORTED, "kd_dwconv_fwd_fanout_lattice: shape not eligible (kd_dwconv_lattice_ok)");
+    const DwSel c = dw_select(DW_FANOUT, d, n, true, DwFacts{all_aligned16(x, ys, n), 0, false, false}, dw_switches());
+    KD_REQUIRE(c.kernel != DW_EACH, KD_ERR_UNSUPPORTED, "kd_dwconv_fwd_fanout_lattice: the matrix-core kernel refused the call");
+    return kd_internal_dw_mfma_fwd_n(c, d, &x, w_taps, ys, (hipStream_t)stream);
 }
 
 extern "C" int kd_dwconv_fwd_sum_lattice(const kd_dw_desc *d, int32_t n, const void *const *xs, const float *const *w_taps, void *y,
@@ -725,11 +727,10 @@ extern "C" int kd_dwconv_fwd_sum_lattice(const kd_dw_desc *d, int32_t n, const v
     KD_REQUIRE(n >= 2 && n <= 3 && xs && w_taps && y, KD_ERR_INVALID, "kd_dwconv_fwd_sum_lattice: null argument or n not 2, 3");
     for (int i = 0; i < n; ++i) KD_REQUIRE(xs[i] && w_taps[i] && xs[i] != y, KD_ERR_INVALID, "kd_dwconv_fwd_sum_lattice: null / aliasing input %d", i);
     KD_REQUIRE(d->ldy >= d->C && d->ldy % 8 == 0, KD_ERR_INVALID, "kd_dwconv_fwd_sum_lattice: bad ldy");
-    KD_REQUIRE(kd_internal_dw_lattice_ok(d, n), KD_ERR_UNSUPPORTED, "kd_dwconv_fwd_sum_lattice: shape not eligible (kd_dwconv_lattice_ok)");
-    const int took = kd_internal_dw_mfma_fwd_n(d, n, 0, xs, w_taps, &y, nullptr, nullptr, (hipStream_t)stream, 1);
-    if (took < 0) return took;
-    KD_REQUIRE(took, KD_ERR_UNSUPPORTED, "kd_dwconv_fwd_sum_lattice: the matrix-core kernel refused the call");
-    return KD_OK;
+    KD_REQUIRE(dw_lattice_ok(d, n, dw_switches()), KD_ERR_UNSUPPORTED, "kd_dwconv_fwd_sum_lattice: shape not eligible (kd_dwconv_lattice_ok)");
+    const DwSel c = dw_select(DW_SUM, d, n, true, DwFacts{all_aligned16(y, xs, n), 0, false, false}, dw_switches());
+    KD_REQUIRE(c.kernel != DW_EACH, KD_ERR_UNSUPPORTED, "kd_dwconv_fwd_sum_lattice: the matrix-core kernel refused the call");
+    return kd_internal_dw_mfma_fwd_n(c, d, xs, w_taps, &y, (hipStream_t)stream);
 }
 
 extern "C" int kd_dwconv_wgrad_multi_lattice(const kd_dw_desc *d, int32_t n, const void *x, const void *const *dys, float *const *dws,
@@ -740,18 +741,13 @@ extern "C" int kd_dwconv_wgrad_multi_lattice(const kd_dw_desc *d, int32_t n, con
     KD_REQUIRE(n >= 2 && n <= 3 && x && dys && dws && workspace, KD_ERR_INVALID, "kd_dwconv_wgrad_multi_lattice: null argument or n not 2, 3");
     for (int i = 0; i < n; ++i) KD_REQUIRE(dys[i] && dws[i], KD_ERR_INVALID, "kd_dwconv_wgrad_multi_lattice: null gradient %d", i);
     KD_REQUIRE(workspace_bytes >= kd_dwconv_wgrad_multi_workspace(d, n), KD_ERR_WORKSPACE, "kd_dwconv_wgrad_multi_lattice: workspace too small");
-    KD_REQUIRE(kd_internal_dw_lattice_ok(d, n), KD_ERR_UNSUPPORTED, "kd_dwconv_wgrad_multi_lattice: shape not eligible (kd_dwconv_lattice_ok)");
+    KD_REQUIRE(dw_lattice_ok(d, n, dw_switches()), KD_ERR_UNSUPPORTED, "kd_dwconv_wgrad_multi_lattice: shape not eligible (kd_dwconv_lattice_ok)");
     hipStream_t s = (hipStream_t)stream;
-    const int slabs = kd_internal_dw_mfma_wgrad_multi_slabs(d, n);
-    KD_REQUIRE(slabs > 0, KD_ERR_UNSUPPORTED, "kd_dwconv_wgrad_multi_lattice: shape not eligible");
-    const int took = kd_internal_dw_mfma_wgrad_multi(d, n, x, dys, d->C, (float *)workspace, s, 1);
-    if (took < 0) return took;
-    KD_REQUIRE(took, KD_ERR_UNSUPPORTED, "kd_dwconv_wgrad_multi_lattice: the matrix-core kernel refused the call");
-    const int total = d->k * d->k * d->C;
-    for (int i = 0; i < n; ++i) {
-        hipLaunchKernelGGL(dw_slab_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, s, (const float *)workspace + (size_t)i * slabs * total,
-                           dws[i], slabs, d->k * d->k, d->C, accumulate);
-        KD_CHECK_LAUNCH("kd_dwconv_wgrad_multi_lattice(reduce)");
-    }
-    return KD_OK;
+    KD_REQUIRE(dw_select(DW_WGRAD_MULTI, d, n, true, dw_shape_facts(d), dw_switches()).kernel != DW_EACH, KD_ERR_UNSUPPORTED,
+               "kd_dwconv_wgrad_multi_lattice: shape not eligible");
+    const DwSel c = dw_select(DW_WGRAD_MULTI, d, n, true, DwFacts{all_aligned16(x, dys, n), d->C, false, false}, dw_switches());
+    KD_REQUIRE(c.kernel != DW_EACH, KD_ERR_UNSUPPORTED, "kd_dwconv_wgrad_multi_lattice: the matrix-core kernel refused the call");
+    rc = kd_internal_dw_mfma_wgrad_multi(c, d, x, dys, d->C, (float *)workspace, s);
+    if (rc) return rc;
+    return dw_reduce_slabs("kd_dwconv_wgrad_multi_lattice(reduce)", d, (const float *)workspace, c.slabs, n, dws, accumulate, s);
 }

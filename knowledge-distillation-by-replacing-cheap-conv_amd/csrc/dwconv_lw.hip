@@ -28,6 +28,7 @@
 #include <string.h>
 #include <type_traits>
 
+#include "dw_select.h"
 #include "igemm_core.h"
 
 namespace {
@@ -262,16 +263,8 @@ __global__ __launch_bounds__(LNT, 1) void dw_lw_fan3_kernel(DwLwParams p)
 
 }  // namespace
 
-static void dw_lw_split(int N, int C, int nvalid, int *nseg)
-{
-    // one workgroup per CU at a time: aim at two rounds of workgroups over the chip, but keep >= 8 items per workgroup so the
-    // operand build (once per workgroup) and the pipeline fill stay small
-    const long long groups = (long long)N * (C / CG);
-    long long s = (512 + groups - 1) / groups;
-    if (s > nvalid / 8) s = nvalid / 8;
-    if (s < 1) s = 1;
-    *nseg = (int)s;
-}
+static_assert(CG == DW_CG && MAXB == DW_MAXB && TLY == DW_TLY_HALF && TLX == DW_TLX && BUF_OOB == DW_BUF_OOB && LDS_BYTES == DW_LW_LDS,
+              "dw_select.h plans this kernel's work items and states its dynamic LDS");
 
 // Item descriptors of a geometry (the same list for every image and channel group), built on the host once and kept on the device:
 // 16 dwords per non-empty item, in the order the asm reads them (tools/gen_dw_lw.py, D_*).
@@ -303,11 +296,10 @@ ItemTable item_table(const kd_dw_desc *d)
     std::vector<int> host;
     // order: the row tiles of one (class, column tile) back to back -- a tile shares its 8 halo rows with its vertical neighbour, and
     // fetched 9 us apart instead of 25 items apart the second fetch still finds most of them in the XCD's L2
-    static int tile_major = -1;      // A/B: KDCC_DW_LW_ORDER=0 = classes innermost (round 6's first order: the halo rows are fetched from HBM twice)
-    if (tile_major < 0) { const char *v = getenv("KDCC_DW_LW_ORDER"); tile_major = (v && v[0] == '0') ? 1 : 0; }
+    const bool classes_innermost = !dw_switches().lw_order;   // A/B: round 6's first order (the halo rows are fetched from HBM twice)
     for (int e = 0; e < nty * ntx * dl * dl; ++e) {
         int q = e, rx, ry, tx, ty;
-        if (tile_major) {
+        if (classes_innermost) {
             rx = q % dl; q /= dl;
             ry = q % dl; q /= dl;
             tx = q % ntx; ty = q / ntx;
@@ -335,8 +327,7 @@ ItemTable item_table(const kd_dw_desc *d)
         }
         v[15] = ry | (rx << 8) | (ty << 16) | (tx << 24);
         {   // timing-only ablations (tuning build): 1 = no output stores (no valid columns), 2 = no load requests (no valid rows)
-            static int dbg = -1;
-            if (dbg < 0) dbg = KD_TUNING_ENV_INT("KDCC_DW_LW_DBG");
+            const int dbg = dw_switches().lw_dbg;
             if (dbg & 1) v[8] = 0;
             if (dbg & 2) v[2] = 0;
         }
@@ -354,74 +345,49 @@ ItemTable item_table(const kd_dw_desc *d)
 }
 }  // namespace
 
-// The lone-wave fan-out launch: 1 = taken, 0 = not eligible (the caller falls back to dw_mfma_fwd_kernel), < 0 = error.
-int kd_internal_dw_lw_fanout(const kd_dw_desc *d, int nb, const void *x, const float *const *ws, void *const *ys, hipStream_t s)
+// The lone-wave fan-out launch on the grid the selection (dw_select.h) gives.  The one launcher that can find at run time that its
+// kernel cannot run: KD_DW_LW_NO_TABLE = the item table of the geometry could not be allocated or uploaded, nothing was launched
+// (the caller selects again without this kernel).
+int kd_internal_dw_lw_fanout(const DwSel &c, const kd_dw_desc *d, const void *x, const float *const *ws, void *const *ys, hipStream_t s)
 {
-    if (nb != 3) return 0;
-    if (d->dtype != KD_BF16 || d->k != 9 || d->C % CG != 0 || d->ldx % 8 != 0 || d->ldy % 8 != 0) return 0;
-    if (!x || !kd_aligned16(x)) return 0;
-    for (int b = 0; b < nb; ++b)
-        if (!ws[b] || !ys[b] || !kd_aligned16(ys[b])) return 0;
-    if ((long long)d->H * d->W * (d->ldx > d->ldy ? d->ldx : d->ldy) * 2 >= (long long)BUF_OOB) return 0;   // 32-bit buffer offsets per image
-    static int enabled = -1;
-    if (enabled < 0) {
-        const char *e = getenv("KDCC_DW_MFMA"), *l = getenv("KDCC_DW_LW");   // A/B hooks: 0 = the 8-wave kernel (KDCC_DW_LW) / the register kernel
-        enabled = !(e && e[0] == '0') && !(l && l[0] == '0');
-    }
-    if (!enabled) return 0;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) return 0;   // (the table upload is a synchronous copy)
+    const int dbg = dw_switches().lw_dbg;   // timing-only, tuning build
     kd_dw_desc dd = *d;
-    {
-        static int dbg = -1;
-        if (dbg < 0) dbg = KD_TUNING_ENV_INT("KDCC_DW_LW_DBG");
-        if (dbg & 4) dd.ldy = 16;
-        if (dbg & 8) dd.ldx = 16;
-        if (dbg & 16) dd.ldy = 64;
-        if (dbg & 32) dd.ldx = 64;
-    }
-    const ItemTable tabv = item_table(&dd);
-    if (!tabv.dptr) return 0;
-    const ItemTable *tab = &tabv;
+    if (dbg & 4) dd.ldy = 16;
+    if (dbg & 8) dd.ldx = 16;
+    if (dbg & 16) dd.ldy = 64;
+    if (dbg & 32) dd.ldx = 64;
+    const ItemTable tab = item_table(&dd);
+    if (!tab.dptr) return KD_DW_LW_NO_TABLE;
     DwLwParams p;
     for (int b = 0; b < MAXB; ++b) {
         p.x[b] = (const bf16_t *)x;
         p.w[b] = ws[b];
         p.y[b] = (bf16_t *)ys[b];
     }
-    p.items = tab->dptr;
+    p.items = tab.dptr;
     p.N = d->N; p.H = d->H; p.W = d->W; p.C = d->C; p.dil = d->dil; p.ldx = d->ldx; p.ldy = d->ldy;
-    {   // timing-only (tuning build): 4 = outputs / 8 = input addressed as DENSE 16-channel images (32-B pixels side by side): the same
-        // requests on cache- and TLB-friendly addresses.  (Tables are keyed on ldx / ldy, so the descriptors follow.)
-        static int dbg = -1;
-        if (dbg < 0) dbg = KD_TUNING_ENV_INT("KDCC_DW_LW_DBG");
-        if (dbg & 4) p.ldy = 16;
-        if (dbg & 8) p.ldx = 16;
-        // 16 = outputs / 32 = input addressed as channel-planar [C/64][N*H*W][64] tensors (timing: the values land in other places)
-        p.xplane = p.yplane = 0;
-        if (dbg & 16) { p.ldy = 64; p.yplane = (long long)d->N * d->H * d->W * 64; }
-        if (dbg & 32) { p.ldx = 64; p.xplane = (long long)d->N * d->H * d->W * 64; }
-    }
-    p.nitems = tab->nvalid;
-    dw_lw_split(d->N, d->C, tab->nvalid, &p.nseg);
-    p.ncg = d->C / CG;
+    // 4 = outputs / 8 = input addressed as DENSE 16-channel images (32-B pixels side by side): the same requests on cache- and
+    // TLB-friendly addresses.  (Tables are keyed on ldx / ldy, so the descriptors follow.)
+    if (dbg & 4) p.ldy = 16;
+    if (dbg & 8) p.ldx = 16;
+    // 16 = outputs / 32 = input addressed as channel-planar [C/64][N*H*W][64] tensors (timing: the values land in other places)
+    p.xplane = p.yplane = 0;
+    if (dbg & 16) { p.ldy = 64; p.yplane = (long long)d->N * d->H * d->W * 64; }
+    if (dbg & 32) { p.ldx = 64; p.xplane = (long long)d->N * d->H * d->W * 64; }
+    p.nitems = tab.nvalid;     // (== c.nitems: the selection counts the items this table lists)
+    p.nseg = c.nseg;
+    p.ncg = c.ncg;
     p.nty = p.ntx = 0;
-    const long long blocks = (long long)d->N * p.ncg * p.nseg;
-    if (blocks > 0x7fffffffLL || (long long)d->N * d->H * d->W > 0x7fffffffLL) return 0;
     static bool attr_set = false;
     if (!attr_set) {
-        if (hipFuncSetAttribute((const void *)dw_lw_fan3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) {
-            kd_set_error("kd_dwconv_fwd_fanout: cannot reserve %d B of LDS", LDS_BYTES);
+        if (hipFuncSetAttribute((const void *)dw_lw_fan3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, c.lds) != hipSuccess) {
+            kd_set_error("kd_dwconv_fwd_fanout: cannot reserve %d B of LDS", c.lds);
             return KD_ERR_HIP;
         }
         attr_set = true;
     }
-    KD_NOTE_KERNEL("dw_lw_fan3_kernel");
-    hipLaunchKernelGGL(dw_lw_fan3_kernel, dim3((unsigned)blocks), dim3(LNT), LDS_BYTES, s, p);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        kd_set_error("kd_dwconv_fwd_fanout(lw): launch failed: %s", hipGetErrorString(err));
-        return KD_ERR_HIP;
-    }
-    return 1;
+    KD_NOTE_KERNEL(dw_kernel_name(c.kernel));
+    hipLaunchKernelGGL(dw_lw_fan3_kernel, dim3((unsigned)c.blocks), dim3(LNT), c.lds, s, p);
+    KD_CHECK_LAUNCH("kd_dwconv_fwd_fanout(lw)");
+    return KD_OK;
 }

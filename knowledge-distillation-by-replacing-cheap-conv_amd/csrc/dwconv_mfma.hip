@@ -24,10 +24,8 @@
 #include <string.h>
 #include <type_traits>
 
+#include "dw_select.h"
 #include "igemm_core.h"
-
-long long kd_internal_lattice_rows(int N, int H, int W, int dil);
-int kd_internal_dw_lw_fanout(const kd_dw_desc *d, int nb, const void *x, const float *const *ws, void *const *ys, hipStream_t s);
 
 namespace {
 
@@ -890,35 +888,10 @@ __global__ __launch_bounds__(NTW, 1) void dw_mfma_wgrad_multi_kernel(DwWgMultiPa
     }
 }
 
-static void dw_mfma_split3(int N, int C, int H, int W, int dil, int *nty, int *ntx, int *nitems, int *nseg)
-{
-    const int LH = (H + dil - 1) / dil, LW = (W + dil - 1) / dil;
-    *nty = (LH + TLY3 - 1) / TLY3;
-    *ntx = (LW + TLX - 1) / TLX;
-    const long long ni = (long long)*nty * *ntx * dil * dil;
-    *nitems = ni > (1 << 24) ? 0 : (int)ni;
-    const long long groups = (long long)N * (C / CG);
-    long long s = (512 + groups - 1) / groups;
-    if (s > ni / 3) s = ni / 3;
-    if (s < 1) s = 1;
-    *nseg = (int)s;
-}
-
-static void dw_mfma_split(int N, int C, int H, int W, int dil, int *nty, int *ntx, int *nitems, int *nseg)
-{
-    const int LH = (H + dil - 1) / dil, LW = (W + dil - 1) / dil;
-    *nty = (LH + TLY - 1) / TLY;
-    *ntx = (LW + TLX - 1) / TLX;
-    const long long ni = (long long)*nty * *ntx * dil * dil;
-    *nitems = ni > (1 << 24) ? 0 : (int)ni;
-    // one block per CU at a time (LDS): aim at two rounds of blocks over the 256 CUs, but keep >= 3 items per block so
-    // the prefetch has something to overlap with and the per-block set-up is amortised
-    const long long groups = (long long)N * (C / CG);
-    long long s = (512 + groups - 1) / groups;
-    if (s > ni / 3) s = ni / 3;
-    if (s < 1) s = 1;
-    *nseg = (int)s;
-}
+static_assert(CG == DW_CG && MAXB == DW_MAXB && MAXG == DW_MAXB && TLX == DW_TLX && TLY == DW_TLY && TLY3 == DW_TLY_HALF && BUF_OOB == DW_BUF_OOB,
+              "dw_select.h plans these kernels' work items");
+static_assert(LDS_BYTES == DW_FWD_LDS && WTBYTES == DW_FWD_LDS_PER_BRANCH && WG_LDS == DW_WGRAD_LDS && WG3_LDS == DW_WGRAD_MULTI_LDS,
+              "dw_select.h states these kernels' dynamic LDS");
 
 static LpGeom lp_geom(const kd_dw_desc *d)
 {
@@ -926,91 +899,45 @@ static LpGeom lp_geom(const kd_dw_desc *d)
     g.Ly = (d->H + d->dil - 1) / d->dil;
     g.Lx = (d->W + d->dil - 1) / d->dil;
     g.rpi = d->dil * d->dil * g.Ly * g.Lx;
-    g.plane = (long long)kd_internal_lattice_rows(d->N, d->H, d->W, d->dil) * CG;
+    g.plane = dw_lattice_rows(d->N, d->H, d->W, d->dil) * CG;
     return g;
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize, once per kernel
+static int reserve_lds(const void *fn, bool &done, int lds, const char *who)
+{
+    if (!done) {
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
+            kd_set_error("%s: cannot reserve %d B of LDS", who, lds);
+            return KD_ERR_HIP;
+        }
+        done = true;
+    }
+    return KD_OK;
 }
 
 }  // namespace
 
-// Rows per plane of the lattice-planar layout (a multiple of 256: the 1x1 convs' M tile), 0 if the shape has none.
-long long kd_internal_lattice_rows(int N, int H, int W, int dil)
-{
-    if (N < 1 || H < 1 || W < 1 || dil < 1) return 0;
-    const long long Ly = (H + dil - 1) / dil, Lx = (W + dil - 1) / dil;
-    const long long rows = (long long)N * dil * dil * Ly * Lx;
-    return (rows + 255) / 256 * 256;
-}
+// The launchers below fill the params of the kernel the selection (dw_select.h) names and launch it on the grid it gives; what
+// is eligible was decided there.
 
-// Can the fan-out / summing / multi-gradient launches of `nb` branches run on lattice-planar intermediates?  (The matrix-core
-// kernels' own conditions, plus: no work item of the fan-out may be empty while its padded cells exist -- they are zeroed by the
-// item that owns them -- and a plane's rows must stay inside 32-bit buffer offsets.)
-int kd_internal_dw_lattice_ok(const kd_dw_desc *d, int nb)
+// !c.fan: ys[0] = sum_{b < c.nb} dwconv(xs[b], ws[b]);  c.fan: ys[b] = dwconv(xs[0], ws[b]) for b < c.nb.
+// c.lp: the nb-side tensors -- the fan-out's outputs, the sum's inputs -- are lattice-planar.
+int kd_internal_dw_mfma_fwd_n(const DwSel &c, const kd_dw_desc *d, const void *const *xs, const float *const *ws, void *const *ys, hipStream_t s)
 {
-    if (nb < 2 || nb > MAXB || d->dtype != KD_BF16 || d->k != 9 || d->C % CG != 0 || d->ldx % 8 != 0) return 0;
-    static int enabled = -1;
-    if (enabled < 0) {
-        const char *e = getenv("KDCC_DW_MFMA"), *l = getenv("KDCC_DW_LATTICE");   // A/B hooks: 0 = NHWC intermediates
-        enabled = !(e && e[0] == '0') && !(l && l[0] == '0');
-    }
-    if (!enabled) return 0;
-    const LpGeom g = lp_geom(d);
-    if ((long long)g.rpi * CG * 2 >= (long long)BUF_OOB || g.plane * (d->C / CG) > 0x7fffffffLL) return 0;
-    if ((long long)d->H * d->W * d->ldx * 2 >= (long long)BUF_OOB) return 0;
-    const int ry_last = g.Ly - (g.Ly - 1) / TLY * TLY, rx_last = g.Lx - (g.Lx - 1) / TLX * TLX;   // padded extent of the last tile row / column
-    const bool short_y = (d->H % d->dil) != 0, short_x = (d->W % d->dil) != 0;                     // some classes are one row / column shorter
-    if ((short_y && ry_last < 2) || (short_x && rx_last < 2)) return 0;
-    return 1;
-}
-
-// fan == 0: ys[0] = sum_{b < nb} dwconv(xs[b], ws[b]);  fan != 0: ys[b] = dwconv(xs[0], ws[b]) for b < nb -- on the matrix
-// cores.  Returns 1 if the MFMA path took the call, 0 if the shape is not eligible (caller falls back to the register kernel,
-// one launch per term), < 0 on a launch error.
-// lp != 0 (nb >= 2, kd_internal_dw_lattice_ok): the nb-side tensors -- the fan-out's outputs, the sum's inputs -- are lattice-planar.
-int kd_internal_dw_mfma_fwd_n(const kd_dw_desc *d, int nb, int fan, const void *const *xs, const float *const *ws, void *const *ys,
-                              const float *bias, const kd_dw_epilogue *ep, hipStream_t s, int lp)
-{
-    if (nb < 1 || nb > MAXB) return 0;
-    if (lp && !kd_internal_dw_lattice_ok(d, nb)) return 0;
-    if (nb == 1) fan = 0;
-    if (d->dtype != KD_BF16 || d->k != 9 || d->C % CG != 0 || d->ldx % 8 != 0 || d->ldy % 8 != 0) return 0;
-    for (int b = 0; b < nb; ++b) {
-        if (!ws[b]) return 0;
-        if (!(fan ? ys[b] && kd_aligned16(ys[b]) : xs[b] && kd_aligned16(xs[b]))) return 0;
-    }
-    if (!xs[0] || !ys[0] || !kd_aligned16(xs[0]) || !kd_aligned16(ys[0])) return 0;
-    if ((long long)d->H * d->W * d->ldx * 2 >= (long long)BUF_OOB) return 0;   // buffer-load offsets are 32-bit per image
-    // Calls with a bias or an epilogue stay on the register kernel: their extra operands are read per pixel in 32-B
-    // (16-channel) pieces here, which the memory system serves at about a third of the rate of the register kernel's
-    // 128-B-per-pixel rows (measured: 1.22 vs 0.99 ms at 4096 channels, mask + residual, 2 images).
-    if (bias || (ep && (ep->res_pre || ep->mask || ep->res_post))) return 0;
-    if (fan && nb >= 2 && !lp) {     // round 6: the fan-out on the lone-wave kernel (dwconv_lw.hip) where it applies
-        const int took = kd_internal_dw_lw_fanout(d, nb, xs[0], ws, ys, s);
-        if (took != 0) return took;
-    }
+    const int nb = c.nb, fan = c.fan, lp = c.lp;
     DwMfmaParams p;
-    static int enabled = -1;
-    if (enabled < 0) {
-        const char *e = getenv("KDCC_DW_MFMA");   // A/B hook: 0 = always use the register kernel
-        enabled = !(e && e[0] == '0');
-    }
-    if (!enabled) return 0;
     p.x = (const bf16_t *)xs[0]; p.w = ws[0]; p.y = (bf16_t *)ys[0];
     for (int b = 1; b < MAXB; ++b) {
         p.xs[b - 1] = (const bf16_t *)(!fan && b < nb ? xs[b] : xs[0]);
         p.ys[b - 1] = (bf16_t *)(fan && b < nb ? ys[b] : ys[0]);
         p.ws[b - 1] = b < nb ? ws[b] : ws[0];
     }
-    { static int dbg = -1; if (dbg < 0) dbg = KD_TUNING_ENV_INT("KDCC_DW_DBG"); p.dbg = dbg; }   // phase ablations: tuning build only
-    p.N = d->N; p.H = d->H; p.W = d->W; p.C = d->C; p.dil = d->dil; p.ldx = d->ldx; p.ldy = d->ldy;
+    p.dbg = dw_switches().dbg;   // phase ablations: tuning build only
+    // (ldy: the lattice fan-out has no NHWC output; its cells are dense)
+    p.N = d->N; p.H = d->H; p.W = d->W; p.C = d->C; p.dil = d->dil; p.ldx = d->ldx; p.ldy = fan && lp ? d->C : d->ldy;
     p.lp = lp_geom(d);
-    // (a second, independent workgroup per CU on half-height items was built and measured slower -- the Toeplitz rebuilds multiply:
-    // profiles/r05_dw_anatomy.md, commit dc356ad)
-    dw_mfma_split(d->N, d->C, d->H, d->W, d->dil, &p.nty, &p.ntx, &p.nitems, &p.nseg);
-    p.ncg = d->C / CG;
-    if (p.nitems <= 0) return 0;
-    const long long blocks = (long long)d->N * p.ncg * p.nseg;
-    if (blocks > 0x7fffffffLL || (long long)d->N * d->H * d->W > 0x7fffffffLL) return 0;
-    const int lds = LDS_BYTES + (nb - 1) * WTBYTES;
+    p.nty = c.nty; p.ntx = c.ntx; p.nitems = c.nitems; p.nseg = c.nseg; p.ncg = c.ncg;
     typedef void (*kern_t)(DwMfmaParams);
     const kern_t fn = nb == 1 ? dw_mfma_fwd_kernel<1, false>
                     : lp ? (nb == 2 ? (fan ? dw_mfma_fwd_kernel<2, true, true> : dw_mfma_fwd_kernel<2, false, true>)
@@ -1018,135 +945,48 @@ int kd_internal_dw_mfma_fwd_n(const kd_dw_desc *d, int nb, int fan, const void *
                     : nb == 2 ? (fan ? dw_mfma_fwd_kernel<2, true> : dw_mfma_fwd_kernel<2, false>)
                               : (fan ? dw_mfma_fwd_kernel<3, true> : dw_mfma_fwd_kernel<3, false>);
     static bool attr_set[2][2][MAXB + 1] = {};
-    if (!attr_set[lp ? 1 : 0][fan ? 1 : 0][nb]) {
-        if (hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            kd_set_error("kd_dwconv_fwd: cannot reserve %d B of LDS", lds);
-            return KD_ERR_HIP;
-        }
-        attr_set[lp ? 1 : 0][fan ? 1 : 0][nb] = true;
-    }
-    KD_NOTE_KERNEL(nb == 1 ? "dw_mfma_fwd_kernel<1,false>"
-                   : lp ? (nb == 2 ? (fan ? "dw_mfma_fwd_kernel<2,true,lattice>" : "dw_mfma_fwd_kernel<2,false,lattice>")
-                                   : (fan ? "dw_mfma_fwd_kernel<3,true,lattice>" : "dw_mfma_fwd_kernel<3,false,lattice>"))
-                   : nb == 2 ? (fan ? "dw_mfma_fwd_kernel<2,true>" : "dw_mfma_fwd_kernel<2,false>")
-                             : (fan ? "dw_mfma_fwd_kernel<3,true>" : "dw_mfma_fwd_kernel<3,false>"));
-    hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(NT), lds, s, p);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        kd_set_error("kd_dwconv_fwd(mfma): launch failed: %s", hipGetErrorString(err));
-        return KD_ERR_HIP;
-    }
-    return 1;
+    if (int rc = reserve_lds((const void *)fn, attr_set[lp ? 1 : 0][fan ? 1 : 0][nb], c.lds, "kd_dwconv_fwd")) return rc;
+    KD_NOTE_KERNEL(dw_kernel_name(c.kernel));
+    hipLaunchKernelGGL(fn, dim3((unsigned)c.blocks), dim3(NT), c.lds, s, p);
+    KD_CHECK_LAUNCH("kd_dwconv_fwd(mfma)");
+    return KD_OK;
 }
 
-int kd_internal_dw_mfma_fwd(const kd_dw_desc *d, const void *x, const float *w_taps, const float *bias,
-                            const kd_dw_epilogue *ep, void *y, hipStream_t s)
+// Partial sums go to `part`, c.slabs slabs of [81][C] fp32 (the caller reduces them).
+int kd_internal_dw_mfma_wgrad(const DwSel &c, const kd_dw_desc *d, const void *x, const void *dy, int ld_dy, float *part, hipStream_t s)
 {
-    return kd_internal_dw_mfma_fwd_n(d, 1, 0, &x, &w_taps, &y, bias, ep, s, 0);
-}
-
-static bool dw_mfma_wgrad_eligible(const kd_dw_desc *d, const void *x, const void *dy, int ld_dy)
-{
-    if (d->dtype != KD_BF16 || d->k != 9 || d->C % CG != 0 || d->ldx % 8 != 0 || ld_dy % 8 != 0) return false;
-    if ((x && !kd_aligned16(x)) || (dy && !kd_aligned16(dy))) return false;
-    if ((long long)d->N * d->H * d->W > 0x7fffffffLL) return false;
-    if ((long long)d->H * d->W * (d->ldx > ld_dy ? d->ldx : ld_dy) * 2 >= (long long)BUF_OOB) return false;   // 32-bit buffer offsets
-    static int enabled = -1;
-    if (enabled < 0) {
-        const char *e = getenv("KDCC_DW_MFMA");
-        enabled = !(e && e[0] == '0');
-    }
-    return enabled != 0;
-}
-
-// Slabs of [81][C] fp32 partial sums the MFMA weight-gradient path writes (0 = path not eligible).
-int kd_internal_dw_mfma_wgrad_slabs(const kd_dw_desc *d)
-{
-    if (!dw_mfma_wgrad_eligible(d, nullptr, nullptr, 8)) return 0;
-    int nty, ntx, nitems, nseg;
-    dw_mfma_split(d->N, d->C, d->H, d->W, d->dil, &nty, &ntx, &nitems, &nseg);
-    return nitems > 0 ? d->N * nseg : 0;
-}
-
-// 1 = partial sums written to `part` (caller reduces the slabs), 0 = not eligible, < 0 = error.
-int kd_internal_dw_mfma_wgrad(const kd_dw_desc *d, const void *x, const void *dy, int ld_dy, float *part, hipStream_t s)
-{
-    if (!dw_mfma_wgrad_eligible(d, x, dy, ld_dy)) return 0;
     DwWgMfmaParams p;
     p.x = (const bf16_t *)x; p.g = (const bf16_t *)dy; p.part = part;
     p.N = d->N; p.H = d->H; p.W = d->W; p.C = d->C; p.dil = d->dil; p.ldx = d->ldx; p.ldg = ld_dy;
-    dw_mfma_split(d->N, d->C, d->H, d->W, d->dil, &p.nty, &p.ntx, &p.nitems, &p.nseg);
-    p.ncg = d->C / CG;
-    if (p.nitems <= 0) return 0;
-    const long long blocks = (long long)d->N * p.ncg * p.nseg;
-    if (blocks > 0x7fffffffLL) return 0;
+    p.nty = c.nty; p.ntx = c.ntx; p.nitems = c.nitems; p.nseg = c.nseg; p.ncg = c.ncg;
     static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void *)dw_mfma_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WG_LDS) !=
-            hipSuccess) {
-            kd_set_error("kd_dwconv_wgrad: cannot reserve %d B of LDS", WG_LDS);
-            return KD_ERR_HIP;
-        }
-        attr_set = true;
-    }
-    KD_NOTE_KERNEL("dw_mfma_wgrad_kernel");
-    hipLaunchKernelGGL(dw_mfma_wgrad_kernel, dim3((unsigned)blocks), dim3(NTW), WG_LDS, s, p);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        kd_set_error("kd_dwconv_wgrad(mfma): launch failed: %s", hipGetErrorString(err));
-        return KD_ERR_HIP;
-    }
-    return 1;
+    if (int rc = reserve_lds((const void *)dw_mfma_wgrad_kernel, attr_set, c.lds, "kd_dwconv_wgrad")) return rc;
+    KD_NOTE_KERNEL(dw_kernel_name(c.kernel));
+    hipLaunchKernelGGL(dw_mfma_wgrad_kernel, dim3((unsigned)c.blocks), dim3(NTW), c.lds, s, p);
+    KD_CHECK_LAUNCH("kd_dwconv_wgrad(mfma)");
+    return KD_OK;
 }
 
 // ---- several weight gradients over one input (kd_dwconv_wgrad_multi) -------------------------------------------------------
-// Slabs of [81][C] fp32 partial sums PER BRANCH the fused path writes (0 = not eligible: the caller runs one launch per branch).
-int kd_internal_dw_mfma_wgrad_multi_slabs(const kd_dw_desc *d, int n)
+// Partial sums of every branch go to `part` ([branch][c.slabs][81][C]).  c.lp: the gradients dys[] are lattice-planar (ld_dy = C).
+int kd_internal_dw_mfma_wgrad_multi(const DwSel &c, const kd_dw_desc *d, const void *x, const void *const *dys, int ld_dy, float *part, hipStream_t s)
 {
-    if (n < 2 || n > MAXG || !dw_mfma_wgrad_eligible(d, nullptr, nullptr, 8)) return 0;
-    int nty, ntx, nitems, nseg;
-    dw_mfma_split3(d->N, d->C, d->H, d->W, d->dil, &nty, &ntx, &nitems, &nseg);
-    return nitems > 0 ? d->N * nseg : 0;
-}
-
-// 1 = partial sums of every branch written to `part` ([branch][slab][81][C]), 0 = not eligible, < 0 = error.
-// lp != 0: the gradients dys[] are lattice-planar (ld_dy is ignored)
-int kd_internal_dw_mfma_wgrad_multi(const kd_dw_desc *d, int n, const void *x, const void *const *dys, int ld_dy, float *part, hipStream_t s, int lp)
-{
-    if (n < 2 || n > MAXG) return 0;
-    if (lp) { if (!kd_internal_dw_lattice_ok(d, n)) return 0; ld_dy = d->C; }
-    for (int b = 0; b < n; ++b)
-        if (!dw_mfma_wgrad_eligible(d, x, dys[b], ld_dy)) return 0;
+    const int n = c.nb, lp = c.lp;
     DwWgMultiParams p;
     p.x = (const bf16_t *)x;
     for (int b = 0; b < MAXG; ++b) p.g[b] = (const bf16_t *)dys[b < n ? b : 0];
     p.part = part;
     p.N = d->N; p.H = d->H; p.W = d->W; p.C = d->C; p.dil = d->dil; p.ldx = d->ldx; p.ldg = ld_dy;
     p.lp = lp_geom(d);
-    dw_mfma_split3(d->N, d->C, d->H, d->W, d->dil, &p.nty, &p.ntx, &p.nitems, &p.nseg);
-    p.ncg = d->C / CG;
-    p.nslabs = d->N * p.nseg;
-    if (p.nitems <= 0) return 0;
-    const long long blocks = (long long)d->N * p.ncg * p.nseg;
-    if (blocks > 0x7fffffffLL) return 0;
+    p.nty = c.nty; p.ntx = c.ntx; p.nitems = c.nitems; p.nseg = c.nseg; p.ncg = c.ncg;
+    p.nslabs = c.slabs;
     typedef void (*kern_t)(DwWgMultiParams);
     const kern_t fn = lp ? (n == 2 ? dw_mfma_wgrad_multi_kernel<2, true> : dw_mfma_wgrad_multi_kernel<3, true>)
                          : (n == 2 ? dw_mfma_wgrad_multi_kernel<2> : dw_mfma_wgrad_multi_kernel<3>);
     static bool attr_set[2][MAXG + 1] = {};
-    if (!attr_set[lp ? 1 : 0][n]) {
-        if (hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, WG3_LDS) != hipSuccess) {
-            kd_set_error("kd_dwconv_wgrad_multi: cannot reserve %d B of LDS", WG3_LDS);
-            return KD_ERR_HIP;
-        }
-        attr_set[lp ? 1 : 0][n] = true;
-    }
-    KD_NOTE_KERNEL(lp ? (n == 2 ? "dw_mfma_wgrad_multi_kernel<2,lattice>" : "dw_mfma_wgrad_multi_kernel<3,lattice>")
-                      : (n == 2 ? "dw_mfma_wgrad_multi_kernel<2>" : "dw_mfma_wgrad_multi_kernel<3>"));
-    hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(NTW), WG3_LDS, s, p);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        kd_set_error("kd_dwconv_wgrad_multi(mfma): launch failed: %s", hipGetErrorString(err));
-        return KD_ERR_HIP;
-    }
-    return 1;
+    if (int rc = reserve_lds((const void *)fn, attr_set[lp ? 1 : 0][n], c.lds, "kd_dwconv_wgrad_multi")) return rc;
+    KD_NOTE_KERNEL(dw_kernel_name(c.kernel));
+    hipLaunchKernelGGL(fn, dim3((unsigned)c.blocks), dim3(NTW), c.lds, s, p);
+    KD_CHECK_LAUNCH("kd_dwconv_wgrad_multi(mfma)");
+    return KD_OK;
 }

@@ -339,17 +339,43 @@ def _dw_desc(x, k, pad, dil, y=None):
     return DwDesc(dt_of(x), N, H, W, Cc, k, pad, dil, nhwc_ld(x), nhwc_ld(y) if y is not None else Cc)
 
 
+# The checks the depthwise wrappers share (`who` names the public function in the message)
+def _dw_taps(who, w_taps, k, Cc):
+    for w in w_taps:
+        if tuple(w.shape) != (k * k, Cc) or w.dtype != torch.float32 or not w.is_contiguous():
+            raise ValueError(f"{who}: w_taps must be contiguous fp32 [k*k][C]")
+
+
+def _dw_grads(who, dws, k, Cc):
+    for dw in dws:
+        if dw.dtype != torch.float32 or dw.numel() != Cc * k * k or not dw.is_contiguous():
+            raise ValueError(f"{who}: dw must be contiguous fp32 (C,1,k,k)")
+
+
+def _dw_out(who, out, shape, like):
+    """`out`, or a new tensor, as an NHWC view of `shape` in `like`'s dtype."""
+    if out is None:
+        out = torch.empty(shape, dtype=like.dtype, device=like.device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != like.dtype:
+        raise ValueError(f"{who}: bad output view")
+    return out
+
+
+def _ptrs(ts):
+    return (C.c_void_p * len(ts))(*[_ptr(t) for t in ts])
+
+
+def _lattice_t(ts):
+    return [t.t for t in ts]
+
+
 def dwconv(x, w_taps, k, pad, dil, bias=None, out=None, res_pre=None, mask=None, mask_scale=None, res_post=None):
     _need_cuda(x, w_taps, bias, out, res_pre, mask, mask_scale, res_post)
     if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()):
         bias = bias.detach().float().contiguous()      # the kernel reads fp32 (C) (a bf16 module's parameter is not)
     N, H, W, Cc = x.shape
-    if tuple(w_taps.shape) != (k * k, Cc) or w_taps.dtype != torch.float32 or not w_taps.is_contiguous():
-        raise ValueError("dwconv: w_taps must be contiguous fp32 [k*k][C]")
-    if out is None:
-        out = torch.empty((N, H, W, Cc), dtype=x.dtype, device=x.device)
-    if tuple(out.shape) != (N, H, W, Cc) or out.dtype != x.dtype:
-        raise ValueError("dwconv: bad output view")
+    _dw_taps("dwconv", [w_taps], k, Cc)
+    out = _dw_out("dwconv", out, (N, H, W, Cc), x)
     d = _dw_desc(x, k, pad, dil, out)
     ep = None
     if res_pre is not None or mask is not None or res_post is not None:
@@ -386,32 +412,61 @@ def scale_by_device_scalar_(x, scale):
     return x
 
 
+def _dwconv_sum(xs, w_taps, k, pad, dil, out, lattice):
+    """dwconv_sum and its lattice twin: the inputs are NHWC views, or Lattice tensors whose cells are dense (pixel stride C)."""
+    who, tag = ("dwconv_sum_lattice", " [lattice]") if lattice else ("dwconv_sum", "")
+    N, H, W, Cc = xs[0].shape
+    _need_cuda(*(_lattice_t(xs) if lattice else xs), *w_taps, out)
+    if not lattice:
+        ld = nhwc_ld(xs[0])
+        if any(tuple(x.shape) != (N, H, W, Cc) or x.dtype != xs[0].dtype or nhwc_ld(x) != ld for x in xs):
+            raise ValueError("dwconv_sum: inputs must share shape, dtype and pixel stride")
+    _dw_taps(who, w_taps, k, Cc)
+    out = _dw_out(who, out, (N, H, W, Cc), xs[0])
+    d = DwDesc(dt_of(out), N, H, W, Cc, k, pad, dil, Cc if lattice else nhwc_ld(xs[0]), nhwc_ld(out))
+    n = len(xs)
+    entry = "kd_dwconv_fwd_sum_lattice" if lattice else "kd_dwconv_fwd_sum"
+    e0 = _prof_start()
+    check(getattr(_lib.lib(), entry)(C.byref(d), n, _ptrs(_lattice_t(xs) if lattice else xs), _ptrs(w_taps), _ptr(out), stream_ptr()), entry)
+    _prof_stop(e0, "depthwise", out.numel() * out.element_size() * (1 + n) if lattice else _nbytes(out, *xs),
+               f"dw sum of {n} {k}x{k} d{dil} {H}x{W} C{Cc}{tag}")
+    return out
+
+
 def dwconv_sum(xs, w_taps, k, pad, dil, out=None):
     """out = sum_i dwconv(xs[i], w_taps[i]): the input gradient of a tensor that feeds several depthwise convs of one geometry
     (deeplabv3.py:64-75, the ASPP input under its replaced branches), summed inside one launch where the shape allows."""
     xs, w_taps = list(xs), list(w_taps)
     if not xs or len(xs) != len(w_taps):
         raise ValueError("dwconv_sum: need as many tap tables as inputs")
-    _need_cuda(*xs, *w_taps, out)
-    N, H, W, Cc = xs[0].shape
-    ld = nhwc_ld(xs[0])
-    for x, w in zip(xs, w_taps):
-        if tuple(x.shape) != (N, H, W, Cc) or x.dtype != xs[0].dtype or nhwc_ld(x) != ld:
-            raise ValueError("dwconv_sum: inputs must share shape, dtype and pixel stride")
-        if tuple(w.shape) != (k * k, Cc) or w.dtype != torch.float32 or not w.is_contiguous():
-            raise ValueError("dwconv_sum: w_taps must be contiguous fp32 [k*k][C]")
-    if out is None:
-        out = torch.empty((N, H, W, Cc), dtype=xs[0].dtype, device=xs[0].device)
-    if tuple(out.shape) != (N, H, W, Cc) or out.dtype != xs[0].dtype:
-        raise ValueError("dwconv_sum: bad output view")
-    d = _dw_desc(xs[0], k, pad, dil, out)
-    n = len(xs)
-    xp = (C.c_void_p * n)(*[_ptr(x) for x in xs])
-    wp = (C.c_void_p * n)(*[_ptr(w) for w in w_taps])
+    return _dwconv_sum(xs, w_taps, k, pad, dil, out, False)
+
+
+def _dwconv_fanout(x, w_taps, k, pad, dil, outs, lattice):
+    """dwconv_fanout and its lattice twin: the outputs are NHWC views of one pixel stride, or Lattice tensors."""
+    who, tag = ("dwconv_fanout_lattice", " [lattice]") if lattice else ("dwconv_fanout", "")
+    N, H, W, Cc = x.shape
+    _dw_taps(who, w_taps, k, Cc)
+    if outs is None:
+        outs = [Lattice(N, H, W, Cc, dil, x.dtype, x.device) if lattice else torch.empty((N, H, W, Cc), dtype=x.dtype, device=x.device) for _ in w_taps]
+    outs = list(outs)
+    if lattice:
+        if len(outs) != len(w_taps) or any(o.shape != (N, H, W, Cc) or o.dil != dil or o.dtype != x.dtype for o in outs):
+            raise ValueError("dwconv_fanout_lattice: need one matching Lattice per tap table")
+    else:
+        if len(outs) != len(w_taps):
+            raise ValueError("dwconv_fanout: need one output per tap table")
+        ld = nhwc_ld(outs[0])
+        if any(tuple(o.shape) != (N, H, W, Cc) or o.dtype != x.dtype or nhwc_ld(o) != ld for o in outs):
+            raise ValueError("dwconv_fanout: outputs must share shape, dtype and pixel stride")
+    d = _dw_desc(x, k, pad, dil, None if lattice else outs[0])
+    n = len(outs)
+    entry = "kd_dwconv_fwd_fanout_lattice" if lattice else "kd_dwconv_fwd_fanout"
     e0 = _prof_start()
-    check(_lib.lib().kd_dwconv_fwd_sum(C.byref(d), n, xp, wp, _ptr(out), stream_ptr()), "kd_dwconv_fwd_sum")
-    _prof_stop(e0, "depthwise", _nbytes(out, *xs), f"dw sum of {n} {k}x{k} d{dil} {H}x{W} C{Cc}")
-    return out
+    check(getattr(_lib.lib(), entry)(C.byref(d), n, _ptr(x), _ptrs(w_taps), _ptrs(_lattice_t(outs) if lattice else outs), stream_ptr()), entry)
+    _prof_stop(e0, "depthwise", x.numel() * x.element_size() * (1 + n) if lattice else _nbytes(x, *outs),
+               f"dw fan-out of {n} {k}x{k} d{dil} {H}x{W} C{Cc}{tag}")
+    return outs
 
 
 def dwconv_fanout(x, w_taps, k, pad, dil, outs=None):
@@ -421,27 +476,7 @@ def dwconv_fanout(x, w_taps, k, pad, dil, outs=None):
     if not w_taps:
         raise ValueError("dwconv_fanout: no tap tables")
     _need_cuda(x, *w_taps, *(outs or []))
-    N, H, W, Cc = x.shape
-    for w in w_taps:
-        if tuple(w.shape) != (k * k, Cc) or w.dtype != torch.float32 or not w.is_contiguous():
-            raise ValueError("dwconv_fanout: w_taps must be contiguous fp32 [k*k][C]")
-    if outs is None:
-        outs = [torch.empty((N, H, W, Cc), dtype=x.dtype, device=x.device) for _ in w_taps]
-    outs = list(outs)
-    if len(outs) != len(w_taps):
-        raise ValueError("dwconv_fanout: need one output per tap table")
-    ld = nhwc_ld(outs[0])
-    for o in outs:
-        if tuple(o.shape) != (N, H, W, Cc) or o.dtype != x.dtype or nhwc_ld(o) != ld:
-            raise ValueError("dwconv_fanout: outputs must share shape, dtype and pixel stride")
-    d = _dw_desc(x, k, pad, dil, outs[0])
-    n = len(outs)
-    wp = (C.c_void_p * n)(*[_ptr(w) for w in w_taps])
-    yp = (C.c_void_p * n)(*[_ptr(o) for o in outs])
-    e0 = _prof_start()
-    check(_lib.lib().kd_dwconv_fwd_fanout(C.byref(d), n, _ptr(x), wp, yp, stream_ptr()), "kd_dwconv_fwd_fanout")
-    _prof_stop(e0, "depthwise", _nbytes(x, *outs), f"dw fan-out of {n} {k}x{k} d{dil} {H}x{W} C{Cc}")
-    return outs
+    return _dwconv_fanout(x, w_taps, k, pad, dil, outs, False)
 
 
 def dwconv_wgrad(x, dy, dw, k, pad, dil, accumulate=False, workspace=None):
@@ -449,8 +484,7 @@ def dwconv_wgrad(x, dy, dw, k, pad, dil, accumulate=False, workspace=None):
     N, H, W, Cc = x.shape
     if tuple(dy.shape) != (N, H, W, Cc) or dy.dtype != x.dtype:
         raise ValueError("dwconv_wgrad: x / dy mismatch")
-    if dw.dtype != torch.float32 or dw.numel() != Cc * k * k or not dw.is_contiguous():
-        raise ValueError("dwconv_wgrad: dw must be contiguous fp32 (C,1,k,k)")
+    _dw_grads("dwconv_wgrad", [dw], k, Cc)
     d = _dw_desc(x, k, pad, dil)
     need = _lib.lib().kd_dwconv_wgrad_workspace(C.byref(d))
     if workspace is None or workspace.numel() * workspace.element_size() < need:
@@ -462,6 +496,27 @@ def dwconv_wgrad(x, dy, dw, k, pad, dil, accumulate=False, workspace=None):
     return dw
 
 
+def _dwconv_wgrad_multi(x, dys, dws, k, pad, dil, accumulate, lattice):
+    """dwconv_wgrad_multi and its lattice twin, once the gradients dys (NHWC views of one pixel stride, or Lattice tensors) are checked."""
+    who, tag = ("dwconv_wgrad_multi_lattice", " [lattice]") if lattice else ("dwconv_wgrad_multi", "")
+    N, H, W, Cc = x.shape
+    _dw_grads(who, dws, k, Cc)
+    d = _dw_desc(x, k, pad, dil)
+    n = len(dys)
+    need = _lib.lib().kd_dwconv_wgrad_multi_workspace(C.byref(d), n)
+    workspace = _ws(need, x.device)
+    yp, wp = _ptrs(_lattice_t(dys) if lattice else dys), _ptrs(dws)
+    e0 = _prof_start()
+    if lattice:
+        rc = _lib.lib().kd_dwconv_wgrad_multi_lattice(C.byref(d), n, _ptr(x), yp, wp, int(accumulate), _ptr(workspace), need, stream_ptr())
+    else:
+        rc = _lib.lib().kd_dwconv_wgrad_multi(C.byref(d), n, _ptr(x), yp, nhwc_ld(dys[0]), wp, int(accumulate), _ptr(workspace), need, stream_ptr())
+    check(rc, "kd_" + who)
+    _prof_stop(e0, "depthwise", x.numel() * x.element_size() * (1 + n) if lattice else _nbytes(x, *dys),
+               f"dw wgrad of {n} {k}x{k} d{dil} {H}x{W} C{Cc}{tag}")
+    return dws
+
+
 def dwconv_wgrad_multi(x, dys, dws, k, pad, dil, accumulate=False):
     """dws[i] = weight gradient of dwconv(x, .) given dys[i]: several depthwise convs of one geometry reading the same tensor
     (deeplabv3.py:71-75, the replaced ASPP branches); one launch for two or three branches where the shape allows."""
@@ -471,22 +526,9 @@ def dwconv_wgrad_multi(x, dys, dws, k, pad, dil, accumulate=False):
     _need_cuda(x, *dys, *dws)
     N, H, W, Cc = x.shape
     ld = nhwc_ld(dys[0])
-    for dy, dw in zip(dys, dws):
-        if tuple(dy.shape) != (N, H, W, Cc) or dy.dtype != x.dtype or nhwc_ld(dy) != ld:
-            raise ValueError("dwconv_wgrad_multi: every dy must match x's shape / dtype and share one pixel stride")
-        if dw.dtype != torch.float32 or dw.numel() != Cc * k * k or not dw.is_contiguous():
-            raise ValueError("dwconv_wgrad_multi: dw must be contiguous fp32 (C,1,k,k)")
-    d = _dw_desc(x, k, pad, dil)
-    n = len(dys)
-    need = _lib.lib().kd_dwconv_wgrad_multi_workspace(C.byref(d), n)
-    workspace = _ws(need, x.device)
-    yp = (C.c_void_p * n)(*[_ptr(t) for t in dys])
-    wp = (C.c_void_p * n)(*[_ptr(t) for t in dws])
-    e0 = _prof_start()
-    check(_lib.lib().kd_dwconv_wgrad_multi(C.byref(d), n, _ptr(x), yp, ld, wp, int(accumulate), _ptr(workspace), need, stream_ptr()),
-          "kd_dwconv_wgrad_multi")
-    _prof_stop(e0, "depthwise", _nbytes(x, *dys), f"dw wgrad of {n} {k}x{k} d{dil} {H}x{W} C{Cc}")
-    return dws
+    if any(tuple(dy.shape) != (N, H, W, Cc) or dy.dtype != x.dtype or nhwc_ld(dy) != ld for dy in dys):
+        raise ValueError("dwconv_wgrad_multi: every dy must match x's shape / dtype and share one pixel stride")
+    return _dwconv_wgrad_multi(x, dys, dws, k, pad, dil, accumulate, False)
 
 
 # ------------------------------------------------------------------ lattice-planar intermediates (include/kdcc.h)
@@ -566,23 +608,7 @@ def dwconv_fanout_lattice(x, w_taps, k, pad, dil, outs=None):
     """dwconv_fanout with lattice-planar outputs (n = 2, 3; dwconv_lattice_ok)."""
     w_taps = list(w_taps)
     _need_cuda(x, *w_taps)
-    N, H, W, Cc = x.shape
-    for w in w_taps:
-        if tuple(w.shape) != (k * k, Cc) or w.dtype != torch.float32 or not w.is_contiguous():
-            raise ValueError("dwconv_fanout_lattice: w_taps must be contiguous fp32 [k*k][C]")
-    if outs is None:
-        outs = [Lattice(N, H, W, Cc, dil, x.dtype, x.device) for _ in w_taps]
-    outs = list(outs)
-    if len(outs) != len(w_taps) or any(o.shape != (N, H, W, Cc) or o.dil != dil or o.dtype != x.dtype for o in outs):
-        raise ValueError("dwconv_fanout_lattice: need one matching Lattice per tap table")
-    d = _dw_desc(x, k, pad, dil)
-    n = len(outs)
-    wp = (C.c_void_p * n)(*[_ptr(w) for w in w_taps])
-    yp = (C.c_void_p * n)(*[_ptr(o.t) for o in outs])
-    e0 = _prof_start()
-    check(_lib.lib().kd_dwconv_fwd_fanout_lattice(C.byref(d), n, _ptr(x), wp, yp, stream_ptr()), "kd_dwconv_fwd_fanout_lattice")
-    _prof_stop(e0, "depthwise", x.numel() * x.element_size() * (1 + n), f"dw fan-out of {n} {k}x{k} d{dil} {H}x{W} C{Cc} [lattice]")
-    return outs
+    return _dwconv_fanout(x, w_taps, k, pad, dil, outs, True)
 
 
 def dwconv_sum_lattice(xs, w_taps, k, pad, dil, out=None):
@@ -590,23 +616,7 @@ def dwconv_sum_lattice(xs, w_taps, k, pad, dil, out=None):
     xs, w_taps = list(xs), list(w_taps)
     if len(xs) != len(w_taps) or not xs or any(not xs[0].same_geometry(x) for x in xs) or xs[0].dil != dil:
         raise ValueError("dwconv_sum_lattice: need matching Lattice inputs, one tap table each")
-    N, H, W, Cc = xs[0].shape
-    _need_cuda(*[x.t for x in xs], *w_taps, out)
-    for w in w_taps:
-        if tuple(w.shape) != (k * k, Cc) or w.dtype != torch.float32 or not w.is_contiguous():
-            raise ValueError("dwconv_sum_lattice: w_taps must be contiguous fp32 [k*k][C]")
-    if out is None:
-        out = torch.empty((N, H, W, Cc), dtype=xs[0].dtype, device=xs[0].device)
-    if tuple(out.shape) != (N, H, W, Cc) or out.dtype != xs[0].dtype:
-        raise ValueError("dwconv_sum_lattice: bad output view")
-    d = DwDesc(dt_of(out), N, H, W, Cc, k, pad, dil, Cc, nhwc_ld(out))
-    n = len(xs)
-    xp = (C.c_void_p * n)(*[_ptr(x.t) for x in xs])
-    wp = (C.c_void_p * n)(*[_ptr(w) for w in w_taps])
-    e0 = _prof_start()
-    check(_lib.lib().kd_dwconv_fwd_sum_lattice(C.byref(d), n, xp, wp, _ptr(out), stream_ptr()), "kd_dwconv_fwd_sum_lattice")
-    _prof_stop(e0, "depthwise", out.numel() * out.element_size() * (1 + n), f"dw sum of {n} {k}x{k} d{dil} {H}x{W} C{Cc} [lattice]")
-    return out
+    return _dwconv_sum(xs, w_taps, k, pad, dil, out, True)
 
 
 def dwconv_wgrad_multi_lattice(x, dys, dws, k, pad, dil, accumulate=False):
@@ -615,21 +625,8 @@ def dwconv_wgrad_multi_lattice(x, dys, dws, k, pad, dil, accumulate=False):
     N, H, W, Cc = x.shape
     if len(dys) != len(dws) or not dys or any(dy.shape != (N, H, W, Cc) or dy.dil != dil or dy.dtype != x.dtype for dy in dys):
         raise ValueError("dwconv_wgrad_multi_lattice: need one matching Lattice gradient per weight gradient")
-    _need_cuda(x, *[dy.t for dy in dys], *dws)
-    for dw in dws:
-        if dw.dtype != torch.float32 or dw.numel() != Cc * k * k or not dw.is_contiguous():
-            raise ValueError("dwconv_wgrad_multi_lattice: dw must be contiguous fp32 (C,1,k,k)")
-    d = _dw_desc(x, k, pad, dil)
-    n = len(dys)
-    need = _lib.lib().kd_dwconv_wgrad_multi_workspace(C.byref(d), n)
-    workspace = _ws(need, x.device)
-    yp = (C.c_void_p * n)(*[_ptr(t.t) for t in dys])
-    wp = (C.c_void_p * n)(*[_ptr(t) for t in dws])
-    e0 = _prof_start()
-    check(_lib.lib().kd_dwconv_wgrad_multi_lattice(C.byref(d), n, _ptr(x), yp, wp, int(accumulate), _ptr(workspace), need, stream_ptr()),
-          "kd_dwconv_wgrad_multi_lattice")
-    _prof_stop(e0, "depthwise", x.numel() * x.element_size() * (1 + n), f"dw wgrad of {n} {k}x{k} d{dil} {H}x{W} C{Cc} [lattice]")
-    return dws
+    _need_cuda(x, *_lattice_t(dys), *dws)
+    return _dwconv_wgrad_multi(x, dys, dws, k, pad, dil, accumulate, True)
 
 
 # ------------------------------------------------------------------------------ trunk plumbing

@@ -12,6 +12,8 @@ pytestmark = pytest.mark.gpu
 
 from oracle import oracle as orc  # noqa: E402
 
+import _dw_dispatch_cases as D  # noqa: E402
+
 
 @pytest.fixture(scope="module")
 def K():
@@ -497,41 +499,26 @@ def test_pw_wgrad(K, dt, shape):
     assert_close(dw.cpu().numpy(), 2 * ref, dt, "pw_wgrad accumulate")
 
 
-DW_CASES = [(2, 24, 32, 16, 9, 20, 5), (1, 8, 8, 16, 3, 1, 1), (1, 23, 37, 72, 9, 20, 5), (2, 6, 50, 8, 9, 20, 5),
-            # matrix-core path (bf16, C % 16 == 0): several lattice tiles with real halos, dil 1, ragged last tiles
-            (1, 140, 270, 32, 9, 20, 5), (1, 40, 70, 16, 9, 4, 1), (2, 64, 128, 48, 9, 20, 5)]
-
-
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
-@pytest.mark.parametrize("case", DW_CASES)
+@pytest.mark.parametrize("case", D.DW_CASES)
 def test_dwconv_fwd_dgrad_wgrad(K, dt, case):
     N, H, W, Cc, k, p, d = case
     x, w = q(rnd(N, Cc, H, W), dt), rnd(Cc, 1, k, k, scale=1.0 / k)
     gy = q(rnd(N, Cc, H, W), dt)
     wd = torch.from_numpy(w).cuda()
     y = K.dwconv(dev_nhwc(x, dt), K.pack_dw_weight(wd), k, p, d)
-    mfma = dt == "bf16" and k == 9 and Cc % 16 == 0    # the matrix-core kernels' domain (dwconv_mfma.hip)
-    selected("dw_mfma_fwd_kernel<1,false>" if mfma else f"dwconv_fwd_kernel<{dt}>", f"dw fwd {case} {dt}")
+    selected(D.fwd_kernel(dt, case), f"dw fwd {case} {dt}")
     assert_close(host_nchw(y), orc.conv2d_fwd(x, w, pad=p, dil=d, groups=Cc), dt, "dw fwd")
     gx = K.dwconv(dev_nhwc(gy, dt), K.pack_dw_weight(wd, flip=True), k, p, d)
     assert_close(host_nchw(gx), orc.conv2d_dgrad(gy, w, x.shape, pad=p, dil=d, groups=Cc), dt, "dw dgrad")
     dw = torch.zeros((Cc, 1, k, k), device="cuda")
     K.dwconv_wgrad(dev_nhwc(x, dt), dev_nhwc(gy, dt), dw, k, p, d)
-    selected("dw_mfma_wgrad_kernel" if mfma else f"dwconv_wgrad_kernel<{dt}>", f"dw wgrad {case} {dt}")
+    selected(D.wgrad_kernel(dt, case), f"dw wgrad {case} {dt}")
     assert_close(dw.cpu().numpy(), orc.conv2d_wgrad(x, gy, w.shape, pad=p, dil=d, groups=Cc), dt, "dw wgrad")
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
-@pytest.mark.parametrize("case", [
-    # N, H, W, C, k, pad, dil, inputs
-    (2, 24, 32, 16, 9, 20, 5, 3),        # one lattice tile per residue class (the ASPP shape in small)
-    (1, 140, 270, 32, 9, 20, 5, 3),      # several tiles with real halos, ragged last tiles
-    (1, 40, 70, 16, 9, 4, 1, 2),         # two inputs, dil 1
-    (2, 64, 128, 48, 9, 20, 5, 3),       # three channel groups
-    (1, 23, 37, 72, 9, 20, 5, 3),        # C % 16 != 0: register kernels chained through res_post
-    (1, 24, 32, 16, 9, 20, 5, 4),        # more inputs than one launch sums
-    (1, 8, 8, 16, 3, 1, 1, 2),           # 3x3
-])
+@pytest.mark.parametrize("case", D.SUM_CASES)
 def test_dwconv_sum(K, dt, case):
     """kd_dwconv_fwd_sum: the ASPP input gradient = sum of the branches' depthwise input gradients (deeplabv3.py:64-75),
     against the sum of the oracle's per-branch dgrads; bf16 sums in fp32 registers inside one launch (n <= 3)."""
@@ -541,8 +528,7 @@ def test_dwconv_sum(K, dt, case):
     ref = sum(orc.conv2d_dgrad(g, w, g.shape, pad=p, dil=d, groups=Cc) for g, w in zip(gs, ws))
     taps = [K.pack_dw_weight(torch.from_numpy(w).cuda(), flip=True) for w in ws]
     out = K.dwconv_sum([dev_nhwc(g, dt) for g in gs], taps, k, d * (k - 1) - p, d)
-    if dt == "bf16" and k == 9 and Cc % 16 == 0 and n <= 3:
-        selected(f"dw_mfma_fwd_kernel<{n},false>", f"dw sum {case}")
+    selected(D.sum_kernels(dt, case)[-1], f"dw sum {case}")
     assert_close(host_nchw(out), ref, dt, f"dw sum of {n}")
     if n <= 3:   # same numbers as the chained launches up to the rounding of the running bf16 sum
         run = None
@@ -552,16 +538,7 @@ def test_dwconv_sum(K, dt, case):
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
-@pytest.mark.parametrize("case", [
-    (2, 24, 32, 16, 9, 20, 5, 3),        # one half-height tile pair per residue class (the ASPP shape in small)
-    (1, 140, 270, 32, 9, 20, 5, 3),      # several tiles in both directions with real halos, ragged last tiles
-    (1, 40, 70, 16, 9, 4, 1, 2),         # two branches, dil 1: four row tiles, two column tiles
-    (2, 64, 128, 48, 9, 20, 5, 3),       # three channel groups
-    (1, 67, 33, 16, 9, 20, 5, 3),        # 14 lattice rows: a 13-row and a 1-row tile (fewer rows than fetch slots)
-    (1, 23, 37, 72, 9, 20, 5, 3),        # C % 16 != 0: one register-kernel launch per branch
-    (1, 24, 32, 16, 9, 20, 5, 4),        # four branches: three fused + one single
-    (1, 8, 8, 16, 3, 1, 1, 2),           # 3x3
-])
+@pytest.mark.parametrize("case", D.WGRAD_MULTI_CASES)
 def test_dwconv_wgrad_multi(K, dt, case):
     """kd_dwconv_wgrad_multi: the depthwise weight gradients of the ASPP branches over their one input (deeplabv3.py:71-75),
     each against the oracle; bf16 9x9 branches share one staging of x and its operand windows (dw_mfma_wgrad_multi_kernel)."""
@@ -571,8 +548,7 @@ def test_dwconv_wgrad_multi(K, dt, case):
     dws = [torch.full((Cc, 1, k, k), 5.0, device="cuda") for _ in range(n)]
     xd, gd = dev_nhwc(x, dt), [dev_nhwc(g, dt) for g in gs]
     K.dwconv_wgrad_multi(xd, gd, dws, k, p, d)
-    if dt == "bf16" and k == 9 and Cc % 16 == 0:
-        selected("dw_mfma_wgrad_kernel" if n % 3 == 1 else f"dw_mfma_wgrad_multi_kernel<{3 if n % 3 == 0 else 2}>", f"dw wgrad of {n} {case}")
+    selected(D.wgrad_multi_kernels(dt, case)[-1], f"dw wgrad of {n} {case}")
     refs = [orc.conv2d_wgrad(x, g, (Cc, 1, k, k), pad=p, dil=d, groups=Cc) for g in gs]
     for i, (dw, ref) in enumerate(zip(dws, refs)):
         assert_close(dw.cpu().numpy(), ref, dt, f"dw wgrad of {n}, branch {i}")
@@ -582,10 +558,7 @@ def test_dwconv_wgrad_multi(K, dt, case):
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
-@pytest.mark.parametrize("case", [
-    (2, 24, 32, 16, 9, 20, 5, 3), (1, 140, 270, 32, 9, 20, 5, 3), (1, 40, 70, 16, 9, 4, 1, 2), (2, 64, 128, 48, 9, 20, 5, 3),
-    (1, 23, 37, 72, 9, 20, 5, 3), (1, 24, 32, 16, 9, 20, 5, 5), (1, 8, 8, 16, 3, 1, 1, 2),
-])
+@pytest.mark.parametrize("case", D.FANOUT_CASES)
 def test_dwconv_fanout(K, dt, case):
     """kd_dwconv_fwd_fanout: the ASPP branches' depthwise convs over one input (deeplabv3.py:71-75), each output against the
     oracle.  Three bf16 9x9 branches run on the lone-wave kernel (dwconv_lw.hip: resident operands, K slots, generated item loop);
@@ -597,9 +570,8 @@ def test_dwconv_fanout(K, dt, case):
     taps = [K.pack_dw_weight(torch.from_numpy(w).cuda()) for w in ws]
     xd = dev_nhwc(x, dt)
     outs = K.dwconv_fanout(xd, taps, k, p, d)
-    mfma = dt == "bf16" and k == 9 and Cc % 16 == 0
-    if mfma and n <= 3:
-        selected("dw_lw_fan3_kernel" if n == 3 else f"dw_mfma_fwd_kernel<{n},true>", f"dw fan-out {case}")
+    mfma = D.mfma(dt, case)
+    selected(D.fanout_kernels(dt, case)[-1], f"dw fan-out {case}")
     for i, (o, w) in enumerate(zip(outs, ws)):
         assert_close(host_nchw(o), orc.conv2d_fwd(x, w, pad=p, dil=d, groups=Cc), dt, f"dw fan-out {i}")
         single = K.dwconv(xd, taps[i], k, p, d)
@@ -612,43 +584,87 @@ def test_dwconv_fanout(K, dt, case):
             assert torch.equal(o, single), f"fan-out output {i} differs from the single launch"
 
 
-@pytest.mark.parametrize("case", [
-    # N, H, W, C: shapes that walk the lone-wave fan-out kernel's item pipeline (dwconv_lw.hip), 9x9 / dilation 5 / 3 branches
-    (1, 128, 256, 32),       # the ASPP map: 50 items per (image, channel group), every item with 4 column tiles
-    (2, 65, 130, 16),        # H, W multiples of dil; 13-row tiles exactly
-    (1, 131, 523, 16),       # three row tiles (one of a single row), three column tiles per class, ragged ones
-    (3, 7, 9, 16),           # a residue class of 2 x 2 pixels: one short item per class, single column tile
-    (1, 5, 5, 48),           # one pixel per class, three channel groups
-    (1, 266, 40, 16),        # five row tiles, 8 columns
-    (2, 10, 30, 16, 1),      # dilation 1, ONE work item per workgroup (the item loop's exit on its first pass)
-    (1, 20, 30, 32, 1),      # dilation 1, two items per workgroup (nothing to stage behind the second)
-    (1, 40, 120, 16, 2),     # dilation 2: four classes of 20 x 60, two row tiles and two column tiles each
-])
+@pytest.mark.parametrize("case", D.LONE_WAVE_CASES)
 def test_dwconv_fanout_lone_wave_shapes(K, case):
     """dw_lw_fan3_kernel against the oracle on the geometries its work-item descriptors distinguish: tiles in both directions,
     ragged last tiles, classes shorter than a tile, items with fewer than four column tiles, one-item workgroups."""
-    N, H, W, Cc = case[:4]
-    d = case[4] if len(case) > 4 else 5
-    k, p, dt = 9, 4 * d, "bf16"
+    N, H, W, Cc, k, p, d, _ = D.lone_wave_case(case)
+    dt = "bf16"
     x = q(rnd(N, Cc, H, W), dt)
     ws = [rnd(Cc, 1, k, k, scale=1.0 / k) for _ in range(3)]
     taps = [K.pack_dw_weight(torch.from_numpy(w).cuda()) for w in ws]
     outs = [torch.full((N, H, W, Cc), 7.0, dtype=torch.bfloat16, device="cuda") for _ in range(3)]     # stale data: every pixel must be written
     K.dwconv_fanout(dev_nhwc(x, dt), taps, k, p, d, outs=outs)
+    assert D.fanout_kernels(dt, D.lone_wave_case(case)) == ["dw_lw_fan3_kernel"]
     selected("dw_lw_fan3_kernel", f"dw fan-out {case}")
     for i, (o, w) in enumerate(zip(outs, ws)):
         assert_close(host_nchw(o), orc.conv2d_fwd(x, w, pad=p, dil=d, groups=Cc), dt, f"dw fan-out {case} branch {i}")
 
 
-LATTICE_CASES = [
-    # N, H, W, C, k, pad, dil, branches -- bf16 only (the lattice-planar intermediates of the replaced ASPP branches)
-    (2, 24, 32, 16, 9, 20, 5, 3),        # H, W not multiples of dil: classes one row / column shorter, padded cells
-    (1, 128, 256, 32, 9, 20, 5, 3),      # the ASPP map itself: 26 x 52 lattice, one tile per class (last row / column padded)
-    (1, 140, 270, 32, 9, 20, 5, 3),      # several tiles per class with real halos, ragged last tiles
-    (2, 40, 70, 16, 9, 4, 1, 2),         # two branches, dil 1: one class, many tiles, nothing padded
-    (2, 64, 128, 48, 9, 20, 5, 2),       # three channel groups (three planes), two branches
-    (3, 65, 130, 16, 9, 20, 5, 3),       # H, W multiples of dil: no padded cells; tail rows of the plane only
-]
+DW_VIEW_SHAPE = (1, 24, 32, 16, 9, 20, 5)     # N, H, W, C, k, pad, dil
+DW_VIEW_SENTINEL = 3.0
+
+
+@pytest.fixture(scope="module")
+def dw_view_ref():
+    """Inputs and oracle results of the two view cases below, computed once (a generator of its own: RNG's sequence is left alone)."""
+    N, H, W, Cc, k, p, d = DW_VIEW_SHAPE
+    rng = np.random.default_rng(4321)
+    xs = [q(rng.standard_normal((N, Cc, H, W)).astype(np.float32), "bf16") for _ in range(3)]     # xs[0] doubles as the one input of the fan-out / the gradients' x
+    ws = [(rng.standard_normal((Cc, 1, k, k)) / k).astype(np.float32) for _ in range(3)]
+    fwd = [orc.conv2d_fwd(xs[0], w, pad=p, dil=d, groups=Cc) for w in ws]
+    total = fwd[0] + sum(orc.conv2d_fwd(x, w, pad=p, dil=d, groups=Cc) for x, w in zip(xs[1:], ws[1:]))
+    wgrad = [orc.conv2d_wgrad(xs[0], g, (Cc, 1, k, k), pad=p, dil=d, groups=Cc) for g in xs]
+    return dict(xs=xs, ws=ws, fwd=fwd, sum=total, wgrad=wgrad)
+
+
+@pytest.mark.parametrize("channels,offset", [(24, 4), (20, 0)], ids=["pointer_8B_aligned", "ld_not_multiple_of_8"])
+def test_dwconv_views_outside_the_matrix_core_gates(K, dw_view_ref, channels, offset):
+    """bf16 9x9 on 16 channels that sit in a wider buffer: at channel offset 4 of 24 (the pointer is 8-B but not 16-B aligned) and
+    as the first 16 of 20 (pixel stride not a multiple of 8).  Neither is the matrix-core kernels' to take: the forward, the sum
+    of three, the fan-out of three and both weight gradients run on the register kernels and nothing else, match the oracle, and
+    leave the buffer's other channels alone."""
+    from kdcc_amd import _lib
+    N, H, W, Cc, k, p, d = DW_VIEW_SHAPE
+    r, dt = dw_view_ref, "bf16"
+    bufs = []
+
+    def view(a=None):
+        buf = torch.full((N, H, W, channels), DW_VIEW_SENTINEL, dtype=torch.bfloat16, device="cuda")
+        v = buf[..., offset:offset + Cc]
+        if a is not None:
+            v.copy_(dev_nhwc(a, dt))
+        bufs.append(buf)
+        assert v.data_ptr() % 16 == (8 if offset else 0) and v.stride(2) == channels
+        return v
+
+    xs = [view(x) for x in r["xs"]]
+    taps = [K.pack_dw_weight(torch.from_numpy(w).cuda()) for w in r["ws"]]
+    with _lib.kernel_log() as log:
+        y = K.dwconv(xs[0], taps[0], k, p, d, out=view())
+        selected("dwconv_fwd_kernel<bf16>", "dw fwd on a view")
+        total = K.dwconv_sum(xs, taps, k, p, d, out=view())
+        selected("dwconv_fwd_kernel<bf16>", "dw sum on views")
+        fan = K.dwconv_fanout(xs[0], taps, k, p, d, outs=[view() for _ in range(3)])
+        selected("dwconv_fwd_kernel<bf16>", "dw fan-out on views")
+        dw = torch.zeros((Cc, 1, k, k), device="cuda")
+        K.dwconv_wgrad(xs[0], xs[1], dw, k, p, d)
+        selected("dwconv_wgrad_kernel<bf16>", "dw wgrad on views")
+        dws = [torch.zeros((Cc, 1, k, k), device="cuda") for _ in range(3)]
+        K.dwconv_wgrad_multi(xs[0], xs, dws, k, p, d)
+        selected("dwconv_wgrad_kernel<bf16>", "dw wgrad of 3 on views")
+    assert log.counts == {"dwconv_fwd_kernel<bf16>": 7, "dwconv_wgrad_kernel<bf16>": 4}, log.counts
+    assert_close(host_nchw(y), r["fwd"][0], dt, "dw fwd on a view")
+    assert_close(host_nchw(total), r["sum"], dt, "dw sum on views")
+    for i in range(3):
+        assert_close(host_nchw(fan[i]), r["fwd"][i], dt, f"dw fan-out on views, branch {i}")
+        assert_close(dws[i].cpu().numpy(), r["wgrad"][i], dt, f"dw wgrad of 3 on views, branch {i}")
+    assert_close(dw.cpu().numpy(), r["wgrad"][1], dt, "dw wgrad on views")
+    for i, buf in enumerate(bufs):
+        rest = torch.cat((buf[..., :offset], buf[..., offset + Cc:]), dim=-1)
+        assert bool((rest == DW_VIEW_SENTINEL).all()), f"buffer {i}: channels outside the view were written"
+    for x, a in zip(xs, r["xs"]):
+        assert torch.equal(x, dev_nhwc(a, dt)), "an input was written"
 
 
 def _lattice_of(K, a, dil):
@@ -659,7 +675,7 @@ def _lattice_of(K, a, dil):
     return K.Lattice(N, H, W, Cc, dil, t=rows.reshape(rows.shape[0], Cc // 16, 16).permute(1, 0, 2).contiguous())
 
 
-@pytest.mark.parametrize("case", LATTICE_CASES)
+@pytest.mark.parametrize("case", D.LATTICE_CASES)
 def test_lattice_rows_round_trip(K, case):
     """kd_lattice_rows_move: image order -> lattice order -> image order is the identity; rows of cells without a pixel are zero;
     the row of pixel (n, y, x) is the one include/kdcc.h states."""
@@ -681,7 +697,7 @@ def test_lattice_rows_round_trip(K, case):
     assert torch.equal(back, xd)
 
 
-@pytest.mark.parametrize("case", LATTICE_CASES)
+@pytest.mark.parametrize("case", D.LATTICE_CASES)
 def test_dwconv_fanout_lattice(K, case):
     """kd_dwconv_fwd_fanout_lattice: the same values as kd_dwconv_fwd_fanout, bit for bit, in the lattice-planar layout -- padded
     cells and tail rows zero -- and each output against the oracle."""
@@ -698,7 +714,7 @@ def test_dwconv_fanout_lattice(K, case):
         used = N * d * d * (-(-H // d)) * (-(-W // d))
         o.t[:, used:].zero_()
     K.dwconv_fanout_lattice(xd, taps, k, p, d, outs=outs)
-    selected(f"dw_mfma_fwd_kernel<{n},true,lattice>", f"dw fan-out lattice {case}")
+    selected(D.lattice_kernels(case)[0], f"dw fan-out lattice {case}")
     plain = [K.dwconv(xd, t, k, p, d) for t in taps]     # (the 8-wave kernel's arithmetic; the NHWC fan-out of three runs on dw_lw_fan3_kernel)
     for i, (o, w) in enumerate(zip(outs, ws)):
         assert torch.equal(o.to_nhwc(), plain[i]), f"lattice fan-out output {i} differs from the NHWC launch"
@@ -708,7 +724,7 @@ def test_dwconv_fanout_lattice(K, case):
         assert_close(host_nchw(o.to_nhwc()), orc.conv2d_fwd(x, w, pad=p, dil=d, groups=Cc), dt, f"dw fan-out lattice {i}")
 
 
-@pytest.mark.parametrize("case", LATTICE_CASES)
+@pytest.mark.parametrize("case", D.LATTICE_CASES)
 def test_dwconv_sum_lattice(K, case):
     """kd_dwconv_fwd_sum_lattice: bit-identical to kd_dwconv_fwd_sum on the same values, and against the oracle's summed dgrads."""
     N, H, W, Cc, k, p, d, n = case
@@ -718,14 +734,14 @@ def test_dwconv_sum_lattice(K, case):
     taps = [K.pack_dw_weight(torch.from_numpy(w).cuda(), flip=True) for w in ws]
     lat = [_lattice_of(K, g, d) for g in gs]
     out = K.dwconv_sum_lattice(lat, taps, k, d * (k - 1) - p, d)
-    selected(f"dw_mfma_fwd_kernel<{n},false,lattice>", f"dw sum lattice {case}")
+    selected(D.lattice_kernels(case)[1], f"dw sum lattice {case}")
     plain = K.dwconv_sum([dev_nhwc(g, dt) for g in gs], taps, k, d * (k - 1) - p, d)
     assert torch.equal(out, plain), "lattice sum differs from the NHWC launch"
     ref = sum(orc.conv2d_dgrad(g, w, g.shape, pad=p, dil=d, groups=Cc) for g, w in zip(gs, ws))
     assert_close(host_nchw(out), ref, dt, f"dw sum lattice of {n}")
 
 
-@pytest.mark.parametrize("case", LATTICE_CASES)
+@pytest.mark.parametrize("case", D.LATTICE_CASES)
 def test_dwconv_wgrad_multi_lattice(K, case):
     """kd_dwconv_wgrad_multi_lattice: bit-identical to kd_dwconv_wgrad_multi, each branch against the oracle, accumulate too."""
     N, H, W, Cc, k, p, d, n = case
@@ -736,7 +752,7 @@ def test_dwconv_wgrad_multi_lattice(K, case):
     lat = [_lattice_of(K, g, d) for g in gs]
     dws = [torch.full((Cc, 1, k, k), 5.0, device="cuda") for _ in range(n)]
     K.dwconv_wgrad_multi_lattice(xd, lat, dws, k, p, d)
-    selected(f"dw_mfma_wgrad_multi_kernel<{n},lattice>", f"dw wgrad lattice {case}")
+    selected(D.lattice_kernels(case)[2], f"dw wgrad lattice {case}")
     plain = [torch.empty((Cc, 1, k, k), device="cuda") for _ in range(n)]
     K.dwconv_wgrad_multi(xd, [dev_nhwc(g, dt) for g in gs], plain, k, p, d)
     refs = [orc.conv2d_wgrad(x, g, (Cc, 1, k, k), pad=p, dil=d, groups=Cc) for g in gs]
