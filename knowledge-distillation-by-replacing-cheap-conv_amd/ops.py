@@ -1195,23 +1195,33 @@ def edge_aspp(acts, w, scale, shift, out):
     return out
 
 
-def canny(x_nchw, low=10, high=100, sweeps=8, max_rounds=64):
+def canny(x_nchw, low=10, high=100, sweeps=8, max_rounds=None, return_rounds=False):
     """Device Canny of the uint8-cast batch (N,3,H,W) -> (N,H,W) fp32 0/255.  Hysteresis runs `sweeps` sweeps per round and
-    reads one device int between rounds (the reference round-trips the whole image through the host here)."""
+    reads one device int between rounds (the reference round-trips the whole image through the host here) until a round's
+    last sweep promotes nothing: the result is the hysteresis fixed point, never a partial map.  max_rounds bounds the rounds
+    (the first included) and raises when it is reached without convergence; its default, ceil(H*W / sweeps) + 1, cannot bind:
+    every sweep but the last promotes at least one pixel of the image that converges last.  return_rounds: -> (map, rounds)."""
     _need_cuda(x_nchw)
     if x_nchw.dtype != torch.float32 or not x_nchw.is_contiguous() or x_nchw.shape[1] != 3:
         raise ValueError("canny: expects a contiguous fp32 (N,3,H,W) batch")
     N, _, H, W = x_nchw.shape
+    if sweeps < 1:
+        raise ValueError("canny: sweeps must be at least 1")
+    if max_rounds is None:
+        max_rounds = -(-H * W // sweeps) + 1
     out = torch.empty((N, H, W), dtype=torch.float32, device=x_nchw.device)
     changed = torch.zeros(1, dtype=torch.int32, device=x_nchw.device)
     need = _lib.lib().kd_canny_workspace(N, H, W)
     ws = _ws(need, x_nchw.device)
     check(_lib.lib().kd_canny(_ptr(x_nchw), N, H, W, low, high, sweeps, _ptr(out), _ptr(changed), _ptr(ws), need, stream_ptr()), "kd_canny")
-    for _ in range(max_rounds):
-        if int(changed.item()) == 0:
-            break
+    rounds = 1
+    while int(changed.item()) != 0:
+        if rounds >= max_rounds:
+            raise _lib.KdccError(f"canny: hysteresis of the {N} x {H} x {W} batch has not converged after {rounds} rounds "
+                                 f"({rounds * sweeps} sweeps)")
         check(_lib.lib().kd_canny_continue(N, H, W, sweeps, _ptr(out), _ptr(changed), _ptr(ws), need, stream_ptr()), "kd_canny_continue")
-    return out
+        rounds += 1
+    return (out, rounds) if return_rounds else out
 
 
 # ------------------------------------------------------------------------- Gated-SCNN shape stream, backward pieces

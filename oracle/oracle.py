@@ -217,12 +217,13 @@ def miou(conf):
         return float(np.nanmean(tp / (conf.sum(0) + conf.sum(1) - tp)))
 
 
-def canny_ref(img_u8, low=10, high=100):
+def canny_ref(img_u8, low=10, high=100, return_rounds=False):
     """Canny edge map of an (H, W, 3) uint8 image as cv2.Canny(img, low, high) documents it (aperture 3, L1 gradient):
     Sobel per channel with replicated borders, the channel of largest |gx| + |gy| wins, non-maximum suppression on the
     quantised direction (tan 22.5 / 67.5 degrees in 2^15 fixed point), double threshold, 8-connected hysteresis.
     PARITY UNPINNED: opencv-python is not in this image; this restates the published algorithm and is what
-    the device kernel kd_canny is checked against.  Returns (H, W) uint8 with values 0 / 255."""
+    the device kernel kd_canny is checked against.  Returns (H, W) uint8 with values 0 / 255; with return_rounds also the number
+    of rounds of the growth loop below that promoted a pixel (each round reaches one neighbour further from a strong seed)."""
     img = np.asarray(img_u8, dtype=np.int64)
     H, W, _ = img.shape
     p = np.pad(img, ((1, 1), (1, 1), (0, 0)), mode="edge")
@@ -247,6 +248,7 @@ def canny_ref(img_u8, low=10, high=100):
     keep &= mag > low
     strong = keep & (mag > high)
     weak = keep & ~strong
+    rounds = 0
     while True:
         sp = np.pad(strong, 1)
         near = np.zeros_like(strong)
@@ -259,7 +261,9 @@ def canny_ref(img_u8, low=10, high=100):
             break
         strong |= grow
         weak &= ~grow
-    return (strong * 255).astype(np.uint8)
+        rounds += 1
+    edges = (strong * 255).astype(np.uint8)
+    return (edges, rounds) if return_rounds else edges
 
 
 def radam_step(p, g, m, v, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
