@@ -1534,21 +1534,39 @@ static int pair_impl(const char *who, int kind, const kd_view3 *s, const kd_view
         const int gdt = grad ? grad->dtype : s->dtype;
 #define KD_PAIR(K, TS, TT, TG) hipLaunchKernelGGL((pair_nhwc_kernel<K, TS, TT, TG>), dim3(nb), dim3(256), lds, st, (const TS *)s->ptr, \
                                                   (const TT *)t->ptr, (TG *)gp, C, npix, invT, gscale, partial)
-#define KD_PAIR_DT(K)                                                                                       \
-        if (s->dtype == KD_F32 && t->dtype == KD_F32 && gdt == KD_F32) KD_PAIR(K, float, float, float);       \
-        else if (s->dtype == KD_F32 && t->dtype == KD_BF16 && gdt == KD_F32) KD_PAIR(K, float, bf16_t, float); \
-        else if (s->dtype == KD_BF16 && t->dtype == KD_BF16 && gdt == KD_BF16) KD_PAIR(K, bf16_t, bf16_t, bf16_t); \
-        else if (s->dtype == KD_BF16 && t->dtype == KD_F32 && gdt == KD_BF16) KD_PAIR(K, bf16_t, float, bf16_t); \
-        else if (s->dtype == KD_F32 && t->dtype == KD_F32) KD_PAIR(K, float, float, bf16_t);                  \
-        else if (s->dtype == KD_F32 && t->dtype == KD_BF16) KD_PAIR(K, float, bf16_t, bf16_t);                \
-        else if (s->dtype == KD_BF16 && t->dtype == KD_BF16) KD_PAIR(K, bf16_t, bf16_t, float);               \
-        else KD_PAIR(K, bf16_t, float, float)
-        if (kind == PAIR_KLD) { KD_PAIR_DT(PAIR_KLD); }
-        else if (kind == PAIR_JSD) { KD_PAIR_DT(PAIR_JSD); }
-        else { KD_PAIR_DT(PAIR_EKL); }
+        // (N0 .. N7: the note of each storage-type form, in the order of the chain; a macro argument is a statement, so that
+        // every literal stands in a KD_NOTE_PLUMBING of its own next to the launch it names)
+#define KD_PAIR_DT(K, N0, N1, N2, N3, N4, N5, N6, N7)                                                                 \
+        if (s->dtype == KD_F32 && t->dtype == KD_F32 && gdt == KD_F32) { N0; KD_PAIR(K, float, float, float); }       \
+        else if (s->dtype == KD_F32 && t->dtype == KD_BF16 && gdt == KD_F32) { N1; KD_PAIR(K, float, bf16_t, float); } \
+        else if (s->dtype == KD_BF16 && t->dtype == KD_BF16 && gdt == KD_BF16) { N2; KD_PAIR(K, bf16_t, bf16_t, bf16_t); } \
+        else if (s->dtype == KD_BF16 && t->dtype == KD_F32 && gdt == KD_BF16) { N3; KD_PAIR(K, bf16_t, float, bf16_t); } \
+        else if (s->dtype == KD_F32 && t->dtype == KD_F32) { N4; KD_PAIR(K, float, float, bf16_t); }                  \
+        else if (s->dtype == KD_F32 && t->dtype == KD_BF16) { N5; KD_PAIR(K, float, bf16_t, bf16_t); }                \
+        else if (s->dtype == KD_BF16 && t->dtype == KD_BF16) { N6; KD_PAIR(K, bf16_t, bf16_t, float); }               \
+        else { N7; KD_PAIR(K, bf16_t, float, float); }
+        if (kind == PAIR_KLD) {
+            KD_PAIR_DT(PAIR_KLD, KD_NOTE_PLUMBING("pair_nhwc_kernel<kld,f32,f32,f32>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<kld,f32,bf16,f32>"),
+                       KD_NOTE_PLUMBING("pair_nhwc_kernel<kld,bf16,bf16,bf16>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<kld,bf16,f32,bf16>"),
+                       KD_NOTE_PLUMBING("pair_nhwc_kernel<kld,f32,f32,bf16>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<kld,f32,bf16,bf16>"),
+                       KD_NOTE_PLUMBING("pair_nhwc_kernel<kld,bf16,bf16,f32>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<kld,bf16,f32,f32>"))
+        } else if (kind == PAIR_JSD) {
+            KD_PAIR_DT(PAIR_JSD, KD_NOTE_PLUMBING("pair_nhwc_kernel<jsd,f32,f32,f32>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<jsd,f32,bf16,f32>"),
+                       KD_NOTE_PLUMBING("pair_nhwc_kernel<jsd,bf16,bf16,bf16>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<jsd,bf16,f32,bf16>"),
+                       KD_NOTE_PLUMBING("pair_nhwc_kernel<jsd,f32,f32,bf16>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<jsd,f32,bf16,bf16>"),
+                       KD_NOTE_PLUMBING("pair_nhwc_kernel<jsd,bf16,bf16,f32>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<jsd,bf16,f32,f32>"))
+        } else {
+            KD_PAIR_DT(PAIR_EKL, KD_NOTE_PLUMBING("pair_nhwc_kernel<ekl,f32,f32,f32>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<ekl,f32,bf16,f32>"),
+                       KD_NOTE_PLUMBING("pair_nhwc_kernel<ekl,bf16,bf16,bf16>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<ekl,bf16,f32,bf16>"),
+                       KD_NOTE_PLUMBING("pair_nhwc_kernel<ekl,f32,f32,bf16>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<ekl,f32,bf16,bf16>"),
+                       KD_NOTE_PLUMBING("pair_nhwc_kernel<ekl,bf16,bf16,f32>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<ekl,bf16,f32,f32>"))
+        }
 #undef KD_PAIR_DT
 #undef KD_PAIR
     } else {
+        if (kind == PAIR_KLD) KD_NOTE_PLUMBING("pair_kernel<kld>");
+        else if (kind == PAIR_JSD) KD_NOTE_PLUMBING("pair_kernel<jsd>");
+        else KD_NOTE_PLUMBING("pair_kernel<ekl>");
         auto fn = kind == PAIR_KLD ? pair_kernel<PAIR_KLD> : kind == PAIR_JSD ? pair_kernel<PAIR_JSD> : pair_kernel<PAIR_EKL>;
         hipLaunchKernelGGL(fn, dim3(nb), dim3(256), 0, st, v3(s), v3(t), m3(grad), invT, gscale, N, C, (long long)P, partial);
     }
@@ -1581,13 +1599,17 @@ extern "C" int kd_hint_mse(const kd_view3 *s, const kd_view3 *t, float num_class
     int nb;
     if (dense_same(s, t, grad, N, C, P)) {
         nb = blocks_for(numel / 8);
-        if (s->dtype == KD_BF16)
+        if (s->dtype == KD_BF16) {
+            KD_NOTE_PLUMBING("mse_vec_kernel<bf16>");
             hipLaunchKernelGGL(mse_vec_kernel<bf16_t>, dim3(nb), dim3(256), 0, st, (const bf16_t *)s->ptr, (const bf16_t *)t->ptr,
                                (bf16_t *)(grad ? grad->ptr : nullptr), gscale, numel / 8, partial);
-        else
+        } else {
+            KD_NOTE_PLUMBING("mse_vec_kernel<f32>");
             hipLaunchKernelGGL(mse_vec_kernel<float>, dim3(nb), dim3(256), 0, st, (const float *)s->ptr, (const float *)t->ptr,
                                (float *)(grad ? grad->ptr : nullptr), gscale, numel / 8, partial);
+        }
     } else {
+        KD_NOTE_PLUMBING("mse_strided_kernel");
         nb = blocks_for(numel);
         hipLaunchKernelGGL(mse_strided_kernel, dim3(nb), dim3(256), 0, st, v3(s), v3(t), m3(grad), gscale, N, C, (long long)P,
                            s->sC == 1 ? 1 : 0, partial);
@@ -1612,6 +1634,7 @@ extern "C" int kd_weighted_hint_mse(const kd_view3 *s, const kd_view3 *t, const 
     const size_t nblocks = (size_t)grid.x * grid.y * grid.z;
     double *partial = (double *)workspace;
     float *wsum = (float *)((char *)workspace + 2 * (nblocks > (size_t)MAX_BLOCKS ? nblocks : (size_t)MAX_BLOCKS) * sizeof(double));
+    KD_NOTE_PLUMBING("whmse_kernel");
     hipLaunchKernelGGL(wsum_kernel, dim3(N), dim3(64), 0, st, w, w_per_sample, N, C, wsum);
     hipLaunchKernelGGL(whmse_kernel, grid, dim3(256), 0, st, v3(s), v3(t), m3(grad), w, w_per_sample, (const float *)wsum,
                        grad_scale, N, C, (long long)P, per_chunk, partial);
@@ -1633,13 +1656,17 @@ static int ce2d_impl(const char *who, const kd_view3 *x, const int64_t *target, 
     hipStream_t st = (hipStream_t)stream;
     if ((size_t)256 * C * sizeof(float) <= 65536 && x->sC == 1 && x->sP == C && (x->sN == (long long)C * P || N == 1)) {
         const size_t lds = (size_t)256 * C * sizeof(float);   // <= the 64-KiB default dynamic-LDS limit, else the strided kernel
-        if (x->dtype == KD_F32)
+        if (x->dtype == KD_F32) {
+            KD_NOTE_PLUMBING("ce2d_nhwc_kernel<f32>");
             hipLaunchKernelGGL(ce2d_nhwc_kernel<float>, dim3(nb), dim3(256), lds, st, (const float *)x->ptr, target, ignore_index, C,
                                (long long)N * P, partial, count, class_weight);
-        else
+        } else {
+            KD_NOTE_PLUMBING("ce2d_nhwc_kernel<bf16>");
             hipLaunchKernelGGL(ce2d_nhwc_kernel<bf16_t>, dim3(nb), dim3(256), lds, st, (const bf16_t *)x->ptr, target, ignore_index,
                                C, (long long)N * P, partial, count, class_weight);
+        }
     } else {
+        KD_NOTE_PLUMBING("ce2d_kernel");
         hipLaunchKernelGGL(ce2d_kernel, dim3(nb), dim3(256), 0, st, v3(x), target, ignore_index, N, C, (long long)P, partial, count, class_weight);
     }
     KD_CHECK_LAUNCH(who);
@@ -1708,6 +1735,7 @@ extern "C" int kd_ce2d_up(const float *x_lo, const int64_t *target, int32_t igno
     double *partial = (double *)workspace, *count = partial + MAX_BLOCKS;
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)2 * UP_NW * C * sizeof(float);
+    if (C == 19) KD_NOTE_PLUMBING("ce2d_up_kernel<19>"); else KD_NOTE_PLUMBING("ce2d_up_kernel<0>");
     hipLaunchKernelGGL(C == 19 ? ce2d_up_kernel<19> : ce2d_up_kernel<0>, dim3(u.nb), dim3(256), lds, st, x_lo, target, ignore_index, u.g, u.nchunks,
                        u.cpr, partial, count);
     KD_CHECK_LAUNCH("kd_ce2d_up");
@@ -1726,6 +1754,7 @@ extern "C" int kd_kldiv_up(const float *s_lo, const float *t_lo, float temperatu
     double *partial = (double *)workspace;
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)4 * UP_NW * C * sizeof(float);
+    if (C == 19) KD_NOTE_PLUMBING("pair_up_kernel<kld,19>"); else KD_NOTE_PLUMBING("pair_up_kernel<kld,0>");
     hipLaunchKernelGGL((C == 19 ? pair_up_kernel<PAIR_KLD, 19> : pair_up_kernel<PAIR_KLD, 0>), dim3(u.nb), dim3(256), lds, st, s_lo, t_lo, u.g,
                        1.f / temperature, u.nchunks, u.cpr, partial);
     KD_CHECK_LAUNCH("kd_kldiv_up");
@@ -1746,6 +1775,7 @@ extern "C" int kd_jsdiv_up(const float *s_lo, const float *t_lo, float temperatu
     double *partial = (double *)workspace;
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)4 * UP_NW * C * sizeof(float);
+    if (C == 19) KD_NOTE_PLUMBING("pair_up_kernel<jsd,19>"); else KD_NOTE_PLUMBING("pair_up_kernel<jsd,0>");
     hipLaunchKernelGGL((C == 19 ? pair_up_kernel<PAIR_JSD, 19> : pair_up_kernel<PAIR_JSD, 0>), dim3(u.nb), dim3(256), lds, st, s_lo, t_lo, u.g,
                        1.f / temperature, u.nchunks, u.cpr, partial);
     KD_CHECK_LAUNCH("kd_jsdiv_up");
@@ -1786,6 +1816,7 @@ extern "C" int kd_logit_metrics_up(const float *s_lo, const float *t_lo, const i
             return KD_ERR_UNSUPPORTED;
         }
     }
+    if (C == 19) KD_NOTE_PLUMBING("logit_metrics_up_kernel<19>"); else KD_NOTE_PLUMBING("logit_metrics_up_kernel<0>");
     hipLaunchKernelGGL(fn, dim3(u.nb), dim3(256), lds, st, s_lo, t_lo, target, ignore_index, u.g, u.nchunks, u.cpr, partial,
                        (unsigned long long *)conf_s, (unsigned long long *)conf_t);
     KD_CHECK_LAUNCH("kd_logit_metrics_up");
@@ -1901,14 +1932,21 @@ extern "C" int kd_kldiv_multi(const kd_view3 *s, const kd_multi_targets *targets
         nb = (int)std::min<long long>((rows + 3) / 4, MT_MAX_BLOCKS);
 #define KD_MTW(NCH, VEC) hipLaunchKernelGGL((mt_wave_kernel<NCH, VEC, false>), dim3(nb), dim3(256), 0, st, sv, mt, gv, labels, ignore_index, \
                                             invT, gk, sup_scale, C, (long long)P, rows, cnt, ncount, pkd, pce)
-        if (C <= 256) { if (vec) KD_MTW(1, true); else KD_MTW(1, false); }
-        else { if (vec) KD_MTW(4, true); else KD_MTW(4, false); }
+        if (C <= 256) {
+            if (vec) { KD_NOTE_PLUMBING("mt_wave_kernel<1,vec>"); KD_MTW(1, true); }
+            else { KD_NOTE_PLUMBING("mt_wave_kernel<1,novec>"); KD_MTW(1, false); }
+        } else {
+            if (vec) { KD_NOTE_PLUMBING("mt_wave_kernel<4,vec>"); KD_MTW(4, true); }
+            else { KD_NOTE_PLUMBING("mt_wave_kernel<4,novec>"); KD_MTW(4, false); }
+        }
 #undef KD_MTW
     } else if (path == MT_NHWC) {
+        KD_NOTE_PLUMBING("kldm_nhwc_kernel");
         nb = (int)std::min<long long>((rows + 255) / 256, MT_MAX_BLOCKS);
         hipLaunchKernelGGL(kldm_nhwc_kernel, dim3(nb), dim3(256), (size_t)3 * 256 * C * sizeof(float), st, sv, mt, gv, labels, ignore_index,
                            invT, gk, sup_scale, C, rows, cnt, ncount, pkd, pce);
     } else {
+        KD_NOTE_PLUMBING("kldm_kernel");
         nb = (int)std::min<long long>((rows + 255) / 256, MT_MAX_BLOCKS);
         hipLaunchKernelGGL(kldm_kernel<false>, dim3(nb), dim3(256), 0, st, sv, mt, gv, labels, ignore_index, invT, gk, sup_scale, C,
                            (long long)P, rows, cnt, ncount, pkd, pce);
@@ -1944,10 +1982,16 @@ extern "C" int kd_softmax_mean(const kd_multi_targets *logits, float temperature
         const int nb = (int)std::min<long long>((rows + 3) / 4, MT_MAX_BLOCKS);
 #define KD_SMW(NCH, VEC) hipLaunchKernelGGL((mt_wave_kernel<NCH, VEC, true>), dim3(nb), dim3(256), 0, st, none, mt, gv, (const int64_t *)nullptr, 0, \
                                             invT, 0.f, 0.f, C, (long long)P, rows, (const double *)nullptr, 0, (double *)nullptr, (double *)nullptr)
-        if (C <= 256) { if (vec) KD_SMW(1, true); else KD_SMW(1, false); }
-        else { if (vec) KD_SMW(4, true); else KD_SMW(4, false); }
+        if (C <= 256) {
+            if (vec) { KD_NOTE_PLUMBING("mt_wave_kernel<1,vec,smean>"); KD_SMW(1, true); }
+            else { KD_NOTE_PLUMBING("mt_wave_kernel<1,novec,smean>"); KD_SMW(1, false); }
+        } else {
+            if (vec) { KD_NOTE_PLUMBING("mt_wave_kernel<4,vec,smean>"); KD_SMW(4, true); }
+            else { KD_NOTE_PLUMBING("mt_wave_kernel<4,novec,smean>"); KD_SMW(4, false); }
+        }
 #undef KD_SMW
     } else {
+        KD_NOTE_PLUMBING("kldm_kernel<smean>");
         const int nb = (int)std::min<long long>((rows + 255) / 256, MT_MAX_BLOCKS);
         hipLaunchKernelGGL(kldm_kernel<true>, dim3(nb), dim3(256), 0, st, none, mt, gv, (const int64_t *)nullptr, 0, invT, 0.f, 0.f, C,
                            (long long)P, rows, (const double *)nullptr, 0, (double *)nullptr, (double *)nullptr);
@@ -1973,6 +2017,7 @@ extern "C" int kd_focal(const kd_view3 *x, const int64_t *target, const float *a
     const long long total = (long long)N * P;
     const int nb = (int)min((total + 255) / 256, (long long)FOCAL_MAX_BLOCKS);
     hipStream_t st = (hipStream_t)stream;
+    KD_NOTE_PLUMBING("focal_kernel");
     hipLaunchKernelGGL(focal_kernel, dim3(nb), dim3(256), 0, st, v3(x), target, alpha, gamma, ignore_index, N, C, (long long)P, a_map, ce_map, partial);
     KD_CHECK_LAUNCH("kd_focal");
     hipLaunchKernelGGL(focal_finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, nb, (int)reduction, (double)total, stats,
@@ -1990,6 +2035,7 @@ extern "C" int kd_focal_grad(const kd_view3 *x, const int64_t *target, const flo
     KD_REQUIRE(reduction >= 0 && reduction <= 2, KD_ERR_INVALID, "kd_focal_grad: reduction is 0 (none), 1 (mean) or 2 (sum)");
     KD_REQUIRE(reduction == 0 ? (a_map && ce_map) : stats != nullptr, KD_ERR_INVALID,
                "kd_focal_grad: 'none' needs the forward's per-pixel maps, 'mean' / 'sum' its stats");
+    KD_NOTE_PLUMBING("focal_grad_kernel");
     hipLaunchKernelGGL(focal_grad_kernel, dim3(blocks_for((long long)N * P)), dim3(256), 0, (hipStream_t)stream, v3(x), target, alpha, gamma,
                        ignore_index, (int)reduction, N, C, (long long)P, stats, upstream, a_map, ce_map, m3(grad));
     KD_CHECK_LAUNCH("kd_focal_grad");
@@ -2012,6 +2058,7 @@ extern "C" int kd_focal_up(const float *x_lo, const int64_t *target, const float
     double *partial = (double *)workspace;
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)2 * UP_NW * C * sizeof(float);
+    if (C == 19) KD_NOTE_PLUMBING("focal_up_kernel<19>"); else KD_NOTE_PLUMBING("focal_up_kernel<0>");
     hipLaunchKernelGGL(C == 19 ? focal_up_kernel<19> : focal_up_kernel<0>, dim3(u.nb), dim3(256), lds, st, x_lo, target, alpha, gamma, ignore_index,
                        u.g, u.nchunks, u.cpr, partial);
     KD_CHECK_LAUNCH("kd_focal_up");
@@ -2060,14 +2107,22 @@ extern "C" int kd_topk_hint_mse(const kd_view3 *s, const kd_view3 *t, int32_t K,
             const long long n8 = numel / 8;
 #define KD_TOPK_VEC(T, CF) hipLaunchKernelGGL((topk_grad_vec_kernel<T, CF>), dim3(blocks_for(n8)), dim3(256), 0, st, (const T *)s->ptr, \
                                               (const T *)t->ptr, (T *)grad->ptr, (const float *)mk, gscale, C, (long long)P, n8)
-            if (s->dtype == KD_BF16) { if (cfast) KD_TOPK_VEC(bf16_t, true); else KD_TOPK_VEC(bf16_t, false); }
-            else { if (cfast) KD_TOPK_VEC(float, true); else KD_TOPK_VEC(float, false); }
+            if (s->dtype == KD_BF16) {
+                if (cfast) { KD_NOTE_PLUMBING("topk_grad_vec_kernel<bf16,cfast>"); KD_TOPK_VEC(bf16_t, true); }
+                else { KD_NOTE_PLUMBING("topk_grad_vec_kernel<bf16,pfast>"); KD_TOPK_VEC(bf16_t, false); }
+            } else {
+                if (cfast) { KD_NOTE_PLUMBING("topk_grad_vec_kernel<f32,cfast>"); KD_TOPK_VEC(float, true); }
+                else { KD_NOTE_PLUMBING("topk_grad_vec_kernel<f32,pfast>"); KD_TOPK_VEC(float, false); }
+            }
 #undef KD_TOPK_VEC
         } else {
+            KD_NOTE_PLUMBING("topk_grad_kernel");
             hipLaunchKernelGGL(topk_grad_kernel, dim3(blocks_for(numel)), dim3(256), 0, st, v3(s), v3(t), m3(grad), (const float *)mk, gscale,
                                N, C, (long long)P, s->sC == 1 ? 1 : 0);
         }
         KD_CHECK_LAUNCH("kd_topk_hint_mse(grad)");
+    } else {
+        KD_NOTE_PLUMBING("topk_nograd");
     }
     hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)part, (int)N, 1.0 / ((double)P * denom), (const double *)nullptr, loss);
     KD_CHECK_LAUNCH("kd_topk_hint_mse(finish)");
@@ -2084,6 +2139,7 @@ static int ce2d_grad_impl(const char *who, const kd_view3 *x, const int64_t *tar
     double *count = (double *)workspace;
     const int nb = blocks_for((long long)N * P);
     hipStream_t st = (hipStream_t)stream;
+    KD_NOTE_PLUMBING("ce2d_grad_kernel");
     hipLaunchKernelGGL(ce2d_count_kernel, dim3(nb), dim3(256), 0, st, target, ignore_index, C, (long long)N * P, count, class_weight);
     KD_CHECK_LAUNCH(who);
     hipLaunchKernelGGL(ce2d_grad_kernel, dim3(nb), dim3(256), 0, st, v3(x), target, ignore_index, N, C, (long long)P, m3(grad), grad_scale,
@@ -2124,13 +2180,17 @@ extern "C" int kd_confusion(const kd_view3 *x, const int64_t *target, int32_t N,
     if ((size_t)256 * C * sizeof(float) + (size_t)C * C * sizeof(unsigned int) <= 65536 && x->sC == 1 && x->sP == C &&
         (x->sN == (long long)C * P || N == 1)) {
         const size_t lds = (size_t)256 * C * sizeof(float) + (size_t)C * C * sizeof(unsigned int);
-        if (x->dtype == KD_F32)
+        if (x->dtype == KD_F32) {
+            KD_NOTE_PLUMBING("confusion_nhwc_kernel<f32>");
             hipLaunchKernelGGL(confusion_nhwc_kernel<float>, dim3(nb), dim3(256), lds, st, (const float *)x->ptr, target, C,
                                (long long)N * P, (unsigned long long *)conf);
-        else
+        } else {
+            KD_NOTE_PLUMBING("confusion_nhwc_kernel<bf16>");
             hipLaunchKernelGGL(confusion_nhwc_kernel<bf16_t>, dim3(nb), dim3(256), lds, st, (const bf16_t *)x->ptr, target, C,
                                (long long)N * P, (unsigned long long *)conf);
+        }
     } else {
+        KD_NOTE_PLUMBING("confusion_kernel");
         hipLaunchKernelGGL(confusion_kernel, dim3(nb), dim3(256), (size_t)C * C * sizeof(unsigned int), st, v3(x), target, N, C,
                            (long long)P, (unsigned long long *)conf);
     }
@@ -2153,6 +2213,7 @@ extern "C" int kd_radam_step(float *p, const float *g, float *exp_avg, float *ex
                     (1 - pow((double)beta1, step));
     else
         step_size = 1.0 / (1 - pow((double)beta1, step));
+    KD_NOTE_PLUMBING("radam_kernel");
     hipLaunchKernelGGL(radam_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, exp_avg, exp_avg_sq,
                        (long long)n, beta1, beta2, eps, (float)((double)weight_decay * lr), (float)(step_size * lr), rect);
     KD_CHECK_LAUNCH("kd_radam_step");
@@ -2166,12 +2227,15 @@ extern "C" int kd_scale_by_device_scalar(void *x, int32_t dtype, int64_t n, cons
     KD_REQUIRE(kd_aligned16(x), KD_ERR_INVALID, "kd_scale_by_device_scalar: x must be 16-B aligned");
     const long long n8 = n / 8;
     const unsigned blocks = blocks_for(n8 > 0 ? n8 : 1);
-    if (dtype == KD_BF16)
+    if (dtype == KD_BF16) {
+        KD_NOTE_PLUMBING("scale_by_device_scalar_kernel<bf16>");
         hipLaunchKernelGGL(scale_by_device_scalar_kernel<bf16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (bf16_t *)x, n8,
                            (long long)n, scale);
-    else
+    } else {
+        KD_NOTE_PLUMBING("scale_by_device_scalar_kernel<f32>");
         hipLaunchKernelGGL(scale_by_device_scalar_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (float *)x, n8,
                            (long long)n, scale);
+    }
     KD_CHECK_LAUNCH("kd_scale_by_device_scalar");
     return KD_OK;
 }
@@ -2215,6 +2279,7 @@ extern "C" int kd_radam_step_multi(const kd_radam_tensor *ts, int32_t count, kd_
         }
         b.blk0[k] = nb;
         b.count = k;
+        KD_NOTE_PLUMBING("radam_multi_kernel");
         hipLaunchKernelGGL(radam_multi_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, b);
         KD_CHECK_LAUNCH("kd_radam_step_multi");
         done += k;

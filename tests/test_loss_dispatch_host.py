@@ -1,0 +1,176 @@
+"""Keeps tests/_loss_dispatch_cases.py honest without a GPU: every KD_NOTE_PLUMBING literal of csrc/losses.hip has a row, every
+row names a literal the source declares, every row's restated gate yields the row's literal, adjacent rows of a gate land on
+different kernels, every second-trip row exceeds its grid cap, every reference runs, is finite and has the declared shape, and
+the reduction rows' claims about a single fp32 chain hold."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import _criteria_ref as CR
+import _loss_dispatch_cases as L
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SOURCE = os.path.join(ROOT, "knowledge-distillation-by-replacing-cheap-conv_amd", "csrc", "losses.hip")
+REFUSED = "(refused)"
+
+
+def source_text():
+    with open(SOURCE) as f:
+        return f.read()
+
+
+def declared_literals():
+    return set(re.findall(r'KD_NOTE_PLUMBING\("([^"]+)"\)', source_text()))
+
+
+def test_every_noted_literal_has_a_row_and_every_row_names_a_noted_literal():
+    declared = declared_literals()
+    assert len(declared) >= 71, "the scan found too few KD_NOTE_PLUMBING literals in losses.hip: has the macro been renamed?"
+    covered = {c["kernel"] for c in L.CASES} - {REFUSED}
+    missing = sorted(declared - covered)
+    assert not missing, f"dispatch branches of losses.hip without a row in tests/_loss_dispatch_cases.py: {missing}"
+    unknown = sorted(covered - declared)
+    assert not unknown, f"rows name kernels losses.hip does not declare: {unknown}"
+
+
+def test_the_conv_log_macro_does_not_appear_in_losses_hip():
+    assert "KD_NOTE_KERNEL" not in source_text()
+
+
+def test_case_ids_are_unique():
+    ids = L.ids(L.CASES)
+    assert len(ids) == len(set(ids))
+
+
+@pytest.mark.parametrize("c", L.CASES, ids=L.ids(L.CASES))
+def test_the_restated_gate_yields_the_rows_literal(c):
+    assert L.rule(c) == c["kernel"], f"{c['id']}: the launcher's gate, as restated, picks {L.rule(c)}; the row says {c['kernel']}"
+    assert bool(c.get("refused")) == (c["kernel"] == REFUSED)
+
+
+def test_adjacent_rows_of_every_gate_land_on_different_kernels():
+    gates = {}
+    for c in L.CASES:
+        if "gate" in c:
+            gates.setdefault(c["gate"][:-1], {}).setdefault(c["gate"][-1], set()).add(c["kernel"])
+    want = {"pair-lds", "ce-lds", "conf-lds", "mse-numel8", "mse-align", "topk-c8", "topk-p8", "up-c19", "mt-c256", "mt-c1024", "mt-narrow-c",
+            "mt-narrow-rows"}
+    assert {g[0] for g in gates} == want
+    for g, sides in gates.items():
+        assert set(sides) == {0, 1}, f"gate {g}: a side without a row"
+        assert len(sides[0]) == 1 and len(sides[1]) == 1 and sides[0] != sides[1], f"gate {g}: both sides reach {sides}"
+
+
+def test_the_confusion_gate_cuts_where_the_inequality_says():
+    """256 x C floats + C x C counters within 64 KiB: true up to C = 53, false from 54 (not at 51 / 52, as a comment once had it)."""
+    fits = [C for C in range(1, 65) if 256 * C * 4 + C * C * 4 <= L.LDS]
+    assert fits == list(range(1, 54))
+    by_c = {c["shape"][1]: c["kernel"] for c in L.cases_of("confusion") if c["id"].split(":")[1] in ("C51", "C52", "C53", "C54")}
+    assert by_c == {51: "confusion_nhwc_kernel<f32>", 52: "confusion_nhwc_kernel<f32>", 53: "confusion_nhwc_kernel<f32>", 54: "confusion_kernel"}
+
+
+TRIPS = [c for c in L.CASES if "second_trip" in c]
+
+
+@pytest.mark.parametrize("c", TRIPS, ids=L.ids(TRIPS))
+def test_grid_stride_rows_exceed_their_grid(c):
+    work, cap_blocks = c["second_trip"]
+    assert work > cap_blocks * 256
+    if "geom" in c:                                  # the _up kernels: one chunk a block and trip
+        assert L.up_chunks(c) > cap_blocks and work == L.up_chunks(c) * 256
+    elif c["op"] in ("kldiv_multi", "softmax_mean") and c["kernel"].startswith("mt_wave"):
+        N, C, P = L.dims(c)                          # four rows a block and trip
+        assert (N * P + 3) // 4 > cap_blocks
+    elif c["op"] == "hint_mse" and c["kernel"].startswith("mse_vec") or c["kernel"].startswith("topk_grad_vec"):
+        assert int(np.prod(c["shape"])) // 8 > cap_blocks * 256
+    elif "shape" in c:
+        N, C, P = L.dims(c)
+        assert (N * C * P if c["op"] in ("hint_mse", "topk") else N * P) > cap_blocks * 256
+
+
+def test_every_capped_family_has_a_second_trip_row():
+    ops = {c["op"] for c in TRIPS}
+    assert ops >= {"pair", "hint_mse", "ce2d", "ce2d_grad", "confusion", "focal", "focal_grad", "ce2d_up", "kldiv_up", "jsdiv_up", "focal_up",
+                   "metrics_up", "kldiv_multi", "softmax_mean", "topk", "radam", "scale"}
+    for op in ("ce2d_up", "kldiv_up", "jsdiv_up", "focal_up", "metrics_up"):
+        assert {c["ac"] for c in TRIPS if c["op"] == op} == {True, False}
+
+
+def test_the_weighted_hint_rows_have_the_chunks_they_claim():
+    for c in L.cases_of("whmse"):
+        assert L.whmse_plan(L.dims(c)[2]) == c["plan"], c["id"]
+    plans = {c["plan"] for c in L.cases_of("whmse")}
+    assert any(p[2] > 0 and p[3] < p[1] for p in plans), "no row with empty trailing chunks and a ragged last one"
+
+
+@pytest.mark.parametrize("c", L.CASES, ids=L.ids(L.CASES))
+def test_reference_runs_is_finite_and_has_the_declared_shape(c):
+    c = L.shrunk(c)
+    inp, ref = L.build(c)
+    for name, shape in L.expected_shapes(c).items():
+        assert tuple(np.shape(ref[name])) == tuple(shape), f"{c['id']}: reference {name} has shape {np.shape(ref[name])}, declared {shape}"
+    for name, v in ref.items():
+        if name != "tensors":
+            assert np.isfinite(np.asarray(v, dtype=np.float64)).all(), f"{c['id']}: reference {name} is not finite"
+    if c.get("all_ignored"):       # the loss is exactly 0 and so is the gradient
+        if c["op"] == "metrics_up":
+            assert ref["out"][0] == 0.0 and ref["out"][1] == 0.0
+        else:
+            assert ref["loss"] == 0.0 and not ref.get("grad", np.zeros(1)).any()
+    if c.get("tie"):
+        norm = (inp["t"].astype(np.float64) ** 2).reshape(c["shape"][0], c["shape"][1], -1).sum(-1)
+        for n, (lo, hi) in enumerate(inp["tie"]):
+            assert norm[n, lo] == norm[n, hi] and lo < hi
+            assert (norm[n] > norm[n, lo]).sum() == c["k"] - 1, "the tied pair does not straddle rank k"
+            assert ref["mask"][n, lo] == 1.0 and ref["mask"][n, hi] == 0.0
+    if c.get("low200"):          # the row is meant to reach jsd_log_q's log-space arm: ps + pt underflows 1e-30 in fp32
+        import torch
+        s, t = torch.from_numpy(inp["s"]), torch.from_numpy(inp["t"])
+        assert float((torch.softmax(s, 1) + torch.softmax(t, 1))[:, 5].max()) < 1e-30
+    if c.get("tzeros"):
+        assert (inp["t"][:, 3] == 0).all()
+
+
+def test_the_dtype_agnostic_pair_formulas_agree_with_the_criteria_reference():
+    import torch
+    g = torch.Generator().manual_seed(5)
+    s, t = torch.randn(3, 7, 4, 5, generator=g, dtype=torch.float64), torch.randn(3, 7, 4, 5, generator=g, dtype=torch.float64)
+    v, sc, gr = L.pair_formula("jsd", s, t, 2.0)
+    rl, rg = CR.jsd(s, t, 2.0)
+    np.testing.assert_allclose(float(v.sum() * sc), float(rl), rtol=1e-12)
+    np.testing.assert_allclose(gr.numpy(), rg.numpy(), rtol=1e-10, atol=1e-15)
+    p = torch.softmax(t, 1)
+    v, sc, gr = L.pair_formula("ekl", s, p, 1.0)
+    rl, rg = CR.ensemble_kl(s, p)
+    np.testing.assert_allclose(float(v.sum() * sc), float(rl), rtol=1e-12)
+    np.testing.assert_allclose(gr.numpy(), rg.numpy(), rtol=1e-10, atol=1e-15)
+
+
+RED = [c for c in L.cases_of(*L.REDUCTIONS) if "chain" in c]
+
+
+def test_every_reduction_family_has_a_chain_row_and_the_mse_rows_bite():
+    for op in L.REDUCTIONS:
+        assert any(c["op"] == op for c in RED), f"{op}: no row says what a single fp32 chain would do"
+    assert all("chain" in c for c in L.cases_of("hint_mse"))
+    assert sum(c["chain"][0] == "bites" for c in L.cases_of("hint_mse")) >= 3
+
+
+@pytest.mark.parametrize("c", RED, ids=L.ids(RED))
+def test_single_fp32_chain_against_the_bound(c):
+    """A row that says it bites: ONE fp32 chain over the row's addends misses the bound the kernel's two-stage reduction is held
+    to, so the row fails a kernel that loses the low bits.  A row that says a single chain stays inside the bound: asserted too,
+    so the table cannot claim more than the data give."""
+    role, arg = c["chain"]
+    inp, ref = L.build(c)
+    err, bound = L.single_chain(c, ref)
+    print(f"{c['id']}: single-chain error / bound = {err / max(bound, 1e-300):.3g}")
+    if role == "bites":
+        assert err > bound, f"{c['id']}: single-chain error {err:.3e} is inside the bound {bound:.3e}: the row proves nothing"
+    elif role == "inside":
+        assert isinstance(arg, str) and arg
+        assert err <= bound, f"{c['id']}: single-chain error {err:.3e} exceeds the bound {bound:.3e}: the row bites, say so"
+    else:
+        assert role == "marginal" and isinstance(arg, str) and arg

@@ -1042,7 +1042,8 @@ def test_losses_bf16_large_vs_oracle(K):
 @pytest.mark.parametrize("Cc", [32, 33, 64, 100])
 def test_logit_losses_channels_last_any_class_count(K, Cc):
     """KLDiv / CE / confusion on channels-last fp32 logits with class counts on both sides of what the NHWC fast paths stage in
-    the default 64 KiB of dynamic LDS (KLDiv: 2 x 256 x C floats, C <= 32; CE: C <= 64; confusion: C <= 51): larger counts -- the
+    the default 64 KiB of dynamic LDS (KLDiv: 2 x 256 x C floats, C <= 32; CE: C <= 64; confusion: 256 x C floats + C x C counters,
+    C <= 53; tests/_loss_dispatch_cases.py restates each gate and test_loss_dispatch_gpu.py asserts both sides): larger counts -- the
     100-class CIFAR heads -- must take the strided kernels, not fail at launch."""
     N, H, W = 2, 9, 13
     s, t = rnd(N, Cc, H, W), rnd(N, Cc, H, W)
