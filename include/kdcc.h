@@ -679,6 +679,40 @@ typedef struct kd_radam_tensor {
 } kd_radam_tensor;
 int kd_radam_step_multi(const kd_radam_tensor *ts, int32_t count, kd_stream_t stream);
 
+/* The steps of torch.optim.SGD, torch.optim.Adam and the reference's AdamW for many tensors in one launch (one launch per 72 /
+ * 48 / 53 tensors), batched like kd_radam_step_multi: `ts` is a HOST array, per-tensor hyper-parameters and step counts, nothing
+ * copied to the device besides the kernel arguments, no allocation, no sync (the call may be captured).  fp32, contiguous;
+ * 16 bytes per lane where p, g and the state of a tensor are all 16-byte aligned, scalar otherwise, same value either way.
+ * The scalar constants (1 - beta^step, lr / bias_correction1, sqrt(bias_correction2), the scheduled lr, 1 - dampening ...) are
+ * computed here in double, as the Python of torch.optim and of the reference computes them, and rounded to float once.
+ *
+ * KD_OPT_SGD (torch/optim/sgd.py, _single_tensor_sgd); state[0] = momentum_buffer, touched only if momentum != 0:
+ *   g = -g if MAXIMIZE;  g += weight_decay * p if weight_decay != 0
+ *   if momentum != 0:  buf = g if FIRST (the buffer does not exist yet: it is written, never read)
+ *                      else buf = momentum * buf + (1 - dampening) * g;   g = g + momentum * buf if NESTEROV else buf
+ *   p -= lr * g
+ * KD_OPT_ADAM (torch/optim/adam.py, _single_tensor_adam, not capturable); state = exp_avg, exp_avg_sq, max_exp_avg_sq (AMSGRAD):
+ *   g = -g if MAXIMIZE;  g += weight_decay * p if weight_decay != 0
+ *   m += (1 - beta1) * (g - m);  v = beta2 * v + (1 - beta2) * g * g;  if AMSGRAD: vmax = max(vmax, v), used in place of v
+ *   p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps),   bc1 = 1 - beta1^step, bc2 = 1 - beta2^step
+ * KD_OPT_ADAMW_REF (the reference's AdamW, utils/optim/radam.py:179-250); state = exp_avg, exp_avg_sq:
+ *   v = beta2 * v + (1 - beta2) * g * g;  m = beta1 * m + (1 - beta1) * g
+ *   slr = warmup > step ? 1e-8 + step * lr / warmup : lr
+ *   p += -weight_decay * slr * p if weight_decay != 0;  p += -(slr * sqrt(bc2) / bc1) * m / (sqrt(v) + eps)
+ * `step` is the per-tensor step count after the increment (unused by KD_OPT_SGD). */
+enum { KD_OPT_SGD = 0, KD_OPT_ADAM = 1, KD_OPT_ADAMW_REF = 2 };
+enum { KD_OPT_FIRST = 1, KD_OPT_NESTEROV = 2, KD_OPT_AMSGRAD = 4, KD_OPT_MAXIMIZE = 8 };
+typedef struct kd_optim_tensor {
+    float *p; const float *g; float *state[3];
+    int64_t n, step;
+    int32_t flags, reserved;
+    double lr, weight_decay, eps, momentum, dampening, beta1, beta2, warmup;
+} kd_optim_tensor;
+int kd_optim_step_multi(int32_t rule, const kd_optim_tensor *ts, int32_t count, kd_stream_t stream);
+/* How kd_optim_step_multi cuts its work (host side only; for tests that want a case either side of each edge): the tensors one
+ * launch of `rule` holds and the elements one block steps. */
+int kd_optim_launch_shape(int32_t rule, int32_t *max_tensors, int32_t *block_elems);
+
 /* ------------------------------------------------- Gated-SCNN shape stream, backward (models/gscnn/gscnn.py:269-314 under autograd)
  * The forward kernels (kd_gated_conv, kd_pointwise_small, kd_edge_attention, kd_edge_aspp) fuse per-pixel algebra; loss.backward()
  * (trainer/layerwise_trainer.py:235) through them -- `aspp` hints, loss terms on the logits, trainable shape-stream parameters --

@@ -24,6 +24,8 @@ def build_tuning():
 KD_F32, KD_BF16 = 0, 1
 KD_PACK_FWD, KD_PACK_DGRAD = 0, 1
 KD_ERR_UNSUPPORTED = -2
+KD_OPT_SGD, KD_OPT_ADAM, KD_OPT_ADAMW_REF = 0, 1, 2
+KD_OPT_FIRST, KD_OPT_NESTEROV, KD_OPT_AMSGRAD, KD_OPT_MAXIMIZE = 1, 2, 4, 8
 
 c_int, c_i64, c_f, c_vp, c_sz = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
 
@@ -50,6 +52,12 @@ class DwDesc(C.Structure):
 class RadamTensor(C.Structure):
     _fields_ = [("p", c_vp), ("g", c_vp), ("exp_avg", c_vp), ("exp_avg_sq", c_vp), ("n", c_i64), ("step", c_int),
                 ("lr", c_f), ("beta1", c_f), ("beta2", c_f), ("eps", c_f), ("weight_decay", c_f)]
+
+
+class OptimTensor(C.Structure):
+    _fields_ = [("p", c_vp), ("g", c_vp), ("state", c_vp * 3), ("n", c_i64), ("step", c_i64), ("flags", c_int), ("reserved", c_int),
+                ("lr", C.c_double), ("weight_decay", C.c_double), ("eps", C.c_double), ("momentum", C.c_double),
+                ("dampening", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("warmup", C.c_double)]
 
 
 class DwEpilogue(C.Structure):
@@ -181,6 +189,8 @@ _SIGS = {
     "kd_confusion": (c_int, [_P(View3), c_vp, c_int, c_int, c_i64, c_vp, c_int, c_vp]),
     "kd_radam_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_f, c_f, c_f, c_f, c_f, c_vp]),
     "kd_radam_step_multi": (c_int, [_P(RadamTensor), c_int, c_vp]),
+    "kd_optim_step_multi": (c_int, [c_int, _P(OptimTensor), c_int, c_vp]),
+    "kd_optim_launch_shape": (c_int, [c_int, _P(c_int), _P(c_int)]),
     "kd_small_linear": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_i64, c_int, c_int, c_vp, c_int, c_vp]),
     "kd_upsample_bilinear_bwd": (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp,
                                          c_sz, c_vp]),

@@ -1797,6 +1797,47 @@ def radam_step(p, g, m, v, step, lr, beta1, beta2, eps, weight_decay):
         torch.autograd.graph.increment_version(t)
 
 
+OPT_RULES = {"sgd": _lib.KD_OPT_SGD, "adam": _lib.KD_OPT_ADAM, "adamw_ref": _lib.KD_OPT_ADAMW_REF}
+OPT_FIRST, OPT_NESTEROV, OPT_AMSGRAD, OPT_MAXIMIZE = _lib.KD_OPT_FIRST, _lib.KD_OPT_NESTEROV, _lib.KD_OPT_AMSGRAD, _lib.KD_OPT_MAXIMIZE
+
+
+def optim_launch_shape(rule):
+    """(tensors one launch of `rule` holds, elements one block steps) of kd_optim_step_multi."""
+    mt, be = C.c_int32(), C.c_int32()
+    check(_lib.lib().kd_optim_launch_shape(OPT_RULES[rule] if isinstance(rule, str) else int(rule), C.byref(mt), C.byref(be)),
+          "kd_optim_launch_shape")
+    return mt.value, be.value
+
+
+def optim_step_multi(rule, items):
+    """One optimizer step for many tensors (kd_optim_step_multi, csrc/optim.hip): rule "sgd" (torch.optim.SGD), "adam"
+    (torch.optim.Adam) or "adamw_ref" (the reference's AdamW, utils/optim/radam.py:179-250), the arithmetic stated in include/kdcc.h.
+    items: [(p, g, states, step, flags, hp), ...]
+      states  the state tensors the rule updates in place: sgd (momentum_buffer,) or (); adam (exp_avg, exp_avg_sq[,
+              max_exp_avg_sq]); adamw_ref (exp_avg, exp_avg_sq)
+      step    the tensor's step count after the increment (sgd: unused)
+      flags   OPT_FIRST (sgd: the momentum buffer is new, it is written and not read) | OPT_NESTEROV | OPT_AMSGRAD | OPT_MAXIMIZE
+      hp      (lr, weight_decay, eps, momentum, dampening, beta1, beta2, warmup): Python floats, they reach the library as doubles
+    Runs on the current stream; allocates, copies and synchronises nothing."""
+    if not items:
+        return
+    rule = OPT_RULES[rule] if isinstance(rule, str) else int(rule)
+    arr = (_lib.OptimTensor * len(items))()
+    f32 = torch.float32
+    for i, (p, g, states, step, flags, hp) in enumerate(items):
+        n = p.numel()
+        for t in (p, g, *states):
+            if not t.is_cuda:
+                raise _lib.KdccError("kdcc kernels need device tensors (there is no CPU fallback)")
+            if t.dtype != f32 or not t.is_contiguous() or t.numel() != n:
+                raise TypeError("optim_step_multi: fp32 contiguous tensors of equal size required")
+        sp = [s.data_ptr() for s in states]
+        arr[i] = _lib.OptimTensor(p.data_ptr(), g.data_ptr(), (_lib.c_vp * 3)(*sp), n, int(step), int(flags), 0, *hp)
+    check(_lib.lib().kd_optim_step_multi(rule, arr, len(items), stream_ptr()), "kd_optim_step_multi")
+    # the kernel wrote through raw pointers: tell autograd / version-keyed caches (engine weight packs) about it
+    torch.autograd.graph.increment_version([t for (p, _, states, *_rest) in items for t in (p, *states)])
+
+
 # ------------------------------------------------------------------------- HRNetV2 + OCR (csrc/hrnet_ops.hip)
 def _f32_views(name, *ts):
     for t in ts:
