@@ -50,8 +50,9 @@ void kd_note_kernel(const char *name);
 // The plumbing dispatchers (trunk_ops.hip, bwd_ops.hip, small_ops.hip) say which device kernel they picked through a slot of
 // their own (kd_debug_last_plumbing_kernel): one thread-local pointer, stored and nothing else -- no counters, no table, and
 // the conv log above (its readers attribute time and assert exact name sets by it) never sees these names.  `name` is a string
-// literal, one per distinguishable dispatch branch; tests/test_plumbing_host.py requires a test case for every one of them.
-// The launchers of losses.hip use the same slot; tests/test_loss_dispatch_host.py holds them to the same rule.
+// with static storage (the slot keeps the pointer), one per distinguishable dispatch branch: a literal in the three files above,
+// tests/test_plumbing_host.py requires a test case for every one of them.  The launchers of losses.hip use the same slot with the
+// names of loss_select.h's table (loss_kernel_name); tests/test_loss_dispatch_host.py holds them to the same rule.
 void kd_note_plumbing(const char *name);
 #define KD_NOTE_PLUMBING(name) kd_note_plumbing(name)
 

@@ -8,10 +8,9 @@
 #include <type_traits>
 
 #include "kd_common.h"
+#include "loss_select.h"
 
 namespace {
-
-constexpr int MAX_BLOCKS = 2048;
 
 // K per-thread sums -> out[q][blockIdx.x], q < K: a wave reduction, then the four waves added in a fixed order
 template <int K> __device__ __forceinline__ void block_partials(const double (&v)[K], double *const (&out)[K])
@@ -184,7 +183,7 @@ __global__ __launch_bounds__(256) void ce2d_nhwc_kernel(const TX *__restrict__ x
 // three kernels (2.3 ms per step).  Here a pixel's C logits are interpolated in registers -- the expression tree of
 // upsample_flat4_kernel: horizontal blend of each source row, then the vertical blend -- from a low-resolution patch staged in LDS: a
 // workgroup takes 256 consecutive output pixels of one output row, i.e. <= UP_NW source columns of two source rows.
-constexpr int UP_NW = 160;
+constexpr int UP_NW = LOSS_UP_NW;   // one value: the header refuses what would not fit, the kernels size their staged patch by it
 
 struct UpGeom { int N, h, w, C, H, W; float sh, sw, oh, ow; };
 
@@ -309,9 +308,9 @@ __global__ __launch_bounds__(256) void ce2d_up_kernel(const float *__restrict__ 
 
 // ---- the analysis step's logged metrics from both low-resolution logit tensors (trainer/analysis_trainer.py:55-81) ---------------------
 // One pass: CE(student), CE(teacher), sum (s - t)^2 and both confusion matrices (argmax = first maximum, as confusion_nhwc_kernel).
-// Partials: [ce_s | ce_t | count | sq] x MET_MAX_BLOCKS doubles inside kd_loss_workspace's 2 * MAX_BLOCKS; the histograms are LDS
+// Partials: [ce_s | ce_t | count | sq] x MET_MAX_BLOCKS doubles inside kd_loss_workspace's 2 * LOSS_MAX_BLOCKS; the histograms are LDS
 // integer atomics flushed once per block (exact in any order).
-constexpr int MET_MAX_BLOCKS = MAX_BLOCKS / 2;
+constexpr int MET_MAX_BLOCKS = LOSS_MET_MAX_BLOCKS;   // one value: the header caps the grid, the kernels stride their partial arrays by it
 
 template <int CT>
 __global__ __launch_bounds__(256) void logit_metrics_up_kernel(const float *__restrict__ s, const float *__restrict__ t,
@@ -625,23 +624,6 @@ inline M3 m3(const kd_mview3 *v)
     return M3{v->ptr, v->dtype, (long long)v->sN, (long long)v->sC, (long long)v->sP};
 }
 inline bool ok_dt(int d) { return d == KD_F32 || d == KD_BF16; }
-inline int blocks_for(long long total)
-{
-    long long b = (total + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > MAX_BLOCKS ? MAX_BLOCKS : b));
-}
-inline bool dense_same(const kd_view3 *a, const kd_view3 *b, const kd_mview3 *g, int N, int C, long long P)
-{
-    // every operand covers exactly N*C*P elements with the same (dense) strides
-    auto dense = [&](long long sN, long long sC, long long sP) {
-        return (sC == 1 && sP == C && sN == (long long)C * P) || (sP == 1 && sC == P && sN == (long long)C * P);
-    };
-    if (!dense(a->sN, a->sC, a->sP)) return false;
-    if (a->sN != b->sN || a->sC != b->sC || a->sP != b->sP || a->dtype != b->dtype) return false;
-    if (g && (g->sN != a->sN || g->sC != a->sC || g->sP != a->sP || g->dtype != a->dtype)) return false;
-    if (!kd_aligned16(a->ptr) || !kd_aligned16(b->ptr) || (g && !kd_aligned16(g->ptr))) return false;
-    return ((long long)N * C * P) % 8 == 0;
-}
 
 // ---- upstream-gradient scale of a fused loss gradient ---------------------------------------------------------------------
 // autograd hands the loss Function d(total)/d(loss) as a device scalar; for `loss = sum of hint losses` (layerwise_trainer.py:
@@ -845,7 +827,7 @@ __global__ __launch_bounds__(256) void pair_up_kernel(const float *__restrict__ 
 //   a  = (1 - p_y')^gamma            (every pixel, ignored ones included)
 //   ce = alpha_y * -log p_y           (valid pixels; 0 at ignored ones) and w = alpha_y (valid pixels)
 // The three sums go to fixed-order partials; the finishing block writes stats = (sum a, sum ce, sum w) and the loss.
-constexpr int FOCAL_MAX_BLOCKS = 2 * MAX_BLOCKS / 3;    // three partial arrays inside kd_loss_workspace's 2 * MAX_BLOCKS doubles
+constexpr int FOCAL_MAX_BLOCKS = LOSS_FOCAL_MAX_BLOCKS;    // (one value, as MET_MAX_BLOCKS) three partial arrays inside kd_loss_workspace's 2 * LOSS_MAX_BLOCKS doubles
 
 // x^g for x in [0, 1], g >= -1 through the hardware exp / log (powf is a long library sequence); 0^0 = 1 like torch.pow
 __device__ __forceinline__ float focal_pow(float x, float g)
@@ -995,16 +977,6 @@ __global__ __launch_bounds__(256) void focal_grad_kernel(V3 x, const int64_t *__
 //    rank(c) = #{c' : v[c'] > v[c] or (v[c'] == v[c] and c' < c)}, kept iff rank < K (ties: the lower channel first).
 //    Writes the (N,C) mask and the sample's sum over kept channels of sum_p (s-t)^2.
 // 3. topk_grad_kernel: grad = gscale * mask * (s - t).
-constexpr int TOPK_MAX_C = 4096;      // the select block keeps C doubles in LDS (32 KiB)
-constexpr int TOPK_MAX_CHUNKS = 64;
-
-static int topk_chunks(int N, int C, long long P)
-{
-    const long long groups = (long long)N * ((C + 63) / 64);
-    long long ch = 2048 / (groups > 0 ? groups : 1);
-    ch = ch < 1 ? 1 : (ch > TOPK_MAX_CHUNKS ? TOPK_MAX_CHUNKS : ch);
-    return (int)(ch > P ? P : ch);
-}
 
 __global__ __launch_bounds__(256) void topk_sums_kernel(V3 s, V3 t, int C, long long P, long long per_chunk, int nchunk, double *pt2, double *pd2)
 {
@@ -1120,7 +1092,6 @@ __global__ __launch_bounds__(256) void topk_grad_kernel(V3 s, V3 t, M3 g, const 
 //   kldm_nhwc_kernel dense NHWC with few classes and many pixels: 256 pixels per block staged through LDS, one pixel per thread;
 //   kldm_kernel      any strides / any C: one pixel per thread, the operands re-read from cache as pair_kernel does.
 struct MT { V3 t[KD_MULTI_MAX]; float w[KD_MULTI_MAX]; int n; };
-constexpr int MT_MAX_BLOCKS = 2 * MAX_BLOCKS / 3;      // kd / ce / count partials inside kd_loss_workspace's 2 * MAX_BLOCKS doubles
 
 __device__ __forceinline__ float wave_max(float v)
 {
@@ -1499,15 +1470,26 @@ __global__ __launch_bounds__(256) void mt_finish_kernel(const double *pkd, const
 
 }  // namespace
 
-extern "C" size_t kd_loss_workspace(int32_t N, int32_t C, int64_t P)
+// ---- the launchers ---------------------------------------------------------------------------------------------------------------
+// Each entry point checks its arguments, asks the selector of its family (loss_select.h) for the kernel, the grid and the dynamic
+// LDS, notes the kernel's name once and switches over it.
+static_assert((int)PAIR_KLD == LOSS_KLD && (int)PAIR_JSD == LOSS_JSD && (int)PAIR_EKL == LOSS_EKL,
+              "loss_select.h numbers the two-operand criteria like the kernels' template argument");
+
+namespace {
+// A missing kernel is an error, never a silent no-op: a value the family's selector should not return, or one this file was not
+// taught to launch, ends the call here.
+int no_launch(const char *who, const LossSel &sel)
 {
-    // partial sums (+ counts) for up to MAX_BLOCKS blocks, the weighted loss' per-sample weight sums,
-    // and its (P chunks x channel blocks x N) partials
-    const size_t wh_blocks = (size_t)64 * ((C + 255) / 256) * (size_t)N;
-    const size_t nb = wh_blocks > (size_t)MAX_BLOCKS ? wh_blocks : (size_t)MAX_BLOCKS;
-    (void)P;
-    return 2 * nb * sizeof(double) + (size_t)N * sizeof(float) + 64;
+    kd_set_error("%s: no launch for kernel %d", who, (int)sel.kernel);
+    return KD_ERR_UNSUPPORTED;
 }
+// the function to launch for `k`, from (value, function of one signature) pairs; null if k is none of them
+template <typename F> F launch_of(LossKernel) { return nullptr; }
+template <typename F, typename... R> F launch_of(LossKernel k, LossKernel ka, F a, R... rest) { return k == ka ? a : launch_of<F>(k, rest...); }
+}  // namespace
+
+extern "C" size_t kd_loss_workspace(int32_t N, int32_t C, int64_t P) { return loss_workspace_bytes(N, C, P); }
 
 #define KD_LOSS_COMMON(who)                                                                                          \
     KD_REQUIRE(s && t && s->ptr && t->ptr && loss && workspace, KD_ERR_INVALID, who ": null argument");              \
@@ -1516,62 +1498,42 @@ extern "C" size_t kd_loss_workspace(int32_t N, int32_t C, int64_t P)
     KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, P), KD_ERR_WORKSPACE, who ": workspace too small");        \
     KD_REQUIRE(((uintptr_t)workspace & 7) == 0, KD_ERR_INVALID, who ": workspace must be 8-B aligned")
 
-// ---- kd_kldiv / kd_jsdiv / kd_ensemble_kldiv: the entry point sets the scales, this picks the kernel -------------------------------
+// ---- kd_kldiv / kd_jsdiv / kd_ensemble_kldiv: the entry point sets the scales ----------------------------------------------------
+namespace {
+using PairNhwcLaunch = void (*)(const LossSel &, hipStream_t, const void *, const void *, void *, int, long long, float, float, double *);
+template <int K, typename TS, typename TT, typename TG>
+void pair_nhwc_launch(const LossSel &sel, hipStream_t st, const void *s, const void *t, void *g, int C, long long npix, float invT, float gscale,
+                      double *partial)
+{
+    hipLaunchKernelGGL((pair_nhwc_kernel<K, TS, TT, TG>), dim3(sel.blocks), dim3(256), sel.lds, st, (const TS *)s, (const TT *)t, (TG *)g, C, npix,
+                       invT, gscale, partial);
+}
+// in the order of LK_PAIR_NHWC .. LK_PAIR_NHWC_LAST: the kind, then the storage of s, t and the gradient, fp32 before bf16
+#define KD_PAIR_FORMS(K)                                                                                                           \
+    pair_nhwc_launch<K, float, float, float>, pair_nhwc_launch<K, float, float, bf16_t>, pair_nhwc_launch<K, float, bf16_t, float>, \
+    pair_nhwc_launch<K, float, bf16_t, bf16_t>, pair_nhwc_launch<K, bf16_t, float, float>, pair_nhwc_launch<K, bf16_t, float, bf16_t>, \
+    pair_nhwc_launch<K, bf16_t, bf16_t, float>, pair_nhwc_launch<K, bf16_t, bf16_t, bf16_t>
+const PairNhwcLaunch pair_nhwc_launches[] = {KD_PAIR_FORMS(PAIR_KLD), KD_PAIR_FORMS(PAIR_JSD), KD_PAIR_FORMS(PAIR_EKL)};
+#undef KD_PAIR_FORMS
+static_assert(sizeof(pair_nhwc_launches) / sizeof(pair_nhwc_launches[0]) == LK_PAIR_NHWC_LAST - LK_PAIR_NHWC + 1, "a launch per channels-last form");
+}  // namespace
+
 static int pair_impl(const char *who, int kind, const kd_view3 *s, const kd_view3 *t, float invT, int32_t N, int32_t C, int64_t P,
                      float *loss, const kd_mview3 *grad, float gscale, double loss_scale, void *workspace, kd_stream_t stream)
 {
     double *partial = (double *)workspace;
-    const int nb = blocks_for((long long)N * P);
     hipStream_t st = (hipStream_t)stream;
-    auto nhwc = [&](long long sN, long long sC, long long sP) { return sC == 1 && sP == C && (sN == (long long)C * P || N == 1); };
-    // (the fast path stages 2 x 256 x C floats in dynamic LDS; it stays inside the 64-KiB default limit, larger class
-    // counts -- e.g. the 100-class CIFAR heads -- take the strided kernel)
-    const size_t lds = (size_t)2 * 256 * C * sizeof(float);
-    const bool fast = lds <= 65536 && nhwc(s->sN, s->sC, s->sP) && nhwc(t->sN, t->sC, t->sP) && (!grad || nhwc(grad->sN, grad->sC, grad->sP));
-    if (fast) {
-        const long long npix = (long long)N * P;
-        void *gp = grad ? grad->ptr : nullptr;
-        const int gdt = grad ? grad->dtype : s->dtype;
-#define KD_PAIR(K, TS, TT, TG) hipLaunchKernelGGL((pair_nhwc_kernel<K, TS, TT, TG>), dim3(nb), dim3(256), lds, st, (const TS *)s->ptr, \
-                                                  (const TT *)t->ptr, (TG *)gp, C, npix, invT, gscale, partial)
-        // (N0 .. N7: the note of each storage-type form, in the order of the chain; a macro argument is a statement, so that
-        // every literal stands in a KD_NOTE_PLUMBING of its own next to the launch it names)
-#define KD_PAIR_DT(K, N0, N1, N2, N3, N4, N5, N6, N7)                                                                 \
-        if (s->dtype == KD_F32 && t->dtype == KD_F32 && gdt == KD_F32) { N0; KD_PAIR(K, float, float, float); }       \
-        else if (s->dtype == KD_F32 && t->dtype == KD_BF16 && gdt == KD_F32) { N1; KD_PAIR(K, float, bf16_t, float); } \
-        else if (s->dtype == KD_BF16 && t->dtype == KD_BF16 && gdt == KD_BF16) { N2; KD_PAIR(K, bf16_t, bf16_t, bf16_t); } \
-        else if (s->dtype == KD_BF16 && t->dtype == KD_F32 && gdt == KD_BF16) { N3; KD_PAIR(K, bf16_t, float, bf16_t); } \
-        else if (s->dtype == KD_F32 && t->dtype == KD_F32) { N4; KD_PAIR(K, float, float, bf16_t); }                  \
-        else if (s->dtype == KD_F32 && t->dtype == KD_BF16) { N5; KD_PAIR(K, float, bf16_t, bf16_t); }                \
-        else if (s->dtype == KD_BF16 && t->dtype == KD_BF16) { N6; KD_PAIR(K, bf16_t, bf16_t, float); }               \
-        else { N7; KD_PAIR(K, bf16_t, float, float); }
-        if (kind == PAIR_KLD) {
-            KD_PAIR_DT(PAIR_KLD, KD_NOTE_PLUMBING("pair_nhwc_kernel<kld,f32,f32,f32>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<kld,f32,bf16,f32>"),
-                       KD_NOTE_PLUMBING("pair_nhwc_kernel<kld,bf16,bf16,bf16>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<kld,bf16,f32,bf16>"),
-                       KD_NOTE_PLUMBING("pair_nhwc_kernel<kld,f32,f32,bf16>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<kld,f32,bf16,bf16>"),
-                       KD_NOTE_PLUMBING("pair_nhwc_kernel<kld,bf16,bf16,f32>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<kld,bf16,f32,f32>"))
-        } else if (kind == PAIR_JSD) {
-            KD_PAIR_DT(PAIR_JSD, KD_NOTE_PLUMBING("pair_nhwc_kernel<jsd,f32,f32,f32>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<jsd,f32,bf16,f32>"),
-                       KD_NOTE_PLUMBING("pair_nhwc_kernel<jsd,bf16,bf16,bf16>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<jsd,bf16,f32,bf16>"),
-                       KD_NOTE_PLUMBING("pair_nhwc_kernel<jsd,f32,f32,bf16>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<jsd,f32,bf16,bf16>"),
-                       KD_NOTE_PLUMBING("pair_nhwc_kernel<jsd,bf16,bf16,f32>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<jsd,bf16,f32,f32>"))
-        } else {
-            KD_PAIR_DT(PAIR_EKL, KD_NOTE_PLUMBING("pair_nhwc_kernel<ekl,f32,f32,f32>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<ekl,f32,bf16,f32>"),
-                       KD_NOTE_PLUMBING("pair_nhwc_kernel<ekl,bf16,bf16,bf16>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<ekl,bf16,f32,bf16>"),
-                       KD_NOTE_PLUMBING("pair_nhwc_kernel<ekl,f32,f32,bf16>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<ekl,f32,bf16,bf16>"),
-                       KD_NOTE_PLUMBING("pair_nhwc_kernel<ekl,bf16,bf16,f32>"), KD_NOTE_PLUMBING("pair_nhwc_kernel<ekl,bf16,f32,f32>"))
-        }
-#undef KD_PAIR_DT
-#undef KD_PAIR
+    const LossSel sel = loss_select_pair((LossPair)kind, s, t, grad, N, C, P);
+    KD_NOTE_PLUMBING(loss_kernel_name(sel.kernel));
+    if (sel.kernel >= LK_PAIR_NHWC && sel.kernel <= LK_PAIR_NHWC_LAST) {
+        pair_nhwc_launches[sel.kernel - LK_PAIR_NHWC](sel, st, s->ptr, t->ptr, grad ? grad->ptr : nullptr, C, (long long)N * P, invT, gscale, partial);
     } else {
-        if (kind == PAIR_KLD) KD_NOTE_PLUMBING("pair_kernel<kld>");
-        else if (kind == PAIR_JSD) KD_NOTE_PLUMBING("pair_kernel<jsd>");
-        else KD_NOTE_PLUMBING("pair_kernel<ekl>");
-        auto fn = kind == PAIR_KLD ? pair_kernel<PAIR_KLD> : kind == PAIR_JSD ? pair_kernel<PAIR_JSD> : pair_kernel<PAIR_EKL>;
-        hipLaunchKernelGGL(fn, dim3(nb), dim3(256), 0, st, v3(s), v3(t), m3(grad), invT, gscale, N, C, (long long)P, partial);
+        auto fn = launch_of(sel.kernel, LK_PAIR_KLD, pair_kernel<PAIR_KLD>, LK_PAIR_JSD, pair_kernel<PAIR_JSD>, LK_PAIR_EKL, pair_kernel<PAIR_EKL>);
+        if (!fn) return no_launch(who, sel);
+        hipLaunchKernelGGL(fn, dim3(sel.blocks), dim3(256), 0, st, v3(s), v3(t), m3(grad), invT, gscale, N, C, (long long)P, partial);
     }
     KD_CHECK_LAUNCH(who);
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, nb, loss_scale, (const double *)nullptr, loss);
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, sel.blocks, loss_scale, (const double *)nullptr, loss);
     KD_CHECK_LAUNCH(who);
     return KD_OK;
 }
@@ -1587,246 +1549,6 @@ extern "C" int kd_kldiv(const kd_view3 *s, const kd_view3 *t, float temperature,
     return pair_impl("kd_kldiv", PAIR_KLD, s, t, 1.f / temperature, N, C, P, loss, grad, gscale, scale, workspace, stream);
 }
 
-extern "C" int kd_hint_mse(const kd_view3 *s, const kd_view3 *t, float num_classes, int32_t N, int32_t C, int64_t P,
-                           float *loss, const kd_mview3 *grad, float grad_scale, void *workspace, size_t workspace_bytes,
-                           kd_stream_t stream)
-{
-    KD_LOSS_COMMON("kd_hint_mse");
-    double *partial = (double *)workspace;
-    const long long numel = (long long)N * C * P;
-    const float gscale = grad_scale * 2.f * num_classes / (float)numel;
-    hipStream_t st = (hipStream_t)stream;
-    int nb;
-    if (dense_same(s, t, grad, N, C, P)) {
-        nb = blocks_for(numel / 8);
-        if (s->dtype == KD_BF16) {
-            KD_NOTE_PLUMBING("mse_vec_kernel<bf16>");
-            hipLaunchKernelGGL(mse_vec_kernel<bf16_t>, dim3(nb), dim3(256), 0, st, (const bf16_t *)s->ptr, (const bf16_t *)t->ptr,
-                               (bf16_t *)(grad ? grad->ptr : nullptr), gscale, numel / 8, partial);
-        } else {
-            KD_NOTE_PLUMBING("mse_vec_kernel<f32>");
-            hipLaunchKernelGGL(mse_vec_kernel<float>, dim3(nb), dim3(256), 0, st, (const float *)s->ptr, (const float *)t->ptr,
-                               (float *)(grad ? grad->ptr : nullptr), gscale, numel / 8, partial);
-        }
-    } else {
-        KD_NOTE_PLUMBING("mse_strided_kernel");
-        nb = blocks_for(numel);
-        hipLaunchKernelGGL(mse_strided_kernel, dim3(nb), dim3(256), 0, st, v3(s), v3(t), m3(grad), gscale, N, C, (long long)P,
-                           s->sC == 1 ? 1 : 0, partial);
-    }
-    KD_CHECK_LAUNCH("kd_hint_mse");
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, nb, (double)num_classes / (double)numel,
-                       (const double *)nullptr, loss);
-    KD_CHECK_LAUNCH("kd_hint_mse(finish)");
-    return KD_OK;
-}
-
-extern "C" int kd_weighted_hint_mse(const kd_view3 *s, const kd_view3 *t, const float *w, int32_t w_per_sample, int32_t N,
-                                    int32_t C, int64_t P, float *loss, const kd_mview3 *grad, float grad_scale, void *workspace,
-                                    size_t workspace_bytes, kd_stream_t stream)
-{
-    KD_LOSS_COMMON("kd_weighted_hint_mse");
-    KD_REQUIRE(w, KD_ERR_INVALID, "kd_weighted_hint_mse: null weight");
-    hipStream_t st = (hipStream_t)stream;
-    const int chunks = (int)(P < 64 ? P : 64);
-    const long long per_chunk = (P + chunks - 1) / chunks;
-    const dim3 grid((unsigned)chunks, (unsigned)((C + 255) / 256), (unsigned)N);
-    const size_t nblocks = (size_t)grid.x * grid.y * grid.z;
-    double *partial = (double *)workspace;
-    float *wsum = (float *)((char *)workspace + 2 * (nblocks > (size_t)MAX_BLOCKS ? nblocks : (size_t)MAX_BLOCKS) * sizeof(double));
-    KD_NOTE_PLUMBING("whmse_kernel");
-    hipLaunchKernelGGL(wsum_kernel, dim3(N), dim3(64), 0, st, w, w_per_sample, N, C, wsum);
-    hipLaunchKernelGGL(whmse_kernel, grid, dim3(256), 0, st, v3(s), v3(t), m3(grad), w, w_per_sample, (const float *)wsum,
-                       grad_scale, N, C, (long long)P, per_chunk, partial);
-    KD_CHECK_LAUNCH("kd_weighted_hint_mse");
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, (int)nblocks, 1.0 / (double)N,
-                       (const double *)nullptr, loss);
-    KD_CHECK_LAUNCH("kd_weighted_hint_mse(finish)");
-    return KD_OK;
-}
-
-static int ce2d_impl(const char *who, const kd_view3 *x, const int64_t *target, const float *class_weight, int32_t sum_reduction, int32_t ignore_index,
-                     int32_t N, int32_t C, int64_t P, float *loss, void *workspace, size_t workspace_bytes, kd_stream_t stream)
-{
-    KD_REQUIRE(x && x->ptr && target && loss && workspace, KD_ERR_INVALID, "%s: null argument", who);
-    KD_REQUIRE(ok_dt(x->dtype) && N > 0 && C > 0 && P > 0, KD_ERR_INVALID, "%s: bad argument", who);
-    KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, P), KD_ERR_WORKSPACE, "%s: workspace too small", who);
-    double *partial = (double *)workspace, *count = partial + MAX_BLOCKS;
-    const int nb = blocks_for((long long)N * P);
-    hipStream_t st = (hipStream_t)stream;
-    if ((size_t)256 * C * sizeof(float) <= 65536 && x->sC == 1 && x->sP == C && (x->sN == (long long)C * P || N == 1)) {
-        const size_t lds = (size_t)256 * C * sizeof(float);   // <= the 64-KiB default dynamic-LDS limit, else the strided kernel
-        if (x->dtype == KD_F32) {
-            KD_NOTE_PLUMBING("ce2d_nhwc_kernel<f32>");
-            hipLaunchKernelGGL(ce2d_nhwc_kernel<float>, dim3(nb), dim3(256), lds, st, (const float *)x->ptr, target, ignore_index, C,
-                               (long long)N * P, partial, count, class_weight);
-        } else {
-            KD_NOTE_PLUMBING("ce2d_nhwc_kernel<bf16>");
-            hipLaunchKernelGGL(ce2d_nhwc_kernel<bf16_t>, dim3(nb), dim3(256), lds, st, (const bf16_t *)x->ptr, target, ignore_index,
-                               C, (long long)N * P, partial, count, class_weight);
-        }
-    } else {
-        KD_NOTE_PLUMBING("ce2d_kernel");
-        hipLaunchKernelGGL(ce2d_kernel, dim3(nb), dim3(256), 0, st, v3(x), target, ignore_index, N, C, (long long)P, partial, count, class_weight);
-    }
-    KD_CHECK_LAUNCH(who);
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, nb, 1.0, sum_reduction ? (const double *)nullptr : (const double *)count, loss);
-    KD_CHECK_LAUNCH(who);
-    return KD_OK;
-}
-
-extern "C" int kd_ce2d(const kd_view3 *x, const int64_t *target, int32_t ignore_index, int32_t N, int32_t C, int64_t P,
-                       float *loss, void *workspace, size_t workspace_bytes, kd_stream_t stream)
-{
-    return ce2d_impl("kd_ce2d", x, target, nullptr, 0, ignore_index, N, C, P, loss, workspace, workspace_bytes, stream);
-}
-
-extern "C" int kd_ce2d_weighted(const kd_view3 *x, const int64_t *target, const float *class_weight, int32_t sum_reduction, int32_t ignore_index,
-                                int32_t N, int32_t C, int64_t P, float *loss, void *workspace, size_t workspace_bytes, kd_stream_t stream)
-{
-    return ce2d_impl("kd_ce2d_weighted", x, target, class_weight, sum_reduction, ignore_index, N, C, P, loss, workspace, workspace_bytes, stream);
-}
-
-// ---- kd_ce2d_up / kd_kldiv_up / kd_jsdiv_up / kd_focal_up / kd_logit_metrics_up: from the low-resolution logits (see ce2d_up_kernel) ----
-static bool up_geom(UpGeom &g, int32_t N, int32_t h, int32_t w, int32_t C, int32_t H, int32_t W, int32_t align_corners)
-{
-    g.N = N; g.h = h; g.w = w; g.C = C; g.H = H; g.W = W;
-    g.sh = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
-    g.sw = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
-    g.oh = 0.f; g.ow = 0.f;
-    if (!align_corners) {
-        g.sh = (float)h / (float)H; g.sw = (float)w / (float)W;
-        g.oh = 0.5f * g.sh - 0.5f; g.ow = 0.5f * g.sw - 0.5f;
-    }
-    // source columns one 256-pixel chunk can touch (the kernels stage them in LDS)
-    return (int)(255.f * g.sw) + 3 <= UP_NW;
-}
-
-// What the five entry points share after their own argument checks: the workspace and resampling-ratio checks, the geometry, the
-// chunking (cpr chunks of 256 output pixels per output row) and the block count.  An entry point describes itself in an UpEntry:
-// its name for the messages, how many partials its finishing kernel's layout holds, whether its ratio message names the scale.
-struct UpEntry { const char *who; int max_blocks; bool say_scale; };
-struct UpPlan { UpGeom g; int cpr, nb; long long nchunks; };
-static int up_plan(UpPlan &u, const UpEntry &e, int32_t N, int32_t h, int32_t w, int32_t C, int32_t H, int32_t W, int32_t align_corners,
-                   size_t workspace_bytes)
-{
-    KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, (int64_t)H * W), KD_ERR_WORKSPACE, "%s: workspace too small", e.who);
-    if (!up_geom(u.g, N, h, w, C, H, W, align_corners)) {
-        if (e.say_scale)
-            kd_set_error("%s: a 256-pixel chunk spans more than %d source columns (scale %dx%d -> %dx%d): materialise the logits", e.who, UP_NW, h, w, H, W);
-        else
-            kd_set_error("%s: a 256-pixel chunk spans more than %d source columns: materialise the logits", e.who, UP_NW);
-        return KD_ERR_UNSUPPORTED;
-    }
-    u.cpr = (W + 255) / 256;
-    u.nchunks = (long long)N * H * u.cpr;
-    u.nb = (int)(u.nchunks < e.max_blocks ? u.nchunks : e.max_blocks);
-    return KD_OK;
-}
-
-extern "C" int kd_ce2d_up(const float *x_lo, const int64_t *target, int32_t ignore_index, int32_t N, int32_t h, int32_t w, int32_t C,
-                          int32_t H, int32_t W, int32_t align_corners, float *loss, void *workspace, size_t workspace_bytes,
-                          kd_stream_t stream)
-{
-    KD_REQUIRE(x_lo && target && loss && workspace, KD_ERR_INVALID, "kd_ce2d_up: null argument");
-    KD_REQUIRE(N > 0 && h > 0 && w > 0 && C > 0 && C <= 48 && H > 0 && W > 0, KD_ERR_INVALID, "kd_ce2d_up: bad argument (C <= 48: the staged patch fits 64 KiB of LDS)");
-    UpPlan u;
-    if (const int rc = up_plan(u, UpEntry{"kd_ce2d_up", MAX_BLOCKS, true}, N, h, w, C, H, W, align_corners, workspace_bytes)) return rc;
-    double *partial = (double *)workspace, *count = partial + MAX_BLOCKS;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t lds = (size_t)2 * UP_NW * C * sizeof(float);
-    if (C == 19) KD_NOTE_PLUMBING("ce2d_up_kernel<19>"); else KD_NOTE_PLUMBING("ce2d_up_kernel<0>");
-    hipLaunchKernelGGL(C == 19 ? ce2d_up_kernel<19> : ce2d_up_kernel<0>, dim3(u.nb), dim3(256), lds, st, x_lo, target, ignore_index, u.g, u.nchunks,
-                       u.cpr, partial, count);
-    KD_CHECK_LAUNCH("kd_ce2d_up");
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, u.nb, 1.0, (const double *)count, loss);
-    KD_CHECK_LAUNCH("kd_ce2d_up(finish)");
-    return KD_OK;
-}
-
-extern "C" int kd_kldiv_up(const float *s_lo, const float *t_lo, float temperature, int32_t N, int32_t h, int32_t w, int32_t C, int32_t H,
-                           int32_t W, int32_t align_corners, float *loss, void *workspace, size_t workspace_bytes, kd_stream_t stream)
-{
-    KD_REQUIRE(s_lo && t_lo && loss && workspace, KD_ERR_INVALID, "kd_kldiv_up: null argument");
-    KD_REQUIRE(N > 0 && h > 0 && w > 0 && C > 0 && C <= 24 && H > 0 && W > 0 && temperature > 0.f, KD_ERR_INVALID, "kd_kldiv_up: bad argument (C <= 24: two staged patches fit 64 KiB of LDS)");
-    UpPlan u;
-    if (const int rc = up_plan(u, UpEntry{"kd_kldiv_up", MAX_BLOCKS, false}, N, h, w, C, H, W, align_corners, workspace_bytes)) return rc;
-    double *partial = (double *)workspace;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t lds = (size_t)4 * UP_NW * C * sizeof(float);
-    if (C == 19) KD_NOTE_PLUMBING("pair_up_kernel<kld,19>"); else KD_NOTE_PLUMBING("pair_up_kernel<kld,0>");
-    hipLaunchKernelGGL((C == 19 ? pair_up_kernel<PAIR_KLD, 19> : pair_up_kernel<PAIR_KLD, 0>), dim3(u.nb), dim3(256), lds, st, s_lo, t_lo, u.g,
-                       1.f / temperature, u.nchunks, u.cpr, partial);
-    KD_CHECK_LAUNCH("kd_kldiv_up");
-    // 'mean' over N*C*P elements, then * T^2 * C  ==  T^2 / (N*P) * sum  (kd_kldiv)
-    const double scale = (double)temperature * temperature / ((double)N * (double)H * (double)W);
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, u.nb, scale, (const double *)nullptr, loss);
-    KD_CHECK_LAUNCH("kd_kldiv_up(finish)");
-    return KD_OK;
-}
-
-extern "C" int kd_jsdiv_up(const float *s_lo, const float *t_lo, float temperature, int32_t N, int32_t h, int32_t w, int32_t C, int32_t H,
-                           int32_t W, int32_t align_corners, float *loss, void *workspace, size_t workspace_bytes, kd_stream_t stream)
-{
-    KD_REQUIRE(s_lo && t_lo && loss && workspace, KD_ERR_INVALID, "kd_jsdiv_up: null argument");
-    KD_REQUIRE(N > 0 && h > 0 && w > 0 && C > 0 && C <= 24 && H > 0 && W > 0 && temperature > 0.f, KD_ERR_INVALID, "kd_jsdiv_up: bad argument (C <= 24: two staged patches fit 64 KiB of LDS)");
-    UpPlan u;
-    if (const int rc = up_plan(u, UpEntry{"kd_jsdiv_up", MAX_BLOCKS, false}, N, h, w, C, H, W, align_corners, workspace_bytes)) return rc;
-    double *partial = (double *)workspace;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t lds = (size_t)4 * UP_NW * C * sizeof(float);
-    if (C == 19) KD_NOTE_PLUMBING("pair_up_kernel<jsd,19>"); else KD_NOTE_PLUMBING("pair_up_kernel<jsd,0>");
-    hipLaunchKernelGGL((C == 19 ? pair_up_kernel<PAIR_JSD, 19> : pair_up_kernel<PAIR_JSD, 0>), dim3(u.nb), dim3(256), lds, st, s_lo, t_lo, u.g,
-                       1.f / temperature, u.nchunks, u.cpr, partial);
-    KD_CHECK_LAUNCH("kd_jsdiv_up");
-    // T^2 / (2N) * sum  (kd_jsdiv)
-    const double scale = (double)temperature * temperature / (2.0 * (double)N);
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, u.nb, scale, (const double *)nullptr, loss);
-    KD_CHECK_LAUNCH("kd_jsdiv_up(finish)");
-    return KD_OK;
-}
-
-extern "C" int kd_logit_metrics_up(const float *s_lo, const float *t_lo, const int64_t *target, int32_t ignore_index, int32_t N, int32_t h,
-                                   int32_t w, int32_t C, int32_t H, int32_t W, int32_t align_corners, float *out, int64_t *conf_s,
-                                   int64_t *conf_t, int32_t accumulate, void *workspace, size_t workspace_bytes, kd_stream_t stream)
-{
-    KD_REQUIRE(s_lo && t_lo && target && out && conf_s && conf_t && workspace, KD_ERR_INVALID, "kd_logit_metrics_up: null argument");
-    KD_REQUIRE(N > 0 && h > 0 && w > 0 && C > 0 && H > 0 && W > 0, KD_ERR_INVALID, "kd_logit_metrics_up: bad argument");
-    KD_REQUIRE(conf_s != conf_t && (((uintptr_t)conf_s | (uintptr_t)conf_t | (uintptr_t)workspace) & 7) == 0, KD_ERR_INVALID,
-               "kd_logit_metrics_up: conf_s / conf_t must be two 8-B aligned matrices, the workspace 8-B aligned");
-    KD_REQUIRE(C <= 48, KD_ERR_UNSUPPORTED, "kd_logit_metrics_up: C <= 48 (got %d): materialise the logits", C);
-    UpPlan u;
-    if (const int rc = up_plan(u, UpEntry{"kd_logit_metrics_up", MET_MAX_BLOCKS, true}, N, h, w, C, H, W, align_corners, workspace_bytes)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (!accumulate) {
-        if (hipMemsetAsync(conf_s, 0, (size_t)C * C * sizeof(int64_t), st) != hipSuccess ||
-            hipMemsetAsync(conf_t, 0, (size_t)C * C * sizeof(int64_t), st) != hipSuccess) {
-            kd_set_error("kd_logit_metrics_up: hipMemsetAsync failed");
-            return KD_ERR_HIP;
-        }
-    }
-    double *partial = (double *)workspace;
-    // two staged patches + two C x C histograms: 50.3 KiB at 19 classes, 138 KiB at 48 (of the CU's 160 KiB)
-    const size_t lds = (size_t)4 * UP_NW * C * sizeof(float) + (size_t)2 * C * C * sizeof(unsigned int);
-    auto fn = C == 19 ? logit_metrics_up_kernel<19> : logit_metrics_up_kernel<0>;
-    if (lds > 65536) {
-        if (hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-            (void)hipGetLastError();
-            kd_set_error("kd_logit_metrics_up: cannot reserve %zu B of LDS", lds);
-            return KD_ERR_UNSUPPORTED;
-        }
-    }
-    if (C == 19) KD_NOTE_PLUMBING("logit_metrics_up_kernel<19>"); else KD_NOTE_PLUMBING("logit_metrics_up_kernel<0>");
-    hipLaunchKernelGGL(fn, dim3(u.nb), dim3(256), lds, st, s_lo, t_lo, target, ignore_index, u.g, u.nchunks, u.cpr, partial,
-                       (unsigned long long *)conf_s, (unsigned long long *)conf_t);
-    KD_CHECK_LAUNCH("kd_logit_metrics_up");
-    hipLaunchKernelGGL(logit_metrics_finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, u.nb,
-                       1.0 / ((double)N * (double)C * (double)H * (double)W), out);
-    KD_CHECK_LAUNCH("kd_logit_metrics_up(finish)");
-    return KD_OK;
-}
-
-// ---- kd_jsdiv / kd_ensemble_kldiv -------------------------------------------------------------------------------------------
 extern "C" int kd_jsdiv(const kd_view3 *s, const kd_view3 *t, float temperature, int32_t N, int32_t C, int64_t P, float *loss,
                         const kd_mview3 *grad, float grad_scale, void *workspace, size_t workspace_bytes, kd_stream_t stream)
 {
@@ -1848,285 +1570,101 @@ extern "C" int kd_ensemble_kldiv(const kd_view3 *s, const kd_view3 *t, int32_t N
     return pair_impl("kd_ensemble_kldiv", PAIR_EKL, s, t, 1.f, N, C, P, loss, grad, gscale, scale, workspace, stream);
 }
 
-// ---- kd_kldiv_multi / kd_softmax_mean ---------------------------------------------------------------------------------------
-namespace {
-// 4-element vector accesses on a class-contiguous row: whole groups of 4 and every row start 4-element aligned
-inline bool row_vec_ok(const void *p, int dt, long long sN, long long sP, int N, int C, long long P)
+extern "C" int kd_hint_mse(const kd_view3 *s, const kd_view3 *t, float num_classes, int32_t N, int32_t C, int64_t P,
+                           float *loss, const kd_mview3 *grad, float grad_scale, void *workspace, size_t workspace_bytes,
+                           kd_stream_t stream)
 {
-    return (C & 3) == 0 && ((uintptr_t)p & (dt == KD_BF16 ? 7u : 15u)) == 0 && (P == 1 || (sP & 3) == 0) && (N == 1 || (sN & 3) == 0);
-}
-inline bool nhwc_dense(long long sN, long long sC, long long sP, int N, int C, long long P)
-{
-    return sC == 1 && sP == C && (sN == (long long)C * P || N == 1);
-}
-// the targets by value, weights divided by their sum; false (error set) on a bad argument
-bool mt_pack(const char *who, const kd_multi_targets *ts, MT &mt)
-{
-    if (!ts || ts->n < 1 || ts->n > KD_MULTI_MAX) {
-        kd_set_error("%s: 1 to %d operands, got %d", who, KD_MULTI_MAX, ts ? (int)ts->n : 0);
-        return false;
-    }
-    double W = 0.0;
-    for (int k = 0; k < ts->n; ++k) {
-        if (!ts->t[k].ptr || !ok_dt(ts->t[k].dtype) || !(ts->w[k] >= 0.f)) {
-            kd_set_error("%s: operand %d: null pointer, bad dtype or negative weight", who, k);
-            return false;
-        }
-        W += (double)ts->w[k];
-    }
-    if (!(W > 0.0) || W > 3.0e38) {
-        kd_set_error("%s: the weights must have a positive finite sum", who);
-        return false;
-    }
-    mt.n = ts->n;
-    for (int k = 0; k < KD_MULTI_MAX; ++k) {
-        mt.t[k] = k < ts->n ? v3(&ts->t[k]) : V3{nullptr, 0, 0, 0, 0};
-        mt.w[k] = k < ts->n ? (float)((double)ts->w[k] / W) : 0.f;
-    }
-    return true;
-}
-enum { MT_WAVE = 0, MT_NHWC = 1, MT_ANY = 2 };
-}  // namespace
-
-extern "C" int kd_kldiv_multi(const kd_view3 *s, const kd_multi_targets *targets, float temperature, const int64_t *labels,
-                              int32_t ignore_index, float kd_scale, float sup_scale, int32_t N, int32_t C, int64_t P, float *losses,
-                              const kd_mview3 *grad, void *workspace, size_t workspace_bytes, kd_stream_t stream)
-{
-    KD_REQUIRE(s && s->ptr && losses && workspace, KD_ERR_INVALID, "kd_kldiv_multi: null argument");
-    KD_REQUIRE(ok_dt(s->dtype) && (!grad || (grad->ptr && ok_dt(grad->dtype))), KD_ERR_INVALID, "kd_kldiv_multi: bad dtype");
-    KD_REQUIRE(N > 0 && C > 0 && P > 0, KD_ERR_INVALID, "kd_kldiv_multi: bad shape");
-    KD_REQUIRE(temperature > 0.f, KD_ERR_INVALID, "kd_kldiv_multi: temperature must be positive");
-    KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, P), KD_ERR_WORKSPACE, "kd_kldiv_multi: workspace too small");
-    KD_REQUIRE(((uintptr_t)workspace & 7) == 0, KD_ERR_INVALID, "kd_kldiv_multi: workspace must be 8-B aligned");
-    MT mt;
-    if (!mt_pack("kd_kldiv_multi", targets, mt)) return KD_ERR_INVALID;
-    hipStream_t st = (hipStream_t)stream;
-    double *pkd = (double *)workspace, *pce = pkd + MT_MAX_BLOCKS, *count = pce + MT_MAX_BLOCKS;
-    const long long rows = (long long)N * P;
-    const V3 sv = v3(s);
-    const M3 gv = m3(grad);
-    bool unit = s->sC == 1 && (!grad || grad->sC == 1);
-    bool dense = nhwc_dense(s->sN, s->sC, s->sP, N, C, P) && (!grad || nhwc_dense(grad->sN, grad->sC, grad->sP, N, C, P));
-    bool vec = row_vec_ok(s->ptr, s->dtype, s->sN, s->sP, N, C, P) &&
-               (!grad || row_vec_ok(grad->ptr, grad->dtype, grad->sN, grad->sP, N, C, P));
-    for (int k = 0; k < mt.n; ++k) {
-        const V3 &t = mt.t[k];
-        unit = unit && t.sC == 1;
-        dense = dense && nhwc_dense(t.sN, t.sC, t.sP, N, C, P);
-        vec = vec && row_vec_ok(t.p, t.dt, t.sN, t.sP, N, C, P);
-    }
-    // few classes and many pixels: a wave per pixel would idle most of its lanes
-    const bool narrow = C < 22 && rows >= 16384;
-    const int path = narrow && dense ? MT_NHWC : (unit && C <= 1024 && !narrow ? MT_WAVE : MT_ANY);
-    const float invT = 1.f / temperature;
-    const float gk = kd_scale * temperature / ((float)N * (float)P);
-    int ncount = 0;
-    if (labels) {
-        ncount = (int)std::min<long long>((rows + 255) / 256, MT_MAX_BLOCKS);
-        hipLaunchKernelGGL(ce2d_count_kernel, dim3(ncount), dim3(256), 0, st, labels, ignore_index, C, rows, count, (const float *)nullptr);
-        KD_CHECK_LAUNCH("kd_kldiv_multi(count)");
-    }
-    const double *cnt = labels ? count : nullptr;
-    int nb;
-    if (path == MT_WAVE) {
-        nb = (int)std::min<long long>((rows + 3) / 4, MT_MAX_BLOCKS);
-#define KD_MTW(NCH, VEC) hipLaunchKernelGGL((mt_wave_kernel<NCH, VEC, false>), dim3(nb), dim3(256), 0, st, sv, mt, gv, labels, ignore_index, \
-                                            invT, gk, sup_scale, C, (long long)P, rows, cnt, ncount, pkd, pce)
-        if (C <= 256) {
-            if (vec) { KD_NOTE_PLUMBING("mt_wave_kernel<1,vec>"); KD_MTW(1, true); }
-            else { KD_NOTE_PLUMBING("mt_wave_kernel<1,novec>"); KD_MTW(1, false); }
-        } else {
-            if (vec) { KD_NOTE_PLUMBING("mt_wave_kernel<4,vec>"); KD_MTW(4, true); }
-            else { KD_NOTE_PLUMBING("mt_wave_kernel<4,novec>"); KD_MTW(4, false); }
-        }
-#undef KD_MTW
-    } else if (path == MT_NHWC) {
-        KD_NOTE_PLUMBING("kldm_nhwc_kernel");
-        nb = (int)std::min<long long>((rows + 255) / 256, MT_MAX_BLOCKS);
-        hipLaunchKernelGGL(kldm_nhwc_kernel, dim3(nb), dim3(256), (size_t)3 * 256 * C * sizeof(float), st, sv, mt, gv, labels, ignore_index,
-                           invT, gk, sup_scale, C, rows, cnt, ncount, pkd, pce);
-    } else {
-        KD_NOTE_PLUMBING("kldm_kernel");
-        nb = (int)std::min<long long>((rows + 255) / 256, MT_MAX_BLOCKS);
-        hipLaunchKernelGGL(kldm_kernel<false>, dim3(nb), dim3(256), 0, st, sv, mt, gv, labels, ignore_index, invT, gk, sup_scale, C,
-                           (long long)P, rows, cnt, ncount, pkd, pce);
-    }
-    KD_CHECK_LAUNCH("kd_kldiv_multi");
-    // per target 'mean' over N*C*P elements, then * T^2 * C  ==  T^2 / (N*P) * sum; the weights already sum to 1
-    const double kd_mul = (double)temperature * temperature / ((double)N * (double)P);
-    hipLaunchKernelGGL(mt_finish_kernel, dim3(1), dim3(256), 0, st, (const double *)pkd, (const double *)pce, nb, cnt, ncount, kd_mul,
-                       kd_scale, sup_scale, losses);
-    KD_CHECK_LAUNCH("kd_kldiv_multi(finish)");
-    return KD_OK;
-}
-
-extern "C" int kd_softmax_mean(const kd_multi_targets *logits, float temperature, int32_t N, int32_t C, int64_t P, const kd_mview3 *out,
-                               kd_stream_t stream)
-{
-    KD_REQUIRE(out && out->ptr && out->dtype == KD_F32, KD_ERR_INVALID, "kd_softmax_mean: out must be an fp32 view");
-    KD_REQUIRE(N > 0 && C > 0 && P > 0, KD_ERR_INVALID, "kd_softmax_mean: bad shape");
-    KD_REQUIRE(temperature > 0.f, KD_ERR_INVALID, "kd_softmax_mean: temperature must be positive");
-    MT mt;
-    if (!mt_pack("kd_softmax_mean", logits, mt)) return KD_ERR_INVALID;
-    hipStream_t st = (hipStream_t)stream;
-    const long long rows = (long long)N * P;
-    const M3 gv = m3(out);
-    bool unit = out->sC == 1, vec = row_vec_ok(out->ptr, out->dtype, out->sN, out->sP, N, C, P);
-    for (int k = 0; k < mt.n; ++k) {
-        unit = unit && mt.t[k].sC == 1;
-        vec = vec && row_vec_ok(mt.t[k].p, mt.t[k].dt, mt.t[k].sN, mt.t[k].sP, N, C, P);
-    }
-    const V3 none{nullptr, 0, 0, 0, 0};
-    const float invT = 1.f / temperature;
-    if (unit && C <= 1024 && !(C < 22 && rows >= 16384)) {
-        const int nb = (int)std::min<long long>((rows + 3) / 4, MT_MAX_BLOCKS);
-#define KD_SMW(NCH, VEC) hipLaunchKernelGGL((mt_wave_kernel<NCH, VEC, true>), dim3(nb), dim3(256), 0, st, none, mt, gv, (const int64_t *)nullptr, 0, \
-                                            invT, 0.f, 0.f, C, (long long)P, rows, (const double *)nullptr, 0, (double *)nullptr, (double *)nullptr)
-        if (C <= 256) {
-            if (vec) { KD_NOTE_PLUMBING("mt_wave_kernel<1,vec,smean>"); KD_SMW(1, true); }
-            else { KD_NOTE_PLUMBING("mt_wave_kernel<1,novec,smean>"); KD_SMW(1, false); }
-        } else {
-            if (vec) { KD_NOTE_PLUMBING("mt_wave_kernel<4,vec,smean>"); KD_SMW(4, true); }
-            else { KD_NOTE_PLUMBING("mt_wave_kernel<4,novec,smean>"); KD_SMW(4, false); }
-        }
-#undef KD_SMW
-    } else {
-        KD_NOTE_PLUMBING("kldm_kernel<smean>");
-        const int nb = (int)std::min<long long>((rows + 255) / 256, MT_MAX_BLOCKS);
-        hipLaunchKernelGGL(kldm_kernel<true>, dim3(nb), dim3(256), 0, st, none, mt, gv, (const int64_t *)nullptr, 0, invT, 0.f, 0.f, C,
-                           (long long)P, rows, (const double *)nullptr, 0, (double *)nullptr, (double *)nullptr);
-    }
-    KD_CHECK_LAUNCH("kd_softmax_mean");
-    return KD_OK;
-}
-
-// ---- kd_focal / kd_focal_grad / kd_focal_up -----------------------------------------------------------------------------------------
-extern "C" int kd_focal(const kd_view3 *x, const int64_t *target, const float *alpha, float gamma, int32_t ignore_index, int32_t reduction,
-                        int32_t N, int32_t C, int64_t P, float *loss, double *stats, float *a_map, float *ce_map, void *workspace,
-                        size_t workspace_bytes, kd_stream_t stream)
-{
-    KD_REQUIRE(x && x->ptr && target && workspace, KD_ERR_INVALID, "kd_focal: null argument");
-    KD_REQUIRE(ok_dt(x->dtype) && N > 0 && C > 0 && P > 0 && gamma >= 0.f, KD_ERR_INVALID, "kd_focal: bad argument");
-    KD_REQUIRE(reduction >= 0 && reduction <= 2, KD_ERR_INVALID, "kd_focal: reduction is 0 (none), 1 (mean) or 2 (sum)");
-    KD_REQUIRE(reduction == 0 || loss, KD_ERR_INVALID, "kd_focal: 'mean' / 'sum' need a loss pointer");
-    KD_REQUIRE(reduction != 0 || (a_map && ce_map), KD_ERR_INVALID, "kd_focal: 'none' needs both per-pixel maps");
-    KD_REQUIRE((a_map == nullptr) == (ce_map == nullptr), KD_ERR_INVALID, "kd_focal: a_map and ce_map go together");
-    KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, P), KD_ERR_WORKSPACE, "kd_focal: workspace too small");
-    KD_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)stats & 7) == 0, KD_ERR_INVALID, "kd_focal: workspace / stats must be 8-B aligned");
+    KD_LOSS_COMMON("kd_hint_mse");
     double *partial = (double *)workspace;
-    const long long total = (long long)N * P;
-    const int nb = (int)min((total + 255) / 256, (long long)FOCAL_MAX_BLOCKS);
+    const long long numel = (long long)N * C * P;
+    const float gscale = grad_scale * 2.f * num_classes / (float)numel;
     hipStream_t st = (hipStream_t)stream;
-    KD_NOTE_PLUMBING("focal_kernel");
-    hipLaunchKernelGGL(focal_kernel, dim3(nb), dim3(256), 0, st, v3(x), target, alpha, gamma, ignore_index, N, C, (long long)P, a_map, ce_map, partial);
-    KD_CHECK_LAUNCH("kd_focal");
-    hipLaunchKernelGGL(focal_finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, nb, (int)reduction, (double)total, stats,
-                       reduction == 0 ? (float *)nullptr : loss);
-    KD_CHECK_LAUNCH("kd_focal(finish)");
-    return KD_OK;
-}
-
-extern "C" int kd_focal_grad(const kd_view3 *x, const int64_t *target, const float *alpha, float gamma, int32_t ignore_index, int32_t reduction,
-                             int32_t N, int32_t C, int64_t P, const double *stats, const float *upstream, const float *a_map,
-                             const float *ce_map, const kd_mview3 *grad, kd_stream_t stream)
-{
-    KD_REQUIRE(x && x->ptr && target && upstream && grad && grad->ptr, KD_ERR_INVALID, "kd_focal_grad: null argument");
-    KD_REQUIRE(ok_dt(x->dtype) && ok_dt(grad->dtype) && N > 0 && C > 0 && P > 0 && gamma >= 0.f, KD_ERR_INVALID, "kd_focal_grad: bad argument");
-    KD_REQUIRE(reduction >= 0 && reduction <= 2, KD_ERR_INVALID, "kd_focal_grad: reduction is 0 (none), 1 (mean) or 2 (sum)");
-    KD_REQUIRE(reduction == 0 ? (a_map && ce_map) : stats != nullptr, KD_ERR_INVALID,
-               "kd_focal_grad: 'none' needs the forward's per-pixel maps, 'mean' / 'sum' its stats");
-    KD_NOTE_PLUMBING("focal_grad_kernel");
-    hipLaunchKernelGGL(focal_grad_kernel, dim3(blocks_for((long long)N * P)), dim3(256), 0, (hipStream_t)stream, v3(x), target, alpha, gamma,
-                       ignore_index, (int)reduction, N, C, (long long)P, stats, upstream, a_map, ce_map, m3(grad));
-    KD_CHECK_LAUNCH("kd_focal_grad");
-    return KD_OK;
-}
-
-extern "C" int kd_focal_up(const float *x_lo, const int64_t *target, const float *alpha, float gamma, int32_t ignore_index, int32_t reduction,
-                           int32_t N, int32_t h, int32_t w, int32_t C, int32_t H, int32_t W, int32_t align_corners, float *loss, double *stats,
-                           void *workspace, size_t workspace_bytes, kd_stream_t stream)
-{
-    KD_REQUIRE(x_lo && target && loss && workspace, KD_ERR_INVALID, "kd_focal_up: null argument");
-    KD_REQUIRE(N > 0 && h > 0 && w > 0 && C > 0 && C <= 48 && H > 0 && W > 0 && gamma >= 0.f, KD_ERR_INVALID,
-               "kd_focal_up: bad argument (C <= 48: the staged patch fits 64 KiB of LDS)");
-    KD_REQUIRE(reduction == 1 || reduction == 2, KD_ERR_INVALID, "kd_focal_up: reduction is 1 (mean) or 2 (sum)");
-    // (the size before the alignment, as this entry point always reported them; up_plan repeats the size check)
-    KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, (int64_t)H * W), KD_ERR_WORKSPACE, "kd_focal_up: workspace too small");
-    KD_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)stats & 7) == 0, KD_ERR_INVALID, "kd_focal_up: workspace / stats must be 8-B aligned");
-    UpPlan u;
-    if (const int rc = up_plan(u, UpEntry{"kd_focal_up", FOCAL_MAX_BLOCKS, false}, N, h, w, C, H, W, align_corners, workspace_bytes)) return rc;
-    double *partial = (double *)workspace;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t lds = (size_t)2 * UP_NW * C * sizeof(float);
-    if (C == 19) KD_NOTE_PLUMBING("focal_up_kernel<19>"); else KD_NOTE_PLUMBING("focal_up_kernel<0>");
-    hipLaunchKernelGGL(C == 19 ? focal_up_kernel<19> : focal_up_kernel<0>, dim3(u.nb), dim3(256), lds, st, x_lo, target, alpha, gamma, ignore_index,
-                       u.g, u.nchunks, u.cpr, partial);
-    KD_CHECK_LAUNCH("kd_focal_up");
-    hipLaunchKernelGGL(focal_finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, u.nb, (int)reduction, (double)N * H * W, stats, loss);
-    KD_CHECK_LAUNCH("kd_focal_up(finish)");
-    return KD_OK;
-}
-
-// ---- kd_topk_hint_mse ------------------------------------------------------------------------------------------------------------
-extern "C" size_t kd_topk_hint_workspace(int32_t N, int32_t C, int64_t P)
-{
-    if (N <= 0 || C <= 0 || P <= 0) return 64;
-    const size_t nc = (size_t)N * C, ch = (size_t)topk_chunks(N, C, P);
-    return 2 * nc * ch * sizeof(double) + (size_t)N * sizeof(double) + nc * sizeof(float) + 64;
-}
-
-extern "C" int kd_topk_hint_mse(const kd_view3 *s, const kd_view3 *t, int32_t K, int32_t N, int32_t C, int64_t P, float *loss,
-                                const kd_mview3 *grad, float grad_scale, float *mask, void *workspace, size_t workspace_bytes, kd_stream_t stream)
-{
-    KD_REQUIRE(s && t && s->ptr && t->ptr && loss && workspace, KD_ERR_INVALID, "kd_topk_hint_mse: null argument");
-    KD_REQUIRE(ok_dt(s->dtype) && ok_dt(t->dtype) && (!grad || ok_dt(grad->dtype)), KD_ERR_INVALID, "kd_topk_hint_mse: bad dtype");
-    KD_REQUIRE(N > 0 && C > 0 && P > 0, KD_ERR_INVALID, "kd_topk_hint_mse: bad shape");
-    KD_REQUIRE(K >= 1 && K <= C, KD_ERR_INVALID, "kd_topk_hint_mse: K = %d channels kept of %d: need 1 <= K <= C", K, C);
-    KD_REQUIRE(C <= TOPK_MAX_C, KD_ERR_UNSUPPORTED, "kd_topk_hint_mse: C = %d > %d channels", C, TOPK_MAX_C);
-    KD_REQUIRE(workspace_bytes >= kd_topk_hint_workspace(N, C, P), KD_ERR_WORKSPACE, "kd_topk_hint_mse: workspace too small");
-    KD_REQUIRE(((uintptr_t)workspace & 7) == 0, KD_ERR_INVALID, "kd_topk_hint_mse: workspace must be 8-B aligned");
-    const int nchunk = topk_chunks(N, C, P);
-    const long long per_chunk = (P + nchunk - 1) / nchunk;
-    const size_t nc = (size_t)N * C;
-    double *pt2 = (double *)workspace, *pd2 = pt2 + nc * nchunk, *part = pd2 + nc * nchunk;
-    float *mk = mask ? mask : (float *)(part + N + (N & 1));   // (16-B aligned: the dense gradient path reads it as float4)
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(topk_sums_kernel, dim3((unsigned)nchunk, (unsigned)((C + 63) / 64), (unsigned)N), dim3(256), 0, st, v3(s), v3(t), C,
-                       (long long)P, per_chunk, nchunk, pt2, pd2);
-    KD_CHECK_LAUNCH("kd_topk_hint_mse(sums)");
-    hipLaunchKernelGGL(topk_select_kernel, dim3(N), dim3(1024), (size_t)C * sizeof(double), st, (const double *)pt2, (const double *)pd2, C,
-                       nchunk, (int)K, mk, part);
-    KD_CHECK_LAUNCH("kd_topk_hint_mse(select)");
-    // loss = sum_n sum_kept mean_p (s-t)^2 / (N K) ; grad = 2 mask (s-t) / (P N K)
-    const double denom = (double)N * (double)K;
-    if (grad) {
-        const float gscale = (float)((double)grad_scale * 2.0 / ((double)P * denom));
-        const long long numel = (long long)nc * P;
-        const bool cfast = s->sC == 1 && s->sP == C;
-        if (dense_same(s, t, grad, N, C, P) && (cfast ? C % 8 == 0 : P % 8 == 0) && kd_aligned16(mk)) {
-            const long long n8 = numel / 8;
-#define KD_TOPK_VEC(T, CF) hipLaunchKernelGGL((topk_grad_vec_kernel<T, CF>), dim3(blocks_for(n8)), dim3(256), 0, st, (const T *)s->ptr, \
-                                              (const T *)t->ptr, (T *)grad->ptr, (const float *)mk, gscale, C, (long long)P, n8)
-            if (s->dtype == KD_BF16) {
-                if (cfast) { KD_NOTE_PLUMBING("topk_grad_vec_kernel<bf16,cfast>"); KD_TOPK_VEC(bf16_t, true); }
-                else { KD_NOTE_PLUMBING("topk_grad_vec_kernel<bf16,pfast>"); KD_TOPK_VEC(bf16_t, false); }
-            } else {
-                if (cfast) { KD_NOTE_PLUMBING("topk_grad_vec_kernel<f32,cfast>"); KD_TOPK_VEC(float, true); }
-                else { KD_NOTE_PLUMBING("topk_grad_vec_kernel<f32,pfast>"); KD_TOPK_VEC(float, false); }
-            }
-#undef KD_TOPK_VEC
-        } else {
-            KD_NOTE_PLUMBING("topk_grad_kernel");
-            hipLaunchKernelGGL(topk_grad_kernel, dim3(blocks_for(numel)), dim3(256), 0, st, v3(s), v3(t), m3(grad), (const float *)mk, gscale,
-                               N, C, (long long)P, s->sC == 1 ? 1 : 0);
-        }
-        KD_CHECK_LAUNCH("kd_topk_hint_mse(grad)");
-    } else {
-        KD_NOTE_PLUMBING("topk_nograd");
+    const LossSel sel = loss_select_mse(s, t, grad, N, C, P);
+    KD_NOTE_PLUMBING(loss_kernel_name(sel.kernel));
+    auto vec = [&](auto z) {
+        using T = decltype(z);
+        hipLaunchKernelGGL(mse_vec_kernel<T>, dim3(sel.blocks), dim3(256), 0, st, (const T *)s->ptr, (const T *)t->ptr,
+                           (T *)(grad ? grad->ptr : nullptr), gscale, numel / 8, partial);
+    };
+    switch (sel.kernel) {
+    case LK_MSE_VEC_F32: vec(float{}); break;
+    case LK_MSE_VEC_BF16: vec(bf16_t{}); break;
+    case LK_MSE_STRIDED:
+        hipLaunchKernelGGL(mse_strided_kernel, dim3(sel.blocks), dim3(256), 0, st, v3(s), v3(t), m3(grad), gscale, N, C, (long long)P,
+                           s->sC == 1 ? 1 : 0, partial);
+        break;
+    default: return no_launch("kd_hint_mse", sel);
     }
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)part, (int)N, 1.0 / ((double)P * denom), (const double *)nullptr, loss);
-    KD_CHECK_LAUNCH("kd_topk_hint_mse(finish)");
+    KD_CHECK_LAUNCH("kd_hint_mse");
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, sel.blocks, (double)num_classes / (double)numel,
+                       (const double *)nullptr, loss);
+    KD_CHECK_LAUNCH("kd_hint_mse(finish)");
     return KD_OK;
+}
+
+extern "C" int kd_weighted_hint_mse(const kd_view3 *s, const kd_view3 *t, const float *w, int32_t w_per_sample, int32_t N,
+                                    int32_t C, int64_t P, float *loss, const kd_mview3 *grad, float grad_scale, void *workspace,
+                                    size_t workspace_bytes, kd_stream_t stream)
+{
+    KD_LOSS_COMMON("kd_weighted_hint_mse");
+    KD_REQUIRE(w, KD_ERR_INVALID, "kd_weighted_hint_mse: null weight");
+    hipStream_t st = (hipStream_t)stream;
+    const LossSel sel = loss_select_whmse(N, C, P);
+    const dim3 grid((unsigned)sel.chunks, (unsigned)((C + 255) / 256), (unsigned)N);
+    double *partial = (double *)workspace;
+    float *wsum = (float *)((char *)workspace + sel.aux_off);
+    KD_NOTE_PLUMBING(loss_kernel_name(LK_WHMSE));      // the one kernel; the selector plans its grid
+    hipLaunchKernelGGL(wsum_kernel, dim3(N), dim3(64), 0, st, w, w_per_sample, N, C, wsum);
+    hipLaunchKernelGGL(whmse_kernel, grid, dim3(256), 0, st, v3(s), v3(t), m3(grad), w, w_per_sample, (const float *)wsum,
+                       grad_scale, N, C, (long long)P, sel.per_chunk, partial);
+    KD_CHECK_LAUNCH("kd_weighted_hint_mse");
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, sel.blocks, 1.0 / (double)N,
+                       (const double *)nullptr, loss);
+    KD_CHECK_LAUNCH("kd_weighted_hint_mse(finish)");
+    return KD_OK;
+}
+
+// ---- kd_ce2d / kd_ce2d_weighted and their gradient ----------------------------------------------------------------------------------
+static int ce2d_impl(const char *who, const kd_view3 *x, const int64_t *target, const float *class_weight, int32_t sum_reduction, int32_t ignore_index,
+                     int32_t N, int32_t C, int64_t P, float *loss, void *workspace, size_t workspace_bytes, kd_stream_t stream)
+{
+    KD_REQUIRE(x && x->ptr && target && loss && workspace, KD_ERR_INVALID, "%s: null argument", who);
+    KD_REQUIRE(ok_dt(x->dtype) && N > 0 && C > 0 && P > 0, KD_ERR_INVALID, "%s: bad argument", who);
+    KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, P), KD_ERR_WORKSPACE, "%s: workspace too small", who);
+    double *partial = (double *)workspace, *count = partial + LOSS_MAX_BLOCKS;
+    hipStream_t st = (hipStream_t)stream;
+    const LossSel sel = loss_select_ce2d(x, N, C, P);
+    KD_NOTE_PLUMBING(loss_kernel_name(sel.kernel));
+    auto nhwc = [&](auto z) {
+        using T = decltype(z);
+        hipLaunchKernelGGL(ce2d_nhwc_kernel<T>, dim3(sel.blocks), dim3(256), sel.lds, st, (const T *)x->ptr, target, ignore_index, C,
+                           (long long)N * P, partial, count, class_weight);
+    };
+    switch (sel.kernel) {
+    case LK_CE2D_NHWC_F32: nhwc(float{}); break;
+    case LK_CE2D_NHWC_BF16: nhwc(bf16_t{}); break;
+    case LK_CE2D:
+        hipLaunchKernelGGL(ce2d_kernel, dim3(sel.blocks), dim3(256), 0, st, v3(x), target, ignore_index, N, C, (long long)P, partial, count, class_weight);
+        break;
+    default: return no_launch(who, sel);
+    }
+    KD_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, sel.blocks, 1.0,
+                       sum_reduction ? (const double *)nullptr : (const double *)count, loss);
+    KD_CHECK_LAUNCH(who);
+    return KD_OK;
+}
+
+extern "C" int kd_ce2d(const kd_view3 *x, const int64_t *target, int32_t ignore_index, int32_t N, int32_t C, int64_t P,
+                       float *loss, void *workspace, size_t workspace_bytes, kd_stream_t stream)
+{
+    return ce2d_impl("kd_ce2d", x, target, nullptr, 0, ignore_index, N, C, P, loss, workspace, workspace_bytes, stream);
+}
+
+extern "C" int kd_ce2d_weighted(const kd_view3 *x, const int64_t *target, const float *class_weight, int32_t sum_reduction, int32_t ignore_index,
+                                int32_t N, int32_t C, int64_t P, float *loss, void *workspace, size_t workspace_bytes, kd_stream_t stream)
+{
+    return ce2d_impl("kd_ce2d_weighted", x, target, class_weight, sum_reduction, ignore_index, N, C, P, loss, workspace, workspace_bytes, stream);
 }
 
 static int ce2d_grad_impl(const char *who, const kd_view3 *x, const int64_t *target, const float *class_weight, int32_t sum_reduction, int32_t ignore_index,
@@ -2137,13 +1675,13 @@ static int ce2d_grad_impl(const char *who, const kd_view3 *x, const int64_t *tar
     KD_REQUIRE(ok_dt(x->dtype) && ok_dt(grad->dtype) && N > 0 && C > 0 && P > 0, KD_ERR_INVALID, "%s: bad argument", who);
     KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, P), KD_ERR_WORKSPACE, "%s: workspace too small", who);
     double *count = (double *)workspace;
-    const int nb = blocks_for((long long)N * P);
+    const LossSel sel = loss_flat(LK_CE2D_GRAD, (long long)N * P);
     hipStream_t st = (hipStream_t)stream;
-    KD_NOTE_PLUMBING("ce2d_grad_kernel");
-    hipLaunchKernelGGL(ce2d_count_kernel, dim3(nb), dim3(256), 0, st, target, ignore_index, C, (long long)N * P, count, class_weight);
+    KD_NOTE_PLUMBING(loss_kernel_name(sel.kernel));
+    hipLaunchKernelGGL(ce2d_count_kernel, dim3(sel.blocks), dim3(256), 0, st, target, ignore_index, C, (long long)N * P, count, class_weight);
     KD_CHECK_LAUNCH(who);
-    hipLaunchKernelGGL(ce2d_grad_kernel, dim3(nb), dim3(256), 0, st, v3(x), target, ignore_index, N, C, (long long)P, m3(grad), grad_scale,
-                       (const double *)count, nb, class_weight, (int)sum_reduction);
+    hipLaunchKernelGGL(ce2d_grad_kernel, dim3(sel.blocks), dim3(256), 0, st, v3(x), target, ignore_index, N, C, (long long)P, m3(grad), grad_scale,
+                       (const double *)count, sel.blocks, class_weight, (int)sum_reduction);
     KD_CHECK_LAUNCH(who);
     return KD_OK;
 }
@@ -2176,70 +1714,370 @@ extern "C" int kd_confusion(const kd_view3 *x, const int64_t *target, int32_t N,
             return KD_ERR_HIP;
         }
     }
-    const int nb = blocks_for((long long)N * P);
-    if ((size_t)256 * C * sizeof(float) + (size_t)C * C * sizeof(unsigned int) <= 65536 && x->sC == 1 && x->sP == C &&
-        (x->sN == (long long)C * P || N == 1)) {
-        const size_t lds = (size_t)256 * C * sizeof(float) + (size_t)C * C * sizeof(unsigned int);
-        if (x->dtype == KD_F32) {
-            KD_NOTE_PLUMBING("confusion_nhwc_kernel<f32>");
-            hipLaunchKernelGGL(confusion_nhwc_kernel<float>, dim3(nb), dim3(256), lds, st, (const float *)x->ptr, target, C,
-                               (long long)N * P, (unsigned long long *)conf);
-        } else {
-            KD_NOTE_PLUMBING("confusion_nhwc_kernel<bf16>");
-            hipLaunchKernelGGL(confusion_nhwc_kernel<bf16_t>, dim3(nb), dim3(256), lds, st, (const bf16_t *)x->ptr, target, C,
-                               (long long)N * P, (unsigned long long *)conf);
-        }
-    } else {
-        KD_NOTE_PLUMBING("confusion_kernel");
-        hipLaunchKernelGGL(confusion_kernel, dim3(nb), dim3(256), (size_t)C * C * sizeof(unsigned int), st, v3(x), target, N, C,
-                           (long long)P, (unsigned long long *)conf);
+    const LossSel sel = loss_select_confusion(x, N, C, P);
+    KD_NOTE_PLUMBING(loss_kernel_name(sel.kernel));
+    auto nhwc = [&](auto z) {
+        using T = decltype(z);
+        hipLaunchKernelGGL(confusion_nhwc_kernel<T>, dim3(sel.blocks), dim3(256), sel.lds, st, (const T *)x->ptr, target, C, (long long)N * P,
+                           (unsigned long long *)conf);
+    };
+    switch (sel.kernel) {
+    case LK_CONFUSION_NHWC_F32: nhwc(float{}); break;
+    case LK_CONFUSION_NHWC_BF16: nhwc(bf16_t{}); break;
+    case LK_CONFUSION:
+        hipLaunchKernelGGL(confusion_kernel, dim3(sel.blocks), dim3(256), sel.lds, st, v3(x), target, N, C, (long long)P, (unsigned long long *)conf);
+        break;
+    default: return no_launch("kd_confusion", sel);
     }
     KD_CHECK_LAUNCH("kd_confusion");
     return KD_OK;
 }
 
-extern "C" int kd_radam_step(float *p, const float *g, float *exp_avg, float *exp_avg_sq, int64_t n, int32_t step, float lr,
-                             float beta1, float beta2, float eps, float weight_decay, kd_stream_t stream)
+// ---- kd_ce2d_up / kd_kldiv_up / kd_jsdiv_up / kd_focal_up / kd_logit_metrics_up: from the low-resolution logits (see ce2d_up_kernel) ----
+// Each asks loss_select_up right after its null checks (the selector is total) and reports a class count above its bound where it
+// always has, with its own message.  What the five share after their own argument checks is here: the workspace and
+// resampling-ratio checks and the geometry the kernels take.  say_scale: the ratio message names the scale.
+static int up_plan(UpGeom &g, const LossSel &sel, const char *who, bool say_scale, int32_t N, int32_t h, int32_t w, int32_t C, int32_t H, int32_t W,
+                   size_t workspace_bytes)
 {
-    KD_REQUIRE(p && g && exp_avg && exp_avg_sq && n > 0 && step >= 1, KD_ERR_INVALID, "kd_radam_step: bad argument");
-    // (N_sma, step_size) exactly as utils/optim/radam.py:64-83 computes (and caches) them
-    const double beta2_t = pow((double)beta2, step);
-    const double nmax = 2.0 / (1.0 - (double)beta2) - 1.0;
-    const double nsma = nmax - 2.0 * step * beta2_t / (1.0 - beta2_t);
-    double step_size;
-    const int rect = nsma >= 5.0;
-    if (rect)
-        step_size = sqrt((1 - beta2_t) * (nsma - 4) / (nmax - 4) * (nsma - 2) / nsma * nmax / (nmax - 2)) /
-                    (1 - pow((double)beta1, step));
-    else
-        step_size = 1.0 / (1 - pow((double)beta1, step));
-    KD_NOTE_PLUMBING("radam_kernel");
-    hipLaunchKernelGGL(radam_kernel, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, exp_avg, exp_avg_sq,
-                       (long long)n, beta1, beta2, eps, (float)((double)weight_decay * lr), (float)(step_size * lr), rect);
-    KD_CHECK_LAUNCH("kd_radam_step");
-    return KD_OK;
-}
-
-extern "C" int kd_scale_by_device_scalar(void *x, int32_t dtype, int64_t n, const float *scale, kd_stream_t stream)
-{
-    KD_REQUIRE(x && scale && n > 0, KD_ERR_INVALID, "kd_scale_by_device_scalar: bad argument");
-    KD_REQUIRE(dtype == KD_F32 || dtype == KD_BF16, KD_ERR_INVALID, "kd_scale_by_device_scalar: bad dtype");
-    KD_REQUIRE(kd_aligned16(x), KD_ERR_INVALID, "kd_scale_by_device_scalar: x must be 16-B aligned");
-    const long long n8 = n / 8;
-    const unsigned blocks = blocks_for(n8 > 0 ? n8 : 1);
-    if (dtype == KD_BF16) {
-        KD_NOTE_PLUMBING("scale_by_device_scalar_kernel<bf16>");
-        hipLaunchKernelGGL(scale_by_device_scalar_kernel<bf16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (bf16_t *)x, n8,
-                           (long long)n, scale);
-    } else {
-        KD_NOTE_PLUMBING("scale_by_device_scalar_kernel<f32>");
-        hipLaunchKernelGGL(scale_by_device_scalar_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (float *)x, n8,
-                           (long long)n, scale);
+    KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, (int64_t)H * W), KD_ERR_WORKSPACE, "%s: workspace too small", who);
+    if (sel.why == LOSS_WHY_SPAN) {
+        if (say_scale)
+            kd_set_error("%s: a 256-pixel chunk spans more than %d source columns (scale %dx%d -> %dx%d): materialise the logits", who, LOSS_UP_NW, h, w, H, W);
+        else
+            kd_set_error("%s: a 256-pixel chunk spans more than %d source columns: materialise the logits", who, LOSS_UP_NW);
+        return KD_ERR_UNSUPPORTED;
     }
-    KD_CHECK_LAUNCH("kd_scale_by_device_scalar");
+    KD_REQUIRE(sel.kernel != LOSS_REFUSED, KD_ERR_UNSUPPORTED, "%s: no kernel selected", who);
+    g = UpGeom{N, h, w, C, H, W, sel.sh, sel.sw, sel.oh, sel.ow};
     return KD_OK;
 }
 
+extern "C" int kd_ce2d_up(const float *x_lo, const int64_t *target, int32_t ignore_index, int32_t N, int32_t h, int32_t w, int32_t C,
+                          int32_t H, int32_t W, int32_t align_corners, float *loss, void *workspace, size_t workspace_bytes,
+                          kd_stream_t stream)
+{
+    KD_REQUIRE(x_lo && target && loss && workspace, KD_ERR_INVALID, "kd_ce2d_up: null argument");
+    const LossSel sel = loss_select_up(LOSS_UP_CE2D, N, h, w, C, H, W, align_corners);
+    KD_REQUIRE(N > 0 && h > 0 && w > 0 && C > 0 && sel.why != LOSS_WHY_CLASSES && H > 0 && W > 0, KD_ERR_INVALID, "kd_ce2d_up: bad argument (C <= 48: the staged patch fits 64 KiB of LDS)");
+    UpGeom g;
+    if (const int rc = up_plan(g, sel, "kd_ce2d_up", true, N, h, w, C, H, W, workspace_bytes)) return rc;
+    double *partial = (double *)workspace, *count = partial + LOSS_MAX_BLOCKS;
+    hipStream_t st = (hipStream_t)stream;
+    KD_NOTE_PLUMBING(loss_kernel_name(sel.kernel));
+    auto fn = launch_of(sel.kernel, LK_CE2D_UP_19, ce2d_up_kernel<19>, LK_CE2D_UP_0, ce2d_up_kernel<0>);
+    if (!fn) return no_launch("kd_ce2d_up", sel);
+    hipLaunchKernelGGL(fn, dim3(sel.blocks), dim3(256), sel.lds, st, x_lo, target, ignore_index, g, sel.nchunks, sel.cpr, partial, count);
+    KD_CHECK_LAUNCH("kd_ce2d_up");
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, sel.blocks, 1.0, (const double *)count, loss);
+    KD_CHECK_LAUNCH("kd_ce2d_up(finish)");
+    return KD_OK;
+}
+
+// kd_kldiv_up / kd_jsdiv_up: the same call on the kernel of their kind; loss_scale as kd_kldiv / kd_jsdiv
+static int pair_up_impl(const char *who, const char *who_finish, LossUpOp op, const float *s_lo, const float *t_lo, float temperature, int32_t N, int32_t h, int32_t w, int32_t C,
+                        int32_t H, int32_t W, int32_t align_corners, float *loss, double loss_scale, void *workspace, size_t workspace_bytes,
+                        kd_stream_t stream)
+{
+    KD_REQUIRE(s_lo && t_lo && loss && workspace, KD_ERR_INVALID, "%s: null argument", who);
+    const LossSel sel = loss_select_up(op, N, h, w, C, H, W, align_corners);
+    KD_REQUIRE(N > 0 && h > 0 && w > 0 && C > 0 && sel.why != LOSS_WHY_CLASSES && H > 0 && W > 0 && temperature > 0.f, KD_ERR_INVALID,
+               "%s: bad argument (C <= 24: two staged patches fit 64 KiB of LDS)", who);
+    UpGeom g;
+    if (const int rc = up_plan(g, sel, who, false, N, h, w, C, H, W, workspace_bytes)) return rc;
+    double *partial = (double *)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    KD_NOTE_PLUMBING(loss_kernel_name(sel.kernel));
+    auto fn = launch_of(sel.kernel, LK_KLDIV_UP_19, pair_up_kernel<PAIR_KLD, 19>, LK_KLDIV_UP_0, pair_up_kernel<PAIR_KLD, 0>, LK_JSDIV_UP_19,
+                        pair_up_kernel<PAIR_JSD, 19>, LK_JSDIV_UP_0, pair_up_kernel<PAIR_JSD, 0>);
+    if (!fn) return no_launch(who, sel);
+    hipLaunchKernelGGL(fn, dim3(sel.blocks), dim3(256), sel.lds, st, s_lo, t_lo, g, 1.f / temperature, sel.nchunks, sel.cpr, partial);
+    KD_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, sel.blocks, loss_scale, (const double *)nullptr, loss);
+    KD_CHECK_LAUNCH(who_finish);
+    return KD_OK;
+}
+
+extern "C" int kd_kldiv_up(const float *s_lo, const float *t_lo, float temperature, int32_t N, int32_t h, int32_t w, int32_t C, int32_t H,
+                           int32_t W, int32_t align_corners, float *loss, void *workspace, size_t workspace_bytes, kd_stream_t stream)
+{
+    // 'mean' over N*C*P elements, then * T^2 * C  ==  T^2 / (N*P) * sum  (kd_kldiv)
+    const double scale = (double)temperature * temperature / ((double)N * (double)H * (double)W);
+    return pair_up_impl("kd_kldiv_up", "kd_kldiv_up(finish)", LOSS_UP_KLDIV, s_lo, t_lo, temperature, N, h, w, C, H, W, align_corners, loss, scale, workspace, workspace_bytes, stream);
+}
+
+extern "C" int kd_jsdiv_up(const float *s_lo, const float *t_lo, float temperature, int32_t N, int32_t h, int32_t w, int32_t C, int32_t H,
+                           int32_t W, int32_t align_corners, float *loss, void *workspace, size_t workspace_bytes, kd_stream_t stream)
+{
+    // T^2 / (2N) * sum  (kd_jsdiv)
+    const double scale = (double)temperature * temperature / (2.0 * (double)N);
+    return pair_up_impl("kd_jsdiv_up", "kd_jsdiv_up(finish)", LOSS_UP_JSDIV, s_lo, t_lo, temperature, N, h, w, C, H, W, align_corners, loss, scale, workspace, workspace_bytes, stream);
+}
+
+extern "C" int kd_logit_metrics_up(const float *s_lo, const float *t_lo, const int64_t *target, int32_t ignore_index, int32_t N, int32_t h,
+                                   int32_t w, int32_t C, int32_t H, int32_t W, int32_t align_corners, float *out, int64_t *conf_s,
+                                   int64_t *conf_t, int32_t accumulate, void *workspace, size_t workspace_bytes, kd_stream_t stream)
+{
+    KD_REQUIRE(s_lo && t_lo && target && out && conf_s && conf_t && workspace, KD_ERR_INVALID, "kd_logit_metrics_up: null argument");
+    KD_REQUIRE(N > 0 && h > 0 && w > 0 && C > 0 && H > 0 && W > 0, KD_ERR_INVALID, "kd_logit_metrics_up: bad argument");
+    KD_REQUIRE(conf_s != conf_t && (((uintptr_t)conf_s | (uintptr_t)conf_t | (uintptr_t)workspace) & 7) == 0, KD_ERR_INVALID,
+               "kd_logit_metrics_up: conf_s / conf_t must be two 8-B aligned matrices, the workspace 8-B aligned");
+    const LossSel sel = loss_select_up(LOSS_UP_METRICS, N, h, w, C, H, W, align_corners);
+    KD_REQUIRE(sel.why != LOSS_WHY_CLASSES, KD_ERR_UNSUPPORTED, "kd_logit_metrics_up: C <= 48 (got %d): materialise the logits", C);
+    UpGeom g;
+    if (const int rc = up_plan(g, sel, "kd_logit_metrics_up", true, N, h, w, C, H, W, workspace_bytes)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (!accumulate) {
+        if (hipMemsetAsync(conf_s, 0, (size_t)C * C * sizeof(int64_t), st) != hipSuccess ||
+            hipMemsetAsync(conf_t, 0, (size_t)C * C * sizeof(int64_t), st) != hipSuccess) {
+            kd_set_error("kd_logit_metrics_up: hipMemsetAsync failed");
+            return KD_ERR_HIP;
+        }
+    }
+    double *partial = (double *)workspace;
+    auto fn = launch_of(sel.kernel, LK_METRICS_UP_19, logit_metrics_up_kernel<19>, LK_METRICS_UP_0, logit_metrics_up_kernel<0>);
+    if (!fn) return no_launch("kd_logit_metrics_up", sel);
+    // two staged patches + two C x C histograms: 50.3 KiB at 19 classes, 138 KiB at 48 (of the CU's 160 KiB)
+    if (sel.lds > LOSS_LDS_DEFAULT) {
+        if (hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel.lds) != hipSuccess) {
+            (void)hipGetLastError();
+            kd_set_error("kd_logit_metrics_up: cannot reserve %zu B of LDS", sel.lds);
+            return KD_ERR_UNSUPPORTED;
+        }
+    }
+    KD_NOTE_PLUMBING(loss_kernel_name(sel.kernel));
+    hipLaunchKernelGGL(fn, dim3(sel.blocks), dim3(256), sel.lds, st, s_lo, t_lo, target, ignore_index, g, sel.nchunks, sel.cpr, partial,
+                       (unsigned long long *)conf_s, (unsigned long long *)conf_t);
+    KD_CHECK_LAUNCH("kd_logit_metrics_up");
+    hipLaunchKernelGGL(logit_metrics_finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, sel.blocks,
+                       1.0 / ((double)N * (double)C * (double)H * (double)W), out);
+    KD_CHECK_LAUNCH("kd_logit_metrics_up(finish)");
+    return KD_OK;
+}
+
+// ---- kd_kldiv_multi / kd_softmax_mean ---------------------------------------------------------------------------------------
+namespace {
+// the targets by value, weights divided by their sum; false (error set) on a bad argument
+bool mt_pack(const char *who, const kd_multi_targets *ts, MT &mt)
+{
+    if (!ts || ts->n < 1 || ts->n > KD_MULTI_MAX) {
+        kd_set_error("%s: 1 to %d operands, got %d", who, KD_MULTI_MAX, ts ? (int)ts->n : 0);
+        return false;
+    }
+    double W = 0.0;
+    for (int k = 0; k < ts->n; ++k) {
+        if (!ts->t[k].ptr || !ok_dt(ts->t[k].dtype) || !(ts->w[k] >= 0.f)) {
+            kd_set_error("%s: operand %d: null pointer, bad dtype or negative weight", who, k);
+            return false;
+        }
+        W += (double)ts->w[k];
+    }
+    if (!(W > 0.0) || W > 3.0e38) {
+        kd_set_error("%s: the weights must have a positive finite sum", who);
+        return false;
+    }
+    mt.n = ts->n;
+    for (int k = 0; k < KD_MULTI_MAX; ++k) {
+        mt.t[k] = k < ts->n ? v3(&ts->t[k]) : V3{nullptr, 0, 0, 0, 0};
+        mt.w[k] = k < ts->n ? (float)((double)ts->w[k] / W) : 0.f;
+    }
+    return true;
+}
+}  // namespace
+
+// Both entry points launch through this; kd_softmax_mean has no student, labels, scales or partials.
+static int multi_launch(const char *who, const LossSel &sel, hipStream_t st, V3 sv, const MT &mt, M3 gv, const int64_t *labels, int ignore_index,
+                        float invT, float gk, float sup_scale, int C, long long P, long long rows, const double *cnt, int ncount, double *pkd,
+                        double *pce)
+{
+    KD_NOTE_PLUMBING(loss_kernel_name(sel.kernel));
+    if (sel.kernel == LK_KLDM_NHWC) {
+        hipLaunchKernelGGL(kldm_nhwc_kernel, dim3(sel.blocks), dim3(256), sel.lds, st, sv, mt, gv, labels, ignore_index, invT, gk, sup_scale, C, rows,
+                           cnt, ncount, pkd, pce);
+    } else {
+        auto fn = launch_of(sel.kernel, LK_MT_WAVE_1_VEC, mt_wave_kernel<1, true, false>, LK_MT_WAVE_1_NOVEC, mt_wave_kernel<1, false, false>,
+                            LK_MT_WAVE_4_VEC, mt_wave_kernel<4, true, false>, LK_MT_WAVE_4_NOVEC, mt_wave_kernel<4, false, false>,
+                            LK_SM_WAVE_1_VEC, mt_wave_kernel<1, true, true>, LK_SM_WAVE_1_NOVEC, mt_wave_kernel<1, false, true>,
+                            LK_SM_WAVE_4_VEC, mt_wave_kernel<4, true, true>, LK_SM_WAVE_4_NOVEC, mt_wave_kernel<4, false, true>,
+                            LK_KLDM, kldm_kernel<false>, LK_KLDM_SMEAN, kldm_kernel<true>);
+        if (!fn) return no_launch(who, sel);
+        hipLaunchKernelGGL(fn, dim3(sel.blocks), dim3(256), 0, st, sv, mt, gv, labels, ignore_index, invT, gk, sup_scale, C, P, rows, cnt, ncount, pkd, pce);
+    }
+    KD_CHECK_LAUNCH(who);
+    return KD_OK;
+}
+
+extern "C" int kd_kldiv_multi(const kd_view3 *s, const kd_multi_targets *targets, float temperature, const int64_t *labels,
+                              int32_t ignore_index, float kd_scale, float sup_scale, int32_t N, int32_t C, int64_t P, float *losses,
+                              const kd_mview3 *grad, void *workspace, size_t workspace_bytes, kd_stream_t stream)
+{
+    KD_REQUIRE(s && s->ptr && losses && workspace, KD_ERR_INVALID, "kd_kldiv_multi: null argument");
+    KD_REQUIRE(ok_dt(s->dtype) && (!grad || (grad->ptr && ok_dt(grad->dtype))), KD_ERR_INVALID, "kd_kldiv_multi: bad dtype");
+    KD_REQUIRE(N > 0 && C > 0 && P > 0, KD_ERR_INVALID, "kd_kldiv_multi: bad shape");
+    KD_REQUIRE(temperature > 0.f, KD_ERR_INVALID, "kd_kldiv_multi: temperature must be positive");
+    KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, P), KD_ERR_WORKSPACE, "kd_kldiv_multi: workspace too small");
+    KD_REQUIRE(((uintptr_t)workspace & 7) == 0, KD_ERR_INVALID, "kd_kldiv_multi: workspace must be 8-B aligned");
+    MT mt;
+    if (!mt_pack("kd_kldiv_multi", targets, mt)) return KD_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    double *pkd = (double *)workspace, *pce = pkd + LOSS_MT_MAX_BLOCKS, *count = pce + LOSS_MT_MAX_BLOCKS;
+    const long long rows = (long long)N * P;
+    const LossSel sel = loss_select_multi(s, targets, grad, false, N, C, P);
+    const float gk = kd_scale * temperature / ((float)N * (float)P);
+    int ncount = 0;
+    if (labels) {
+        ncount = loss_blocks_for(rows, LOSS_MT_MAX_BLOCKS);
+        hipLaunchKernelGGL(ce2d_count_kernel, dim3(ncount), dim3(256), 0, st, labels, ignore_index, C, rows, count, (const float *)nullptr);
+        KD_CHECK_LAUNCH("kd_kldiv_multi(count)");
+    }
+    const double *cnt = labels ? count : nullptr;
+    if (const int rc = multi_launch("kd_kldiv_multi", sel, st, v3(s), mt, m3(grad), labels, ignore_index, 1.f / temperature, gk, sup_scale, C, P, rows,
+                                    cnt, ncount, pkd, pce))
+        return rc;
+    // per target 'mean' over N*C*P elements, then * T^2 * C  ==  T^2 / (N*P) * sum; the weights already sum to 1
+    const double kd_mul = (double)temperature * temperature / ((double)N * (double)P);
+    hipLaunchKernelGGL(mt_finish_kernel, dim3(1), dim3(256), 0, st, (const double *)pkd, (const double *)pce, sel.blocks, cnt, ncount, kd_mul,
+                       kd_scale, sup_scale, losses);
+    KD_CHECK_LAUNCH("kd_kldiv_multi(finish)");
+    return KD_OK;
+}
+
+extern "C" int kd_softmax_mean(const kd_multi_targets *logits, float temperature, int32_t N, int32_t C, int64_t P, const kd_mview3 *out,
+                               kd_stream_t stream)
+{
+    KD_REQUIRE(out && out->ptr && out->dtype == KD_F32, KD_ERR_INVALID, "kd_softmax_mean: out must be an fp32 view");
+    KD_REQUIRE(N > 0 && C > 0 && P > 0, KD_ERR_INVALID, "kd_softmax_mean: bad shape");
+    KD_REQUIRE(temperature > 0.f, KD_ERR_INVALID, "kd_softmax_mean: temperature must be positive");
+    MT mt;
+    if (!mt_pack("kd_softmax_mean", logits, mt)) return KD_ERR_INVALID;
+    const LossSel sel = loss_select_multi(nullptr, logits, out, true, N, C, P);
+    return multi_launch("kd_softmax_mean", sel, (hipStream_t)stream, V3{nullptr, 0, 0, 0, 0}, mt, m3(out), nullptr, 0, 1.f / temperature, 0.f, 0.f, C, P,
+                        (long long)N * P, nullptr, 0, nullptr, nullptr);
+}
+
+// ---- kd_focal / kd_focal_grad / kd_focal_up -----------------------------------------------------------------------------------------
+extern "C" int kd_focal(const kd_view3 *x, const int64_t *target, const float *alpha, float gamma, int32_t ignore_index, int32_t reduction,
+                        int32_t N, int32_t C, int64_t P, float *loss, double *stats, float *a_map, float *ce_map, void *workspace,
+                        size_t workspace_bytes, kd_stream_t stream)
+{
+    KD_REQUIRE(x && x->ptr && target && workspace, KD_ERR_INVALID, "kd_focal: null argument");
+    KD_REQUIRE(ok_dt(x->dtype) && N > 0 && C > 0 && P > 0 && gamma >= 0.f, KD_ERR_INVALID, "kd_focal: bad argument");
+    KD_REQUIRE(reduction >= 0 && reduction <= 2, KD_ERR_INVALID, "kd_focal: reduction is 0 (none), 1 (mean) or 2 (sum)");
+    KD_REQUIRE(reduction == 0 || loss, KD_ERR_INVALID, "kd_focal: 'mean' / 'sum' need a loss pointer");
+    KD_REQUIRE(reduction != 0 || (a_map && ce_map), KD_ERR_INVALID, "kd_focal: 'none' needs both per-pixel maps");
+    KD_REQUIRE((a_map == nullptr) == (ce_map == nullptr), KD_ERR_INVALID, "kd_focal: a_map and ce_map go together");
+    KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, P), KD_ERR_WORKSPACE, "kd_focal: workspace too small");
+    KD_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)stats & 7) == 0, KD_ERR_INVALID, "kd_focal: workspace / stats must be 8-B aligned");
+    double *partial = (double *)workspace;
+    const long long total = (long long)N * P;
+    const LossSel sel = loss_flat(LK_FOCAL, total, LOSS_FOCAL_MAX_BLOCKS);
+    hipStream_t st = (hipStream_t)stream;
+    KD_NOTE_PLUMBING(loss_kernel_name(sel.kernel));
+    hipLaunchKernelGGL(focal_kernel, dim3(sel.blocks), dim3(256), 0, st, v3(x), target, alpha, gamma, ignore_index, N, C, (long long)P, a_map, ce_map, partial);
+    KD_CHECK_LAUNCH("kd_focal");
+    hipLaunchKernelGGL(focal_finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, sel.blocks, (int)reduction, (double)total, stats,
+                       reduction == 0 ? (float *)nullptr : loss);
+    KD_CHECK_LAUNCH("kd_focal(finish)");
+    return KD_OK;
+}
+
+extern "C" int kd_focal_grad(const kd_view3 *x, const int64_t *target, const float *alpha, float gamma, int32_t ignore_index, int32_t reduction,
+                             int32_t N, int32_t C, int64_t P, const double *stats, const float *upstream, const float *a_map,
+                             const float *ce_map, const kd_mview3 *grad, kd_stream_t stream)
+{
+    KD_REQUIRE(x && x->ptr && target && upstream && grad && grad->ptr, KD_ERR_INVALID, "kd_focal_grad: null argument");
+    KD_REQUIRE(ok_dt(x->dtype) && ok_dt(grad->dtype) && N > 0 && C > 0 && P > 0 && gamma >= 0.f, KD_ERR_INVALID, "kd_focal_grad: bad argument");
+    KD_REQUIRE(reduction >= 0 && reduction <= 2, KD_ERR_INVALID, "kd_focal_grad: reduction is 0 (none), 1 (mean) or 2 (sum)");
+    KD_REQUIRE(reduction == 0 ? (a_map && ce_map) : stats != nullptr, KD_ERR_INVALID,
+               "kd_focal_grad: 'none' needs the forward's per-pixel maps, 'mean' / 'sum' its stats");
+    const LossSel sel = loss_flat(LK_FOCAL_GRAD, (long long)N * P);
+    KD_NOTE_PLUMBING(loss_kernel_name(sel.kernel));
+    hipLaunchKernelGGL(focal_grad_kernel, dim3(sel.blocks), dim3(256), 0, (hipStream_t)stream, v3(x), target, alpha, gamma,
+                       ignore_index, (int)reduction, N, C, (long long)P, stats, upstream, a_map, ce_map, m3(grad));
+    KD_CHECK_LAUNCH("kd_focal_grad");
+    return KD_OK;
+}
+
+extern "C" int kd_focal_up(const float *x_lo, const int64_t *target, const float *alpha, float gamma, int32_t ignore_index, int32_t reduction,
+                           int32_t N, int32_t h, int32_t w, int32_t C, int32_t H, int32_t W, int32_t align_corners, float *loss, double *stats,
+                           void *workspace, size_t workspace_bytes, kd_stream_t stream)
+{
+    KD_REQUIRE(x_lo && target && loss && workspace, KD_ERR_INVALID, "kd_focal_up: null argument");
+    const LossSel sel = loss_select_up(LOSS_UP_FOCAL, N, h, w, C, H, W, align_corners);
+    KD_REQUIRE(N > 0 && h > 0 && w > 0 && C > 0 && sel.why != LOSS_WHY_CLASSES && H > 0 && W > 0 && gamma >= 0.f, KD_ERR_INVALID,
+               "kd_focal_up: bad argument (C <= 48: the staged patch fits 64 KiB of LDS)");
+    KD_REQUIRE(reduction == 1 || reduction == 2, KD_ERR_INVALID, "kd_focal_up: reduction is 1 (mean) or 2 (sum)");
+    // (the size before the alignment, as this entry point always reported them; up_plan repeats the size check)
+    KD_REQUIRE(workspace_bytes >= kd_loss_workspace(N, C, (int64_t)H * W), KD_ERR_WORKSPACE, "kd_focal_up: workspace too small");
+    KD_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)stats & 7) == 0, KD_ERR_INVALID, "kd_focal_up: workspace / stats must be 8-B aligned");
+    UpGeom g;
+    if (const int rc = up_plan(g, sel, "kd_focal_up", false, N, h, w, C, H, W, workspace_bytes)) return rc;
+    double *partial = (double *)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    KD_NOTE_PLUMBING(loss_kernel_name(sel.kernel));
+    auto fn = launch_of(sel.kernel, LK_FOCAL_UP_19, focal_up_kernel<19>, LK_FOCAL_UP_0, focal_up_kernel<0>);
+    if (!fn) return no_launch("kd_focal_up", sel);
+    hipLaunchKernelGGL(fn, dim3(sel.blocks), dim3(256), sel.lds, st, x_lo, target, alpha, gamma, ignore_index, g, sel.nchunks, sel.cpr, partial);
+    KD_CHECK_LAUNCH("kd_focal_up");
+    hipLaunchKernelGGL(focal_finish_kernel, dim3(1), dim3(256), 0, st, (const double *)partial, sel.blocks, (int)reduction, (double)N * H * W, stats, loss);
+    KD_CHECK_LAUNCH("kd_focal_up(finish)");
+    return KD_OK;
+}
+
+// ---- kd_topk_hint_mse ------------------------------------------------------------------------------------------------------------
+extern "C" size_t kd_topk_hint_workspace(int32_t N, int32_t C, int64_t P) { return loss_topk_workspace_bytes(N, C, P); }
+
+extern "C" int kd_topk_hint_mse(const kd_view3 *s, const kd_view3 *t, int32_t K, int32_t N, int32_t C, int64_t P, float *loss,
+                                const kd_mview3 *grad, float grad_scale, float *mask, void *workspace, size_t workspace_bytes, kd_stream_t stream)
+{
+    KD_REQUIRE(s && t && s->ptr && t->ptr && loss && workspace, KD_ERR_INVALID, "kd_topk_hint_mse: null argument");
+    KD_REQUIRE(ok_dt(s->dtype) && ok_dt(t->dtype) && (!grad || ok_dt(grad->dtype)), KD_ERR_INVALID, "kd_topk_hint_mse: bad dtype");
+    KD_REQUIRE(N > 0 && C > 0 && P > 0, KD_ERR_INVALID, "kd_topk_hint_mse: bad shape");
+    KD_REQUIRE(K >= 1 && K <= C, KD_ERR_INVALID, "kd_topk_hint_mse: K = %d channels kept of %d: need 1 <= K <= C", K, C);
+    const LossSel sel = loss_select_topk(s, t, grad, mask, workspace, N, C, P);
+    KD_REQUIRE(sel.why != LOSS_WHY_TOPK_MAX_C, KD_ERR_UNSUPPORTED, "kd_topk_hint_mse: C = %d > %d channels", C, LOSS_TOPK_MAX_C);
+    KD_REQUIRE(workspace_bytes >= kd_topk_hint_workspace(N, C, P), KD_ERR_WORKSPACE, "kd_topk_hint_mse: workspace too small");
+    KD_REQUIRE(((uintptr_t)workspace & 7) == 0, KD_ERR_INVALID, "kd_topk_hint_mse: workspace must be 8-B aligned");
+    const int nchunk = sel.chunks;
+    const size_t nc = (size_t)N * C;
+    double *pt2 = (double *)workspace, *pd2 = pt2 + nc * nchunk, *part = pd2 + nc * nchunk;
+    float *mk = mask ? mask : (float *)((char *)workspace + sel.aux_off);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(topk_sums_kernel, dim3((unsigned)nchunk, (unsigned)((C + 63) / 64), (unsigned)N), dim3(256), 0, st, v3(s), v3(t), C,
+                       (long long)P, sel.per_chunk, nchunk, pt2, pd2);
+    KD_CHECK_LAUNCH("kd_topk_hint_mse(sums)");
+    hipLaunchKernelGGL(topk_select_kernel, dim3(N), dim3(1024), (size_t)C * sizeof(double), st, (const double *)pt2, (const double *)pd2, C,
+                       nchunk, (int)K, mk, part);
+    KD_CHECK_LAUNCH("kd_topk_hint_mse(select)");
+    // loss = sum_n sum_kept mean_p (s-t)^2 / (N K) ; grad = 2 mask (s-t) / (P N K)
+    const double denom = (double)N * (double)K;
+    const float gscale = (float)((double)grad_scale * 2.0 / ((double)P * denom));
+    const long long numel = (long long)nc * P;
+    KD_NOTE_PLUMBING(loss_kernel_name(sel.kernel));
+    auto vec = [&](auto z, auto cfast) {
+        using T = decltype(z);
+        hipLaunchKernelGGL((topk_grad_vec_kernel<T, decltype(cfast)::value>), dim3(sel.blocks), dim3(256), 0, st, (const T *)s->ptr,
+                           (const T *)t->ptr, (T *)grad->ptr, (const float *)mk, gscale, C, (long long)P, numel / 8);
+    };
+    switch (sel.kernel) {
+    case LK_TOPK_VEC_F32_CFAST: vec(float{}, std::true_type{}); break;
+    case LK_TOPK_VEC_F32_PFAST: vec(float{}, std::false_type{}); break;
+    case LK_TOPK_VEC_BF16_CFAST: vec(bf16_t{}, std::true_type{}); break;
+    case LK_TOPK_VEC_BF16_PFAST: vec(bf16_t{}, std::false_type{}); break;
+    case LK_TOPK_GRAD:
+        hipLaunchKernelGGL(topk_grad_kernel, dim3(sel.blocks), dim3(256), 0, st, v3(s), v3(t), m3(grad), (const float *)mk, gscale, N, C, (long long)P,
+                           s->sC == 1 ? 1 : 0);
+        break;
+    case LK_TOPK_NOGRAD: break;     // no gradient asked for: the sums, the selection and the loss alone
+    default: return no_launch("kd_topk_hint_mse", sel);
+    }
+    if (sel.kernel != LK_TOPK_NOGRAD) KD_CHECK_LAUNCH("kd_topk_hint_mse(grad)");
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, st, (const double *)part, (int)N, 1.0 / ((double)P * denom), (const double *)nullptr, loss);
+    KD_CHECK_LAUNCH("kd_topk_hint_mse(finish)");
+    return KD_OK;
+}
+
+// ---- kd_radam_step / kd_radam_step_multi / kd_scale_by_device_scalar ---------------------------------------------------------------
 // (N_sma, step_size) exactly as utils/optim/radam.py:64-83 computes (and caches) them
 static void radam_constants(int step, float beta1, float beta2, int *rect, double *step_size)
 {
@@ -2251,6 +2089,41 @@ static void radam_constants(int step, float beta1, float beta2, int *rect, doubl
         *step_size = sqrt((1 - beta2_t) * (nsma - 4) / (nmax - 4) * (nsma - 2) / nsma * nmax / (nmax - 2)) / (1 - pow((double)beta1, step));
     else
         *step_size = 1.0 / (1 - pow((double)beta1, step));
+}
+
+extern "C" int kd_radam_step(float *p, const float *g, float *exp_avg, float *exp_avg_sq, int64_t n, int32_t step, float lr,
+                             float beta1, float beta2, float eps, float weight_decay, kd_stream_t stream)
+{
+    KD_REQUIRE(p && g && exp_avg && exp_avg_sq && n > 0 && step >= 1, KD_ERR_INVALID, "kd_radam_step: bad argument");
+    int rect;
+    double step_size;
+    radam_constants(step, beta1, beta2, &rect, &step_size);
+    const LossSel sel = loss_flat(LK_RADAM, n);
+    KD_NOTE_PLUMBING(loss_kernel_name(sel.kernel));
+    hipLaunchKernelGGL(radam_kernel, dim3(sel.blocks), dim3(256), 0, (hipStream_t)stream, p, g, exp_avg, exp_avg_sq,
+                       (long long)n, beta1, beta2, eps, (float)((double)weight_decay * lr), (float)(step_size * lr), rect);
+    KD_CHECK_LAUNCH("kd_radam_step");
+    return KD_OK;
+}
+
+extern "C" int kd_scale_by_device_scalar(void *x, int32_t dtype, int64_t n, const float *scale, kd_stream_t stream)
+{
+    KD_REQUIRE(x && scale && n > 0, KD_ERR_INVALID, "kd_scale_by_device_scalar: bad argument");
+    KD_REQUIRE(dtype == KD_F32 || dtype == KD_BF16, KD_ERR_INVALID, "kd_scale_by_device_scalar: bad dtype");
+    KD_REQUIRE(kd_aligned16(x), KD_ERR_INVALID, "kd_scale_by_device_scalar: x must be 16-B aligned");
+    const LossSel sel = loss_select_scale(dtype, n);
+    KD_NOTE_PLUMBING(loss_kernel_name(sel.kernel));
+    auto run = [&](auto z) {
+        using T = decltype(z);
+        hipLaunchKernelGGL(scale_by_device_scalar_kernel<T>, dim3(sel.blocks), dim3(256), 0, (hipStream_t)stream, (T *)x, (long long)(n / 8), (long long)n, scale);
+    };
+    switch (sel.kernel) {
+    case LK_SCALE_F32: run(float{}); break;
+    case LK_SCALE_BF16: run(bf16_t{}); break;
+    default: return no_launch("kd_scale_by_device_scalar", sel);
+    }
+    KD_CHECK_LAUNCH("kd_scale_by_device_scalar");
+    return KD_OK;
 }
 
 extern "C" int kd_radam_step_multi(const kd_radam_tensor *ts, int32_t count, kd_stream_t stream)
@@ -2279,7 +2152,7 @@ extern "C" int kd_radam_step_multi(const kd_radam_tensor *ts, int32_t count, kd_
         }
         b.blk0[k] = nb;
         b.count = k;
-        KD_NOTE_PLUMBING("radam_multi_kernel");
+        KD_NOTE_PLUMBING(loss_kernel_name(LK_RADAM_MULTI));
         hipLaunchKernelGGL(radam_multi_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, b);
         KD_CHECK_LAUNCH("kd_radam_step_multi");
         done += k;

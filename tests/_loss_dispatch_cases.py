@@ -2,10 +2,11 @@
 points of csrc/losses.hip, rows on both sides of every numeric gate, a grid-stride second trip per capped grid, tails, views of
 wider buffers and values that bite; the seeded inputs of each row and its float64 reference on the CPU.
 
-Every row names the KD_NOTE_PLUMBING literal it is meant to reach (`kernel`) and `rule(c)` predicts that literal from the row
-alone, by a restatement of the launcher's gate (the source lines are quoted next to each restatement).
-tests/test_loss_dispatch_host.py checks, without a GPU, that every literal of losses.hip has a row, that every row's rule gives the
-row's literal and that every reference runs.  Nothing here touches the device or the library.
+Every row names the kernel it is meant to reach (`kernel`: the name the launcher notes, loss_kernel_name() of csrc/loss_select.h)
+and `rule(c)` predicts that name from the row alone, by a restatement of the family's selector in csrc/loss_select.h (the source
+lines are quoted next to each restatement).  tests/test_loss_dispatch_host.py checks, without a GPU, that every name of the table has
+a row, that every row's rule gives the row's name and that every reference runs; tests/test_loss_select_host.py holds the compiled
+selectors against the rules.  Nothing here touches the device or the library.
 
 Operands are logical (N, C, H, W) or (N, C) arrays; a row's `lay` says how each one lies in memory:
   "nchw"  dense, pixels fastest        "cl"      dense channels-last (the engine's logits layout)
@@ -27,13 +28,13 @@ import _ensemble_ref as ER
 
 DT = {"f32": torch.float32, "bf16": torch.bfloat16}
 U = 2.0 ** -24
-MAX_BLOCKS = 2048                       # losses.hip: "constexpr int MAX_BLOCKS = 2048;"
-FOCAL_MAX_BLOCKS = 2 * MAX_BLOCKS // 3  # "constexpr int FOCAL_MAX_BLOCKS = 2 * MAX_BLOCKS / 3;"
-MT_MAX_BLOCKS = 2 * MAX_BLOCKS // 3     # "constexpr int MT_MAX_BLOCKS = 2 * MAX_BLOCKS / 3;"
-MET_MAX_BLOCKS = MAX_BLOCKS // 2        # "constexpr int MET_MAX_BLOCKS = MAX_BLOCKS / 2;"
-UP_NW = 160                             # "constexpr int UP_NW = 160;"
-LDS = 65536                             # the default dynamic-LDS limit the gates compare with
-RADAM_BLK = 256 * 8                     # "constexpr int RADAM_BLK = 256 * 8;"
+MAX_BLOCKS = 2048                       # loss_select.h: "constexpr int LOSS_MAX_BLOCKS = 2048;"
+FOCAL_MAX_BLOCKS = 2 * MAX_BLOCKS // 3  # "constexpr int LOSS_FOCAL_MAX_BLOCKS = 2 * LOSS_MAX_BLOCKS / 3;"
+MT_MAX_BLOCKS = 2 * MAX_BLOCKS // 3     # "constexpr int LOSS_MT_MAX_BLOCKS = 2 * LOSS_MAX_BLOCKS / 3;"
+MET_MAX_BLOCKS = MAX_BLOCKS // 2        # "constexpr int LOSS_MET_MAX_BLOCKS = LOSS_MAX_BLOCKS / 2;"
+UP_NW = 160                             # "constexpr int LOSS_UP_NW = 160;"
+LDS = 65536                             # "constexpr size_t LOSS_LDS_DEFAULT = 65536;": the default dynamic-LDS limit the gates compare with
+RADAM_BLK = 256 * 8                     # losses.hip: "constexpr int RADAM_BLK = 256 * 8;"
 KD_MULTI_MAX = 16                       # include/kdcc.h
 SENTINEL = 7.0
 
@@ -104,21 +105,21 @@ def lays(c):
 
 
 def blocks_for(total):
-    """losses.hip blocks_for(): "long long b = (total + 255) / 256; return b < 1 ? 1 : (b > MAX_BLOCKS ? MAX_BLOCKS : b);" """
+    """loss_select.h loss_blocks_for(), cap = LOSS_MAX_BLOCKS: "const long long b = (total + 255) / 256; return (int)(b < 1 ? 1 : (b > cap ? cap : b));" """
     return max(1, min((total + 255) // 256, MAX_BLOCKS))
 
 
 def nhwc(st, N, C, P):
-    """pair_impl: "auto nhwc = [&](sN, sC, sP) { return sC == 1 && sP == C && (sN == (long long)C * P || N == 1); };"
-    (ce2d_impl, kd_confusion and nhwc_dense() spell the same test out)."""
+    """loss_select.h loss_nhwc(): "return v->sC == 1 && v->sP == C && (v->sN == (int64_t)C * P || N == 1);" (every family asks it)."""
     sN, sC, sP = st
     return sC == 1 and sP == C and (sN == C * P or N == 1)
 
 
 def dense_same(c):
-    """losses.hip dense_same(): every operand dense in one of the two orders ("(sC == 1 && sP == C && sN == C * P) || (sP == 1 &&
-    sC == P && sN == C * P)"), "a->sN != b->sN || ... || a->dtype != b->dtype" -> false, the same for g, "!kd_aligned16(a->ptr) ||
-    !kd_aligned16(b->ptr) || (g && !kd_aligned16(g->ptr))" -> false, then "return ((long long)N * C * P) % 8 == 0;" """
+    """loss_select.h loss_dense_same(): every operand dense in one of the two orders ("(a->sC == 1 && a->sP == C && a->sN == C * P) ||
+    (a->sP == 1 && a->sC == P && a->sN == C * P)"), "a->sN != b->sN || ... || a->dtype != b->dtype" -> false, the same for g,
+    "!loss_aligned16(a->ptr) || !loss_aligned16(b->ptr) || (g && !loss_aligned16(g->ptr))" -> false, then
+    "return ((long long)N * C * P) % 8 == 0;" """
     N, C, P = dims(c)
     ls, lt, lg = lays(c)
     sdt, tdt, gdt = c["sdt"], c["tdt"], c.get("gdt", c["sdt"])
@@ -136,9 +137,10 @@ def dense_same(c):
 
 # ============================================================================== the two-operand criteria: kldiv / jsdiv / ensemble_kldiv
 def pair_rule(c):
-    """pair_impl: "const size_t lds = (size_t)2 * 256 * C * sizeof(float);"
-    "const bool fast = lds <= 65536 && nhwc(s) && nhwc(t) && (!grad || nhwc(grad));" then the KD_PAIR_DT chain on
-    (s->dtype, t->dtype, gdt) with "const int gdt = grad ? grad->dtype : s->dtype;" """
+    """loss_select_pair: "const size_t lds = (size_t)2 * 256 * C * sizeof(float);"
+    "if (lds <= LOSS_LDS_DEFAULT && loss_nhwc(s, N, C, P) && loss_nhwc(t, N, C, P) && (!grad || loss_nhwc(grad, N, C, P)))" then
+    "LK_PAIR_NHWC + 8 * kind + 4 * (s->dtype == KD_BF16) + 2 * (t->dtype == KD_BF16) + (gdt == KD_BF16)" with
+    "const int gdt = grad ? grad->dtype : s->dtype;", else "LK_PAIR_KLD + kind" """
     N, C, P = dims(c)
     fast = 2 * 256 * C * 4 <= LDS and all(nhwc(strides(l, c["shape"]), N, C, P) for l in lays(c) if l is not None)
     if not fast:
@@ -239,8 +241,8 @@ def build_pair(c):
 
 # ================================================================================================================ kd_hint_mse
 def mse_rule(c):
-    """kd_hint_mse: "if (dense_same(s, t, grad, N, C, P)) { ... if (s->dtype == KD_BF16) mse_vec_kernel<bf16_t> else
-    mse_vec_kernel<float> } else mse_strided_kernel" """
+    """loss_select_mse: "if (loss_dense_same(s, t, grad, N, C, P)) return loss_flat((LossKernel)(LK_MSE_VEC_F32 + (s->dtype == KD_BF16)),
+    numel / 8);" else "return loss_flat(LK_MSE_STRIDED, numel);" """
     if dense_same(c):
         return f"mse_vec_kernel<{c['sdt']}>"
     return "mse_strided_kernel"
@@ -294,7 +296,8 @@ def build_mse(c):
 
 # ======================================================================================================= kd_weighted_hint_mse
 def whmse_plan(P):
-    """kd_weighted_hint_mse: "const int chunks = (int)(P < 64 ? P : 64); const long long per_chunk = (P + chunks - 1) / chunks;"
+    """loss_select_whmse: "c.chunks = (int)(P < LOSS_WHMSE_MAX_CHUNKS ? P : LOSS_WHMSE_MAX_CHUNKS);" (64)
+    "c.per_chunk = c.chunks > 0 ? (P + c.chunks - 1) / c.chunks : 0;"
     -> (chunks, per_chunk, empty trailing chunks, pixels of the last non-empty chunk)."""
     chunks = P if P < 64 else 64
     per = (P + chunks - 1) // chunks
@@ -338,7 +341,7 @@ def build_whmse(c):
 
 # ======================================================================================= kd_ce2d / kd_ce2d_weighted and their gradient
 def ce_rule(c):
-    """ce2d_impl: "if ((size_t)256 * C * sizeof(float) <= 65536 && x->sC == 1 && x->sP == C && (x->sN == (long long)C * P || N == 1))"
+    """loss_select_ce2d: "const size_t lds = (size_t)256 * C * sizeof(float);" "if (lds <= LOSS_LDS_DEFAULT && loss_nhwc(x, N, C, P))"
     -> ce2d_nhwc_kernel<float | bf16_t>, else ce2d_kernel"""
     N, C, P = dims(c)
     if 256 * C * 4 <= LDS and nhwc(strides(c["lay"], c["shape"]), N, C, P):
@@ -433,8 +436,8 @@ def build_ce(c):
 
 # ============================================================================================================== kd_confusion
 def conf_rule(c):
-    """kd_confusion: "if ((size_t)256 * C * sizeof(float) + (size_t)C * C * sizeof(unsigned int) <= 65536 && x->sC == 1 &&
-    x->sP == C && (x->sN == (long long)C * P || N == 1))" -> confusion_nhwc_kernel<float | bf16_t>, else confusion_kernel.
+    """loss_select_confusion: "hist = (size_t)C * C * sizeof(unsigned int), lds = (size_t)256 * C * sizeof(float) + hist;"
+    "if (lds <= LOSS_LDS_DEFAULT && loss_nhwc(x, N, C, P))" -> confusion_nhwc_kernel<float | bf16_t>, else confusion_kernel.
     256 * 4 * C + 4 * C^2 <= 65536 holds up to C = 53 (65 508 B) and fails from C = 54 (66 960 B)."""
     N, C, P = dims(c)
     if 256 * C * 4 + C * C * 4 <= LDS and nhwc(strides(c["lay"], c["shape"]), N, C, P):
@@ -493,8 +496,9 @@ UP_NAME = {"ce2d_up": "ce2d_up_kernel<{}>", "kldiv_up": "pair_up_kernel<kld,{}>"
 
 
 def up_rule(c):
-    """The five launchers: "C <= 48" / "C <= 24" (KD_REQUIRE), up_geom's "return (int)(255.f * g.sw) + 3 <= UP_NW;" (g.sw = (w - 1) /
-    (W - 1) with align_corners, w / W without), then "C == 19 ? ..._kernel<19> : ..._kernel<0>".  None: the call is refused."""
+    """loss_select_up: "if (C > loss_up_max_classes(op))" (48, or 24 for the two divergences), then (int)(255.f * c.sw) + 3 <=
+    LOSS_UP_NW as "if (!(255.f * c.sw < (float)(LOSS_UP_NW - 2)))" (c.sw = (w - 1) / (W - 1) with align_corners, w / W without),
+    then "LK_CE2D_UP_0 + 2 * op + (C == 19)": ..._kernel<19> or ..._kernel<0>.  None: the call is refused."""
     N, h, w, C, H, W = c["geom"]
     if C > UP_LIMIT[c["op"]]:
         return None
@@ -505,7 +509,7 @@ def up_rule(c):
 
 
 def up_chunks(c):
-    """up_plan: "u.cpr = (W + 255) / 256; u.nchunks = (long long)N * H * u.cpr;" """
+    """loss_select_up: "c.cpr = (W + 255) / 256; c.nchunks = (long long)N * H * c.cpr;" """
     N, h, w, C, H, W = c["geom"]
     return N * H * ((W + 255) // 256)
 
@@ -652,8 +656,8 @@ def build_focal(c):
 
 # ========================================================================================================== kd_topk_hint_mse
 def topk_rule(c):
-    """kd_topk_hint_mse: no gradient -> "topk_nograd"; "const bool cfast = s->sC == 1 && s->sP == C;"
-    "if (dense_same(s, t, grad, N, C, P) && (cfast ? C % 8 == 0 : P % 8 == 0) && kd_aligned16(mk))" -> topk_grad_vec_kernel<T, CF>,
+    """loss_select_topk: no gradient -> "topk_nograd"; "const bool cfast = s->sC == 1 && s->sP == C;"
+    "if (loss_dense_same(s, t, grad, N, C, P) && (cfast ? C % 8 == 0 : P % 8 == 0) && (mk & 15u) == 0)" -> topk_grad_vec_kernel<T, CF>,
     else topk_grad_kernel.  (mk: the caller's (N, C) fp32 mask or the workspace's own, both 16-B aligned here.)"""
     N, C, P = dims(c)
     if not c.get("gdt", c["sdt"]):
@@ -729,8 +733,8 @@ def build_topk(c):
 
 # ============================================================================================ kd_kldiv_multi / kd_softmax_mean
 def row_vec_ok(lay, dt, shape):
-    """losses.hip row_vec_ok(): "(C & 3) == 0 && ((uintptr_t)p & (dt == KD_BF16 ? 7u : 15u)) == 0 && (P == 1 || (sP & 3) == 0) &&
-    (N == 1 || (sN & 3) == 0)" """
+    """loss_select.h loss_row_vec_ok(): "(C & 3) == 0 && ((uintptr_t)v->ptr & (v->dtype == KD_BF16 ? 7u : 15u)) == 0 && (P == 1 ||
+    (v->sP & 3) == 0) && (N == 1 || (v->sN & 3) == 0)" """
     N, C, P = (shape[0], shape[1], 1) if len(shape) == 2 else (shape[0], shape[1], shape[2] * shape[3])
     sN, sC, sP = strides(lay, shape)
     base_ok = lay != "off1"        # a slice starts 8 elements in: 32 B of fp32, 16 B of bf16
@@ -738,13 +742,12 @@ def row_vec_ok(lay, dt, shape):
 
 
 def multi_rule(c):
-    """kd_kldiv_multi: "bool unit = s->sC == 1 && (!grad || grad->sC == 1);" (and every target's), "bool dense = nhwc_dense(s)
-    && (!grad || nhwc_dense(grad))" (and every target's), vec = row_vec_ok of all of them;
+    """loss_select_multi: "bool unit = (!s || s->sC == 1) && (!g || g->sC == 1);" (and every target's), "bool dense = !smean &&
+    (!s || loss_nhwc(s, N, C, P)) && (!g || loss_nhwc(g, N, C, P));" (and every target's), vec = loss_row_vec_ok of all of them;
     "const bool narrow = C < 22 && rows >= 16384;"
-    "const int path = narrow && dense ? MT_NHWC : (unit && C <= 1024 && !narrow ? MT_WAVE : MT_ANY);"
-    MT_WAVE: "if (C <= 256) { vec ? <1, true> : <1, false> } else { vec ? <4, true> : <4, false> }".
-    kd_softmax_mean: the same without the student and without MT_NHWC: "if (unit && C <= 1024 && !(C < 22 && rows >= 16384))" the
-    four wave forms, else kldm_kernel<true>."""
+    "if (narrow && dense)" -> kldm_nhwc_kernel, "else if (unit && C <= 1024 && !narrow)" -> the wave kernel
+    "LK_MT_WAVE_1_VEC + 4 * smean + 2 * (C > 256) + !vec", else kldm_kernel / kldm_kernel<smean>.
+    kd_softmax_mean asks the same function without a student and with smean (no NHWC kernel for it)."""
     N, C, P = dims(c)
     rows = N * P
     smean = c["op"] == "softmax_mean"
@@ -913,7 +916,7 @@ def build(c):
 
 
 def rule(c):
-    """The literal the launcher's gate, restated above, picks for the row ("(refused)" when it launches nothing); entry points
+    """The name the family's selector, restated above, picks for the row ("(refused)" when nothing is launched); entry points
     with one kernel have no gate to restate."""
     op = c["op"]
     if op == "topk" and not 1 <= c["k"] <= c["shape"][1]:       # "KD_REQUIRE(K >= 1 && K <= C, ...)"

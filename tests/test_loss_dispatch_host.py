@@ -1,9 +1,12 @@
-"""Keeps tests/_loss_dispatch_cases.py honest without a GPU: every KD_NOTE_PLUMBING literal of csrc/losses.hip has a row, every
-row names a literal the source declares, every row's restated gate yields the row's literal, adjacent rows of a gate land on
+"""Keeps tests/_loss_dispatch_cases.py honest without a GPU: every name the launchers of csrc/losses.hip can note (the table of
+csrc/loss_select.h, compiled for the host) has a row, every row names one of them, every kernel value the selectors can return is
+launched by losses.hip, every row's restated gate yields the row's name, adjacent rows of a gate land on
 different kernels, every second-trip row exceeds its grid cap, every reference runs, is finite and has the declared shape, and
 the reduction rows' claims about a single fp32 chain hold."""
+import ctypes
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -12,7 +15,9 @@ import _criteria_ref as CR
 import _loss_dispatch_cases as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "knowledge-distillation-by-replacing-cheap-conv_amd", "csrc", "losses.hip")
+CSRC = os.path.join(ROOT, "knowledge-distillation-by-replacing-cheap-conv_amd", "csrc")
+SOURCE = os.path.join(CSRC, "losses.hip")
+WRAP = os.path.join(ROOT, "tests", "loss_select_host")
 REFUSED = "(refused)"
 
 
@@ -22,17 +27,40 @@ def source_text():
 
 
 def declared_literals():
-    return set(re.findall(r'KD_NOTE_PLUMBING\("([^"]+)"\)', source_text()))
+    """The names of loss_kernel_name(): the launchers note nothing else (the third test below)."""
+    subprocess.check_call(["make", "-s", "-C", WRAP])
+    so = ctypes.CDLL(os.path.join(WRAP, "_build", "libloss_select.so"))
+    so.ls_name.restype = ctypes.c_char_p
+    names = [so.ls_name(k).decode() for k in range(so.ls_refused())]
+    assert len(names) == len(set(names))
+    return set(names)
 
 
 def test_every_noted_literal_has_a_row_and_every_row_names_a_noted_literal():
     declared = declared_literals()
-    assert len(declared) >= 71, "the scan found too few KD_NOTE_PLUMBING literals in losses.hip: has the macro been renamed?"
+    assert len(declared) >= 71, "the name table of loss_select.h has too few names: has a family left it?"
     covered = {c["kernel"] for c in L.CASES} - {REFUSED}
     missing = sorted(declared - covered)
     assert not missing, f"dispatch branches of losses.hip without a row in tests/_loss_dispatch_cases.py: {missing}"
     unknown = sorted(covered - declared)
     assert not unknown, f"rows name kernels losses.hip does not declare: {unknown}"
+
+
+def test_every_selectable_kernel_is_launched_by_losses_hip():
+    """Every enumerator of LossKernel but LOSS_REFUSED is named in the code of losses.hip: no value is selectable but unlaunchable."""
+    with open(os.path.join(CSRC, "loss_select.h")) as f:
+        header = re.sub(r"//[^\n]*|/\*.*?\*/", "", f.read(), flags=re.S)
+    body = re.search(r"enum\s+LossKernel\s*\{(.*?)\};", header, flags=re.S).group(1)
+    enumerators = [e.split("=")[0].strip() for e in body.split(",") if e.strip()]
+    assert enumerators[-1] == "LOSS_REFUSED" and len(enumerators) >= 49 and len(set(enumerators)) == len(enumerators)
+    code = re.sub(r"//[^\n]*|/\*.*?\*/", "", source_text(), flags=re.S)
+    missing = [e for e in enumerators[:-1] if not re.search(r"\b%s\b" % e, code)]
+    assert not missing, f"kernel values loss_select.h can return and losses.hip never launches: {missing}"
+
+
+def test_losses_hip_notes_no_literal_of_its_own():
+    assert 'KD_NOTE_PLUMBING("' not in source_text()
+    assert "KD_NOTE_PLUMBING(loss_kernel_name(" in source_text()
 
 
 def test_the_conv_log_macro_does_not_appear_in_losses_hip():
