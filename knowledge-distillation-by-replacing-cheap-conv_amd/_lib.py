@@ -269,7 +269,8 @@ def last_kernel():
 
 def last_plumbing_kernel():
     """Name of the device kernel the calling thread's last plumbing dispatch selected (trunk_ops / bwd_ops / small_ops, and the
-    criterion, metric and optimizer entry points of losses.hip); independent of last_kernel() and of the counted log."""
+    criterion, metric and optimizer entry points of losses.hip, and the float4 / scalar choice of the NHWC BatchNorm and
+    average-pool entry points of bn_nhwc.hip / dense_ops.hip); independent of last_kernel() and of the counted log."""
     return lib().kd_debug_last_plumbing_kernel().decode()
 
 

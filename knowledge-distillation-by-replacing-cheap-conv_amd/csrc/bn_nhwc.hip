@@ -169,13 +169,19 @@ extern "C" int kd_bn_nhwc_bwd(const float *gy, int32_t ldg, const float *x, int3
                            dbeta, (int)accumulate);
         KD_CHECK_LAUNCH("kd_bn_nhwc_bwd(finish)");
     }
-    if (!dx) return KD_OK;
-    if (vec4_ok(C, {{gy, ldg}, {x, ldx}, {relu ? y : nullptr, ldy}, {res, ldres}, {dx, lddx}}))
+    if (!dx) {
+        KD_NOTE_PLUMBING("bn_nhwc_grad_finish_kernel");
+        return KD_OK;
+    }
+    if (vec4_ok(C, {{gy, ldg}, {x, ldx}, {relu ? y : nullptr, ldy}, {res, ldres}, {dx, lddx}})) {
+        KD_NOTE_PLUMBING("bn_nhwc_dx_kernel<4>");
         hipLaunchKernelGGL(bn_nhwc_dx_kernel<4>, dim3(grid_for(M * (C / 4))), dim3(TPB), 0, s, g, gy, ldg, x, ldx, y, ldy, res, ldres, dx,
                            lddx, gamma, save_mean, save_invstd, (const float *)sums, (int)(training != 0), (int)relu);
-    else
+    } else {
+        KD_NOTE_PLUMBING("bn_nhwc_dx_kernel<1>");
         hipLaunchKernelGGL(bn_nhwc_dx_kernel<1>, dim3(grid_for(M * C)), dim3(TPB), 0, s, g, gy, ldg, x, ldx, y, ldy, res, ldres, dx, lddx,
                            gamma, save_mean, save_invstd, (const float *)sums, (int)(training != 0), (int)relu);
+    }
     KD_CHECK_LAUNCH("kd_bn_nhwc_bwd(dx)");
     return KD_OK;
 }

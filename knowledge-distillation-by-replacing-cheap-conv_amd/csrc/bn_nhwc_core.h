@@ -184,11 +184,14 @@ inline void launch_batch_stats(const BnGeom &g, const float *x, int ldx, float *
 inline void launch_apply(const BnGeom &g, const float *x, int ldx, float *y, int ldy, const float *gamma, const float *beta,
                          const float *mean, const float *invstd, int relu, hipStream_t s)
 {
-    if (vec4_ok(g.C, {{x, ldx}, {y, ldy}}))
+    if (vec4_ok(g.C, {{x, ldx}, {y, ldy}})) {
+        KD_NOTE_PLUMBING("bn_nhwc_apply_kernel<4>");
         hipLaunchKernelGGL(bn_nhwc_apply_kernel<4>, dim3(grid_for(g.M * (g.C / 4))), dim3(TPB), 0, s, g, x, ldx, y, ldy, gamma, beta, mean, invstd,
                            relu);
-    else
+    } else {
+        KD_NOTE_PLUMBING("bn_nhwc_apply_kernel<1>");
         hipLaunchKernelGGL(bn_nhwc_apply_kernel<1>, dim3(grid_for(g.M * g.C)), dim3(TPB), 0, s, g, x, ldx, y, ldy, gamma, beta, mean, invstd, relu);
+    }
 }
 
 inline size_t bn_workspace_bytes(long long M, int C)

@@ -148,10 +148,13 @@ extern "C" int kd_avgpool2x2_nhwc(const float *x, int32_t ldx, float *y, int32_t
     KD_REQUIRE(ldx >= C && ldy >= C, KD_ERR_INVALID, "kd_avgpool2x2_nhwc: pixel stride below C");
     hipStream_t s = (hipStream_t)stream;
     const long long outs = (long long)N * g.Ho * g.Wo;
-    if (vec4_ok(C, {{x, ldx}, {y, ldy}}))
+    if (vec4_ok(C, {{x, ldx}, {y, ldy}})) {
+        KD_NOTE_PLUMBING("avgpool2x2_kernel<4>");
         hipLaunchKernelGGL(avgpool2x2_kernel<4>, dim3(grid_for(outs * (C / 4))), dim3(TPB), 0, s, g, x, ldx, y, ldy);
-    else
+    } else {
+        KD_NOTE_PLUMBING("avgpool2x2_kernel<1>");
         hipLaunchKernelGGL(avgpool2x2_kernel<1>, dim3(grid_for(outs * C)), dim3(TPB), 0, s, g, x, ldx, y, ldy);
+    }
     KD_CHECK_LAUNCH("kd_avgpool2x2_nhwc");
     return KD_OK;
 }
@@ -165,10 +168,13 @@ extern "C" int kd_avgpool2x2_nhwc_bwd(const float *gy, int32_t ldg, float *gx, i
     KD_REQUIRE(ldg >= C && ldgx >= C, KD_ERR_INVALID, "kd_avgpool2x2_nhwc_bwd: pixel stride below C");
     hipStream_t s = (hipStream_t)stream;
     const long long ins = (long long)N * H * W;
-    if (vec4_ok(C, {{gy, ldg}, {gx, ldgx}}))
+    if (vec4_ok(C, {{gy, ldg}, {gx, ldgx}})) {
+        KD_NOTE_PLUMBING("avgpool2x2_bwd_kernel<4>");
         hipLaunchKernelGGL(avgpool2x2_bwd_kernel<4>, dim3(grid_for(ins * (C / 4))), dim3(TPB), 0, s, g, gy, ldg, gx, ldgx);
-    else
+    } else {
+        KD_NOTE_PLUMBING("avgpool2x2_bwd_kernel<1>");
         hipLaunchKernelGGL(avgpool2x2_bwd_kernel<1>, dim3(grid_for(ins * C)), dim3(TPB), 0, s, g, gy, ldg, gx, ldgx);
+    }
     KD_CHECK_LAUNCH("kd_avgpool2x2_nhwc_bwd");
     return KD_OK;
 }

@@ -52,7 +52,9 @@ void kd_note_kernel(const char *name);
 // the conv log above (its readers attribute time and assert exact name sets by it) never sees these names.  `name` is a string
 // with static storage (the slot keeps the pointer), one per distinguishable dispatch branch: a literal in the three files above,
 // tests/test_plumbing_host.py requires a test case for every one of them.  The launchers of losses.hip use the same slot with the
-// names of loss_select.h's table (loss_kernel_name); tests/test_loss_dispatch_host.py holds them to the same rule.
+// names of loss_select.h's table (loss_kernel_name); tests/test_loss_dispatch_host.py holds them to the same rule.  So do the
+// fp32 NHWC BatchNorm and average-pool entry points (bn_nhwc_core.h's launch_apply, bn_nhwc.hip, dense_ops.hip) for their
+// float4 / scalar choice, with literals of their own that tests/test_nhwc_support_host.py holds to a row each.
 void kd_note_plumbing(const char *name);
 #define KD_NOTE_PLUMBING(name) kd_note_plumbing(name)
 
