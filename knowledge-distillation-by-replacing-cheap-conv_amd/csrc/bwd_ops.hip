@@ -4,16 +4,9 @@
 // All kernels are HBM-bound streams over NHWC tensors; every reduction has a fixed order (two stages, no float atomics),
 // so results are bit-reproducible run to run.
 #include "kd_common.h"
+#include "plumb_select.h"
 
 namespace {
-
-inline int grid_for(long long total, int cap = 16384)
-{
-    long long b = (total + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-inline bool ok_dt(int d) { return d == KD_F32 || d == KD_BF16; }
-inline bool vec_ok(const void *p, int ld, int es) { return !p || (kd_aligned16(p) && (ld * es) % 16 == 0); }
 
 // ---- d relu(bn(x)) / dx on a gradient ------------------------------------------------------------------------------------
 template <typename T>
@@ -430,7 +423,7 @@ __global__ __launch_bounds__(256) void broadcast_add_kernel(const float *__restr
 // ---- stem conv weight gradient: dW[64][3][3][3] = sum_pixels dy[p][64] x x_nchw[p + tap][3] -------------------------------
 // persistent blocks over (image row, 256-column segment) work items; the 3 x 258 x 3 input patch goes to LDS, thread =
 // (output channel, pixel phase): 27 running sums each; block partials -> fixed-order reduce.
-constexpr int SW_SEG = 256;
+constexpr int SW_SEG = PLUMB_SW_SEG;
 
 template <typename T>
 __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float *__restrict__ x, const T *__restrict__ dy, int lddy, int N, int H,
@@ -573,88 +566,6 @@ __global__ void stem_wgrad_finish_kernel(const float *__restrict__ part, int nbl
     dw[e] = accumulate ? dw[e] + (float)s : (float)s;
 }
 
-}  // namespace
-
-extern "C" int kd_relu_bn_bwd(int32_t dtype, const void *g, int32_t ldg, const void *mask, int32_t ldm, const float *scale,
-                              const void *res, int32_t ldres, void *y, int32_t ldy, int64_t M, int32_t C, kd_stream_t stream)
-{
-    KD_REQUIRE(g && mask && scale && y && M > 0 && C > 0, KD_ERR_INVALID, "kd_relu_bn_bwd: bad argument");
-    KD_REQUIRE(ok_dt(dtype), KD_ERR_INVALID, "kd_relu_bn_bwd: bad dtype");
-    const int es = kd_elem_size(dtype);
-    KD_REQUIRE(C % 8 == 0 && vec_ok(g, ldg, es) && vec_ok(mask, ldm, es) && vec_ok(res, ldres, es) && vec_ok(y, ldy, es) &&
-                   kd_aligned16(scale),
-               KD_ERR_INVALID, "kd_relu_bn_bwd: C %% 8 and 16-B aligned views required");
-    const int nb = grid_for((long long)M * (C / 8));
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == KD_BF16) KD_NOTE_PLUMBING("relu_bn_bwd_kernel<bf16>");
-    else KD_NOTE_PLUMBING("relu_bn_bwd_kernel<f32>");
-    if (dtype == KD_BF16)
-        hipLaunchKernelGGL(relu_bn_bwd_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t *)g, ldg, (const bf16_t *)mask, ldm,
-                           scale, (const bf16_t *)res, ldres, (bf16_t *)y, ldy, (long long)M, C / 8);
-    else
-        hipLaunchKernelGGL(relu_bn_bwd_kernel<float>, dim3(nb), dim3(256), 0, s, (const float *)g, ldg, (const float *)mask, ldm, scale,
-                           (const float *)res, ldres, (float *)y, ldy, (long long)M, C / 8);
-    KD_CHECK_LAUNCH("kd_relu_bn_bwd");
-    return KD_OK;
-}
-
-static int cs_chunks(long long rows)
-{
-    long long c = (rows + 511) / 512;        // >= 512 rows (64 per thread) per block, at most 1024 chunks
-    return (int)(c < 1 ? 1 : (c > 1024 ? 1024 : c));
-}
-
-extern "C" size_t kd_channel_sums_workspace(int32_t groups, int64_t rows_per_group, int32_t C)
-{
-    return (size_t)groups * cs_chunks(rows_per_group) * 2 * (size_t)C * sizeof(float);
-}
-
-extern "C" int kd_channel_sums(int32_t dtype, const void *g, int32_t ldg, const void *sub, int32_t ldsub, const void *a, int32_t lda,
-                               int32_t groups, int64_t rows_per_group, int32_t C, float *s1, float *s2, void *workspace,
-                               size_t workspace_bytes, kd_stream_t stream)
-{
-    KD_REQUIRE(g && s1 && workspace && groups > 0 && rows_per_group > 0 && C > 0, KD_ERR_INVALID, "kd_channel_sums: bad argument");
-    KD_REQUIRE(ok_dt(dtype), KD_ERR_INVALID, "kd_channel_sums: bad dtype");
-    KD_REQUIRE(!a || s2, KD_ERR_INVALID, "kd_channel_sums: `a` given without s2");
-    KD_REQUIRE(workspace_bytes >= kd_channel_sums_workspace(groups, rows_per_group, C), KD_ERR_WORKSPACE,
-               "kd_channel_sums: workspace too small");
-    const int es = kd_elem_size(dtype);
-    const bool vec = C % 8 == 0 && vec_ok(g, ldg, es) && vec_ok(sub, ldsub, es) && vec_ok(a, lda, es);
-    const int nvec = vec ? (C + 7) / 8 : C;
-    const int lc = nvec > 16 ? 32 : (nvec > 8 ? 16 : (nvec > 4 ? 8 : 4));   // channel lanes of a block, as in the kernel
-    // row chunks: ~2048 blocks over (groups, channel blocks, chunks) fill the chip; more only lengthens the second stage
-    // (never more than the workspace was sized for)
-    int chunks = cs_chunks(rows_per_group);
-    {
-        const long long other = (long long)groups * ((nvec + lc - 1) / lc);
-        const long long want = (2048 + other - 1) / other;
-        if (want < chunks) chunks = (int)(want < 16 ? 16 : want);
-        if (chunks > cs_chunks(rows_per_group)) chunks = cs_chunks(rows_per_group);
-    }
-    const dim3 grid((unsigned)chunks, (unsigned)((nvec + lc - 1) / lc), (unsigned)groups);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == KD_BF16) {
-        if (vec) KD_NOTE_PLUMBING("channel_sums_partial_kernel<bf16,8>");
-        else KD_NOTE_PLUMBING("channel_sums_partial_kernel<bf16,1>");
-    } else {
-        if (vec) KD_NOTE_PLUMBING("channel_sums_partial_kernel<f32,8>");
-        else KD_NOTE_PLUMBING("channel_sums_partial_kernel<f32,1>");
-    }
-    if (dtype == KD_BF16) {
-        if (vec) hipLaunchKernelGGL((channel_sums_partial_kernel<bf16_t, 8>), grid, dim3(256), 0, s, (const bf16_t *)g, ldg, (const bf16_t *)sub, ldsub, (const bf16_t *)a, lda, (long long)rows_per_group, C, chunks, (float *)workspace);
-        else hipLaunchKernelGGL((channel_sums_partial_kernel<bf16_t, 1>), grid, dim3(256), 0, s, (const bf16_t *)g, ldg, (const bf16_t *)sub, ldsub, (const bf16_t *)a, lda, (long long)rows_per_group, C, chunks, (float *)workspace);
-    } else {
-        if (vec) hipLaunchKernelGGL((channel_sums_partial_kernel<float, 8>), grid, dim3(256), 0, s, (const float *)g, ldg, (const float *)sub, ldsub, (const float *)a, lda, (long long)rows_per_group, C, chunks, (float *)workspace);
-        else hipLaunchKernelGGL((channel_sums_partial_kernel<float, 1>), grid, dim3(256), 0, s, (const float *)g, ldg, (const float *)sub, ldsub, (const float *)a, lda, (long long)rows_per_group, C, chunks, (float *)workspace);
-    }
-    KD_CHECK_LAUNCH("kd_channel_sums");
-    hipLaunchKernelGGL(channel_sums_finish_kernel, dim3((unsigned)(groups * ((C + 15) / 16))), dim3(256), 0, s, (const float *)workspace,
-                       groups, chunks, C, s1, a ? s2 : (float *)nullptr);
-    KD_CHECK_LAUNCH("kd_channel_sums(finish)");
-    return KD_OK;
-}
-
-namespace {
 // rows [chunk * per, ...) of part[R][2][C] -> out[chunk][2][C] (fp64 accumulators, fixed order): first stage of
 // kd_bn_sums_finish for the full-resolution layers (32768 partial rows and more)
 __global__ __launch_bounds__(256) void bn_sums_stage_kernel(const float *__restrict__ part, int R, int C, int per, float *__restrict__ out)
@@ -685,34 +596,91 @@ __global__ __launch_bounds__(256) void bn_sums_stage_kernel(const float *__restr
         out[(size_t)chunk * 2 * C + C + c] = (float)sh[1][0][cl];
     }
 }
+
+inline dim3 dim3_of(const PlumbGrid &g) { return dim3(g.x, g.y, g.z); }
+
 }  // namespace
 
-static int bn_sums_chunk(int rows) { return rows > 16384 ? 256 : 64; }   // rows per first-stage block
-
-extern "C" size_t kd_bn_sums_finish_workspace(int32_t rows, int32_t C)
+// Every entry point below: its argument checks, its selector (plumb_select.h), the selected kernel's name noted once, then a
+// switch over sel.kernel to the instantiation on the selector's grids.
+extern "C" int kd_relu_bn_bwd(int32_t dtype, const void *g, int32_t ldg, const void *mask, int32_t ldm, const float *scale,
+                              const void *res, int32_t ldres, void *y, int32_t ldy, int64_t M, int32_t C, kd_stream_t stream)
 {
-    return rows > 256 ? (size_t)((rows + bn_sums_chunk(rows) - 1) / bn_sums_chunk(rows)) * 2 * (size_t)C * sizeof(float) : 0;
+    KD_REQUIRE(g && mask && scale && y && M > 0 && C > 0, KD_ERR_INVALID, "kd_relu_bn_bwd: bad argument");
+    KD_REQUIRE(plumb_dtype_ok(dtype), KD_ERR_INVALID, "kd_relu_bn_bwd: bad dtype");
+    const int es = kd_elem_size(dtype);
+    KD_REQUIRE(C % 8 == 0 && plumb_vec_ok(g, ldg, es) && plumb_vec_ok(mask, ldm, es) && plumb_vec_ok(res, ldres, es) && plumb_vec_ok(y, ldy, es) &&
+                   kd_aligned16(scale),
+               KD_ERR_INVALID, "kd_relu_bn_bwd: C %% 8 and 16-B aligned views required");
+    const PlumbSel sel = plumb_select_relu_bn_bwd(dtype, M, C);
+    const dim3 grid = dim3_of(sel.grid);
+    hipStream_t s = (hipStream_t)stream;
+    KD_NOTE_PLUMBING(plumb_kernel_name(sel.kernel));
+    if (sel.kernel == PK_RELU_BN_BWD_BF16)
+        hipLaunchKernelGGL(relu_bn_bwd_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t *)g, ldg, (const bf16_t *)mask, ldm,
+                           scale, (const bf16_t *)res, ldres, (bf16_t *)y, ldy, (long long)M, C / 8);
+    else
+        hipLaunchKernelGGL(relu_bn_bwd_kernel<float>, grid, dim3(256), 0, s, (const float *)g, ldg, (const float *)mask, ldm, scale,
+                           (const float *)res, ldres, (float *)y, ldy, (long long)M, C / 8);
+    KD_CHECK_LAUNCH("kd_relu_bn_bwd");
+    return KD_OK;
 }
+
+extern "C" size_t kd_channel_sums_workspace(int32_t groups, int64_t rows_per_group, int32_t C)
+{
+    return plumb_channel_sums_workspace(groups, rows_per_group, C);
+}
+
+extern "C" int kd_channel_sums(int32_t dtype, const void *g, int32_t ldg, const void *sub, int32_t ldsub, const void *a, int32_t lda,
+                               int32_t groups, int64_t rows_per_group, int32_t C, float *s1, float *s2, void *workspace,
+                               size_t workspace_bytes, kd_stream_t stream)
+{
+    KD_REQUIRE(g && s1 && workspace && groups > 0 && rows_per_group > 0 && C > 0, KD_ERR_INVALID, "kd_channel_sums: bad argument");
+    KD_REQUIRE(plumb_dtype_ok(dtype), KD_ERR_INVALID, "kd_channel_sums: bad dtype");
+    KD_REQUIRE(!a || s2, KD_ERR_INVALID, "kd_channel_sums: `a` given without s2");
+    KD_REQUIRE(workspace_bytes >= plumb_channel_sums_workspace(groups, rows_per_group, C), KD_ERR_WORKSPACE,
+               "kd_channel_sums: workspace too small");
+    const PlumbSel sel = plumb_select_channel_sums(dtype, g, ldg, sub, ldsub, a, lda, groups, rows_per_group, C);
+    const dim3 grid = dim3_of(sel.grid);
+    hipStream_t s = (hipStream_t)stream;
+    KD_NOTE_PLUMBING(plumb_kernel_name(sel.kernel));
+#define KD_CS(T, VEC)                                                                                                                 \
+    hipLaunchKernelGGL((channel_sums_partial_kernel<T, VEC>), grid, dim3(256), 0, s, (const T *)g, ldg, (const T *)sub, ldsub, (const T *)a, \
+                       lda, (long long)rows_per_group, C, sel.chunks, (float *)workspace);                                            \
+    break
+    switch (sel.kernel) {
+    case PK_CS_BF16_8: KD_CS(bf16_t, 8);
+    case PK_CS_BF16_1: KD_CS(bf16_t, 1);
+    case PK_CS_F32_8: KD_CS(float, 8);
+    default: KD_CS(float, 1);
+    }
+#undef KD_CS
+    KD_CHECK_LAUNCH("kd_channel_sums");
+    hipLaunchKernelGGL(channel_sums_finish_kernel, dim3_of(sel.grid2), dim3(256), 0, s, (const float *)workspace, groups, sel.chunks, C, s1,
+                       a ? s2 : (float *)nullptr);
+    KD_CHECK_LAUNCH("kd_channel_sums(finish)");
+    return KD_OK;
+}
+
+extern "C" size_t kd_bn_sums_finish_workspace(int32_t rows, int32_t C) { return plumb_bn_sums_finish_workspace(rows, C); }
 
 extern "C" int kd_bn_sums_finish(const float *part, int32_t rows, int32_t C, float *s1, float *s2, void *workspace, size_t workspace_bytes,
                                  kd_stream_t stream)
 {
     KD_REQUIRE(part && s1 && s2 && rows > 0 && C > 0, KD_ERR_INVALID, "kd_bn_sums_finish: bad argument");
+    const PlumbSel sel = plumb_select_bn_sums_finish(rows, C);
     hipStream_t s = (hipStream_t)stream;
-    if (rows > 256) {
-        // (C / 16 blocks walking 2048 rows each took 36 us per call, 41 calls per mode-B step: the rows are split first)
-        KD_REQUIRE(workspace && workspace_bytes >= kd_bn_sums_finish_workspace(rows, C), KD_ERR_WORKSPACE, "kd_bn_sums_finish: workspace too small");
-        const int per = bn_sums_chunk(rows), chunks = (rows + per - 1) / per;
-        if (per == 256) KD_NOTE_PLUMBING("bn_sums_stage_kernel<256 rows>");
-        else KD_NOTE_PLUMBING("bn_sums_stage_kernel<64 rows>");
-        hipLaunchKernelGGL(bn_sums_stage_kernel, dim3((unsigned)((C + 15) / 16), (unsigned)chunks), dim3(256), 0, s, part, rows, C, per, (float *)workspace);
+    // (C / 16 blocks walking 2048 rows each took 36 us per call, 41 calls per mode-B step: the rows are split first)
+    const bool staged = sel.kernel != PK_CS_FINISH;
+    KD_REQUIRE(!staged || (workspace && workspace_bytes >= plumb_bn_sums_finish_workspace(rows, C)), KD_ERR_WORKSPACE,
+               "kd_bn_sums_finish: workspace too small");
+    KD_NOTE_PLUMBING(plumb_kernel_name(sel.kernel));
+    if (staged) {
+        hipLaunchKernelGGL(bn_sums_stage_kernel, dim3_of(sel.grid), dim3(256), 0, s, part, rows, C, sel.per, (float *)workspace);
         KD_CHECK_LAUNCH("kd_bn_sums_finish(stage)");
         part = (const float *)workspace;
-        rows = chunks;
-    } else {
-        KD_NOTE_PLUMBING("channel_sums_finish_kernel");
     }
-    hipLaunchKernelGGL(channel_sums_finish_kernel, dim3((unsigned)((C + 15) / 16)), dim3(256), 0, s, part, 1, rows, C, s1, s2);
+    hipLaunchKernelGGL(channel_sums_finish_kernel, dim3_of(sel.grid2), dim3(256), 0, s, part, 1, sel.chunks, C, s1, s2);
     KD_CHECK_LAUNCH("kd_bn_sums_finish");
     return KD_OK;
 }
@@ -721,77 +689,54 @@ extern "C" int kd_bn_eval_param_grads(const float *s1, const float *s2, const fl
                                       float *dgamma, float *dbeta, int32_t C, int32_t accumulate, kd_stream_t stream)
 {
     KD_REQUIRE(s1 && s2 && scale && gamma && beta && dgamma && dbeta && C > 0, KD_ERR_INVALID, "kd_bn_eval_param_grads: bad argument");
-    KD_NOTE_PLUMBING("bn_eval_param_grads_kernel");
-    hipLaunchKernelGGL(bn_eval_param_grads_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, s1, s2, scale, gamma, beta,
-                       dgamma, dbeta, C, accumulate);
+    const PlumbSel sel = plumb_select_bn_eval_param_grads(C);
+    KD_NOTE_PLUMBING(plumb_kernel_name(sel.kernel));
+    hipLaunchKernelGGL(bn_eval_param_grads_kernel, dim3_of(sel.grid), dim3(256), 0, (hipStream_t)stream, s1, s2, scale, gamma, beta, dgamma,
+                       dbeta, C, accumulate);
     KD_CHECK_LAUNCH("kd_bn_eval_param_grads");
     return KD_OK;
 }
 
-extern "C" size_t kd_maxpool3x3s2_bwd_workspace(int32_t N, int32_t H, int32_t W, int32_t C)
-{
-    return (size_t)N * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1) * (size_t)((C + 7) / 8) * 8;   // one byte per window and channel
-}
+extern "C" size_t kd_maxpool3x3s2_bwd_workspace(int32_t N, int32_t H, int32_t W, int32_t C) { return plumb_maxpool_bwd_workspace(N, H, W, C); }
 
 extern "C" int kd_maxpool3x3s2_bwd(int32_t dtype, const void *x, int32_t ldx, const void *gy, int32_t ldgy, void *gx, int32_t ldgx,
                                    int32_t N, int32_t H, int32_t W, int32_t C, void *workspace, size_t workspace_bytes,
                                    kd_stream_t stream)
 {
     KD_REQUIRE(x && gy && gx && N > 0 && H > 0 && W > 0 && C > 0, KD_ERR_INVALID, "kd_maxpool3x3s2_bwd: bad argument");
-    KD_REQUIRE(ok_dt(dtype), KD_ERR_INVALID, "kd_maxpool3x3s2_bwd: bad dtype");
-    const int es = kd_elem_size(dtype);
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const bool vec = C % 8 == 0 && vec_ok(x, ldx, es) && vec_ok(gy, ldgy, es) && vec_ok(gx, ldgx, es);
+    KD_REQUIRE(plumb_dtype_ok(dtype), KD_ERR_INVALID, "kd_maxpool3x3s2_bwd: bad dtype");
+    const PlumbSel sel = plumb_select_maxpool_bwd(dtype, x, ldx, gy, ldgy, gx, ldgx, N, H, W, C, workspace, workspace_bytes);
+    const dim3 g1 = dim3_of(sel.grid), g2 = dim3_of(sel.grid2);
+    const int Ho = sel.Ho, Wo = sel.Wo, C8 = C / 8;
     hipStream_t s = (hipStream_t)stream;
-    if (vec && workspace && workspace_bytes >= kd_maxpool3x3s2_bwd_workspace(N, H, W, C) && ((uintptr_t)workspace & 7) == 0) {
-        const int C8 = C / 8;
-        const dim3 g1((unsigned)((Wo * C8 + 255) / 256), (unsigned)Ho, (unsigned)N), g2((unsigned)((W * C8 + 255) / 256), (unsigned)H, (unsigned)N);
-        if (dtype == KD_BF16) KD_NOTE_PLUMBING("maxpool_argmax_kernel<bf16>");
-        else KD_NOTE_PLUMBING("maxpool_argmax_kernel<f32>");
-        if (dtype == KD_BF16) {
-            hipLaunchKernelGGL(maxpool_argmax_kernel<bf16_t>, g1, dim3(256), 0, s, (const bf16_t *)x, ldx, (uint2 *)workspace, N, H, W, C8, Ho, Wo);
-            hipLaunchKernelGGL(maxpool_bwd_gather_kernel<bf16_t>, g2, dim3(256), 0, s, (const uint2 *)workspace, (const bf16_t *)gy, ldgy, (bf16_t *)gx, ldgx, N, H, W, C8, Ho, Wo);
-        } else {
-            hipLaunchKernelGGL(maxpool_argmax_kernel<float>, g1, dim3(256), 0, s, (const float *)x, ldx, (uint2 *)workspace, N, H, W, C8, Ho, Wo);
-            hipLaunchKernelGGL(maxpool_bwd_gather_kernel<float>, g2, dim3(256), 0, s, (const uint2 *)workspace, (const float *)gy, ldgy, (float *)gx, ldgx, N, H, W, C8, Ho, Wo);
-        }
-        KD_CHECK_LAUNCH("kd_maxpool3x3s2_bwd");
-        return KD_OK;
+    KD_NOTE_PLUMBING(plumb_kernel_name(sel.kernel));
+#define KD_MP_TWO_PASS(T)                                                                                                                     \
+    hipLaunchKernelGGL(maxpool_argmax_kernel<T>, g1, dim3(256), 0, s, (const T *)x, ldx, (uint2 *)workspace, N, H, W, C8, Ho, Wo);            \
+    KD_CHECK_LAUNCH("kd_maxpool3x3s2_bwd(argmax)");                                                                                           \
+    hipLaunchKernelGGL(maxpool_bwd_gather_kernel<T>, g2, dim3(256), 0, s, (const uint2 *)workspace, (const T *)gy, ldgy, (T *)gx, ldgx, N, H, W, \
+                       C8, Ho, Wo);                                                                                                           \
+    break
+#define KD_MP_ONE_PASS(T, VEC)                                                                                                              \
+    hipLaunchKernelGGL((maxpool_bwd_kernel<T, VEC>), g1, dim3(256), 0, s, (const T *)x, ldx, (const T *)gy, ldgy, (T *)gx, ldgx, N, H, W, C, Ho, \
+                       Wo);                                                                                                                 \
+    break
+    switch (sel.kernel) {
+    case PK_MP_ARGMAX_BF16: KD_MP_TWO_PASS(bf16_t);
+    case PK_MP_ARGMAX_F32: KD_MP_TWO_PASS(float);
+    case PK_MPB_BF16_8: KD_MP_ONE_PASS(bf16_t, 8);
+    case PK_MPB_BF16_1: KD_MP_ONE_PASS(bf16_t, 1);
+    case PK_MPB_F32_8: KD_MP_ONE_PASS(float, 8);
+    default: KD_MP_ONE_PASS(float, 1);
     }
-    const dim3 g((unsigned)((W * (vec ? C / 8 : C) + 255) / 256), (unsigned)H, (unsigned)N);
-    if (dtype == KD_BF16) {
-        if (vec) KD_NOTE_PLUMBING("maxpool_bwd_kernel<bf16,8>");
-        else KD_NOTE_PLUMBING("maxpool_bwd_kernel<bf16,1>");
-    } else {
-        if (vec) KD_NOTE_PLUMBING("maxpool_bwd_kernel<f32,8>");
-        else KD_NOTE_PLUMBING("maxpool_bwd_kernel<f32,1>");
-    }
-    if (dtype == KD_BF16) {
-        if (vec) hipLaunchKernelGGL((maxpool_bwd_kernel<bf16_t, 8>), g, dim3(256), 0, s, (const bf16_t *)x, ldx, (const bf16_t *)gy, ldgy, (bf16_t *)gx, ldgx, N, H, W, C, Ho, Wo);
-        else hipLaunchKernelGGL((maxpool_bwd_kernel<bf16_t, 1>), g, dim3(256), 0, s, (const bf16_t *)x, ldx, (const bf16_t *)gy, ldgy, (bf16_t *)gx, ldgx, N, H, W, C, Ho, Wo);
-    } else {
-        if (vec) hipLaunchKernelGGL((maxpool_bwd_kernel<float, 8>), g, dim3(256), 0, s, (const float *)x, ldx, (const float *)gy, ldgy, (float *)gx, ldgx, N, H, W, C, Ho, Wo);
-        else hipLaunchKernelGGL((maxpool_bwd_kernel<float, 1>), g, dim3(256), 0, s, (const float *)x, ldx, (const float *)gy, ldgy, (float *)gx, ldgx, N, H, W, C, Ho, Wo);
-    }
+#undef KD_MP_TWO_PASS
+#undef KD_MP_ONE_PASS
     KD_CHECK_LAUNCH("kd_maxpool3x3s2_bwd");
     return KD_OK;
 }
 
 extern "C" size_t kd_upsample_bilinear_ac_bwd_workspace(int32_t N, int32_t H, int32_t W, int32_t C, int32_t Ho, int32_t Wo)
 {
-    (void)H; (void)Wo;
-    return (size_t)N * Ho * W * C * sizeof(float);
-}
-
-extern "C" int kd_upsample_bilinear_bwd(const void *gy, int32_t gy_dtype, int32_t ldgy, void *gx, int32_t gx_dtype, int32_t ldgx,
-                                        int32_t N, int32_t H, int32_t W, int32_t C, int32_t Ho, int32_t Wo, int32_t align_corners,
-                                        void *workspace, size_t workspace_bytes, kd_stream_t stream);
-
-extern "C" int kd_upsample_bilinear_ac_bwd(const void *gy, int32_t gy_dtype, int32_t ldgy, void *gx, int32_t gx_dtype, int32_t ldgx,
-                                           int32_t N, int32_t H, int32_t W, int32_t C, int32_t Ho, int32_t Wo, void *workspace,
-                                           size_t workspace_bytes, kd_stream_t stream)
-{
-    return kd_upsample_bilinear_bwd(gy, gy_dtype, ldgy, gx, gx_dtype, ldgx, N, H, W, C, Ho, Wo, 1, workspace, workspace_bytes, stream);
+    return plumb_upsample_bwd_workspace(N, H, W, C, Ho, Wo);
 }
 
 extern "C" int kd_upsample_bilinear_bwd(const void *gy, int32_t gy_dtype, int32_t ldgy, void *gx, int32_t gx_dtype, int32_t ldgx,
@@ -800,68 +745,60 @@ extern "C" int kd_upsample_bilinear_bwd(const void *gy, int32_t gy_dtype, int32_
 {
     KD_REQUIRE(gy && gx && workspace && N > 0 && H > 0 && W > 0 && C > 0 && Ho > 0 && Wo > 0, KD_ERR_INVALID,
                "kd_upsample_bilinear_ac_bwd: bad argument");
-    KD_REQUIRE(ok_dt(gy_dtype) && ok_dt(gx_dtype), KD_ERR_INVALID, "kd_upsample_bilinear_ac_bwd: bad dtype");
-    KD_REQUIRE(workspace_bytes >= kd_upsample_bilinear_ac_bwd_workspace(N, H, W, C, Ho, Wo), KD_ERR_WORKSPACE,
+    KD_REQUIRE(plumb_dtype_ok(gy_dtype) && plumb_dtype_ok(gx_dtype), KD_ERR_INVALID, "kd_upsample_bilinear_ac_bwd: bad dtype");
+    KD_REQUIRE(workspace_bytes >= plumb_upsample_bwd_workspace(N, H, W, C, Ho, Wo), KD_ERR_WORKSPACE,
                "kd_upsample_bilinear_ac_bwd: workspace too small");
-    float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;   // the forward kernel's scales and offsets (kd_upsample_bilinear)
-    float sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
-    float oh = 0.f, ow = 0.f;
-    if (!align_corners) {
-        sh = (float)H / (float)Ho; sw = (float)W / (float)Wo;
-        oh = 0.5f * sh - 0.5f; ow = 0.5f * sw - 0.5f;
-    }
+    const PlumbSel sel = plumb_select_upsample_bwd(gy, gy_dtype, ldgy, gx, gx_dtype, ldgx, N, H, W, C, Ho, Wo, align_corners, workspace);
+    const dim3 g1 = dim3_of(sel.grid), g2 = dim3_of(sel.grid2);
     hipStream_t s = (hipStream_t)stream;
     float *tmp = (float *)workspace;
-    const bool vec = C % 8 == 0 && vec_ok(gy, ldgy, kd_elem_size(gy_dtype)) && vec_ok(gx, ldgx, kd_elem_size(gx_dtype)) && kd_aligned16(tmp);
-    const int cv = vec ? C / 8 : C;
-    const dim3 g1((unsigned)((W * cv + 255) / 256), (unsigned)Ho, (unsigned)N);
+    KD_NOTE_PLUMBING(plumb_kernel_name(sel.kernel));
     // <gy dtype (pass 1 reads it), gx dtype (pass 2 writes it), VEC of both passes>
-    if (gy_dtype == KD_BF16 && gx_dtype == KD_BF16) {
-        if (vec) KD_NOTE_PLUMBING("upsample_bwd_kernel<bf16,bf16,8>");
-        else KD_NOTE_PLUMBING("upsample_bwd_kernel<bf16,bf16,1>");
-    } else if (gy_dtype == KD_BF16) {
-        if (vec) KD_NOTE_PLUMBING("upsample_bwd_kernel<bf16,f32,8>");
-        else KD_NOTE_PLUMBING("upsample_bwd_kernel<bf16,f32,1>");
-    } else if (gx_dtype == KD_BF16) {
-        if (vec) KD_NOTE_PLUMBING("upsample_bwd_kernel<f32,bf16,8>");
-        else KD_NOTE_PLUMBING("upsample_bwd_kernel<f32,bf16,1>");
-    } else {
-        if (vec) KD_NOTE_PLUMBING("upsample_bwd_kernel<f32,f32,8>");
-        else KD_NOTE_PLUMBING("upsample_bwd_kernel<f32,f32,1>");
-    }
-    if (vec) {
-        if (gy_dtype == KD_BF16) hipLaunchKernelGGL((upsample_bwd_w_kernel<bf16_t, 8>), g1, dim3(256), 0, s, (const bf16_t *)gy, ldgy, tmp, N, Ho, Wo, W, C, sw, ow);
-        else hipLaunchKernelGGL((upsample_bwd_w_kernel<float, 8>), g1, dim3(256), 0, s, (const float *)gy, ldgy, tmp, N, Ho, Wo, W, C, sw, ow);
-    } else {
-        if (gy_dtype == KD_BF16) hipLaunchKernelGGL((upsample_bwd_w_kernel<bf16_t, 1>), g1, dim3(256), 0, s, (const bf16_t *)gy, ldgy, tmp, N, Ho, Wo, W, C, sw, ow);
-        else hipLaunchKernelGGL((upsample_bwd_w_kernel<float, 1>), g1, dim3(256), 0, s, (const float *)gy, ldgy, tmp, N, Ho, Wo, W, C, sw, ow);
+#define KD_UPB_W(TG, VEC)                                                                                                                 \
+    hipLaunchKernelGGL((upsample_bwd_w_kernel<TG, VEC>), g1, dim3(256), 0, s, (const TG *)gy, ldgy, tmp, N, Ho, Wo, W, C, sel.sw, sel.ow); \
+    break
+#define KD_UPB_H(TX, VEC)                                                                                                                        \
+    hipLaunchKernelGGL((upsample_bwd_h_kernel<TX, VEC>), g2, dim3(256), 0, s, (const float *)tmp, (TX *)gx, ldgx, N, Ho, H, W, C, sel.sh, sel.oh); \
+    break
+    switch (sel.kernel) {
+    case PK_UPB_BF16_BF16_8: case PK_UPB_BF16_F32_8: KD_UPB_W(bf16_t, 8);
+    case PK_UPB_F32_BF16_8: case PK_UPB_F32_F32_8: KD_UPB_W(float, 8);
+    case PK_UPB_BF16_BF16_1: case PK_UPB_BF16_F32_1: KD_UPB_W(bf16_t, 1);
+    default: KD_UPB_W(float, 1);
     }
     KD_CHECK_LAUNCH("kd_upsample_bilinear_ac_bwd(w)");
-    const dim3 g2((unsigned)((W * cv + 255) / 256), (unsigned)H, (unsigned)N);
-    if (vec) {
-        if (gx_dtype == KD_BF16) hipLaunchKernelGGL((upsample_bwd_h_kernel<bf16_t, 8>), g2, dim3(256), 0, s, (const float *)tmp, (bf16_t *)gx, ldgx, N, Ho, H, W, C, sh, oh);
-        else hipLaunchKernelGGL((upsample_bwd_h_kernel<float, 8>), g2, dim3(256), 0, s, (const float *)tmp, (float *)gx, ldgx, N, Ho, H, W, C, sh, oh);
-    } else {
-        if (gx_dtype == KD_BF16) hipLaunchKernelGGL((upsample_bwd_h_kernel<bf16_t, 1>), g2, dim3(256), 0, s, (const float *)tmp, (bf16_t *)gx, ldgx, N, Ho, H, W, C, sh, oh);
-        else hipLaunchKernelGGL((upsample_bwd_h_kernel<float, 1>), g2, dim3(256), 0, s, (const float *)tmp, (float *)gx, ldgx, N, Ho, H, W, C, sh, oh);
+    switch (sel.kernel) {
+    case PK_UPB_BF16_BF16_8: case PK_UPB_F32_BF16_8: KD_UPB_H(bf16_t, 8);
+    case PK_UPB_BF16_F32_8: case PK_UPB_F32_F32_8: KD_UPB_H(float, 8);
+    case PK_UPB_BF16_BF16_1: case PK_UPB_F32_BF16_1: KD_UPB_H(bf16_t, 1);
+    default: KD_UPB_H(float, 1);
     }
+#undef KD_UPB_W
+#undef KD_UPB_H
     KD_CHECK_LAUNCH("kd_upsample_bilinear_ac_bwd(h)");
     return KD_OK;
+}
+
+extern "C" int kd_upsample_bilinear_ac_bwd(const void *gy, int32_t gy_dtype, int32_t ldgy, void *gx, int32_t gx_dtype, int32_t ldgx,
+                                           int32_t N, int32_t H, int32_t W, int32_t C, int32_t Ho, int32_t Wo, void *workspace,
+                                           size_t workspace_bytes, kd_stream_t stream)
+{
+    return kd_upsample_bilinear_bwd(gy, gy_dtype, ldgy, gx, gx_dtype, ldgx, N, H, W, C, Ho, Wo, 1, workspace, workspace_bytes, stream);
 }
 
 extern "C" int kd_zero_insert(int32_t dtype, const void *x, int32_t ldx, void *y, int32_t ldy, int32_t N, int32_t H, int32_t W,
                               int32_t C, int32_t stride, int32_t Hy, int32_t Wy, kd_stream_t stream)
 {
     KD_REQUIRE(x && y && N > 0 && H > 0 && W > 0 && C > 0 && stride >= 1, KD_ERR_INVALID, "kd_zero_insert: bad argument");
-    KD_REQUIRE(ok_dt(dtype), KD_ERR_INVALID, "kd_zero_insert: bad dtype");
+    KD_REQUIRE(plumb_dtype_ok(dtype), KD_ERR_INVALID, "kd_zero_insert: bad dtype");
     KD_REQUIRE(Hy >= (H - 1) * stride + 1 && Wy >= (W - 1) * stride + 1, KD_ERR_INVALID, "kd_zero_insert: output too small");
     const int es = kd_elem_size(dtype);
-    KD_REQUIRE(C % 8 == 0 && vec_ok(x, ldx, es) && vec_ok(y, ldy, es), KD_ERR_INVALID, "kd_zero_insert: C %% 8 and 16-B alignment required");
-    const dim3 g((unsigned)((Wy * (C / 8) + 255) / 256), (unsigned)Hy, (unsigned)N);
+    KD_REQUIRE(C % 8 == 0 && plumb_vec_ok(x, ldx, es) && plumb_vec_ok(y, ldy, es), KD_ERR_INVALID, "kd_zero_insert: C %% 8 and 16-B alignment required");
+    const PlumbSel sel = plumb_select_zero_insert(dtype, N, C, Hy, Wy);
+    const dim3 g = dim3_of(sel.grid);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == KD_BF16) KD_NOTE_PLUMBING("zero_insert_kernel<bf16>");
-    else KD_NOTE_PLUMBING("zero_insert_kernel<f32>");
-    if (dtype == KD_BF16) hipLaunchKernelGGL(zero_insert_kernel<bf16_t>, g, dim3(256), 0, s, (const bf16_t *)x, ldx, (bf16_t *)y, ldy, H, W, C / 8, stride, Hy, Wy);
+    KD_NOTE_PLUMBING(plumb_kernel_name(sel.kernel));
+    if (sel.kernel == PK_ZERO_INSERT_BF16) hipLaunchKernelGGL(zero_insert_kernel<bf16_t>, g, dim3(256), 0, s, (const bf16_t *)x, ldx, (bf16_t *)y, ldy, H, W, C / 8, stride, Hy, Wy);
     else hipLaunchKernelGGL(zero_insert_kernel<float>, g, dim3(256), 0, s, (const float *)x, ldx, (float *)y, ldy, H, W, C / 8, stride, Hy, Wy);
     KD_CHECK_LAUNCH("kd_zero_insert");
     return KD_OK;
@@ -871,51 +808,45 @@ extern "C" int kd_broadcast_add(int32_t dtype, const float *v, void *y, int32_t 
                                 int32_t accumulate, kd_stream_t stream)
 {
     KD_REQUIRE(v && y && N > 0 && HW > 0 && C > 0, KD_ERR_INVALID, "kd_broadcast_add: bad argument");
-    KD_REQUIRE(ok_dt(dtype), KD_ERR_INVALID, "kd_broadcast_add: bad dtype");
-    KD_REQUIRE(C % 8 == 0 && kd_aligned16(v) && vec_ok(y, ldy, kd_elem_size(dtype)), KD_ERR_INVALID,
+    KD_REQUIRE(plumb_dtype_ok(dtype), KD_ERR_INVALID, "kd_broadcast_add: bad dtype");
+    KD_REQUIRE(C % 8 == 0 && kd_aligned16(v) && plumb_vec_ok(y, ldy, kd_elem_size(dtype)), KD_ERR_INVALID,
                "kd_broadcast_add: C %% 8 and 16-B alignment required");
-    const int nb = grid_for((long long)N * HW * (C / 8));
+    const PlumbSel sel = plumb_select_broadcast_add(dtype, N, HW, C);
+    const dim3 g = dim3_of(sel.grid);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == KD_BF16) KD_NOTE_PLUMBING("broadcast_add_kernel<bf16>");
-    else KD_NOTE_PLUMBING("broadcast_add_kernel<f32>");
-    if (dtype == KD_BF16) hipLaunchKernelGGL(broadcast_add_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, v, (bf16_t *)y, ldy, N, (long long)HW, C / 8, alpha, accumulate);
-    else hipLaunchKernelGGL(broadcast_add_kernel<float>, dim3(nb), dim3(256), 0, s, v, (float *)y, ldy, N, (long long)HW, C / 8, alpha, accumulate);
+    KD_NOTE_PLUMBING(plumb_kernel_name(sel.kernel));
+    if (sel.kernel == PK_BCAST_ADD_BF16) hipLaunchKernelGGL(broadcast_add_kernel<bf16_t>, g, dim3(256), 0, s, v, (bf16_t *)y, ldy, N, (long long)HW, C / 8, alpha, accumulate);
+    else hipLaunchKernelGGL(broadcast_add_kernel<float>, g, dim3(256), 0, s, v, (float *)y, ldy, N, (long long)HW, C / 8, alpha, accumulate);
     KD_CHECK_LAUNCH("kd_broadcast_add");
     return KD_OK;
 }
 
-static int stem_blocks(int N, int H, int W)
-{
-    const long long items = (long long)N * H * ((W + SW_SEG - 1) / SW_SEG);
-    return (int)(items < 768 ? items : 768);   // three 256-thread blocks per CU (41 KiB of LDS each): one round
-}
-
-extern "C" size_t kd_stem_wgrad_workspace(int32_t N, int32_t H, int32_t W)
-{
-    return (size_t)stem_blocks(N, H, W) * 64 * 27 * sizeof(float);
-}
+extern "C" size_t kd_stem_wgrad_workspace(int32_t N, int32_t H, int32_t W) { return plumb_stem_wgrad_workspace(N, H, W); }
 
 extern "C" int kd_stem_wgrad(int32_t dtype, const float *x_nchw, const void *dy, int32_t ld_dy, float *dw, int32_t N, int32_t H,
                              int32_t W, int32_t accumulate, void *workspace, size_t workspace_bytes, kd_stream_t stream)
 {
     KD_REQUIRE(x_nchw && dy && dw && workspace && N > 0 && H > 0 && W > 0 && ld_dy >= 64, KD_ERR_INVALID, "kd_stem_wgrad: bad argument");
-    KD_REQUIRE(ok_dt(dtype), KD_ERR_INVALID, "kd_stem_wgrad: bad dtype");
-    KD_REQUIRE(workspace_bytes >= kd_stem_wgrad_workspace(N, H, W), KD_ERR_WORKSPACE, "kd_stem_wgrad: workspace too small");
-    const int nb = stem_blocks(N, H, W);
+    KD_REQUIRE(plumb_dtype_ok(dtype), KD_ERR_INVALID, "kd_stem_wgrad: bad dtype");
+    KD_REQUIRE(workspace_bytes >= plumb_stem_wgrad_workspace(N, H, W), KD_ERR_WORKSPACE, "kd_stem_wgrad: workspace too small");
+    const PlumbSel sel = plumb_select_stem_wgrad(dtype, dy, ld_dy, N, H, W);
+    const dim3 g = dim3_of(sel.grid);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == KD_BF16 && ld_dy % 8 == 0 && kd_aligned16(dy)) {
+    KD_NOTE_PLUMBING(plumb_kernel_name(sel.kernel));
+    switch (sel.kernel) {
+    case PK_STEM_WGRAD_MFMA:
         KD_NOTE_KERNEL("stem_wgrad_mfma_kernel");
-        KD_NOTE_PLUMBING("stem_wgrad_mfma_kernel");
-        hipLaunchKernelGGL(stem_wgrad_mfma_kernel, dim3(nb), dim3(256), 0, s, x_nchw, (const bf16_t *)dy, ld_dy, N, H, W, (float *)workspace);
-    } else if (dtype == KD_BF16) {
-        KD_NOTE_PLUMBING("stem_wgrad_kernel<bf16>");
-        hipLaunchKernelGGL(stem_wgrad_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, x_nchw, (const bf16_t *)dy, ld_dy, N, H, W, (float *)workspace);
-    } else {
-        KD_NOTE_PLUMBING("stem_wgrad_kernel<f32>");
-        hipLaunchKernelGGL(stem_wgrad_kernel<float>, dim3(nb), dim3(256), 0, s, x_nchw, (const float *)dy, ld_dy, N, H, W, (float *)workspace);
+        hipLaunchKernelGGL(stem_wgrad_mfma_kernel, g, dim3(256), 0, s, x_nchw, (const bf16_t *)dy, ld_dy, N, H, W, (float *)workspace);
+        break;
+    case PK_STEM_WGRAD_BF16:
+        hipLaunchKernelGGL(stem_wgrad_kernel<bf16_t>, g, dim3(256), 0, s, x_nchw, (const bf16_t *)dy, ld_dy, N, H, W, (float *)workspace);
+        break;
+    default:
+        hipLaunchKernelGGL(stem_wgrad_kernel<float>, g, dim3(256), 0, s, x_nchw, (const float *)dy, ld_dy, N, H, W, (float *)workspace);
     }
     KD_CHECK_LAUNCH("kd_stem_wgrad");
-    hipLaunchKernelGGL(stem_wgrad_finish_kernel, dim3((64 * 27 + 255) / 256), dim3(256), 0, s, (const float *)workspace, nb, dw, accumulate);
+    hipLaunchKernelGGL(stem_wgrad_finish_kernel, dim3_of(sel.grid2), dim3(256), 0, s, (const float *)workspace, sel.blocks, dw, accumulate);
     KD_CHECK_LAUNCH("kd_stem_wgrad(finish)");
     return KD_OK;
 }
+

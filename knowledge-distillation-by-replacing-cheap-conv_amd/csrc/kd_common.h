@@ -50,7 +50,8 @@ void kd_note_kernel(const char *name);
 // The plumbing dispatchers (trunk_ops.hip, bwd_ops.hip, small_ops.hip) say which device kernel they picked through a slot of
 // their own (kd_debug_last_plumbing_kernel): one thread-local pointer, stored and nothing else -- no counters, no table, and
 // the conv log above (its readers attribute time and assert exact name sets by it) never sees these names.  `name` is a string
-// with static storage (the slot keeps the pointer), one per distinguishable dispatch branch: a literal in the three files above,
+// with static storage (the slot keeps the pointer), one per distinguishable dispatch branch: in the three files above an entry of
+// plumb_select.h's table (plumb_kernel_name of the kernel the entry point's selector picked, noted once per call);
 // tests/test_plumbing_host.py requires a test case for every one of them.  The launchers of losses.hip use the same slot with the
 // names of loss_select.h's table (loss_kernel_name); tests/test_loss_dispatch_host.py holds them to the same rule.  So do the
 // fp32 NHWC BatchNorm and average-pool entry points (bn_nhwc_core.h's launch_apply, bn_nhwc.hip, dense_ops.hip) for their

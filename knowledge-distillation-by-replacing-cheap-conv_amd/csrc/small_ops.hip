@@ -5,6 +5,7 @@
 // 0.27 M-parameter network is launch-bound, so these are plain, exact, deterministic kernels (direct convolution, per-channel
 // block reductions in a fixed order) rather than tiled ones.
 #include "kd_common.h"
+#include "plumb_select.h"
 
 namespace {
 
@@ -214,11 +215,7 @@ __global__ __launch_bounds__(256) void bn2d_bwd_kernel(const float *__restrict__
     }
 }
 
-inline int blocks_for(long long total)
-{
-    long long b = (total + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
-}
+inline dim3 dim3_of(const PlumbGrid &g) { return dim3(g.x, g.y, g.z); }
 
 int fill(const kd_dconv_desc *s, DConv &d, const char *who)
 {
@@ -246,8 +243,8 @@ extern "C" int kd_conv2d_direct_fwd(const kd_dconv_desc *s, const float *x, cons
     DConv d;
     if (int rc = fill(s, d, "kd_conv2d_direct_fwd")) return rc;
     KD_REQUIRE(x && w && y, KD_ERR_INVALID, "kd_conv2d_direct_fwd: null argument");
-    hipLaunchKernelGGL(dconv_fwd_kernel, dim3(blocks_for((long long)d.N * d.K * d.Ho * d.Wo)), dim3(256), 0, (hipStream_t)stream, d, x, w,
-                       bias, y);
+    hipLaunchKernelGGL(dconv_fwd_kernel, dim3(plumb_grid((long long)d.N * d.K * d.Ho * d.Wo, PLUMB_CAP_SMALL)), dim3(256), 0, (hipStream_t)stream,
+                       d, x, w, bias, y);
     KD_CHECK_LAUNCH("kd_conv2d_direct_fwd");
     return KD_OK;
 }
@@ -257,7 +254,8 @@ extern "C" int kd_conv2d_direct_dgrad(const kd_dconv_desc *s, const float *dy, c
     DConv d;
     if (int rc = fill(s, d, "kd_conv2d_direct_dgrad")) return rc;
     KD_REQUIRE(dy && w && dx, KD_ERR_INVALID, "kd_conv2d_direct_dgrad: null argument");
-    hipLaunchKernelGGL(dconv_dgrad_kernel, dim3(blocks_for((long long)d.N * d.C * d.H * d.W)), dim3(256), 0, (hipStream_t)stream, d, dy, w, dx);
+    hipLaunchKernelGGL(dconv_dgrad_kernel, dim3(plumb_grid((long long)d.N * d.C * d.H * d.W, PLUMB_CAP_SMALL)), dim3(256), 0, (hipStream_t)stream,
+                       d, dy, w, dx);
     KD_CHECK_LAUNCH("kd_conv2d_direct_dgrad");
     return KD_OK;
 }
@@ -268,14 +266,15 @@ extern "C" int kd_conv2d_direct_wgrad(const kd_dconv_desc *s, const float *x, co
     DConv d;
     if (int rc = fill(s, d, "kd_conv2d_direct_wgrad")) return rc;
     KD_REQUIRE(x && dy && (dw || dbias), KD_ERR_INVALID, "kd_conv2d_direct_wgrad: null argument");
+    const PlumbSel sel = plumb_select_direct_wgrad(d.K, d.Cg);
     hipStream_t st = (hipStream_t)stream;
     if (dw) {
-        KD_NOTE_PLUMBING("dconv_wgrad_kernel");
-        hipLaunchKernelGGL(dconv_wgrad_kernel, dim3((unsigned)(d.K * d.Cg)), dim3(256), 0, st, d, x, dy, dw, accumulate);
+        KD_NOTE_PLUMBING(plumb_kernel_name(sel.kernel));
+        hipLaunchKernelGGL(dconv_wgrad_kernel, dim3_of(sel.grid), dim3(256), 0, st, d, x, dy, dw, accumulate);
         KD_CHECK_LAUNCH("kd_conv2d_direct_wgrad");
     }
     if (dbias) {
-        hipLaunchKernelGGL(dconv_bias_grad_kernel, dim3((unsigned)d.K), dim3(256), 0, st, d, dy, dbias, accumulate);
+        hipLaunchKernelGGL(dconv_bias_grad_kernel, dim3_of(sel.grid2), dim3(256), 0, st, d, dy, dbias, accumulate);
         KD_CHECK_LAUNCH("kd_conv2d_direct_wgrad(bias)");
     }
     return KD_OK;
@@ -288,9 +287,9 @@ extern "C" int kd_bn2d_fwd(const float *x, const float *gamma, const float *beta
     KD_REQUIRE(x && gamma && beta && y && N > 0 && C > 0 && HW > 0, KD_ERR_INVALID, "kd_bn2d_fwd: bad argument");
     KD_REQUIRE(training || (running_mean && running_var), KD_ERR_INVALID, "kd_bn2d_fwd: eval mode needs the running statistics");
     KD_REQUIRE((long long)N * C * HW < (1ll << 31), KD_ERR_UNSUPPORTED, "kd_bn2d_fwd: tensor exceeds 2^31 elements");
-    if (training) KD_NOTE_PLUMBING("bn2d_fwd_kernel<train>");
-    else KD_NOTE_PLUMBING("bn2d_fwd_kernel<eval>");
-    hipLaunchKernelGGL(bn2d_fwd_kernel, dim3((unsigned)C), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, save_mean, save_invstd,
+    const PlumbSel sel = plumb_select_bn2d_fwd(training, C);
+    KD_NOTE_PLUMBING(plumb_kernel_name(sel.kernel));
+    hipLaunchKernelGGL(bn2d_fwd_kernel, dim3_of(sel.grid), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y, save_mean, save_invstd,
                        running_mean, running_var, momentum, eps, training, relu, N, C, HW);
     KD_CHECK_LAUNCH("kd_bn2d_fwd");
     return KD_OK;
@@ -302,9 +301,9 @@ extern "C" int kd_bn2d_bwd(const float *dy, const float *x, const float *y, cons
 {
     KD_REQUIRE(dy && x && gamma && save_mean && save_invstd && N > 0 && C > 0 && HW > 0, KD_ERR_INVALID, "kd_bn2d_bwd: bad argument");
     KD_REQUIRE(!relu || y, KD_ERR_INVALID, "kd_bn2d_bwd: the fused-ReLU backward needs the forward output");
-    if (training) KD_NOTE_PLUMBING("bn2d_bwd_kernel<train>");
-    else KD_NOTE_PLUMBING("bn2d_bwd_kernel<eval>");
-    hipLaunchKernelGGL(bn2d_bwd_kernel, dim3((unsigned)C), dim3(256), 0, (hipStream_t)stream, dy, x, y, gamma, save_mean, save_invstd, dx,
+    const PlumbSel sel = plumb_select_bn2d_bwd(training, C);
+    KD_NOTE_PLUMBING(plumb_kernel_name(sel.kernel));
+    hipLaunchKernelGGL(bn2d_bwd_kernel, dim3_of(sel.grid), dim3(256), 0, (hipStream_t)stream, dy, x, y, gamma, save_mean, save_invstd, dx,
                        dgamma, dbeta, training, relu, accumulate, N, C, HW);
     KD_CHECK_LAUNCH("kd_bn2d_bwd");
     return KD_OK;

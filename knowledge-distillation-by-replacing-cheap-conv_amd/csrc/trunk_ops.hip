@@ -5,9 +5,8 @@
 #include <pthread.h>
 #include <string.h>
 
-#include <type_traits>
-
 #include "kd_common.h"
+#include "plumb_select.h"
 
 static thread_local char g_err[512] = "";
 
@@ -220,8 +219,8 @@ __global__ __launch_bounds__(256) void stem_conv_mfma_kernel(const float *__rest
 // vertical maximum in fp32 registers, rounds it to bf16 into a 16-pixel LDS patch and finishes the horizontal maximum + the
 // consumer's BN/ReLU when the patch is read back as 16-B channel vectors.  Rounding is monotone, so round(max) == max(round):
 // the result is bit for bit what stem_conv_mfma_kernel + maxpool_kernel produce.
-constexpr int SP_COLS = 7;      // pooled columns per wave
-constexpr int SP_ROWS = 16;     // pooled rows per wave segment
+constexpr int SP_COLS = PLUMB_SP_COLS;      // pooled columns per wave
+constexpr int SP_ROWS = PLUMB_SP_ROWS;      // pooled rows per wave segment
 __global__ __launch_bounds__(256) void stem_pool_kernel(const float *__restrict__ x, const float *__restrict__ w, bf16_t *__restrict__ y_raw,
                                                         bf16_t *__restrict__ y_act, const float *__restrict__ scale,
                                                         const float *__restrict__ shift, int N, int H, int W, int Ho, int Wo,
@@ -392,7 +391,7 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const T *__restrict__ x, i
 // instead of 32).  One thread per output element made 16 M short-lived threads with four dependent gathers each: 0.41 ms for
 // a 1.07-GB output that a fill writes in 0.15 ms.  Rows are interpolated along x when loaded ((1-aw)*a + aw*b, as the reference
 // does per output), then along y per output: the same expression tree, 2 instead of 7 operations per element.
-constexpr int UP_RO = 8;
+constexpr int UP_RO = PLUMB_UP_RO;
 template <typename TI, typename TO, int VEC>
 __global__ __launch_bounds__(256) void upsample_kernel(const TI *__restrict__ x, int ldx, TO *__restrict__ y, int ldy, int N,
                                                        int H, int W, int C, int Ho, int Wo, float sh, float sw, float oh, float ow)
@@ -521,7 +520,7 @@ __global__ __launch_bounds__(256) void upsample_flat4_kernel(const TI *__restric
 }
 
 // ---- ASPP image pooling ------------------------------------------------------------------
-constexpr int GAP_CHUNKS = 64;
+constexpr int GAP_CHUNKS = PLUMB_GAP_CHUNKS;
 // partial[chunk][n][c] = sum over the chunk's pixels; block = 32 channel octets x 8 pixel lanes
 template <typename T>
 __global__ __launch_bounds__(256) void gap_partial_kernel(const T *__restrict__ x, int ldx, float *__restrict__ partial,
@@ -639,35 +638,27 @@ __global__ __launch_bounds__(256) void copy_cast_kernel(const void *src, int sdt
     }
 }
 
-inline int grid_for(long long total, int cap = 8192)
-{
-    long long b = (total + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
+inline dim3 dim3_of(const PlumbGrid &g) { return dim3(g.x, g.y, g.z); }
 
 }  // namespace
 
+// Every entry point below: its argument checks, its selector (plumb_select.h), the selected kernel's name noted once, then a
+// switch over sel.kernel to the instantiation on the selector's grid.
 extern "C" int kd_stem_conv(int32_t dtype, const float *x_nchw, const float *w, void *y, int32_t N, int32_t H, int32_t W,
                             kd_stream_t stream)
 {
     KD_REQUIRE(x_nchw && w && y && N > 0 && H > 0 && W > 0, KD_ERR_INVALID, "kd_stem_conv: bad argument");
-    KD_REQUIRE(dtype == KD_F32 || dtype == KD_BF16, KD_ERR_INVALID, "kd_stem_conv: bad dtype");
+    KD_REQUIRE(plumb_dtype_ok(dtype), KD_ERR_INVALID, "kd_stem_conv: bad dtype");
     KD_REQUIRE(kd_aligned16(y), KD_ERR_INVALID, "kd_stem_conv: y must be 16-B aligned");
-    const long long pix = (long long)N * H * W;
-    const dim3 grid((unsigned)((pix + 63) / 64));
+    const PlumbSel sel = plumb_select_stem_conv(dtype, N, H, W);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == KD_BF16) {
-        const int gpr = (W + 15) / 16;
-        const long long ngroups = (long long)N * H * gpr;
-        const long long want = (ngroups + 3) / 4;
-        const unsigned blocks = (unsigned)(want < 256 * 16 ? want : 256 * 16);   // persistent-ish: 16 workgroups per CU
+    KD_NOTE_PLUMBING(plumb_kernel_name(sel.kernel));
+    if (sel.kernel == PK_STEM_CONV_MFMA) {
         KD_NOTE_KERNEL("stem_conv_mfma_kernel");
-        KD_NOTE_PLUMBING("stem_conv_mfma_kernel");
-        hipLaunchKernelGGL(stem_conv_mfma_kernel, dim3(blocks), dim3(256), 0, s, x_nchw, w, (bf16_t *)y, N, H, W, gpr);
+        hipLaunchKernelGGL(stem_conv_mfma_kernel, dim3_of(sel.grid), dim3(256), 0, s, x_nchw, w, (bf16_t *)y, N, H, W, sel.ngx);
     } else {
         KD_NOTE_KERNEL("stem_conv_kernel<f32>");
-        KD_NOTE_PLUMBING("stem_conv_kernel<f32>");
-        hipLaunchKernelGGL(stem_conv_kernel<float>, grid, dim3(256), 0, s, x_nchw, w, (float *)y, N, H, W);
+        hipLaunchKernelGGL(stem_conv_kernel<float>, dim3_of(sel.grid), dim3(256), 0, s, x_nchw, w, (float *)y, N, H, W);
     }
     KD_CHECK_LAUNCH("kd_stem_conv");
     return KD_OK;
@@ -680,14 +671,12 @@ extern "C" int kd_stem_conv_pool(const float *x_nchw, const float *w, void *y_ra
     KD_REQUIRE(!y_act || (scale && shift), KD_ERR_INVALID, "kd_stem_conv_pool: y_act needs scale/shift");
     KD_REQUIRE((!y_raw || kd_aligned16(y_raw)) && (!y_act || kd_aligned16(y_act)), KD_ERR_INVALID,
                "kd_stem_conv_pool: outputs must be 16-B aligned");
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const int ngx = (Wo + SP_COLS - 1) / SP_COLS, nseg = (Ho + SP_ROWS - 1) / SP_ROWS;
-    const long long waves = (long long)N * ngx * nseg;
-    KD_REQUIRE((waves + 3) / 4 <= 0x7fffffffLL, KD_ERR_UNSUPPORTED, "kd_stem_conv_pool: image too large");
+    const PlumbSel sel = plumb_select_stem_conv_pool(N, H, W);
+    KD_REQUIRE(sel.kernel != PLUMB_REFUSED, KD_ERR_UNSUPPORTED, "kd_stem_conv_pool: image too large");
     KD_NOTE_KERNEL("stem_pool_kernel");
-    KD_NOTE_PLUMBING("stem_pool_kernel");
-    hipLaunchKernelGGL(stem_pool_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x_nchw, w,
-                       (bf16_t *)y_raw, (bf16_t *)y_act, scale, shift, N, H, W, Ho, Wo, ngx, nseg);
+    KD_NOTE_PLUMBING(plumb_kernel_name(sel.kernel));
+    hipLaunchKernelGGL(stem_pool_kernel, dim3_of(sel.grid), dim3(256), 0, (hipStream_t)stream, x_nchw, w, (bf16_t *)y_raw,
+                       (bf16_t *)y_act, scale, shift, N, H, W, sel.Ho, sel.Wo, sel.ngx, sel.nseg);
     KD_CHECK_LAUNCH("kd_stem_conv_pool");
     return KD_OK;
 }
@@ -697,56 +686,60 @@ extern "C" int kd_maxpool3x3s2(int32_t dtype, const void *x, int32_t ldx, void *
                                int32_t C, kd_stream_t stream)
 {
     KD_REQUIRE(x && (y_raw || y_act), KD_ERR_INVALID, "kd_maxpool3x3s2: null argument");
-    KD_REQUIRE(dtype == KD_F32 || dtype == KD_BF16, KD_ERR_INVALID, "kd_maxpool3x3s2: bad dtype");
+    KD_REQUIRE(plumb_dtype_ok(dtype), KD_ERR_INVALID, "kd_maxpool3x3s2: bad dtype");
     KD_REQUIRE(!y_act || (scale && shift), KD_ERR_INVALID, "kd_maxpool3x3s2: y_act needs scale/shift");
     const int es = kd_elem_size(dtype);
-    KD_REQUIRE(C % 8 == 0 && kd_aligned16(x) && (ldx * es) % 16 == 0 && (!y_raw || (kd_aligned16(y_raw) && (ld_raw * es) % 16 == 0)) &&
-                   (!y_act || (kd_aligned16(y_act) && (ld_act * es) % 16 == 0)),
-               KD_ERR_INVALID, "kd_maxpool3x3s2: C %% 8 and 16-B alignment required");
-    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    const dim3 g((unsigned)((Wo * (C / 8) + 255) / 256), (unsigned)Ho, (unsigned)N);
+    KD_REQUIRE(C % 8 == 0 && plumb_vec_ok(x, ldx, es) && plumb_vec_ok(y_raw, ld_raw, es) && plumb_vec_ok(y_act, ld_act, es), KD_ERR_INVALID,
+               "kd_maxpool3x3s2: C %% 8 and 16-B alignment required");
+    const PlumbSel sel = plumb_select_maxpool(dtype, N, H, W, C);
+    const dim3 g = dim3_of(sel.grid);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == KD_BF16) KD_NOTE_PLUMBING("maxpool_kernel<bf16>");
-    else KD_NOTE_PLUMBING("maxpool_kernel<f32>");
-    if (dtype == KD_BF16)
+    KD_NOTE_PLUMBING(plumb_kernel_name(sel.kernel));
+    if (sel.kernel == PK_MAXPOOL_BF16)
         hipLaunchKernelGGL(maxpool_kernel<bf16_t>, g, dim3(256), 0, s, (const bf16_t *)x, ldx, (bf16_t *)y_raw, ld_raw,
-                           (bf16_t *)y_act, ld_act, scale, shift, N, H, W, C, Ho, Wo);
+                           (bf16_t *)y_act, ld_act, scale, shift, N, H, W, C, sel.Ho, sel.Wo);
     else
         hipLaunchKernelGGL(maxpool_kernel<float>, g, dim3(256), 0, s, (const float *)x, ldx, (float *)y_raw, ld_raw,
-                           (float *)y_act, ld_act, scale, shift, N, H, W, C, Ho, Wo);
+                           (float *)y_act, ld_act, scale, shift, N, H, W, C, sel.Ho, sel.Wo);
     KD_CHECK_LAUNCH("kd_maxpool3x3s2");
     return KD_OK;
 }
 
-template <typename TI, typename TO>
-static void launch_up(const void *x, int ldx, void *y, int ldy, int N, int H, int W, int C, int Ho, int Wo, bool vec,
-                      bool flat4, hipStream_t s, bool align = true)
-{
-    float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
-    float sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
-    float oh = 0.f, ow = 0.f;
-    if (!align) {
-        sh = (float)H / (float)Ho; sw = (float)W / (float)Wo;
-        oh = 0.5f * sh - 0.5f; ow = 0.5f * sw - 0.5f;
-    }
-    // (the caller's flat4 already implies an fp32 output; the is_same term only keeps the bf16-output instantiations from
-    // compiling a call of the fp32-only flat kernel)
-    if (std::is_same<TO, float>::value && flat4) {
-        const dim3 g((unsigned)((Wo * C / 4 + 255) / 256), (unsigned)((Ho + UP_RO - 1) / UP_RO), (unsigned)N);
-        hipLaunchKernelGGL((upsample_flat4_kernel<TI>), g, dim3(256), 0, s, (const TI *)x, ldx, (float *)y, N, H, W, C, Ho, Wo, sh, sw, oh, ow);
-    } else if (vec) {
-        const dim3 g((unsigned)((Wo * (C / 8) + 255) / 256), (unsigned)((Ho + UP_RO - 1) / UP_RO), (unsigned)N);
-        hipLaunchKernelGGL((upsample_kernel<TI, TO, 8>), g, dim3(256), 0, s, (const TI *)x, ldx, (TO *)y, ldy, N, H, W, C, Ho, Wo,
-                           sh, sw, oh, ow);
-    } else {
-        const dim3 g((unsigned)((Wo * C + 255) / 256), (unsigned)((Ho + UP_RO - 1) / UP_RO), (unsigned)N);
-        hipLaunchKernelGGL((upsample_kernel<TI, TO, 1>), g, dim3(256), 0, s, (const TI *)x, ldx, (TO *)y, ldy, N, H, W, C, Ho, Wo,
-                           sh, sw, oh, ow);
-    }
-}
-
 extern "C" int kd_upsample_bilinear(const void *x, int32_t x_dtype, int32_t ldx, void *y, int32_t y_dtype, int32_t ldy, int32_t N,
-                                    int32_t H, int32_t W, int32_t C, int32_t Ho, int32_t Wo, int32_t align_corners, kd_stream_t stream);
+                                    int32_t H, int32_t W, int32_t C, int32_t Ho, int32_t Wo, int32_t align_corners, kd_stream_t stream)
+{
+    KD_REQUIRE(x && y && N > 0 && H > 0 && W > 0 && C > 0 && Ho > 0 && Wo > 0, KD_ERR_INVALID,
+               "kd_upsample_bilinear_ac: bad argument");
+    KD_REQUIRE(plumb_dtype_ok(x_dtype) && plumb_dtype_ok(y_dtype), KD_ERR_INVALID, "kd_upsample_bilinear_ac: bad dtype");
+    const PlumbSel sel = plumb_select_upsample(x, x_dtype, ldx, y, y_dtype, ldy, N, H, W, C, Ho, Wo, align_corners);
+    const dim3 g = dim3_of(sel.grid);
+    hipStream_t s = (hipStream_t)stream;
+    KD_NOTE_PLUMBING(plumb_kernel_name(sel.kernel));
+#define KD_UP(TI, TO, VEC)                                                                                                              \
+    hipLaunchKernelGGL((upsample_kernel<TI, TO, VEC>), g, dim3(256), 0, s, (const TI *)x, ldx, (TO *)y, ldy, N, H, W, C, Ho, Wo, sel.sh, \
+                       sel.sw, sel.oh, sel.ow);                                                                                         \
+    break
+#define KD_UP_FLAT4(TI)                                                                                                                  \
+    hipLaunchKernelGGL((upsample_flat4_kernel<TI>), g, dim3(256), 0, s, (const TI *)x, ldx, (float *)y, N, H, W, C, Ho, Wo, sel.sh, sel.sw, \
+                       sel.oh, sel.ow);                                                                                                  \
+    break
+    switch (sel.kernel) {
+    case PK_UP_FLAT4_BF16: KD_UP_FLAT4(bf16_t);
+    case PK_UP_BF16_BF16_8: KD_UP(bf16_t, bf16_t, 8);
+    case PK_UP_BF16_BF16_1: KD_UP(bf16_t, bf16_t, 1);
+    case PK_UP_BF16_F32_8: KD_UP(bf16_t, float, 8);
+    case PK_UP_BF16_F32_1: KD_UP(bf16_t, float, 1);
+    case PK_UP_FLAT4_F32: KD_UP_FLAT4(float);
+    case PK_UP_F32_BF16_8: KD_UP(float, bf16_t, 8);
+    case PK_UP_F32_BF16_1: KD_UP(float, bf16_t, 1);
+    case PK_UP_F32_F32_8: KD_UP(float, float, 8);
+    default: KD_UP(float, float, 1);
+    }
+#undef KD_UP
+#undef KD_UP_FLAT4
+    KD_CHECK_LAUNCH("kd_upsample_bilinear_ac");
+    return KD_OK;
+}
 
 extern "C" int kd_upsample_bilinear_ac(const void *x, int32_t x_dtype, int32_t ldx, void *y, int32_t y_dtype, int32_t ldy,
                                        int32_t N, int32_t H, int32_t W, int32_t C, int32_t Ho, int32_t Wo,
@@ -755,76 +748,35 @@ extern "C" int kd_upsample_bilinear_ac(const void *x, int32_t x_dtype, int32_t l
     return kd_upsample_bilinear(x, x_dtype, ldx, y, y_dtype, ldy, N, H, W, C, Ho, Wo, 1, stream);
 }
 
-extern "C" int kd_upsample_bilinear(const void *x, int32_t x_dtype, int32_t ldx, void *y, int32_t y_dtype, int32_t ldy, int32_t N,
-                                    int32_t H, int32_t W, int32_t C, int32_t Ho, int32_t Wo, int32_t align_corners, kd_stream_t stream)
-{
-    const bool al = align_corners != 0;
-    KD_REQUIRE(x && y && N > 0 && H > 0 && W > 0 && C > 0 && Ho > 0 && Wo > 0, KD_ERR_INVALID,
-               "kd_upsample_bilinear_ac: bad argument");
-    KD_REQUIRE((x_dtype == KD_F32 || x_dtype == KD_BF16) && (y_dtype == KD_F32 || y_dtype == KD_BF16), KD_ERR_INVALID,
-               "kd_upsample_bilinear_ac: bad dtype");
-    const bool vec = C % 8 == 0 && kd_aligned16(x) && kd_aligned16(y) && (ldx * kd_elem_size(x_dtype)) % 16 == 0 &&
-                     (ldy * kd_elem_size(y_dtype)) % 16 == 0;
-    // dense fp32 rows of an odd channel count (the logits): four floats of the flattened (wo, c) row per thread
-    const bool flat4 = !vec && y_dtype == KD_F32 && ldy == C && ((long long)Wo * C) % 4 == 0 && kd_aligned16(y);
-    hipStream_t s = (hipStream_t)stream;
-    if (x_dtype == KD_BF16 && y_dtype == KD_BF16) {
-        if (vec) KD_NOTE_PLUMBING("upsample_kernel<bf16,bf16,8>");
-        else KD_NOTE_PLUMBING("upsample_kernel<bf16,bf16,1>");
-        launch_up<bf16_t, bf16_t>(x, ldx, y, ldy, N, H, W, C, Ho, Wo, vec, flat4, s, al);
-    } else if (x_dtype == KD_BF16) {
-        if (flat4) KD_NOTE_PLUMBING("upsample_flat4_kernel<bf16>");
-        else if (vec) KD_NOTE_PLUMBING("upsample_kernel<bf16,f32,8>");
-        else KD_NOTE_PLUMBING("upsample_kernel<bf16,f32,1>");
-        launch_up<bf16_t, float>(x, ldx, y, ldy, N, H, W, C, Ho, Wo, vec, flat4, s, al);
-    } else if (y_dtype == KD_BF16) {
-        if (vec) KD_NOTE_PLUMBING("upsample_kernel<f32,bf16,8>");
-        else KD_NOTE_PLUMBING("upsample_kernel<f32,bf16,1>");
-        launch_up<float, bf16_t>(x, ldx, y, ldy, N, H, W, C, Ho, Wo, vec, flat4, s, al);
-    } else {
-        if (flat4) KD_NOTE_PLUMBING("upsample_flat4_kernel<f32>");
-        else if (vec) KD_NOTE_PLUMBING("upsample_kernel<f32,f32,8>");
-        else KD_NOTE_PLUMBING("upsample_kernel<f32,f32,1>");
-        launch_up<float, float>(x, ldx, y, ldy, N, H, W, C, Ho, Wo, vec, flat4, s, al);
-    }
-    KD_CHECK_LAUNCH("kd_upsample_bilinear_ac");
-    return KD_OK;
-}
+extern "C" size_t kd_aspp_image_pool_workspace(int32_t N, int32_t Cin, int32_t Cout) { return plumb_image_pool_workspace(N, Cin, Cout); }
 
-extern "C" size_t kd_aspp_image_pool_workspace(int32_t N, int32_t Cin, int32_t Cout)
-{
-    return ((size_t)GAP_CHUNKS * N * Cin + (size_t)N * Cin + (size_t)N * Cout) * sizeof(float);
-}
+// the last two launches of both image-pooling entry points: mean[n][ci] -> pooled vector [n][co] -> every pixel of y (defined
+// below them, so that the code object goes on listing the pooling kernels in front of the broadcast)
+static int image_pool_tail(const PlumbSel &sel, const char *who, const float *mean, float *vec, const float *w, const float *scale,
+                           const float *shift, void *y, int ldy, int N, int HW, int Cin, int Cout, hipStream_t s);
 
 extern "C" int kd_aspp_image_pool(int32_t dtype, const void *x, int32_t ldx, const float *w, const float *scale,
                                   const float *shift, void *y, int32_t ldy, int32_t N, int32_t H, int32_t W, int32_t Cin,
                                   int32_t Cout, void *workspace, size_t workspace_bytes, kd_stream_t stream)
 {
     KD_REQUIRE(x && w && scale && shift && y && workspace, KD_ERR_INVALID, "kd_aspp_image_pool: null argument");
-    KD_REQUIRE(dtype == KD_F32 || dtype == KD_BF16, KD_ERR_INVALID, "kd_aspp_image_pool: bad dtype");
+    KD_REQUIRE(plumb_dtype_ok(dtype), KD_ERR_INVALID, "kd_aspp_image_pool: bad dtype");
     const int es = kd_elem_size(dtype);
     KD_REQUIRE(Cin % 8 == 0 && Cout % 8 == 0 && kd_aligned16(x) && kd_aligned16(y) && (ldx * es) % 16 == 0 && (ldy * es) % 16 == 0,
                KD_ERR_INVALID, "kd_aspp_image_pool: channels %% 8 and 16-B alignment required");
-    KD_REQUIRE(workspace_bytes >= kd_aspp_image_pool_workspace(N, Cin, Cout), KD_ERR_WORKSPACE,
-               "kd_aspp_image_pool: workspace too small");
-    float *partial = (float *)workspace;
-    float *mean = partial + (size_t)GAP_CHUNKS * N * Cin;
-    float *vec = mean + (size_t)N * Cin;
+    KD_REQUIRE(workspace_bytes >= plumb_image_pool_workspace(N, Cin, Cout), KD_ERR_WORKSPACE, "kd_aspp_image_pool: workspace too small");
+    const PlumbSel sel = plumb_select_image_pool(dtype, N, H, W, Cin, Cout);
+    float *partial = (float *)((char *)workspace + sel.ws_off[0]), *mean = (float *)((char *)workspace + sel.ws_off[1]);
+    float *vec = (float *)((char *)workspace + sel.ws_off[2]);
     const int HW = H * W;
     hipStream_t s = (hipStream_t)stream;
-    const dim3 g1(GAP_CHUNKS, (Cin + 255) / 256, N);
-    if (dtype == KD_BF16) KD_NOTE_PLUMBING("gap_partial_kernel<bf16>");
-    else KD_NOTE_PLUMBING("gap_partial_kernel<f32>");
-    if (dtype == KD_BF16) hipLaunchKernelGGL(gap_partial_kernel<bf16_t>, g1, dim3(256), 0, s, (const bf16_t *)x, ldx, partial, N, HW, Cin);
-    else hipLaunchKernelGGL(gap_partial_kernel<float>, g1, dim3(256), 0, s, (const float *)x, ldx, partial, N, HW, Cin);
+    KD_NOTE_PLUMBING(plumb_kernel_name(sel.kernel));
+    if (sel.kernel == PK_GAP_PARTIAL_BF16) hipLaunchKernelGGL(gap_partial_kernel<bf16_t>, dim3_of(sel.grid), dim3(256), 0, s, (const bf16_t *)x, ldx, partial, N, HW, Cin);
+    else hipLaunchKernelGGL(gap_partial_kernel<float>, dim3_of(sel.grid), dim3(256), 0, s, (const float *)x, ldx, partial, N, HW, Cin);
     KD_CHECK_LAUNCH("kd_aspp_image_pool(partial)");
-    hipLaunchKernelGGL(gap_finish_kernel, dim3((N * Cin + 255) / 256), dim3(256), 0, s, partial, mean, N, HW, Cin);
-    hipLaunchKernelGGL(img_conv_kernel, dim3((Cout + 3) / 4, N), dim3(256), 0, s, mean, w, scale, shift, vec, Cin, Cout);
-    const long long total = (long long)N * HW * (Cout / 8);
-    if (dtype == KD_BF16) hipLaunchKernelGGL(broadcast_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, vec, (bf16_t *)y, ldy, N, HW, Cout);
-    else hipLaunchKernelGGL(broadcast_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, vec, (float *)y, ldy, N, HW, Cout);
+    hipLaunchKernelGGL(gap_finish_kernel, dim3((N * Cin + 255) / 256), dim3(256), 0, s, partial, mean, N, HW, Cin);   // a thread per (n, ci)
     KD_CHECK_LAUNCH("kd_aspp_image_pool");
-    return KD_OK;
+    return image_pool_tail(sel, "kd_aspp_image_pool", mean, vec, w, scale, shift, y, ldy, N, HW, Cin, Cout, s);
 }
 
 /* kd_aspp_image_pool with the pooled sums already taken: part = the [N*H*W/128][2][Cin] partial rows kd_conv2d_fwd /
@@ -835,21 +787,28 @@ extern "C" int kd_aspp_image_pool_sums(int32_t dtype, const float *part, const f
                                        size_t workspace_bytes, kd_stream_t stream)
 {
     KD_REQUIRE(part && w && scale && shift && y && workspace, KD_ERR_INVALID, "kd_aspp_image_pool_sums: null argument");
-    KD_REQUIRE(dtype == KD_F32 || dtype == KD_BF16, KD_ERR_INVALID, "kd_aspp_image_pool_sums: bad dtype");
+    KD_REQUIRE(plumb_dtype_ok(dtype), KD_ERR_INVALID, "kd_aspp_image_pool_sums: bad dtype");
     const int es = kd_elem_size(dtype);
     KD_REQUIRE(Cout % 8 == 0 && kd_aligned16(y) && (ldy * es) % 16 == 0, KD_ERR_INVALID, "kd_aspp_image_pool_sums: Cout %% 8 and 16-B alignment required");
     KD_REQUIRE(N > 0 && H > 0 && W > 0 && (H * W) % 128 == 0, KD_ERR_INVALID, "kd_aspp_image_pool_sums: an image must be a whole number of 128-pixel rows");
-    KD_REQUIRE(workspace_bytes >= kd_aspp_image_pool_workspace(N, Cin, Cout), KD_ERR_WORKSPACE, "kd_aspp_image_pool_sums: workspace too small");
-    float *mean = (float *)workspace + (size_t)GAP_CHUNKS * N * Cin;
-    float *vec = mean + (size_t)N * Cin;
+    KD_REQUIRE(workspace_bytes >= plumb_image_pool_workspace(N, Cin, Cout), KD_ERR_WORKSPACE, "kd_aspp_image_pool_sums: workspace too small");
+    const PlumbSel sel = plumb_select_image_pool_sums(dtype, N, H, W, Cin, Cout);
+    float *mean = (float *)((char *)workspace + sel.ws_off[1]), *vec = (float *)((char *)workspace + sel.ws_off[2]);
     const int HW = H * W;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(gap_rows_finish_kernel, dim3((Cin + 31) / 32, N), dim3(256), 0, s, part, mean, N, HW / 128, HW, Cin);
-    hipLaunchKernelGGL(img_conv_kernel, dim3((Cout + 3) / 4, N), dim3(256), 0, s, mean, w, scale, shift, vec, Cin, Cout);
-    const long long total = (long long)N * HW * (Cout / 8);
-    if (dtype == KD_BF16) hipLaunchKernelGGL(broadcast_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, s, vec, (bf16_t *)y, ldy, N, HW, Cout);
-    else hipLaunchKernelGGL(broadcast_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, vec, (float *)y, ldy, N, HW, Cout);
+    hipLaunchKernelGGL(gap_rows_finish_kernel, dim3_of(sel.grid), dim3(256), 0, s, part, mean, N, HW / 128, HW, Cin);
     KD_CHECK_LAUNCH("kd_aspp_image_pool_sums");
+    return image_pool_tail(sel, "kd_aspp_image_pool_sums", mean, vec, w, scale, shift, y, ldy, N, HW, Cin, Cout, s);
+}
+
+static int image_pool_tail(const PlumbSel &sel, const char *who, const float *mean, float *vec, const float *w, const float *scale,
+                           const float *shift, void *y, int ldy, int N, int HW, int Cin, int Cout, hipStream_t s)
+{
+    hipLaunchKernelGGL(img_conv_kernel, dim3((Cout + 3) / 4, N), dim3(256), 0, s, mean, w, scale, shift, vec, Cin, Cout);   // a wave per output channel
+    KD_CHECK_LAUNCH(who);
+    if (sel.kernel == PK_GAP_PARTIAL_BF16) hipLaunchKernelGGL(broadcast_kernel<bf16_t>, dim3_of(sel.grid2), dim3(256), 0, s, vec, (bf16_t *)y, ldy, N, HW, Cout);
+    else hipLaunchKernelGGL(broadcast_kernel<float>, dim3_of(sel.grid2), dim3(256), 0, s, vec, (float *)y, ldy, N, HW, Cout);
+    KD_CHECK_LAUNCH(who);
     return KD_OK;
 }
 
@@ -857,9 +816,9 @@ extern "C" int kd_bn_fold(const float *gamma, const float *beta, const float *me
                           float *scale, float *shift, int32_t C, kd_stream_t stream)
 {
     KD_REQUIRE(gamma && beta && mean && var && scale && shift && C > 0, KD_ERR_INVALID, "kd_bn_fold: bad argument");
-    KD_NOTE_PLUMBING("bn_fold_kernel");
-    hipLaunchKernelGGL(bn_fold_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, gamma, beta, mean, var, eps,
-                       scale, shift, C);
+    const PlumbSel sel = plumb_select_bn_fold(C);
+    KD_NOTE_PLUMBING(plumb_kernel_name(sel.kernel));
+    hipLaunchKernelGGL(bn_fold_kernel, dim3_of(sel.grid), dim3(256), 0, (hipStream_t)stream, gamma, beta, mean, var, eps, scale, shift, C);
     KD_CHECK_LAUNCH("kd_bn_fold");
     return KD_OK;
 }
@@ -869,14 +828,12 @@ extern "C" int kd_copy_cast(const void *src, int32_t src_dtype, int64_t s_sN, in
                             kd_stream_t stream)
 {
     KD_REQUIRE(src && dst && N > 0 && C > 0 && P > 0, KD_ERR_INVALID, "kd_copy_cast: bad argument");
-    KD_REQUIRE((src_dtype == KD_F32 || src_dtype == KD_BF16) && (dst_dtype == KD_F32 || dst_dtype == KD_BF16),
-               KD_ERR_INVALID, "kd_copy_cast: bad dtype");
-    const long long total = (long long)N * C * P;
-    if (d_sC == 1) KD_NOTE_PLUMBING("copy_cast_kernel<c_fast>");
-    else KD_NOTE_PLUMBING("copy_cast_kernel<p_fast>");
-    hipLaunchKernelGGL(copy_cast_kernel, dim3(grid_for(total, 1 << 20)), dim3(256), 0, (hipStream_t)stream, src, src_dtype,
-                       (long long)s_sN, (long long)s_sC, (long long)s_sP, dst, dst_dtype, (long long)d_sN, (long long)d_sC,
-                       (long long)d_sP, N, C, (long long)P, d_sC == 1 ? 1 : 0);
+    KD_REQUIRE(plumb_dtype_ok(src_dtype) && plumb_dtype_ok(dst_dtype), KD_ERR_INVALID, "kd_copy_cast: bad dtype");
+    const PlumbSel sel = plumb_select_copy_cast(d_sC, N, C, P);
+    KD_NOTE_PLUMBING(plumb_kernel_name(sel.kernel));
+    hipLaunchKernelGGL(copy_cast_kernel, dim3_of(sel.grid), dim3(256), 0, (hipStream_t)stream, src, src_dtype, (long long)s_sN,
+                       (long long)s_sC, (long long)s_sP, dst, dst_dtype, (long long)d_sN, (long long)d_sC, (long long)d_sP, N, C,
+                       (long long)P, sel.kernel == PK_COPY_CAST_CFAST ? 1 : 0);
     KD_CHECK_LAUNCH("kd_copy_cast");
     return KD_OK;
 }

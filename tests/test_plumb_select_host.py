@@ -1,0 +1,427 @@
+"""The plumbing selection the library really runs (csrc/plumb_select.h: one selector per entry point of trunk_ops.hip, bwd_ops.hip and
+small_ops.hip, the grids, the launch plans, the workspaces), compiled for the host and held against tests/_plumbing_cases.py --
+without a GPU.  The kernel of every row of the GPU test's case table, on the views test_plumbing_gpu.py builds for it; the
+channel-sums plan against P.cs_plan; both sides of every other gate; the workspaces against the parent's formulas; the name
+table and the header's hygiene; the resampling geometry bit for bit."""
+import ctypes as C
+import itertools
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import _plumbing_cases as P
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+WRAP = os.path.join(HERE, "plumb_select_host")
+CSRC = os.path.join(os.path.dirname(HERE), "knowledge-distillation-by-replacing-cheap-conv_amd", "csrc")
+FIELDS = ("kernel", "gx", "gy", "gz", "g2x", "g2y", "g2z", "chunks", "lc", "cblocks", "per", "vec", "flat4", "two_pass", "ws0", "ws1", "ws2",
+          "blocks", "Ho", "Wo", "ngx", "nseg", "sh", "sw", "oh", "ow")
+CONSTS = ("SW_SEG", "STEM_MAX_BLOCKS", "STEM_MFMA_MAX_BLOCKS", "SP_COLS", "SP_ROWS", "GAP_CHUNKS", "UP_RO", "CS_ROWS", "CS_MAX_CHUNKS", "CS_BLOCKS",
+          "CS_MIN_CHUNKS", "BNS_DIRECT_ROWS", "BNS_LONG_ROWS", "BNS_PER", "BNS_PER_LONG", "CAP_TRUNK", "CAP_BWD", "CAP_SMALL", "CAP_COPY")
+DTS = ("f32", "bf16")
+ES = {"f32": 4, "bf16": 2}
+BASE = 0x10000           # a buffer's base (the allocator's are 256-B aligned)
+REFUSED = "(refused)"
+i32, i64, u64, out = C.c_int, C.c_longlong, C.c_ulonglong, C.POINTER(C.c_double)
+SIGS = {"ps_stem_conv": [i32] * 4, "ps_stem_conv_pool": [i32] * 3, "ps_maxpool": [i32] * 5,
+        "ps_upsample": [i64, i32, i32, i64, i32, i32] + [i32] * 7, "ps_image_pool": [i32] * 6, "ps_image_pool_sums": [i32] * 6, "ps_bn_fold": [i32],
+        "ps_copy_cast": [i64, i32, i32, i64], "ps_relu_bn_bwd": [i32, i64, i32], "ps_channel_sums": [i32, i64, i32, i64, i32, i64, i32, i32, i64, i32],
+        "ps_bn_sums_finish": [i32, i32], "ps_bn_eval_param_grads": [i32], "ps_maxpool_bwd": [i32, i64, i32, i64, i32, i64, i32] + [i32] * 4 + [i64, u64],
+        "ps_upsample_bwd": [i64, i32, i32, i64, i32, i32] + [i32] * 7 + [i64], "ps_zero_insert": [i32] * 5, "ps_broadcast_add": [i32, i32, i64, i32],
+        "ps_stem_wgrad": [i32, i64, i32, i32, i32, i32], "ps_direct_wgrad": [i32, i32], "ps_bn2d_fwd": [i32, i32], "ps_bn2d_bwd": [i32, i32]}
+
+
+def load():
+    subprocess.check_call(["make", "-s", "-C", WRAP])
+    so = C.CDLL(os.path.join(WRAP, "_build", "libplumb_select.so"))
+    so.ps_name.restype = C.c_char_p
+    so.ps_const.restype = i64
+    so.ps_grid.restype, so.ps_grid.argtypes = C.c_uint, [i64, i32]
+    so.ps_vec_ok.argtypes = [i64, i32, i32]
+    so.ps_geom.argtypes = [i32] * 5 + [C.POINTER(C.c_float)]
+    so.ps_cs_chunks.argtypes = [i64]
+    for name, args in (("channel_sums", [i32, i64, i32]), ("bn_sums_finish", [i32, i32]), ("maxpool_bwd", [i32] * 4), ("upsample_bwd", [i32] * 6),
+                       ("stem_wgrad", [i32] * 3), ("image_pool", [i32] * 3)):
+        fn = getattr(so, "ps_ws_" + name)
+        fn.restype, fn.argtypes = u64, args
+    for name, args in SIGS.items():
+        getattr(so, name).argtypes = args + [out]
+    return so
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return load()
+
+
+def consts(lib):
+    return {n: lib.ps_const(i) for i, n in enumerate(CONSTS)}
+
+
+def call(lib, fn, *args):
+    o = (C.c_double * len(FIELDS))()
+    getattr(lib, "ps_" + fn)(*args, o)
+    sel = dict(zip(FIELDS, o))
+    for k in FIELDS[:22]:
+        sel[k] = int(sel[k])
+    sel["name"] = REFUSED if sel["kernel"] == lib.ps_refused() else lib.ps_name(sel["kernel"]).decode()
+    sel["grid"], sel["grid2"] = (sel["gx"], sel["gy"], sel["gz"]), (sel["g2x"], sel["g2y"], sel["g2z"])
+    return sel
+
+
+def view(dt, Cc, sliced=False, ld=None, off=8):
+    """(pointer value, leading dimension) of test_plumbing_gpu.dev / out_view: a dense tensor, or a channel slice at element `off`
+    of a buffer `ld` (default C + 16) wide."""
+    return (BASE + off * ES[dt], ld or Cc + 16) if sliced else (BASE, Cc)
+
+
+def select(lib, c):
+    """The selector of the row's entry point on the shape, dtype and views test_plumbing_gpu.py hands the library for the row."""
+    op = c["op"]
+    d = lambda k="dt": DTS.index(c[k])
+    if op == "channel_sums":
+        N, H, W, Cc = c["shape"]
+        groups, rows = (N, H * W) if c["per_image"] else (1, N * H * W)
+        g = view(c["dt"], Cc, "g" in c["sliced"], c.get("slice_ld"), c.get("slice_off", 8))
+        sub = view(c["dt"], Cc, "sub" in c["sliced"]) if c["sub"] else (0, 0)
+        a = view(c["dt"], Cc, "a" in c["sliced"]) if c["a"] else (0, 0)
+        return call(lib, "channel_sums", d(), *g, *sub, *a, groups, rows, Cc)
+    if op == "bn_sums_finish":
+        return call(lib, "bn_sums_finish", c["rows"], c["C"])
+    if op == "relu_bn_bwd":
+        N, H, W, Cc = c["shape"]
+        return call(lib, "relu_bn_bwd", d(), N * H * W, Cc)
+    if op == "broadcast_add":
+        N, H, W, Cc = c["shape"]
+        return call(lib, "broadcast_add", d(), N, H * W, Cc)
+    if op == "aspp_image_pool":
+        return call(lib, "image_pool", d(), c["N"], *c["HW"], c["Cin"], c["Cout"])
+    if op == "maxpool":
+        return call(lib, "maxpool", d(), *c["shape"])
+    if op == "maxpool_bwd":
+        N, H, W, Cc = c["shape"]
+        x = view(c["dt"], Cc, True, Cc + 1, 0) if c["path"] == "scalar" else view(c["dt"], Cc)
+        need = lib.ps_ws_maxpool_bwd(N, H, W, Cc)
+        ws = (BASE, need) if c["path"] in ("argmax", "dense") else (0, 0)
+        return call(lib, "maxpool_bwd", d(), *x, *view(c["dt"], Cc), *view(c["dt"], Cc), N, H, W, Cc, *ws)
+    if op in ("upsample", "upsample_bwd"):
+        Cc = c["C"]
+        ld, off = (Cc + 16, 8) if Cc % 8 == 0 else (Cc + 13, 5)
+        (H, W), (Ho, Wo) = c["hin"], c["hout"]
+        if op == "upsample":
+            x, y = view(c["ti"], Cc, Cc % 8 == 0 and c["sliced"]), view(c["to"], Cc, c["sliced"], ld, off)
+            return call(lib, "upsample", x[0], d("ti"), x[1], y[0], d("to"), y[1], c["N"], H, W, Cc, Ho, Wo, int(c["align"]))
+        gy, gx = view(c["tg"], Cc), view(c["tx"], Cc, c["sliced"], ld, off)
+        return call(lib, "upsample_bwd", gy[0], d("tg"), gy[1], gx[0], d("tx"), gx[1], c["N"], H, W, Cc, Ho, Wo, int(c["align"]), BASE)
+    if op == "zero_insert":
+        N, H, W, Cc = c["shape"]
+        s = c["stride"]
+        return call(lib, "zero_insert", d(), N, Cc, (H - 1) * s + 1 + c["extra"][0], (W - 1) * s + 1 + c["extra"][1])
+    if op == "copy_cast":
+        N, Cc, H, W = c["shape"]
+        return call(lib, "copy_cast", H * W if c["dst"] == "nchw" else 1, N, Cc, H * W)
+    if op == "bn_fold":
+        return call(lib, "bn_fold", c["C"])
+    if op == "bn_eval_param_grads":
+        return call(lib, "bn_eval_param_grads", c["C"])
+    if op == "stem_conv":
+        return call(lib, "stem_conv", d(), *c["shape"])
+    if op == "stem_conv_pool":
+        return call(lib, "stem_conv_pool", *c["shape"])
+    if op == "stem_wgrad":
+        ld, off = {"dense": (64, 0), "ld72": (72, 8), "ld68": (68, 4), "off1": (72, 1)}[c["view"]]
+        return call(lib, "stem_wgrad", d(), BASE + off * ES[c["dt"]], ld, *c["shape"])
+    if op == "direct_wgrad":
+        N, Cc, H, W, K, k, s, p, g, has_b = c["desc"]
+        return call(lib, "direct_wgrad", K, Cc // g)
+    assert op in ("bn2d_fwd", "bn2d_bwd")
+    return call(lib, op, int(c["train"]), c["shape"][1])
+
+
+# ---- the case table ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("c", P.CASES, ids=P.ids(P.CASES))
+def test_every_row_selects_its_kernel(lib, c):
+    sel = select(lib, c)
+    assert sel["name"] == c["kernel"], f"{c['id']}: plumb_select.h picks {sel['name']}, the row says {c['kernel']}"
+    assert min(sel["grid"] + sel["grid2"]) >= 1
+    if "second_trip" in c and c["op"] != "stem_conv":     # the grid the launch really gets is the cap the row claims
+        work, cap = c["second_trip"]
+        assert (sel["grid2"] if c["op"] == "aspp_image_pool" else sel["grid"]) == (cap, 1, 1) and work > cap * 256
+    if c["op"] == "stem_conv" and "second_trip" in c:     # four 16-pixel groups a block and trip
+        assert sel["blocks"] * 4 == c["second_trip"][1] * 256 < c["second_trip"][0]
+
+
+# ---- channel sums: the compiled plan against the restatement the GPU test's bounds use ---------------------------------------------------
+def cs_agree(lib, dt, groups, rows, Cc, vec, ptr=BASE):
+    sel = call(lib, "channel_sums", DTS.index(dt), ptr, Cc if vec else Cc + 1, 0, 0, 0, 0, groups, rows, Cc)
+    plan = P.cs_plan(groups, rows, Cc, vec)
+    assert sel["name"] == f"channel_sums_partial_kernel<{dt},{8 if vec else 1}>" and sel["vec"] == vec
+    got = dict(chunks=sel["chunks"], cs_chunks=lib.ps_cs_chunks(rows), lc=sel["lc"], cblocks=sel["cblocks"])
+    assert got == {k: plan[k] for k in got}, (groups, rows, Cc, vec)
+    assert sel["grid"] == (plan["chunks"], plan["cblocks"], groups) and sel["grid2"] == (groups * -(-Cc // 16), 1, 1)
+    # the partials the first pass writes fit the workspace the header reports
+    assert groups * sel["chunks"] * 2 * Cc * 4 <= lib.ps_ws_channel_sums(groups, rows, Cc)
+    return plan
+
+
+def test_channel_sums_plan_on_every_row_and_on_the_sweep(lib):
+    for c in P.cases_of("channel_sums"):
+        N, H, W, Cc = c["shape"]
+        groups, rows = (N, H * W) if c["per_image"] else (1, N * H * W)
+        sel, plan = select(lib, c), P.cs_plan(groups, rows, Cc, c["vec"] == 8)
+        got = dict(chunks=sel["chunks"], cs_chunks=lib.ps_cs_chunks(rows), lc=sel["lc"], cblocks=sel["cblocks"])
+        assert got == {k: plan[k] for k in got}, c["id"]
+    seen = set()
+    for groups, rows, Cc in itertools.product((1, 2, 16, 64), (1, 511, 512, 513, 8200, 70000, 524287, 524288, 524289),
+                                              (3, 8, 19, 32, 33, 64, 72, 128, 136, 256, 264, 512)):
+        for vec in ((True, False) if Cc % 8 == 0 else (False,)):
+            plan = cs_agree(lib, "bf16", groups, rows, Cc, vec)
+            seen.add((plan["lc"], plan["cs_chunks"] == 1024, plan["want"] < plan["cs_chunks"], plan["chunks"] == 16 and plan["want"] < 16))
+    assert {s[0] for s in seen} == {4, 8, 16, 32} and all({s[i] for s in seen} == {True, False} for i in (1, 2, 3))
+
+
+# ---- both sides of every other gate ---------------------------------------------------------------------------------------------------
+def test_vector_gates_c_mod_8_base_offset_and_leading_dimension(lib):
+    """C % 8; base offset 0 / one element / 16 B; ld * es % 16 -- through the predicate and through every selector that asks it."""
+    for dt in DTS:
+        es, n = ES[dt], DTS.index(dt)
+        for off, ld in itertools.product((0, es, 16), (32, 32 + 16 // es, 33, 32 + 8 // es)):
+            ok = off % 16 == 0 and ld * es % 16 == 0
+            assert bool(lib.ps_vec_ok(BASE + off, ld, es)) == ok
+            for Cc in (32, 33):
+                vec = ok and Cc % 8 == 0
+                v = 8 if vec else 1
+                assert call(lib, "channel_sums", n, BASE + off, ld, 0, 0, 0, 0, 1, 100, Cc)["name"] == f"channel_sums_partial_kernel<{dt},{v}>"
+                for slot in (2, 4):             # the operand that decides may be any of the three: `sub`, `a`
+                    args = [BASE, 48, 0, 0, 0, 0]
+                    args[slot:slot + 2] = [BASE + off, ld]
+                    assert call(lib, "channel_sums", n, *args, 1, 100, Cc)["name"] == f"channel_sums_partial_kernel<{dt},{v}>"
+                sel = call(lib, "maxpool_bwd", n, BASE + off, ld, BASE, 48, BASE, 48, 2, 5, 7, Cc, 0, 0)
+                assert sel["name"] == f"maxpool_bwd_kernel<{dt},{v}>" and sel["grid"] == (-(-7 * (Cc // 8 if vec else Cc) // 256), 5, 2)
+                sel = call(lib, "upsample_bwd", BASE, n, 48, BASE + off, n, ld, 2, 5, 7, Cc, 9, 14, 1, BASE)
+                assert sel["name"] == f"upsample_bwd_kernel<{dt},{dt},{v}>"
+                sel = call(lib, "upsample", BASE + off, n, ld, BASE, 1, 48, 2, 5, 7, Cc, 9, 14, 1)
+                assert sel["name"] == f"upsample_kernel<{dt},bf16,{v}>"
+        assert lib.ps_vec_ok(0, 33, es), "an absent operand never stands in the way"
+    # the backward upsample also needs its fp32 intermediate 16-B aligned
+    assert call(lib, "upsample_bwd", BASE, 0, 8, BASE, 0, 8, 1, 5, 7, 8, 9, 14, 1, BASE + 8)["name"] == "upsample_bwd_kernel<f32,f32,1>"
+    assert [lib.ps_dtype_ok(d) for d in (-1, 0, 1, 2)] == [0, 1, 1, 0]
+
+
+def test_upsample_flat4_gate(lib):
+    """flat4: ldy == C, (Wo * C) % 4 == 0, an fp32 output, a 16-B aligned base -- and only when the vector kernel is out."""
+    up = lambda ti, to, Cc, Wo, ldy=None, yoff=0, ldx=None: call(lib, "upsample", BASE, DTS.index(ti), ldx or Cc, BASE + yoff, DTS.index(to), ldy or Cc,
+                                                                 2, 5, 7, Cc, 9, Wo, 1)
+    for ti in DTS:
+        sel = up(ti, "f32", 19, 12)
+        assert sel["name"] == f"upsample_flat4_kernel<{ti}>" and sel["flat4"] and not sel["vec"] and sel["grid"] == (-(-(12 * 19 // 4) // 256), 2, 2)
+        assert up(ti, "f32", 19, 13)["name"] == f"upsample_kernel<{ti},f32,1>"                 # (Wo * C) % 4 != 0
+        assert up(ti, "f32", 19, 12, ldy=32)["name"] == f"upsample_kernel<{ti},f32,1>"         # a slice: ldy != C
+        assert up(ti, "f32", 19, 12, yoff=4)["name"] == f"upsample_kernel<{ti},f32,1>"         # base not 16-B aligned
+        assert up(ti, "bf16", 19, 12)["name"] == f"upsample_kernel<{ti},bf16,1>"               # fp32 output only
+        sel = up(ti, "f32", 8, 12)
+        assert sel["name"] == f"upsample_kernel<{ti},f32,8>" and sel["vec"] and not sel["flat4"]  # only when !vec ...
+        assert up(ti, "f32", 8, 12, ldx=9)["name"] == f"upsample_flat4_kernel<{ti}>"           # ... e.g. C % 8 == 0 behind a misaligned input
+
+
+def test_bn_sums_finish_gates(lib):
+    K = consts(lib)
+    assert (K["BNS_DIRECT_ROWS"], K["BNS_LONG_ROWS"], K["BNS_PER"], K["BNS_PER_LONG"]) == (256, 16384, 64, 256)
+    for rows, name, per in ((256, "channel_sums_finish_kernel", 0), (257, "bn_sums_stage_kernel<64 rows>", 64),
+                            (16384, "bn_sums_stage_kernel<64 rows>", 64), (16385, "bn_sums_stage_kernel<256 rows>", 256)):
+        for Cc in (8, 24, 256):
+            sel = call(lib, "bn_sums_finish", rows, Cc)
+            chunks = -(-rows // per) if per else rows
+            assert (sel["name"], sel["per"], sel["chunks"]) == (name, per, chunks)
+            assert sel["grid2"] == (-(-Cc // 16), 1, 1) and sel["grid"] == (-(-Cc // 16), chunks if per else 1, 1)
+            assert (chunks * 2 * Cc * 4 if per else 0) == lib.ps_ws_bn_sums_finish(rows, Cc)
+
+
+def test_stem_wgrad_gates(lib):
+    K = consts(lib)
+    assert (K["STEM_MAX_BLOCKS"], K["SW_SEG"]) == (768, 256)
+    sw = lambda dt, off, ld, shape=(2, 11, 270): call(lib, "stem_wgrad", DTS.index(dt), BASE + off, ld, *shape)
+    assert [sw("bf16", 0, ld)["name"] for ld in (64, 72, 68, 65)] == ["stem_wgrad_mfma_kernel"] * 2 + ["stem_wgrad_kernel<bf16>"] * 2     # ld_dy % 8
+    assert [sw("bf16", off, 72)["name"] for off in (0, 16, 2, 8)] == ["stem_wgrad_mfma_kernel"] * 2 + ["stem_wgrad_kernel<bf16>"] * 2     # dy alignment
+    assert {sw("f32", off, ld)["name"] for off in (0, 4) for ld in (64, 68)} == {"stem_wgrad_kernel<f32>"}
+    for dt, items in itertools.product(DTS, (767, 768, 769)):                   # N * H work items of one 256-column segment
+        sel = sw(dt, 0, 64, (1, items, 256))
+        assert sel["blocks"] == min(items, 768) == sel["grid"][0] and sel["grid2"] == (7, 1, 1)
+        assert sel["blocks"] * 64 * 27 * 4 == lib.ps_ws_stem_wgrad(1, items, 256)
+    assert sw("bf16", 0, 64, (1, 3, 257))["blocks"] == 6                        # a second segment from column 257 on
+
+
+def test_maxpool_bwd_workspace_gates(lib):
+    """Absent, one byte short, 4-B-misaligned and exact: only the last is the two-pass kernel, the others the one-pass (no refusal)."""
+    N, H, W, Cc = 2, 13, 18, 16
+    need = lib.ps_ws_maxpool_bwd(N, H, W, Cc)
+    assert need == N * 7 * 9 * 16
+    for dt in DTS:
+        mp = lambda ws, nbytes, Cq=Cc: call(lib, "maxpool_bwd", DTS.index(dt), BASE, Cq, BASE, Cq, BASE, Cq, N, H, W, Cq, ws, nbytes)
+        for ws, nbytes in ((0, 0), (0, need), (BASE, need - 1), (BASE + 4, need)):
+            sel = mp(ws, nbytes)
+            assert sel["name"] == f"maxpool_bwd_kernel<{dt},8>" and not sel["two_pass"] and sel["grid"] == sel["grid2"] == (-(-W * 2 // 256), H, N)
+        for ws in (BASE, BASE + 8):
+            sel = mp(ws, need)
+            assert sel["name"] == f"maxpool_argmax_kernel<{dt}>" and sel["two_pass"]
+            assert sel["grid"] == (-(-9 * 2 // 256), 7, N) and sel["grid2"] == (-(-W * 2 // 256), H, N) and (sel["Ho"], sel["Wo"]) == (7, 9)
+        assert mp(BASE, lib.ps_ws_maxpool_bwd(N, H, W, 19), 19)["name"] == f"maxpool_bwd_kernel<{dt},1>"      # the workspace never helps the scalar kernel
+
+
+def test_copy_cast_and_the_grid_caps(lib):
+    K = consts(lib)
+    assert (K["CAP_TRUNK"], K["CAP_BWD"], K["CAP_SMALL"], K["CAP_COPY"]) == (8192, 16384, 65536, 1 << 20)
+    for d_sC, name in ((1, "copy_cast_kernel<c_fast>"), (2, "copy_cast_kernel<p_fast>"), (35, "copy_cast_kernel<p_fast>")):
+        assert call(lib, "copy_cast", d_sC, 2, 19, 35)["name"] == name
+    for cap in (K["CAP_TRUNK"], K["CAP_BWD"], K["CAP_SMALL"], K["CAP_COPY"]):
+        assert [lib.ps_grid(cap * 256 + d, cap) for d in (-1, 0, 1)] == [cap, cap, cap] and lib.ps_grid(cap * 256 - 256, cap) == cap - 1
+        assert [lib.ps_grid(t, cap) for t in (-5, 0, 1, 256, 257)] == [1, 1, 1, 1, 2]
+    cap = K["CAP_COPY"]      # through the entry points' selectors: cap * 256 - 1, cap * 256 and cap * 256 + 1 items
+    assert [call(lib, "copy_cast", 1, 1, 1, cap * 256 + d)["grid"][0] for d in (-256, -1, 0, 1)] == [cap - 1, cap, cap, cap]
+    cap = K["CAP_BWD"]       # a thread owns 8 channels
+    for fn, args in (("relu_bn_bwd", lambda items: (0, items, 8)), ("broadcast_add", lambda items: (0, 1, items, 8))):
+        assert [call(lib, fn, *args(cap * 256 + d))["grid"][0] for d in (-256, -1, 0, 1)] == [cap - 1, cap, cap, cap]
+    cap = K["CAP_TRUNK"]     # the image-pool broadcast: N * H * W * Cout / 8 items
+    assert [call(lib, "image_pool", 0, 1, 1, cap * 256 + d, 8, 8)["grid2"][0] for d in (-256, -1, 0, 1)] == [cap - 1, cap, cap, cap]
+
+
+def test_stem_conv_pool_refuses_the_first_wave_count_above_the_grid_limit(lib):
+    K = consts(lib)
+    assert (K["SP_COLS"], K["SP_ROWS"]) == (7, 16)
+    limit = 4 * (2 ** 31 - 1)
+    # one row segment (H = 1); 4 column groups (W = 43 -> 22 pooled columns) x (2^31 - 1) images = the limit exactly ...
+    sel = call(lib, "stem_conv_pool", 2 ** 31 - 1, 1, 43)
+    assert (sel["ngx"], sel["nseg"]) == (4, 1) and (2 ** 31 - 1) * 4 == limit and sel["name"] == "stem_pool_kernel" and sel["grid"] == (2 ** 31 - 1, 1, 1)
+    # ... and the limit + 1 = 29 x 296204641: 29 column groups (W = 393 -> 197 pooled columns)
+    sel = call(lib, "stem_conv_pool", 296204641, 1, 393)
+    assert (sel["ngx"], sel["nseg"]) == (29, 1) and 296204641 * 29 == limit + 1 and sel["name"] == REFUSED
+    sel = call(lib, "stem_conv_pool", 2, 20, 28)
+    assert (sel["Ho"], sel["Wo"], sel["ngx"], sel["nseg"], sel["grid"]) == (10, 14, 2, 1, (1, 1, 1))
+
+
+def test_the_other_plans(lib):
+    K = consts(lib)
+    assert (K["STEM_MFMA_MAX_BLOCKS"], K["GAP_CHUNKS"], K["UP_RO"], K["CS_ROWS"], K["CS_MAX_CHUNKS"], K["CS_BLOCKS"], K["CS_MIN_CHUNKS"]) == (4096, 64, 8, 512, 1024, 2048, 16)
+    sel = call(lib, "stem_conv", 0, 3, 1, 21)
+    assert (sel["name"], sel["grid"]) == ("stem_conv_kernel<f32>", (1, 1, 1)) and call(lib, "stem_conv", 0, 1, 5, 33)["grid"][0] == 3
+    sel = call(lib, "stem_conv", 1, 1, 5, 33)
+    assert (sel["name"], sel["ngx"], sel["blocks"]) == ("stem_conv_mfma_kernel", 3, 4)
+    for dt in DTS:
+        n = DTS.index(dt)
+        sel = call(lib, "maxpool", n, 2, 13, 18, 264)
+        assert (sel["name"], sel["grid"], sel["Ho"], sel["Wo"]) == (f"maxpool_kernel<{dt}>", (2, 7, 2), 7, 9)
+        sel = call(lib, "zero_insert", n, 2, 16, 13, 19)
+        assert (sel["name"], sel["grid"]) == (f"zero_insert_kernel<{dt}>", (1, 13, 2))
+        sel = call(lib, "image_pool", n, 3, 37, 41, 264, 256)
+        assert (sel["name"], sel["grid"], sel["grid2"]) == (f"gap_partial_kernel<{dt}>", (64, 2, 3), (-(-3 * 37 * 41 * 32 // 256), 1, 1))
+        assert (sel["ws0"], sel["ws1"], sel["ws2"]) == (0, 64 * 3 * 264 * 4, 64 * 3 * 264 * 4 + 3 * 264 * 4)
+        sums = call(lib, "image_pool_sums", n, 3, 16, 8, 264, 256)
+        assert sums["grid"] == (9, 3, 1) and (sums["ws1"], sums["ws2"], sums["kernel"]) == (sel["ws1"], sel["ws2"], sel["kernel"])
+    for Cc in (8, 600):
+        assert call(lib, "bn_fold", Cc)["grid"] == call(lib, "bn_eval_param_grads", Cc)["grid"] == (-(-Cc // 256), 1, 1)
+    sel = call(lib, "direct_wgrad", 64, 1)
+    assert (sel["grid"], sel["grid2"]) == ((64, 1, 1), (64, 1, 1)) and call(lib, "direct_wgrad", 32, 16)["grid"] == (512, 1, 1)
+    for train, t in ((0, "eval"), (1, "train"), (2, "train")):
+        assert (call(lib, "bn2d_fwd", train, 16)["name"], call(lib, "bn2d_bwd", train, 16)["name"]) == (f"bn2d_fwd_kernel<{t}>", f"bn2d_bwd_kernel<{t}>")
+        assert call(lib, "bn2d_fwd", train, 16)["grid"] == call(lib, "bn2d_bwd", train, 16)["grid"] == (16, 1, 1)
+    # the upsample grids: UP_RO output rows a thread
+    sel = call(lib, "upsample", BASE, 0, 256, BASE, 0, 256, 1, 7, 10, 256, 18, 23, 1)
+    assert sel["grid"] == (-(-23 * 32 // 256), 3, 1)
+    sel = call(lib, "upsample_bwd", BASE, 0, 19, BASE, 0, 19, 2, 5, 7, 19, 20, 28, 1, BASE)
+    assert sel["grid"] == (1, 20, 2) and sel["grid2"] == (1, 5, 2)
+
+
+# ---- the workspaces: the parent's formulas (the queries are public ABI) ------------------------------------------------------------------
+def parent_cs_workspace(groups, rows, Cc):
+    return groups * min(max((rows + 511) // 512, 1), 1024) * 2 * Cc * 4
+
+
+def parent_bn_sums_workspace(rows, Cc):
+    per = 256 if rows > 16384 else 64
+    return (rows + per - 1) // per * 2 * Cc * 4 if rows > 256 else 0
+
+
+def parent_maxpool_bwd_workspace(N, H, W, Cc):
+    return N * ((H - 1) // 2 + 1) * ((W - 1) // 2 + 1) * ((Cc + 7) // 8) * 8
+
+
+def parent_upsample_bwd_workspace(N, H, W, Cc, Ho, Wo):
+    return N * Ho * W * Cc * 4
+
+
+def parent_stem_wgrad_workspace(N, H, W):
+    return min(N * H * ((W + 255) // 256), 768) * 64 * 27 * 4
+
+
+def parent_image_pool_workspace(N, Cin, Cout):
+    return (64 * N * Cin + N * Cin + N * Cout) * 4
+
+
+def test_the_workspaces_are_the_parents_and_hold_what_the_launchers_put_there(lib):
+    for groups, rows, Cc in itertools.product((1, 2, 16, 64), (1, 511, 512, 513, 70000, 524288, 524289, 1 << 33), (1, 3, 19, 256, 264, 4096)):
+        assert lib.ps_ws_channel_sums(groups, rows, Cc) == parent_cs_workspace(groups, rows, Cc)
+    for rows, Cc in itertools.product((1, 256, 257, 1000, 16384, 16385, 1 << 22), (1, 8, 24, 256, 4096)):
+        assert lib.ps_ws_bn_sums_finish(rows, Cc) == parent_bn_sums_workspace(rows, Cc)
+        sel = call(lib, "bn_sums_finish", rows, Cc)
+        assert (sel["chunks"] * 2 * Cc * 4 if sel["per"] else 0) <= lib.ps_ws_bn_sums_finish(rows, Cc)
+    for N, H, W, Cc in itertools.product((1, 2, 8), (1, 2, 13, 64, 1024), (1, 3, 18, 2048), (1, 8, 19, 64, 264)):
+        need = lib.ps_ws_maxpool_bwd(N, H, W, Cc)
+        assert need == parent_maxpool_bwd_workspace(N, H, W, Cc)
+        if Cc % 8 == 0:      # a uint2 (8 position bytes) per (window, channel octet), as the arg-max grid writes them
+            sel = call(lib, "maxpool_bwd", 0, BASE, Cc, BASE, Cc, BASE, Cc, N, H, W, Cc, BASE, need)
+            assert sel["two_pass"] and N * sel["Ho"] * sel["Wo"] * (Cc // 8) * 8 == need
+        assert lib.ps_ws_stem_wgrad(N, H, W) == parent_stem_wgrad_workspace(N, H, W)
+        assert call(lib, "stem_wgrad", 1, BASE, 64, N, H, W)["blocks"] * 64 * 27 * 4 == lib.ps_ws_stem_wgrad(N, H, W)
+        for Ho, Wo in ((1, 1), (7, 10), (1024, 2048)):
+            assert lib.ps_ws_upsample_bwd(N, H, W, Cc, Ho, Wo) == parent_upsample_bwd_workspace(N, H, W, Cc, Ho, Wo)
+    for N, Cin, Cout in itertools.product((1, 3, 8, 64), (8, 64, 264, 4096), (8, 256, 264)):
+        ws = lib.ps_ws_image_pool(N, Cin, Cout)
+        assert ws == parent_image_pool_workspace(N, Cin, Cout)
+        for fn in ("image_pool", "image_pool_sums"):
+            sel = call(lib, fn, 0, N, 16, 8, Cin, Cout)
+            assert sel["ws0"] == 0 and sel["ws0"] + 64 * N * Cin * 4 <= sel["ws1"] and sel["ws1"] + N * Cin * 4 <= sel["ws2"] and sel["ws2"] + N * Cout * 4 <= ws
+
+
+# ---- names and hygiene ------------------------------------------------------------------------------------------------------------------
+def test_the_names_are_distinct_and_every_one_has_a_row(lib):
+    n = lib.ps_refused()
+    names = [lib.ps_name(k).decode() for k in range(n)]
+    assert lib.ps_name(n) is None and lib.ps_name(-1) is None
+    assert len(set(names)) == n == 56
+    assert set(names) == {c["kernel"] for c in P.CASES}
+
+
+def test_the_selection_header_is_plain_host_code():
+    with open(os.path.join(CSRC, "plumb_select.h")) as f:
+        text = re.sub(r"//[^\n]*|/\*.*?\*/", "", f.read(), flags=re.S)
+    assert not re.search(r"\bhip\w*|\bgetenv\b", text, flags=re.I)
+    assert re.findall(r"#include\s*(\S+)", text) == ["<stddef.h>", "<stdint.h>", '"../../include/kdcc.h"']
+
+
+# ---- the resampling geometry: the parent's float expressions, bit for bit ----------------------------------------------------------------
+def parent_geom(h, w, H, W, align):
+    f = np.float32
+    sh = f(h - 1) / f(H - 1) if H > 1 else f(0)
+    sw = f(w - 1) / f(W - 1) if W > 1 else f(0)
+    oh = ow = f(0)
+    if not align:
+        sh, sw = f(h) / f(H), f(w) / f(W)
+        oh, ow = f(0.5) * sh - f(0.5), f(0.5) * sw - f(0.5)
+    return [sh, sw, oh, ow]
+
+
+def test_the_geometry_is_the_parents_bit_for_bit(lib):
+    src, dst = (1, 2, 33, 64, 128), (1, 2, 67, 256, 1024)
+    for h, w, H, W, align in itertools.product(src, src, dst, dst, (1, 0)):
+        got = (C.c_float * 4)()
+        lib.ps_geom(h, w, H, W, align, got)
+        want = np.array(parent_geom(h, w, H, W, align), dtype=np.float32)
+        assert np.array(got, dtype=np.float32).tobytes() == want.tobytes(), (h, w, H, W, align)
+        # ... and both directions hand their kernels exactly these four floats
+        fwd = call(lib, "upsample", BASE, 0, 8, BASE, 0, 8, 1, h, w, 8, H, W, align)
+        bwd = call(lib, "upsample_bwd", BASE, 0, 8, BASE, 0, 8, 1, h, w, 8, H, W, align, BASE)
+        for sel in (fwd, bwd):
+            assert np.array([sel[k] for k in ("sh", "sw", "oh", "ow")], dtype=np.float32).tobytes() == want.tobytes()

@@ -1,5 +1,6 @@
-"""Keeps tests/_plumbing_cases.py honest without a GPU: every KD_NOTE_PLUMBING literal in the three plumbing sources has a case,
-every case names a literal the sources declare, every case's float64 reference runs and has the declared shape, the launch
+"""Keeps tests/_plumbing_cases.py honest without a GPU: every name the three plumbing sources can note (the table of
+csrc/plumb_select.h, compiled for the host) has a case, every case names one of them, the table is the set of literals the sources
+noted before they had a table, every case's float64 reference runs and has the declared shape, the launch
 plans the cases claim follow from the dispatcher's rules, and the large-offset channel really separates the kernel's
 decomposition from a single fp32 chain where a case says so."""
 import os
@@ -15,23 +16,52 @@ CSRC = os.path.join(ROOT, "knowledge-distillation-by-replacing-cheap-conv_amd", 
 SOURCES = ("trunk_ops.hip", "bwd_ops.hip", "small_ops.hip")
 
 
+# the KD_NOTE_PLUMBING("...") literals of the three sources as they stood before the names moved into plumb_select.h's table
+# (recorded once with re.findall(r'KD_NOTE_PLUMBING\("([^"]+)"\)', source)): kd_debug_last_plumbing_kernel's vocabulary
+PARENT_LITERALS = frozenset((
+    "bn2d_bwd_kernel<eval>", "bn2d_bwd_kernel<train>", "bn2d_fwd_kernel<eval>", "bn2d_fwd_kernel<train>",
+    "bn_eval_param_grads_kernel", "bn_fold_kernel", "bn_sums_stage_kernel<256 rows>", "bn_sums_stage_kernel<64 rows>",
+    "broadcast_add_kernel<bf16>", "broadcast_add_kernel<f32>", "channel_sums_finish_kernel",
+    "channel_sums_partial_kernel<bf16,1>", "channel_sums_partial_kernel<bf16,8>", "channel_sums_partial_kernel<f32,1>",
+    "channel_sums_partial_kernel<f32,8>", "copy_cast_kernel<c_fast>", "copy_cast_kernel<p_fast>", "dconv_wgrad_kernel",
+    "gap_partial_kernel<bf16>", "gap_partial_kernel<f32>", "maxpool_argmax_kernel<bf16>", "maxpool_argmax_kernel<f32>",
+    "maxpool_bwd_kernel<bf16,1>", "maxpool_bwd_kernel<bf16,8>", "maxpool_bwd_kernel<f32,1>", "maxpool_bwd_kernel<f32,8>",
+    "maxpool_kernel<bf16>", "maxpool_kernel<f32>", "relu_bn_bwd_kernel<bf16>", "relu_bn_bwd_kernel<f32>",
+    "stem_conv_kernel<f32>", "stem_conv_mfma_kernel", "stem_pool_kernel", "stem_wgrad_kernel<bf16>", "stem_wgrad_kernel<f32>",
+    "stem_wgrad_mfma_kernel", "upsample_bwd_kernel<bf16,bf16,1>", "upsample_bwd_kernel<bf16,bf16,8>",
+    "upsample_bwd_kernel<bf16,f32,1>", "upsample_bwd_kernel<bf16,f32,8>", "upsample_bwd_kernel<f32,bf16,1>",
+    "upsample_bwd_kernel<f32,bf16,8>", "upsample_bwd_kernel<f32,f32,1>", "upsample_bwd_kernel<f32,f32,8>",
+    "upsample_flat4_kernel<bf16>", "upsample_flat4_kernel<f32>", "upsample_kernel<bf16,bf16,1>",
+    "upsample_kernel<bf16,bf16,8>", "upsample_kernel<bf16,f32,1>", "upsample_kernel<bf16,f32,8>",
+    "upsample_kernel<f32,bf16,1>", "upsample_kernel<f32,bf16,8>", "upsample_kernel<f32,f32,1>", "upsample_kernel<f32,f32,8>",
+    "zero_insert_kernel<bf16>", "zero_insert_kernel<f32>"))
+
+
 def declared_literals():
-    out = {}
-    for name in SOURCES:
-        with open(os.path.join(CSRC, name)) as f:
-            for lit in re.findall(r'KD_NOTE_PLUMBING\("([^"]+)"\)', f.read()):
-                out.setdefault(lit, name)
-    return out
+    """The names the launchers can note: the compiled table of csrc/plumb_select.h."""
+    from test_plumb_select_host import load
+    lib = load()
+    return {lib.ps_name(k).decode(): "plumb_select.h" for k in range(lib.ps_refused())}
 
 
 def test_every_noted_literal_has_a_case_and_every_case_names_a_noted_literal():
     declared = declared_literals()
-    assert len(declared) >= 40, "the scan found too few KD_NOTE_PLUMBING literals: has the macro been renamed?"
+    assert len(PARENT_LITERALS) == 56 and set(declared) == PARENT_LITERALS, sorted(set(declared) ^ PARENT_LITERALS)
     covered = {c["kernel"] for c in P.CASES}
     missing = sorted(set(declared) - covered)
     assert not missing, f"dispatch branches without a case in tests/_plumbing_cases.py: {[(m, declared[m]) for m in missing]}"
     unknown = sorted(covered - set(declared))
     assert not unknown, f"cases name kernels no source declares: {unknown}"
+
+
+def test_every_note_goes_through_the_table():
+    """No source notes a string literal any more: every KD_NOTE_PLUMBING takes plumb_kernel_name(sel.kernel)."""
+    for name in SOURCES:
+        with open(os.path.join(CSRC, name)) as f:
+            text = f.read()
+        assert not re.search(r'KD_NOTE_PLUMBING\(\s*"', text), name
+        notes = re.findall(r'KD_NOTE_PLUMBING\(([^;]*)\);', text)
+        assert notes and set(notes) == {"plumb_kernel_name(sel.kernel)"}, (name, notes)
 
 
 def test_the_conv_log_macro_is_untouched_in_the_plumbing_sources():
