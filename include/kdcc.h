@@ -427,6 +427,26 @@ int kd_bn_nhwc_bwd(const float *gy, int32_t ldg, const float *x, int32_t ldx, co
                    const float *save_invstd, float *dgamma, float *dbeta, int32_t accumulate, int32_t training, int32_t relu,
                    void *workspace, size_t workspace_bytes, kd_stream_t stream);
 
+/* ------------------------------------------------- BatchNorm2d on NHWC bf16 views (Wide-ResNet CIFAR path in bf16, csrc/bn_nhwc_lp.hip)
+ * kd_bn_nhwc_fwd / kd_bn_nhwc_bwd with x, y, gy, res and dx in bf16 storage (leading dimensions in elements); every per-channel
+ * vector -- gamma, beta, the saved and running statistics, dgamma, dbeta -- stays fp32.  The semantics are the fp32 entry points',
+ * flag for flag: train / eval, relu, res added to dx, dx == NULL (parameter gradients only), accumulate, the running statistics
+ * updated in train mode with the unbiased variance.  dx may alias res exactly (same base and stride); no other overlap.
+ * Numerics: operands are widened to fp32 on load; the statistics are the fp32 kernels' (per-128-pixel partials shifted by the
+ *   block's first value, merged in fp64 with Chan's update in a fixed order, no atomics: bit-reproducible); y and dx are rounded to
+ *   nearest-even once, at the store; the backward's ReLU mask is y > 0 on the stored bf16 y.
+ * Vector path (8 channels = 16 B per lane) when C % 8 == 0, every base is 16-B aligned and every ld * 2 % 16 == 0; otherwise
+ *   scalar (csrc/bn_lp_select.h decides).  Any M >= 1 and C >= 1.
+ * workspace: kd_bn_nhwc_lp_workspace(M, C) bytes (train-mode forward; backward whenever a reduction is needed). */
+size_t kd_bn_nhwc_lp_workspace(int64_t M, int32_t C);
+int kd_bn_nhwc_lp_fwd(const void *x, int32_t ldx, void *y, int32_t ldy, int64_t M, int32_t C, const float *gamma, const float *beta,
+                      float *save_mean, float *save_invstd, float *running_mean, float *running_var, float momentum, float eps,
+                      int32_t training, int32_t relu, void *workspace, size_t workspace_bytes, kd_stream_t stream);
+int kd_bn_nhwc_lp_bwd(const void *gy, int32_t ldg, const void *x, int32_t ldx, const void *y, int32_t ldy, const void *res,
+                      int32_t ldres, void *dx, int32_t lddx, int64_t M, int32_t C, const float *gamma, const float *save_mean,
+                      const float *save_invstd, float *dgamma, float *dbeta, int32_t accumulate, int32_t training, int32_t relu,
+                      void *workspace, size_t workspace_bytes, kd_stream_t stream);
+
 /* ------------------------------------------------- DenseNet-BC CIFAR path (models/cifar_models/densenet.py, csrc/dense_ops.hip)
  * All fp32 on (M = N*H*W, C) views with pixel strides ld* >= C, like kd_bn_nhwc_*.
  * kd_bn_nhwc_stats: the train-mode batch statistics of kd_bn_nhwc_fwd alone -- mean, invstd = 1/sqrt(var + eps) and

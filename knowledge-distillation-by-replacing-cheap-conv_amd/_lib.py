@@ -124,6 +124,11 @@ _SIGS = {
                                c_vp, c_sz, c_vp]),
     "kd_bn_nhwc_bwd": (c_int, [c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp,
                                c_vp, c_int, c_int, c_int, c_vp, c_sz, c_vp]),
+    "kd_bn_nhwc_lp_workspace": (c_sz, [c_i64, c_int]),
+    "kd_bn_nhwc_lp_fwd": (c_int, [c_vp, c_int, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f, c_f, c_int, c_int,
+                                  c_vp, c_sz, c_vp]),
+    "kd_bn_nhwc_lp_bwd": (c_int, [c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp,
+                                  c_vp, c_int, c_int, c_int, c_vp, c_sz, c_vp]),
     "kd_bn_nhwc_stats": (c_int, [c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_f, c_vp, c_sz, c_vp]),
     "kd_bn_nhwc_apply": (c_int, [c_vp, c_int, c_vp, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f, c_int, c_vp]),
     "kd_avgpool2x2_nhwc": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),

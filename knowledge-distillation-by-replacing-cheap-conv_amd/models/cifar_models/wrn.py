@@ -3,9 +3,13 @@ reference's module tree and state-dict keys (models/cifar_models/wrn.py): conv1,
 relu2, conv2, convShortcut}, bn1, relu, fc -- so a checkpoint loads through forgiving_state_restore.  Same initialisation rule.
 
 Channels-last throughout: the image is laid out NHWC by the stem conv, every later tensor is an NCHW-logical view with NHWC
-strides.  Convolutions are nn_hip.Conv2dNHWC (MFMA implicit GEMM, fp32) and BatchNorm nn_hip.BatchNorm2dNHWC (kd_bn_nhwc_*);
+strides.  Convolutions are nn_hip.Conv2dNHWC (MFMA implicit GEMM) and BatchNorm nn_hip.BatchNorm2dNHWC (kd_bn_nhwc_*);
 the residual add rides in conv2's epilogue.  The 8x8 average pool and the 640 -> classes linear layer are torch ops (like the
 ResNet path's `linear`).
+
+The activation dtype is the input's: fp32, or bf16 (a bf16 channels-last batch runs every conv and BN in bf16 with fp32 parameters,
+through both paths below; the last bn1 + ReLU output is cast to fp32 before the pool, so the logits are fp32 either way).  In bf16
+the convs' K granule is 64 channels: the 16- and 160-channel tensors live in buffers zero-padded to 64 / 192 (nn_hip.new_padded).
 
 Eval mode without autograd (the frozen teacher, validation) runs a block as two conv launches: conv1's epilogue applies bn2 +
 ReLU (folded to scale / shift), conv2's adds the shortcut and writes both the block output and the next BN + ReLU of it.  That
@@ -71,13 +75,14 @@ class BasicBlock(nn.Module):
         self.conv2._check()
         s2, b2 = self.bn2.folded()
         _, h = self.conv1._run(ah, out_act=True, act_scale=s2, act_shift=b2, act_relu=True, want_raw=False)
+        h = self.conv2._input(nn_hip.mark_padded(h.permute(0, 3, 1, 2)))     # (the view itself; bf16: widened to its zero channels)
         nxt = self._next[0]
         if nxt is None or type(nxt) is not nn_hip.BatchNorm2dNHWC:
             return self.conv2._run(h, res_pre=sc).permute(0, 3, 1, 2)
         s, b = nxt.folded()
         raw, act = self.conv2._run(h, res_pre=sc, out_act=True, act_scale=s, act_shift=b, act_relu=True)
         out = raw.permute(0, 3, 1, 2)
-        setattr(out, _ACT, (nxt, act.permute(0, 3, 1, 2)))
+        setattr(out, _ACT, (nxt, nn_hip.mark_padded(act.permute(0, 3, 1, 2))))
         return out
 
     def forward(self, x):
@@ -142,7 +147,7 @@ class WideResNet(nn.Module):
         a = _take_act(out, self.bn1) if out.is_cuda and not self.training and not torch.is_grad_enabled() else None
         if a is None:
             a = self.bn1(out, relu=True)
-        out = F.avg_pool2d(a, 8)
+        out = F.avg_pool2d(a.float(), 8)      # (bf16 activations end here: pool, fc and the logits are fp32)
         return self.fc(out.reshape(-1, self.nChannels))
 
 

@@ -11,7 +11,10 @@ reset :261-273, train :275-283).  What differs is how forward executes:
     has no StudentEngine plan (`engine_plan` is false): forward runs the frozen teacher under no_grad, then the student's
     modules, and hints are captured by forward hooks;
   * any other architecture (e.g. the CIFAR ResNet-20 plumbing config) falls back to the reference's own
-    mechanism -- module forward + hooks -- with the replaced blocks still HIP-backed.
+    mechanism -- module forward + hooks -- with the replaced blocks still HIP-backed;
+  * a CIFAR WideResNet is such a module graph too, in fp32 unless bf16 is asked for (the `dtype=torch.bfloat16` argument, or a
+    config that holds the key trainer.dtype = "bf16"): then `module_dtype` is bf16, forward / inference cast the batch to bf16
+    channels-last once for teacher and student, hints are bf16, logits fp32; parameters, gradients and checkpoints stay fp32.
 """
 import copy
 import gc
@@ -23,6 +26,7 @@ from torch import nn
 from ..deeplabv3 import DeepWV3Plus
 from ..gscnn import GSCNN
 from ..hrnet_ocr import HighResolutionNet
+from ..cifar_models.wrn import WideResNet
 from ...lazy import LazyLogits
 from .transform_blocks import DepthwiseSeparableBlock
 
@@ -64,6 +68,11 @@ class DepthwiseStudent(nn.Module):
                 raise TypeError("a HighResolutionNet student is fp32 only (bf16 is not implemented for this network)")
             dtype = torch.float32
         self.dtype = dtype
+        # The module-graph networks ignore self.dtype (its bf16 default is the engine's).  A WideResNet alone can be switched, and
+        # only by asking: the dtype argument, or the config key itself.
+        self._module_dtype = torch.float32
+        if isinstance(self.student, WideResNet) and (dtype if self._dtype_explicit else self._config_dtype(config)) == torch.bfloat16:
+            self._module_dtype = torch.bfloat16
         self._engine = None
         self._teacher_ready = None
         self._side_stream = None
@@ -184,6 +193,31 @@ class DepthwiseStudent(nn.Module):
         return reduce(step, block_name.split(BLOCKS_LEVEL_SPLIT_CHAR), model)
 
     # ------------------------------------------------------------------ execution
+    @staticmethod
+    def _config_dtype(config):
+        """bf16 / fp32 when the config holds the key trainer.dtype with such a value, else None."""
+        try:
+            trainer = config['trainer']
+            if 'dtype' not in trainer:
+                return None
+            name = str(trainer['dtype'])
+        except (KeyError, TypeError, AttributeError):
+            return None
+        return {'bf16': torch.bfloat16, 'bfloat16': torch.bfloat16, 'fp32': torch.float32, 'float32': torch.float32, 'f32': torch.float32}.get(name)
+
+    @property
+    def module_dtype(self):
+        """Activation dtype of a module-graph student and its teacher (read-only): fp32, or bf16 for a WideResNet that was asked to."""
+        return self._module_dtype
+
+    def _module_graph_batch(self, x):
+        """The batch as teacher and student read it: as it is in fp32; one bf16 channels-last cast shared by both otherwise."""
+        if self._module_dtype == torch.float32:
+            return x
+        if not x.is_cuda:
+            raise RuntimeError("a bf16 WideResNet student runs on the GPU only (no CPU fallback)")
+        return x.to(dtype=self._module_dtype, memory_format=torch.channels_last)
+
     @property
     def engine_plan(self):
         """The student executes through a StudentEngine plan (DeepWV3Plus / GSCNN)."""
@@ -288,6 +322,7 @@ class DepthwiseStudent(nn.Module):
         if not self.engine_plan:
             if self.fused:
                 self._check_module_graph_input(x)
+            x = self._module_graph_batch(x)
             with torch.no_grad():
                 teacher_pred = self.teacher(x)
             return self.student(x), teacher_pred
@@ -358,7 +393,7 @@ class DepthwiseStudent(nn.Module):
         if not self.engine_plan:
             if self.fused:
                 self._check_module_graph_input(x)
-            return self.student(x)
+            return self.student(self._module_graph_batch(x))
         from ...engine import run_student
         engine = self._student_engine()
         engine.hint_names = []

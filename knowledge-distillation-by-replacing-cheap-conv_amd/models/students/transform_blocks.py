@@ -74,6 +74,10 @@ class DepthwiseSeparableBlock(nn.Module):
 
     def forward(self, x):
         k, pad, dil = self.geometry
+        if x.dtype == torch.bfloat16 and (self.in_channels % 64 or self.out_channels % 64):
+            # (never the NCHW small-shape kernels, which are fp32: a bf16 network does not change dtype in the middle)
+            raise ValueError(f"DepthwiseSeparableBlock in bf16: {self.in_channels} -> {self.out_channels} channels, both must be multiples "
+                             f"of 64 (the K granule of the bf16 MFMA pointwise conv and of its input-gradient conv)")
         if x.is_cuda and _small_shape(x, self.pointwise_conv):
             from ...nn_hip import conv2d
             mid = conv2d(x, self.separable_conv.weight, self.separable_conv.bias, 1, pad, dil, self.in_channels)

@@ -130,13 +130,16 @@ class BatchNorm2d(nn.BatchNorm2d):
 
 # ------------------------------------------------------------------ channels-last modules (Wide-ResNet, DenseNet, HRNet-OCR)
 # NCHW-logical tensors with NHWC strides (torch.channels_last): the MFMA implicit-GEMM convolutions (kd_conv2d_fwd /
-# kd_conv2d_wgrad / kd_pw_wgrad, fp32) and BatchNorm on NHWC views (kd_bn_nhwc_*) read and write them without a layout copy.
+# kd_conv2d_wgrad / kd_pw_wgrad) and BatchNorm on NHWC views (kd_bn_nhwc_*) read and write them without a layout copy.  fp32
+# everywhere; Conv2dNHWC and BatchNorm2dNHWC also take bf16 activations (fp32 parameters and parameter gradients).
 _CIN_GRANULE = 32      # fp32 K granule of kd_conv2d_fwd: fewer input channels are zero-padded up to it (the 3->16 stem, 16->160)
+_GRANULE = {torch.float32: _CIN_GRANULE, torch.bfloat16: 64}   # ... per activation dtype: kd_conv2d_fwd takes Cin % 64 in bf16
 _PADDED = "_nhwc_pad"  # tensor attribute: its NHWC storage continues with zero channels up to this pixel stride
 
 
-def _granule_up(c):
-    return -(-c // _CIN_GRANULE) * _CIN_GRANULE
+def _granule_up(c, dtype=torch.float32):
+    g = _GRANULE[dtype]
+    return -(-c // g) * g
 
 
 def _copy_cast(src, dst):
@@ -157,7 +160,7 @@ def _nhwc(t):
     v = t.permute(0, 2, 3, 1)
     try:
         ops.nhwc_ld(v)
-        if v.data_ptr() % 16 == 0 and v.stride(2) % 4 == 0:
+        if v.data_ptr() % 16 == 0 and (v.stride(2) * v.element_size()) % 16 == 0:
             return v
     except ValueError:
         pass
@@ -168,18 +171,18 @@ def _nhwc(t):
 
 
 def _nhwc_padded(t, cpad):
-    """(N,C,H,W)-logical tensor -> (N,H,W,cpad) fp32 buffer, channels >= C zero (the conv's K granule)."""
+    """(N,C,H,W)-logical tensor -> (N,H,W,cpad) buffer of its dtype, channels >= C zero (the conv's K granule): a padding copy."""
     N, Cc, H, W = t.shape
     out = torch.zeros((N, H, W, cpad), dtype=t.dtype, device=t.device)
     _copy_cast(t, out[..., :Cc].permute(0, 3, 1, 2))
     return out
 
 
-def new_padded(shape, device):
-    """(N,H,W,C) fp32 view for a kernel to fill.  When C is no multiple of the conv granule the view is the channel prefix of a
+def new_padded(shape, device, dtype=torch.float32):
+    """(N,H,W,C) view for a kernel to fill.  When C is no multiple of the dtype's conv granule the view is the channel prefix of a
     buffer whose pixel stride is the granule above C, with a zero tail: tagged with mark_padded(), a conv reads it in place."""
     N, H, W, Cc = shape
-    buf = torch.empty((N, H, W, _granule_up(Cc)), dtype=torch.float32, device=device)
+    buf = torch.empty((N, H, W, _granule_up(Cc, dtype)), dtype=dtype, device=device)
     if buf.shape[3] != Cc:
         buf[..., Cc:].zero_()
     return buf[..., :Cc]
@@ -188,7 +191,7 @@ def new_padded(shape, device):
 def mark_padded(t):
     """Tag an NCHW-logical tensor whose storage came from new_padded() (and was written through its view only)."""
     v = t.permute(0, 2, 3, 1)
-    cpad = _granule_up(v.shape[3])
+    cpad = _granule_up(v.shape[3], t.dtype)
     if cpad != v.shape[3] and v.stride(3) == 1 and v.stride(2) == cpad:
         setattr(t, _PADDED, cpad)
     return t
@@ -209,7 +212,7 @@ class _ConvNHWCFn(torch.autograd.Function):
     def backward(ctx, gy):
         mod = ctx.mod
         (xh,) = ctx.saved_tensors
-        co, cop = mod.out_channels, mod.cout_pad
+        co, cop = mod.out_channels, mod._cout_pad(gy.dtype)
         g = _nhwc(gy) if co == cop else _nhwc_padded(gy, cop)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
@@ -222,7 +225,7 @@ class _ConvNHWCFn(torch.autograd.Function):
 
 
 class Conv2dNHWC(nn.Conv2d):
-    """nn.Conv2d (3x3 or 1x1, square stride / padding, no groups, optional bias) on channels-last fp32 device tensors:
+    """nn.Conv2d (3x3 or 1x1, square stride / padding, no groups, optional bias) on channels-last fp32 or bf16 device tensors:
     forward kd_conv2d_fwd; input gradient kd_conv2d_fwd on KD_PACK_DGRAD weights (zero-inserted first for stride 2);
     weight gradient kd_conv2d_wgrad / kd_pw_wgrad, computed only for a weight that requires grad; the bias is the forward
     epilogue's per-channel shift (scale 1, no ReLU), its gradient a channel sum taken only when it requires grad.  Packed
@@ -230,6 +233,12 @@ class Conv2dNHWC(nn.Conv2d):
     optimizer step.  Fewer than 32 input channels are zero-padded to 32 (weights packed with cin_pad, the input copied into a
     zeroed 32-channel buffer); an input whose storage is already zero-padded to that granule (tagged by its producer, see
     new_padded() / mark_padded()) is read in place instead.
+    bf16 activations (this class only, not Conv2dNHWCBias): the parameters stay fp32 and are packed to bf16 (the cache is keyed by
+    dtype as well as mode); outputs, the residual and the input gradient are bf16; bias and fold vectors stay fp32; the weight
+    gradient comes back in fp32.  The K granule is 64: an input channel count that is no multiple of it (16 -> 64, 160 -> 192) is
+    read from a zero-padded buffer as above, and in the backward the output gradient -- the K operand of the input-gradient conv
+    -- is padded likewise (a padding copy: gradients arrive untagged), with the weights packed to match.  The activated output
+    of the fused eval path is allocated by new_padded(), so the next conv reads it in place.
     forward(x, residual=None, out=None): residual (the block's shortcut) is added in the conv's epilogue; out, an (N,Ho,Wo,Cout)
     fp32 NHWC view (a channel slice of a wider buffer: a dense block's), receives the result instead of a fresh tensor.
     run_folded() puts an eval-mode BN (+ ReLU) into the epilogue as well.
@@ -253,6 +262,10 @@ class Conv2dNHWC(nn.Conv2d):
                 or self.dilation != (1, 1) or self.groups != 1:
             raise NotImplementedError(f"{type(self).__name__}: 1x1 / 3x3, square stride and padding, no dilation or groups")
 
+    def _check_dtype(self, x):
+        if x.dtype != torch.float32 and (x.dtype != torch.bfloat16 or self.pad_channels):
+            raise TypeError(f"{type(self).__name__} is fp32" + ("" if self.pad_channels else " or bf16"))
+
     @property
     def cin_pad(self):
         return _granule_up(self.in_channels)
@@ -261,6 +274,13 @@ class Conv2dNHWC(nn.Conv2d):
     def cout_pad(self):
         """Channels of the output gradient the backward works on (and rows of the weights packed for it)."""
         return _granule_up(self.out_channels) if self.pad_channels else self.out_channels
+
+    def _cin_pad(self, dtype):
+        return _granule_up(self.in_channels, dtype)
+
+    def _cout_pad(self, dtype):
+        """cout_pad for activations of `dtype`: in bf16 the output gradient is always padded to the K granule of its dgrad conv."""
+        return self.cout_pad if dtype == torch.float32 else _granule_up(self.out_channels, dtype)
 
     @property
     def cout_fwd(self):
@@ -283,10 +303,11 @@ class Conv2dNHWC(nn.Conv2d):
             hit = self._packs[what] = (key, make())
         return hit[1]
 
-    def _pack(self, mode):
+    def _pack(self, mode, dtype=torch.float32):
         w = self.weight
-        rows, cin_pad = (self.cout_fwd, self.cin_pad) if mode == KD_PACK_FWD else (self.cout_pad, None)
-        return self._cached(mode, w, lambda: ops.pack_conv_weight(self._padded_rows(w, rows), torch.float32, mode, cin_pad=cin_pad))
+        rows, cin_pad = (self.cout_fwd, self._cin_pad(dtype)) if mode == KD_PACK_FWD else (self._cout_pad(dtype), None)
+        what = mode if dtype == torch.float32 else (mode, dtype)
+        return self._cached(what, w, lambda: ops.pack_conv_weight(self._padded_rows(w, rows), dtype, mode, cin_pad=cin_pad))
 
     def _shift(self):
         """The bias as the epilogue's shift vector (cout_fwd long), or None."""
@@ -295,11 +316,12 @@ class Conv2dNHWC(nn.Conv2d):
 
     def _prepadded(self, x):
         """The (N,H,W,cin_pad) view of an input whose producer left zero channels behind it, or None."""
-        if self.in_channels != self.cin_pad and getattr(x, _PADDED, 0) == self.cin_pad:
+        cin_pad = self._cin_pad(x.dtype)
+        if self.in_channels != cin_pad and getattr(x, _PADDED, 0) == cin_pad:
             v = x.detach().permute(0, 2, 3, 1)
-            if v.stride(3) == 1 and v.stride(2) == self.cin_pad:
+            if v.stride(3) == 1 and v.stride(2) == cin_pad:
                 N, H, W, _ = v.shape
-                return v.as_strided((N, H, W, self.cin_pad), v.stride())
+                return v.as_strided((N, H, W, cin_pad), v.stride())
         return None
 
     def _input(self, x):
@@ -307,24 +329,26 @@ class Conv2dNHWC(nn.Conv2d):
         pre = self._prepadded(x)
         if pre is not None:
             return pre
-        if self.in_channels != self.cin_pad:
-            return _nhwc_padded(x.detach(), self.cin_pad)
+        if self.in_channels != self._cin_pad(x.dtype):
+            return _nhwc_padded(x.detach(), self._cin_pad(x.dtype))
         return _nhwc(x.detach())
 
     def _run(self, xh, res_pre=None, out_act=False, act_scale=None, act_shift=None, act_relu=False, want_raw=True, raw_into=None):
         """Forward on an (N,H,W,cin_pad) view: raw = conv(xh) + bias [+ res_pre] and, with out_act, act = relu?(act_scale * raw +
-        act_shift) -> raw [, act], (N,Ho,Wo,Cout) fp32 views (raw is raw_into when given, None without want_raw).  The bias
-        rides in the epilogue's shift, so a biased conv gives raw or act, not both."""
+        act_shift) -> raw [, act], (N,Ho,Wo,Cout) views of xh's dtype (raw is raw_into when given, None without want_raw).  The
+        bias rides in the epilogue's shift, so a biased conv gives raw or act, not both.  In bf16 act comes from new_padded()."""
         N, H, W, _ = xh.shape
         k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
         Ho, Wo = ops.conv_out_size(H, k, s, p, 1), ops.conv_out_size(W, k, s, p, 1)
         co, rows = self.out_channels, self.cout_fwd
+        dt = xh.dtype
         if self.pad_channels:
-            new = lambda: new_padded((N, Ho, Wo, rows), xh.device)
+            new = new_act = lambda: new_padded((N, Ho, Wo, rows), xh.device)
         else:
-            new = lambda: torch.empty((N, Ho, Wo, co), dtype=torch.float32, device=xh.device)
+            new = lambda: torch.empty((N, Ho, Wo, co), dtype=dt, device=xh.device)
+            new_act = new if dt == torch.float32 else (lambda: new_padded((N, Ho, Wo, co), xh.device, dt))
         raw = raw_into if raw_into is not None else (new() if want_raw else None)
-        act = new() if out_act else None
+        act = new_act() if out_act else None
         k_raw, k_act, b = raw, act, self._shift()
         if b is not None and out_act:
             if raw is not None:
@@ -335,7 +359,7 @@ class Conv2dNHWC(nn.Conv2d):
         if act_scale is not None and co != rows:
             act_scale, act_shift = self._padded_rows(act_scale), self._padded_rows(act_shift)
         vec = lambda v: None if v is None else v.contiguous()
-        ops.conv2d(xh, self._pack(KD_PACK_FWD), s, p, res_pre=res_pre, out_raw=k_raw, out_act=k_act, act_scale=vec(act_scale),
+        ops.conv2d(xh, self._pack(KD_PACK_FWD, dt), s, p, res_pre=res_pre, out_raw=k_raw, out_act=k_act, act_scale=vec(act_scale),
                    act_shift=vec(act_shift), act_relu=act_relu)
         view = lambda t: t if t is None or co == rows else t[..., :co]
         return (view(raw), view(act)) if out_act else view(raw)
@@ -344,21 +368,22 @@ class Conv2dNHWC(nn.Conv2d):
         """relu?(bn(conv(x) + bias)) for an eval-mode BatchNorm2dNHWC in ONE launch (no autograd: frozen layers only)."""
         self._check()
         s, b = bn.folded()
+        self._check_dtype(x)
         y = self._run(self._input(x), out_act=True, act_scale=s, act_shift=b, act_relu=relu, want_raw=False)[1].permute(0, 3, 1, 2)
-        return mark_padded(y) if self.pad_channels else y
+        return mark_padded(y) if self.pad_channels or x.dtype != torch.float32 else y
 
     def _dgrad(self, g, in_shape):
         N, Cin, H, W = in_shape
         k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
         if s != 1:
             g = ops.zero_insert(g, s, (H - k + 1 + 2 * p, W - k + 1 + 2 * p))
-        dx = torch.empty((N, H, W, Cin), dtype=torch.float32, device=g.device)
-        ops.conv2d(g, self._pack(KD_PACK_DGRAD), 1, k - 1 - p, 1, out_raw=dx)
+        dx = torch.empty((N, H, W, Cin), dtype=g.dtype, device=g.device)
+        ops.conv2d(g, self._pack(KD_PACK_DGRAD, g.dtype), 1, k - 1 - p, 1, out_raw=dx)
         return dx
 
     def _wgrad(self, xh, g):
         k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
-        dw = torch.empty((self.cout_pad, xh.shape[3], k, k), dtype=torch.float32, device=g.device)
+        dw = torch.empty((g.shape[3], xh.shape[3], k, k), dtype=torch.float32, device=g.device)
         if k == 1 and s == 1:
             ops.pw_wgrad(xh, g, dw)
         else:
@@ -377,8 +402,10 @@ class Conv2dNHWC(nn.Conv2d):
             y = super().forward(x)
             return y if residual is None else y + residual
         self._check()
-        if x.dtype != torch.float32:
-            raise TypeError(f"{name} is fp32")
+        self._check_dtype(x)
+        for t in (residual, out):
+            if t is not None and t.dtype != x.dtype:
+                raise ValueError(f"{name}: residual / out of {t.dtype} next to an input of {x.dtype}")
         y = _ConvNHWCFn.apply(x, self.weight, self.bias, residual, self, self._input(x), out)
         return mark_padded(y) if self.pad_channels else y
 
@@ -410,9 +437,10 @@ class _BatchNormNHWCFn(torch.autograd.Function):
         if stats is not None and training:
             mean, invstd, var = stats
             y = ops.bn_nhwc_apply(xh, gamma.contiguous(), beta.contiguous(), mean, invstd, var, running_mean, running_var, momentum, relu)
-        else:
+        else:       # bf16: y goes where the conv that reads it finds its zero channels (the caller tags it, see mark_padded)
+            out = None if x.dtype == torch.float32 else new_padded(tuple(xh.shape), xh.device, x.dtype)
             y, mean, invstd = ops.bn_nhwc_fwd(xh, gamma.contiguous(), beta.contiguous(), running_mean, running_var, training, momentum,
-                                              eps, relu)
+                                              eps, relu, out=out)
         ctx.save_for_backward(xh, y if relu else None, gamma, mean, invstd)
         ctx.flags = (training, relu)
         ctx.chain = chain
@@ -459,7 +487,10 @@ class GradChain:
 class BatchNorm2dNHWC(nn.BatchNorm2d):
     """nn.BatchNorm2d on channels-last fp32 device tensors (kd_bn_nhwc_fwd / kd_bn_nhwc_bwd): batch statistics in train mode,
     running statistics in eval mode, optional fused ReLU (forward(x, relu=True)).  folded() gives the eval-mode
-    (scale, shift) a conv epilogue applies instead, cached per version of the parameters and statistics."""
+    (scale, shift) a conv epilogue applies instead, cached per version of the parameters and statistics.
+    bf16 activations go to kd_bn_nhwc_lp_fwd / _bwd: y and dx are bf16, the parameters, statistics and parameter gradients fp32;
+    y is allocated by new_padded() and tagged, so a Conv2dNHWC reads its 64-channel K granule in place.  Precomputed statistics
+    (forward_with_stats: the DenseNet path) are fp32 only."""
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -471,8 +502,8 @@ class BatchNorm2dNHWC(nn.BatchNorm2d):
     def _check(self, x):
         if not (self.affine and self.track_running_stats) or self.momentum is None:
             raise NotImplementedError("BatchNorm2dNHWC: affine, running statistics, fixed momentum")
-        if x.dtype != torch.float32:
-            raise TypeError("BatchNorm2dNHWC is fp32")
+        if x.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError("BatchNorm2dNHWC is fp32 or bf16")
 
     def folded(self):
         ts = (self.weight, self.bias, self.running_mean, self.running_var)
@@ -485,8 +516,13 @@ class BatchNorm2dNHWC(nn.BatchNorm2d):
         self._check(x)
         if self.training:
             self.num_batches_tracked.add_(1)
-        return _BatchNormNHWCFn.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.training,
-                                      float(self.momentum), float(self.eps), bool(relu), shortcut, stats, chain)
+        if x.dtype != torch.float32 and stats is not None:
+            raise TypeError("BatchNorm2dNHWC: precomputed statistics are fp32 only")
+        out = _BatchNormNHWCFn.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.training,
+                                     float(self.momentum), float(self.eps), bool(relu), shortcut, stats, chain)
+        if x.dtype != torch.float32:
+            mark_padded(out[0] if shortcut else out)
+        return out
 
     def forward(self, x, relu=False, stats=None):
         """stats: (mean, invstd, var_unbiased) of x's channels when the caller has them (see forward_with_stats); device only."""

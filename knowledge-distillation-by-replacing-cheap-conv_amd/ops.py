@@ -946,36 +946,48 @@ def bn2d_bwd(dy, x, y, gamma, mean, invstd, training, relu=False, need_dx=True, 
     return dx, dg, db
 
 
-# ------------------------------------------------------------------------- BatchNorm2d on NHWC fp32 views (WRN path)
+# ------------------------------------------------------------------------- BatchNorm2d on NHWC fp32 / bf16 views (WRN path)
 def _f32vec(*vs):
     for v in vs:
         if v is not None and (not v.is_cuda or v.dtype != torch.float32 or not v.is_contiguous()):
             raise ValueError("bn_nhwc: parameters / statistics must be contiguous fp32 device vectors")
 
 
-def _bn_ws(M, Cc, device):
-    return _ws(_lib.lib().kd_bn_nhwc_workspace(M, Cc), device)
+def _bn_ws(M, Cc, device, lp=False):
+    L = _lib.lib()
+    return _ws((L.kd_bn_nhwc_lp_workspace if lp else L.kd_bn_nhwc_workspace)(M, Cc), device)
+
+
+def _bn_dtype(who, x, *others):
+    """fp32 or bf16, by x; every other activation operand must have x's dtype."""
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{who}: fp32 or bf16 only")
+    for t in others:
+        if t is not None and t.dtype != x.dtype:
+            raise ValueError(f"{who}: operands of mixed dtype ({t.dtype} next to {x.dtype})")
+    return x.dtype == torch.bfloat16
 
 
 def bn_nhwc_fwd(x, gamma, beta, running_mean, running_var, training, momentum, eps, relu=False, out=None):
-    """x (N,H,W,C) fp32 view -> (y, save_mean, save_invstd); y into `out` (an (N,H,W,C) view) when given.
-    Train mode updates the running statistics in place (either may be None)."""
+    """x (N,H,W,C) fp32 or bf16 view -> (y, save_mean, save_invstd); y (x's dtype) into `out` (an (N,H,W,C) view) when given.
+    Train mode updates the running statistics in place (either may be None).  The parameters and statistics are fp32 either way;
+    bf16 goes to kd_bn_nhwc_lp_fwd."""
     _need_cuda(x, out)
     _f32vec(gamma, beta, running_mean, running_var)
-    if x.dtype != torch.float32:
-        raise TypeError("bn_nhwc_fwd: fp32 only")
+    lp = _bn_dtype("bn_nhwc_fwd", x, out)
     N, H, W, Cc = x.shape
     if gamma.numel() != Cc or beta.numel() != Cc:
         raise ValueError(f"bn_nhwc_fwd: {Cc} channels, gamma / beta of {gamma.numel()} / {beta.numel()}")
-    y = torch.empty((N, H, W, Cc), dtype=torch.float32, device=x.device) if out is None else out
-    if tuple(y.shape) != (N, H, W, Cc) or y.dtype != torch.float32:
-        raise ValueError("bn_nhwc_fwd: out must be an fp32 view of the input's shape")
+    y = torch.empty((N, H, W, Cc), dtype=x.dtype, device=x.device) if out is None else out
+    if tuple(y.shape) != (N, H, W, Cc):
+        raise ValueError("bn_nhwc_fwd: out must be a view of the input's shape and dtype")
     mean, invstd = torch.empty(Cc, device=x.device), torch.empty(Cc, device=x.device)
     M = N * H * W
-    ws = _bn_ws(M, Cc, x.device) if training else None
-    check(_lib.lib().kd_bn_nhwc_fwd(_ptr(x), nhwc_ld(x), _ptr(y), nhwc_ld(y), M, Cc, _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd),
-                                    _ptr(running_mean), _ptr(running_var), C.c_float(momentum), C.c_float(eps), int(bool(training)),
-                                    int(bool(relu)), _ptr(ws), 0 if ws is None else ws.numel(), stream_ptr()), "kd_bn_nhwc_fwd")
+    ws = _bn_ws(M, Cc, x.device, lp) if training else None
+    fn, name = (_lib.lib().kd_bn_nhwc_lp_fwd, "kd_bn_nhwc_lp_fwd") if lp else (_lib.lib().kd_bn_nhwc_fwd, "kd_bn_nhwc_fwd")
+    check(fn(_ptr(x), nhwc_ld(x), _ptr(y), nhwc_ld(y), M, Cc, _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd),
+             _ptr(running_mean), _ptr(running_var), C.c_float(momentum), C.c_float(eps), int(bool(training)),
+             int(bool(relu)), _ptr(ws), 0 if ws is None else ws.numel(), stream_ptr()), name)
     if training:    # the kernel updated the running statistics through raw pointers: tell version-keyed caches (BN folds)
         for t in (running_mean, running_var):
             if t is not None:
@@ -989,35 +1001,39 @@ def bn_nhwc_bwd(gy, x, y, gamma, mean, invstd, training, relu=False, res=None, n
                 accumulate=False, out=None):
     """Returns dx (N,H,W,C) | None; dgamma / dbeta (contiguous fp32 (C,)) receive sum g' xhat / sum g' when given (+= with
     accumulate).  res: a gradient view added to dx.  y (the forward output) is read only with relu.
-    out: an (N,H,W,C) fp32 view (a channel prefix of a wider buffer) that receives dx instead of a fresh tensor.  `out` MAY
+    gy, x, y, res and out are all fp32 or all bf16 (kd_bn_nhwc_lp_bwd), dx in that dtype; the per-channel vectors are fp32.
+    out: an (N,H,W,C) view (a channel prefix of a wider buffer) that receives dx instead of a fresh tensor.  `out` MAY
     alias `res` exactly (same base pointer and strides: dx accumulates in place into the gradient it is added to): the dx
     kernel computes element (m, c) in one thread, which loads res[m][c] before it stores dx[m][c] and touches no other element
     of either, and the reductions that precede it read neither.  Any other overlap of `out` with an operand is refused."""
     _need_cuda(gy, x, y, res, out)
     _f32vec(gamma, mean, invstd, dgamma, dbeta)
+    lp = _bn_dtype("bn_nhwc_bwd", x, gy, y, res, out)
+    es = x.element_size()
     N, H, W, Cc = x.shape
     for t in (gy, y, res, out):
-        if t is not None and (tuple(t.shape) != (N, H, W, Cc) or t.dtype != torch.float32):
+        if t is not None and tuple(t.shape) != (N, H, W, Cc):
             raise ValueError("bn_nhwc_bwd: operand mismatch")
     M = N * H * W
     if out is not None:
         if not need_dx:
             raise ValueError("bn_nhwc_bwd: out given with need_dx=False")
-        lo, hi = out.data_ptr(), out.data_ptr() + 4 * ((M - 1) * nhwc_ld(out) + Cc)
+        lo, hi = out.data_ptr(), out.data_ptr() + es * ((M - 1) * nhwc_ld(out) + Cc)
         for t in (gy, x, y if relu else None, res):
             if t is None or (t is res and t.data_ptr() == lo and t.stride() == out.stride()):
                 continue
-            if t.data_ptr() < hi and lo < t.data_ptr() + 4 * ((M - 1) * nhwc_ld(t) + Cc):
+            if t.data_ptr() < hi and lo < t.data_ptr() + es * ((M - 1) * nhwc_ld(t) + Cc):
                 raise ValueError("bn_nhwc_bwd: out overlaps an operand (only an exact alias of res is allowed)")
         dx = out
     else:
-        dx = torch.empty((N, H, W, Cc), dtype=torch.float32, device=x.device) if need_dx else None
-    ws = _bn_ws(M, Cc, x.device) if ((need_dx and training) or dgamma is not None or dbeta is not None) else None
+        dx = torch.empty((N, H, W, Cc), dtype=x.dtype, device=x.device) if need_dx else None
+    ws = _bn_ws(M, Cc, x.device, lp) if ((need_dx and training) or dgamma is not None or dbeta is not None) else None
     ld = lambda t: nhwc_ld(t) if t is not None else 0
-    check(_lib.lib().kd_bn_nhwc_bwd(_ptr(gy), ld(gy), _ptr(x), ld(x), _ptr(y if relu else None), ld(y) if relu else 0, _ptr(res), ld(res),
-                                    _ptr(dx), ld(dx), M, Cc, _ptr(gamma), _ptr(mean), _ptr(invstd), _ptr(dgamma), _ptr(dbeta),
-                                    int(bool(accumulate)), int(bool(training)), int(bool(relu)), _ptr(ws),
-                                    0 if ws is None else ws.numel(), stream_ptr()), "kd_bn_nhwc_bwd")
+    fn, name = (_lib.lib().kd_bn_nhwc_lp_bwd, "kd_bn_nhwc_lp_bwd") if lp else (_lib.lib().kd_bn_nhwc_bwd, "kd_bn_nhwc_bwd")
+    check(fn(_ptr(gy), ld(gy), _ptr(x), ld(x), _ptr(y if relu else None), ld(y) if relu else 0, _ptr(res), ld(res),
+             _ptr(dx), ld(dx), M, Cc, _ptr(gamma), _ptr(mean), _ptr(invstd), _ptr(dgamma), _ptr(dbeta),
+             int(bool(accumulate)), int(bool(training)), int(bool(relu)), _ptr(ws),
+             0 if ws is None else ws.numel(), stream_ptr()), name)
     if out is not None:
         torch.autograd.graph.increment_version(out)
     return dx
