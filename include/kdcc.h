@@ -819,6 +819,25 @@ int kd_ocr_attend_bwd(const float *g, int32_t ldg, const float *query, int32_t l
                       int32_t lddq, float *d_key, float *d_value, int32_t N, int64_t HW, int32_t K, int32_t Ck, float scale, void *workspace,
                       size_t workspace_bytes, kd_stream_t stream);
 
+/* ------------------------------------------------- CIFAR batches from a device-resident dataset
+ * Replaces, per batch, the torchvision transform chain and the collate + H2D copy of the reference's Cifar10Dataloader /
+ * Cifar100Dataloader (data_loader/data_loaders.py:13-53: RandomCrop(32, padding=4), RandomHorizontalFlip, ToTensor, Normalize,
+ * one PIL image at a time with num_workers 0) by one launch.
+ *   data    (n,32,32,3) uint8, pixel-interleaved; labels (n) int64: the whole dataset, resident;
+ *   params  (B,4) int32 rows [index, dy, dx, flip], dy, dx in [0, 8] (4, 4, 0: the untransformed image);
+ *   table   (3,256) elements of `dtype`: table[c][v] = ((v / 255) - mean[c]) / std[c], built by the caller;
+ *   out     KD_CIFAR_NCHW: dense (B,3,32,32), `ld` ignored.  KD_CIFAR_NHWC: (B,32,32,ld) pixels, ld >= 3; the kernel writes the
+ *           whole stride of every pixel, zeros in channels [3, ld), so `out` may come uninitialised;
+ *   labels_out (B) int64 = labels[index].
+ * out(b,c,y,x) = table[c][data[index_b][y + dy_b - 4][x' + dx_b - 4][c]], x' = flip_b ? 31 - x : x, and table[c][0] where that
+ * pixel lies outside the image (the reference pads with 0 before ToTensor / Normalize).  No arithmetic on values: bit-identical
+ * to the same composition on the host.  A row whose index, dy or dx is out of range reads nothing outside the dataset: its image
+ * is all padding and its label that of the clamped index.  16-byte stores when `out` is 16-byte aligned, scalar stores otherwise;
+ * B * 1024 * max(ld, 3) <= 2^31 (KD_ERR_UNSUPPORTED beyond). */
+enum { KD_CIFAR_NCHW = 0, KD_CIFAR_NHWC = 1 };
+int kd_cifar_batch(const uint8_t *data, const int64_t *labels, int64_t n, const int32_t *params, int32_t B, const void *table,
+                   int32_t dtype, int32_t layout, void *out, int32_t ld, int64_t *labels_out, kd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,5 +8,5 @@ __version__ = "0.1.0"
 
 from . import _lib  # noqa: F401
 
-from . import losses, models, trainer, utils  # noqa: E402,F401
+from . import data_loader, losses, models, trainer, utils  # noqa: E402,F401
 from .parse_config import ConfigParser  # noqa: E402,F401

@@ -27,6 +27,7 @@ from ..deeplabv3 import DeepWV3Plus
 from ..gscnn import GSCNN
 from ..hrnet_ocr import HighResolutionNet
 from ..cifar_models.wrn import WideResNet
+from ... import nn_hip
 from ...lazy import LazyLogits
 from .transform_blocks import DepthwiseSeparableBlock
 
@@ -211,11 +212,15 @@ class DepthwiseStudent(nn.Module):
         return self._module_dtype
 
     def _module_graph_batch(self, x):
-        """The batch as teacher and student read it: as it is in fp32; one bf16 channels-last cast shared by both otherwise."""
+        """The batch as teacher and student read it: as it is in fp32; one bf16 channels-last cast shared by both otherwise.  A batch
+        that already is bf16 and channels-last, or a zero-padded NHWC view tagged by nn_hip.mark_padded (a device loader's "padded"
+        layout: the cast would copy it and drop the tag), is returned as it is."""
         if self._module_dtype == torch.float32:
             return x
         if not x.is_cuda:
             raise RuntimeError("a bf16 WideResNet student runs on the GPU only (no CPU fallback)")
+        if x.dtype == self._module_dtype and (getattr(x, nn_hip._PADDED, 0) or x.is_contiguous(memory_format=torch.channels_last)):
+            return x
         return x.to(dtype=self._module_dtype, memory_format=torch.channels_last)
 
     @property

@@ -437,8 +437,8 @@ class _BatchNormNHWCFn(torch.autograd.Function):
         if stats is not None and training:
             mean, invstd, var = stats
             y = ops.bn_nhwc_apply(xh, gamma.contiguous(), beta.contiguous(), mean, invstd, var, running_mean, running_var, momentum, relu)
-        else:       # bf16: y goes where the conv that reads it finds its zero channels (the caller tags it, see mark_padded)
-            out = None if x.dtype == torch.float32 else new_padded(tuple(xh.shape), xh.device, x.dtype)
+        else:       # y goes where the conv that reads it finds its zero channels (the caller tags it, see mark_padded)
+            out = new_padded(tuple(xh.shape), xh.device, x.dtype)
             y, mean, invstd = ops.bn_nhwc_fwd(xh, gamma.contiguous(), beta.contiguous(), running_mean, running_var, training, momentum,
                                               eps, relu, out=out)
         ctx.save_for_backward(xh, y if relu else None, gamma, mean, invstd)
@@ -488,8 +488,9 @@ class BatchNorm2dNHWC(nn.BatchNorm2d):
     """nn.BatchNorm2d on channels-last fp32 device tensors (kd_bn_nhwc_fwd / kd_bn_nhwc_bwd): batch statistics in train mode,
     running statistics in eval mode, optional fused ReLU (forward(x, relu=True)).  folded() gives the eval-mode
     (scale, shift) a conv epilogue applies instead, cached per version of the parameters and statistics.
-    bf16 activations go to kd_bn_nhwc_lp_fwd / _bwd: y and dx are bf16, the parameters, statistics and parameter gradients fp32;
-    y is allocated by new_padded() and tagged, so a Conv2dNHWC reads its 64-channel K granule in place.  Precomputed statistics
+    bf16 activations go to kd_bn_nhwc_lp_fwd / _bwd: y and dx are bf16, the parameters, statistics and parameter gradients fp32.
+    In either dtype y is allocated by new_padded() and tagged, so a Conv2dNHWC reads its K granule (32 channels in fp32, 64 in bf16)
+    in place: the Wide-ResNet's 16-channel stem activation needs no padding copy.  Precomputed statistics
     (forward_with_stats: the DenseNet path) are fp32 only."""
 
     def __init__(self, *args, **kwargs):
@@ -520,8 +521,7 @@ class BatchNorm2dNHWC(nn.BatchNorm2d):
             raise TypeError("BatchNorm2dNHWC: precomputed statistics are fp32 only")
         out = _BatchNormNHWCFn.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.training,
                                      float(self.momentum), float(self.eps), bool(relu), shortcut, stats, chain)
-        if x.dtype != torch.float32:
-            mark_padded(out[0] if shortcut else out)
+        mark_padded(out[0] if shortcut else out)
         return out
 
     def forward(self, x, relu=False, stats=None):

@@ -1985,3 +1985,53 @@ def ocr_attend_bwd(g, query, key, value, scale=None):
                                        _ptr(dq), Ck, _ptr(dk), _ptr(dv), N, HW, K, Ck, C.c_float(scale), _ptr(ws), need, stream_ptr()),
           "kd_ocr_attend_bwd")
     return dq, dk, dv
+
+
+# ------------------------------------------------------------------------- CIFAR batches (data_loader)
+def check_cifar_params(params, n):
+    """ValueError unless `params` is an int32 (B,4) table of rows [index, dy, dx, flip] with index in [0, n), dy, dx in [0, 8] and
+    flip in {0, 1}.  Reads the values: a device table is copied to the host first (a synchronisation)."""
+    if params.dim() != 2 or params.shape[1] != 4 or params.shape[0] < 1 or params.dtype != torch.int32:
+        raise ValueError(f"cifar_batch: params must be an int32 (B,4) table, got {params.dtype} {tuple(params.shape)}")
+    p = params.detach().cpu()
+    lo, hi = p.amin(0).tolist(), p.amax(0).tolist()
+    for col, (name, top) in enumerate((("index", n - 1), ("dy", 8), ("dx", 8), ("flip", 1))):
+        if lo[col] < 0 or hi[col] > top:
+            raise ValueError(f"cifar_batch: {name} spans [{lo[col]}, {hi[col]}], allowed [0, {top}]")
+
+
+def cifar_batch(data, labels, params, table, out, labels_out=None, validated=False):
+    """One batch of the CIFAR loaders in one launch (kd_cifar_batch): crop, flip, ToTensor and Normalize as a gather.
+    data (n,32,32,3) uint8 and labels (n,) int64: the resident dataset; params int32 (B,4) rows [index, dy, dx, flip]; table (3,256)
+    of out's dtype (fp32 / bf16).  out is (B,3,32,32)-logical: a dense NCHW tensor, or NHWC storage with any pixel stride ld >= 3
+    (channels_last, or the channel prefix of a wider (B,32,32,ld) buffer) -- then the kernel writes the WHOLE stride of every pixel,
+    zeros in channels [3, ld), so the buffer may come from torch.empty.  -> (out, labels_out).
+    params is checked on the host (check_cifar_params; for a device table that is a copy and a synchronisation) unless the caller
+    has done so already and says validated=True, as the loaders do once per epoch."""
+    _need_cuda(data, labels, params, table, out, labels_out)
+    n = data.shape[0]
+    if data.dtype != torch.uint8 or data.dim() != 4 or tuple(data.shape[1:]) != (32, 32, 3) or n < 1 or not data.is_contiguous():
+        raise ValueError(f"cifar_batch: data must be a contiguous uint8 (n,32,32,3) tensor, got {data.dtype} {tuple(data.shape)}")
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (n,) or not labels.is_contiguous():
+        raise ValueError(f"cifar_batch: labels must be a contiguous int64 ({n},) tensor")
+    if not validated:
+        check_cifar_params(params, n)
+    B = params.shape[0]
+    if params.dtype != torch.int32 or tuple(params.shape) != (B, 4) or not params.is_contiguous():
+        raise ValueError("cifar_batch: params must be a contiguous int32 (B,4) table")
+    dt = dt_of(out)
+    if table.dtype != out.dtype or tuple(table.shape) != (3, 256) or not table.is_contiguous():
+        raise ValueError(f"cifar_batch: table must be a contiguous (3,256) tensor of out's dtype {out.dtype}")
+    if tuple(out.shape) != (B, 3, 32, 32):
+        raise ValueError(f"cifar_batch: out must be ({B},3,32,32)-logical, got {tuple(out.shape)}")
+    if out.is_contiguous():
+        layout, ld = _lib.KD_CIFAR_NCHW, 3
+    else:
+        layout, ld = _lib.KD_CIFAR_NHWC, nhwc_ld(out.permute(0, 2, 3, 1))
+    if labels_out is None:
+        labels_out = torch.empty((B,), dtype=torch.int64, device=out.device)
+    elif labels_out.dtype != torch.int64 or tuple(labels_out.shape) != (B,) or not labels_out.is_contiguous():
+        raise ValueError(f"cifar_batch: labels_out must be a contiguous int64 ({B},) tensor")
+    check(_lib.lib().kd_cifar_batch(_ptr(data), _ptr(labels), n, _ptr(params), B, _ptr(table), dt, layout, _ptr(out), ld, _ptr(labels_out),
+                                    stream_ptr()), "kd_cifar_batch")
+    return out, labels_out
