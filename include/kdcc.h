@@ -427,7 +427,7 @@ int kd_bn_nhwc_bwd(const float *gy, int32_t ldg, const float *x, int32_t ldx, co
                    const float *save_invstd, float *dgamma, float *dbeta, int32_t accumulate, int32_t training, int32_t relu,
                    void *workspace, size_t workspace_bytes, kd_stream_t stream);
 
-/* ------------------------------------------------- BatchNorm2d on NHWC bf16 views (Wide-ResNet CIFAR path in bf16, csrc/bn_nhwc_lp.hip)
+/* ------------------------------------------------- BatchNorm2d on NHWC bf16 views (Wide-ResNet CIFAR path in bf16, csrc/bn_nhwc.hip)
  * kd_bn_nhwc_fwd / kd_bn_nhwc_bwd with x, y, gy, res and dx in bf16 storage (leading dimensions in elements); every per-channel
  * vector -- gamma, beta, the saved and running statistics, dgamma, dbeta -- stays fp32.  The semantics are the fp32 entry points',
  * flag for flag: train / eval, relu, res added to dx, dx == NULL (parameter gradients only), accumulate, the running statistics
@@ -436,7 +436,8 @@ int kd_bn_nhwc_bwd(const float *gy, int32_t ldg, const float *x, int32_t ldx, co
  *   block's first value, merged in fp64 with Chan's update in a fixed order, no atomics: bit-reproducible); y and dx are rounded to
  *   nearest-even once, at the store; the backward's ReLU mask is y > 0 on the stored bf16 y.
  * Vector path (8 channels = 16 B per lane) when C % 8 == 0, every base is 16-B aligned and every ld * 2 % 16 == 0; otherwise
- *   scalar (csrc/bn_lp_select.h decides).  Any M >= 1 and C >= 1.
+ *   scalar (csrc/bn_select.h decides, for both storages; the kernels are the fp32 entry points', csrc/bn_nhwc_core.h, instantiated
+ *   for bf16).  Any M >= 1 and C >= 1.
  * workspace: kd_bn_nhwc_lp_workspace(M, C) bytes (train-mode forward; backward whenever a reduction is needed). */
 size_t kd_bn_nhwc_lp_workspace(int64_t M, int32_t C);
 int kd_bn_nhwc_lp_fwd(const void *x, int32_t ldx, void *y, int32_t ldy, int64_t M, int32_t C, const float *gamma, const float *beta,

@@ -4,10 +4,11 @@
 //   kd_bn_nhwc_stats / kd_bn_nhwc_apply: train-mode BatchNorm split in two.  The batch mean / variance of a channel of the block
 //     buffer is the same for every later layer's norm1 (only gamma, beta and the running buffers differ), so the statistics are
 //     reduced ONCE, when the 32-channel slice is produced, and each norm1 is then a single elementwise pass over its prefix.
-//     The reduction and the normalise pass are the kernels of kd_bn_nhwc_fwd (bn_nhwc_core.h): per channel the same bits.
+//     The reduction and the normalise pass are kd_bn_nhwc_fwd's (bn_nhwc_core.h's bn_stats / bn_apply for float, chosen by
+//     bn_select.h): per channel the same bits.
 //   kd_avgpool2x2_nhwc / _bwd: the transition's AvgPool2d(2, 2) on NHWC views, floor output size (an odd last row / column is
-//     dropped and gets zero gradient).  One thread per output (backward: input) pixel x 4 channels (float4) when C % 4 == 0 and
-//     the views allow it, else per channel; consecutive threads take consecutive channels, so a wave reads whole 256-B /
+//     dropped and gets zero gradient).  One thread per output (backward: input) pixel x 4 channels (float4) when bn_select.h's
+//     bn_vec_ok(4, ...) allows it, else per channel; consecutive threads take consecutive channels, so a wave reads whole 256-B /
 //     1-KiB runs of a pixel.
 #include "bn_nhwc_core.h"
 
@@ -27,24 +28,6 @@ struct PoolGeom {
     int N, H, W, C, Ho, Wo;
 };
 
-template <int V>
-__device__ __forceinline__ void ld_vec(const float *p, float (&v)[V])
-{
-    if constexpr (V == 4) {
-        const float4 a = *(const float4 *)p;
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-    } else {
-        v[0] = p[0];
-    }
-}
-
-template <int V>
-__device__ __forceinline__ void st_vec(float *p, const float (&v)[V])
-{
-    if constexpr (V == 4) *(float4 *)p = make_float4(v[0], v[1], v[2], v[3]);
-    else p[0] = v[0];
-}
-
 // y[n][ho][wo][c] = ((x[2ho][2wo] + x[2ho][2wo+1]) + (x[2ho+1][2wo] + x[2ho+1][2wo+1])) / 4
 template <int V>
 __global__ __launch_bounds__(TPB) void avgpool2x2_kernel(PoolGeom g, const float *__restrict__ x, int ldx, float *__restrict__ y, int ldy)
@@ -60,13 +43,13 @@ __global__ __launch_bounds__(TPB) void avgpool2x2_kernel(PoolGeom g, const float
         const long long n = t / g.Ho;
         const long long pi = (n * g.H + 2 * ho) * g.W + 2 * wo;    // input pixel (2ho, 2wo); 2ho + 1 < H and 2wo + 1 < W
         float a[V], b[V], c[V], d[V], o[V];
-        ld_vec<V>(x + pi * ldx + c0, a);
-        ld_vec<V>(x + (pi + 1) * ldx + c0, b);
-        ld_vec<V>(x + (pi + g.W) * ldx + c0, c);
-        ld_vec<V>(x + (pi + g.W + 1) * ldx + c0, d);
+        ldv<V>(x + pi * ldx + c0, a);
+        ldv<V>(x + (pi + 1) * ldx + c0, b);
+        ldv<V>(x + (pi + g.W) * ldx + c0, c);
+        ldv<V>(x + (pi + g.W + 1) * ldx + c0, d);
 #pragma unroll
         for (int j = 0; j < V; ++j) o[j] = ((a[j] + b[j]) + (c[j] + d[j])) * 0.25f;
-        st_vec<V>(y + po * ldy + c0, o);
+        stv<V>(y + po * ldy + c0, o);
     }
 }
 
@@ -88,11 +71,11 @@ __global__ __launch_bounds__(TPB) void avgpool2x2_bwd_kernel(PoolGeom g, const f
         for (int j = 0; j < V; ++j) o[j] = 0.f;
         if (h < 2 * g.Ho && w < 2 * g.Wo) {
             float v[V];
-            ld_vec<V>(gy + ((n * g.Ho + (h >> 1)) * g.Wo + (w >> 1)) * ldg + c0, v);
+            ldv<V>(gy + ((n * g.Ho + (h >> 1)) * g.Wo + (w >> 1)) * ldg + c0, v);
 #pragma unroll
             for (int j = 0; j < V; ++j) o[j] = v[j] * 0.25f;
         }
-        st_vec<V>(gx + pi * ldgx + c0, o);
+        stv<V>(gx + pi * ldgx + c0, o);
     }
 }
 
@@ -113,10 +96,8 @@ extern "C" int kd_bn_nhwc_stats(const float *x, int32_t ldx, int64_t M, int32_t 
     if (int rc = geom(M, C, g, "kd_bn_nhwc_stats")) return rc;
     KD_REQUIRE(x && mean && invstd && var_unbiased, KD_ERR_INVALID, "kd_bn_nhwc_stats: null argument");
     KD_REQUIRE(ldx >= C, KD_ERR_INVALID, "kd_bn_nhwc_stats: pixel stride below C");
-    KD_REQUIRE(workspace && workspace_bytes >= bn_workspace_bytes(M, C), KD_ERR_WORKSPACE, "kd_bn_nhwc_stats: workspace too small");
-    launch_batch_stats(g, x, ldx, (float *)workspace, mean, invstd, nullptr, nullptr, var_unbiased, 0.f, eps, (hipStream_t)stream);
-    KD_CHECK_LAUNCH("kd_bn_nhwc_stats");
-    return KD_OK;
+    return bn_stats<float>("kd_bn_nhwc_stats", bn_select_fwd(4, x, ldx, nullptr, 0, M, C), g, x, ldx, mean, invstd, nullptr, nullptr, var_unbiased, 0.f,
+                           eps, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int kd_bn_nhwc_apply(const float *x, int32_t ldx, float *y, int32_t ldy, int64_t M, int32_t C, const float *gamma,
@@ -134,9 +115,9 @@ extern "C" int kd_bn_nhwc_apply(const float *x, int32_t ldx, float *y, int32_t l
                            running_var, momentum);
         KD_CHECK_LAUNCH("kd_bn_nhwc_apply(running)");
     }
-    launch_apply(g, x, ldx, y, ldy, gamma, beta, mean, invstd, (int)relu, s);
-    KD_CHECK_LAUNCH("kd_bn_nhwc_apply");
-    return KD_OK;
+    const BnSel sel = bn_select_fwd(4, x, ldx, y, ldy, M, C);
+    KD_NOTE_PLUMBING(bn_kernel_name(sel.kernel));
+    return bn_apply<float>("kd_bn_nhwc_apply", sel, g, x, ldx, y, ldy, gamma, beta, mean, invstd, relu, s);
 }
 
 extern "C" int kd_avgpool2x2_nhwc(const float *x, int32_t ldx, float *y, int32_t ldy, int32_t N, int32_t H, int32_t W, int32_t C,
@@ -148,12 +129,12 @@ extern "C" int kd_avgpool2x2_nhwc(const float *x, int32_t ldx, float *y, int32_t
     KD_REQUIRE(ldx >= C && ldy >= C, KD_ERR_INVALID, "kd_avgpool2x2_nhwc: pixel stride below C");
     hipStream_t s = (hipStream_t)stream;
     const long long outs = (long long)N * g.Ho * g.Wo;
-    if (vec4_ok(C, {{x, ldx}, {y, ldy}})) {
+    if (bn_vec_ok(4, C, x, ldx, y, ldy)) {
         KD_NOTE_PLUMBING("avgpool2x2_kernel<4>");
-        hipLaunchKernelGGL(avgpool2x2_kernel<4>, dim3(grid_for(outs * (C / 4))), dim3(TPB), 0, s, g, x, ldx, y, ldy);
+        hipLaunchKernelGGL(avgpool2x2_kernel<4>, dim3(bn_grid(outs * (C / 4))), dim3(TPB), 0, s, g, x, ldx, y, ldy);
     } else {
         KD_NOTE_PLUMBING("avgpool2x2_kernel<1>");
-        hipLaunchKernelGGL(avgpool2x2_kernel<1>, dim3(grid_for(outs * C)), dim3(TPB), 0, s, g, x, ldx, y, ldy);
+        hipLaunchKernelGGL(avgpool2x2_kernel<1>, dim3(bn_grid(outs * C)), dim3(TPB), 0, s, g, x, ldx, y, ldy);
     }
     KD_CHECK_LAUNCH("kd_avgpool2x2_nhwc");
     return KD_OK;
@@ -168,12 +149,12 @@ extern "C" int kd_avgpool2x2_nhwc_bwd(const float *gy, int32_t ldg, float *gx, i
     KD_REQUIRE(ldg >= C && ldgx >= C, KD_ERR_INVALID, "kd_avgpool2x2_nhwc_bwd: pixel stride below C");
     hipStream_t s = (hipStream_t)stream;
     const long long ins = (long long)N * H * W;
-    if (vec4_ok(C, {{gy, ldg}, {gx, ldgx}})) {
+    if (bn_vec_ok(4, C, gy, ldg, gx, ldgx)) {
         KD_NOTE_PLUMBING("avgpool2x2_bwd_kernel<4>");
-        hipLaunchKernelGGL(avgpool2x2_bwd_kernel<4>, dim3(grid_for(ins * (C / 4))), dim3(TPB), 0, s, g, gy, ldg, gx, ldgx);
+        hipLaunchKernelGGL(avgpool2x2_bwd_kernel<4>, dim3(bn_grid(ins * (C / 4))), dim3(TPB), 0, s, g, gy, ldg, gx, ldgx);
     } else {
         KD_NOTE_PLUMBING("avgpool2x2_bwd_kernel<1>");
-        hipLaunchKernelGGL(avgpool2x2_bwd_kernel<1>, dim3(grid_for(ins * C)), dim3(TPB), 0, s, g, gy, ldg, gx, ldgx);
+        hipLaunchKernelGGL(avgpool2x2_bwd_kernel<1>, dim3(bn_grid(ins * C)), dim3(TPB), 0, s, g, gy, ldg, gx, ldgx);
     }
     KD_CHECK_LAUNCH("kd_avgpool2x2_nhwc_bwd");
     return KD_OK;

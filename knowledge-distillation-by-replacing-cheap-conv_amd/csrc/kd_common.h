@@ -17,14 +17,16 @@ void kd_set_error(const char *fmt, ...);
         }                                \
     } while (0)
 
-#define KD_CHECK_LAUNCH(name)                                                     \
-    do {                                                                          \
-        hipError_t e__ = hipGetLastError();                                       \
-        if (e__ != hipSuccess) {                                                  \
-            kd_set_error("%s: launch failed: %s", (name), hipGetErrorString(e__)); \
-            return KD_ERR_HIP;                                                    \
-        }                                                                         \
+// The launch's name as a format with its arguments, for launchers shared by several entry points: KD_CHECK_LAUNCHF("%s(apply)", who).
+#define KD_CHECK_LAUNCHF(fmt, ...)                                                              \
+    do {                                                                                        \
+        hipError_t e__ = hipGetLastError();                                                     \
+        if (e__ != hipSuccess) {                                                                \
+            kd_set_error(fmt ": launch failed: %s", __VA_ARGS__, hipGetErrorString(e__));       \
+            return KD_ERR_HIP;                                                                  \
+        }                                                                                       \
     } while (0)
+#define KD_CHECK_LAUNCH(name) KD_CHECK_LAUNCHF("%s", (name))
 
 // ---- result-altering diagnostics (skip-the-epilogue timing ablations, dropped kernel phases, in-kernel timestamps) ----
 // exist only in a tuning build (`make TUNING=1` -> libkdcc_hip_tuning.so, loaded with KDCC_LIB=tuning by tools/): the default
@@ -54,8 +56,9 @@ void kd_note_kernel(const char *name);
 // plumb_select.h's table (plumb_kernel_name of the kernel the entry point's selector picked, noted once per call);
 // tests/test_plumbing_host.py requires a test case for every one of them.  The launchers of losses.hip use the same slot with the
 // names of loss_select.h's table (loss_kernel_name); tests/test_loss_dispatch_host.py holds them to the same rule.  So do the
-// fp32 NHWC BatchNorm and average-pool entry points (bn_nhwc_core.h's launch_apply, bn_nhwc.hip, dense_ops.hip) for their
-// float4 / scalar choice, with literals of their own that tests/test_nhwc_support_host.py holds to a row each.
+// NHWC BatchNorm entry points (bn_nhwc_core.h, dense_ops.hip) with the names of bn_select.h's table (bn_kernel_name), and the
+// average-pool entry points of dense_ops.hip for their float4 / scalar choice, with literals of their own;
+// tests/test_nhwc_support_host.py holds the fp32 names and the pool literals to a row each.
 void kd_note_plumbing(const char *name);
 #define KD_NOTE_PLUMBING(name) kd_note_plumbing(name)
 

@@ -1,8 +1,8 @@
 """Case tables of tests/test_nhwc_support_gpu.py: one row per dispatch branch and loop trip of the fp32 NHWC kernels behind the
-classification models and the HRNet-OCR head (csrc/hrnet_ops.hip, bn_nhwc.hip with bn_nhwc_core.h, dense_ops.hip), the seeded
+classification models and the HRNet-OCR head (csrc/hrnet_ops.hip, bn_nhwc.hip with bn_nhwc_core.h and bn_select.h, dense_ops.hip), the seeded
 inputs of each row, its float64 reference written out in plain numpy, and a per-element absolute bound for every output.
 
-A row holds `op`, `id`, `kernel` (the KD_NOTE_PLUMBING literal it must reach, None where the entry point makes no choice), the
+A row holds `op`, `id`, `kernel` (the name the launcher must note, None where the entry point makes no choice), the
 shape, `views` (operand -> (float offset, ld) inside a wider buffer), flags, and `plan`: the trip counts it claims, which
 tests/test_nhwc_support_host.py holds to the launch plans restated below.  Nothing here touches the device or the library.
 
@@ -68,17 +68,18 @@ def ocr_pixels_per_block(HW):
 
 
 def grid_for(total):
-    """bn_nhwc_core.h grid_for: `b = ceil(total / TPB)`, `b < 1 ? 1 : (b > 8192 ? 8192 : b)`."""
+    """bn_select.h bn_grid: `b = ceil(total / BN_TPB)`, `b < 1 ? 1 : (b > BN_CAP ? BN_CAP : b)`, BN_CAP = 8192."""
     return min(max((total + TPB - 1) // TPB, 1), 8192)
 
 
 def nrb(M):
-    """bn_nhwc_core.h geom: `g.nrb = (M + ROWS - 1) / ROWS`."""
+    """bn_select.h bn_row_blocks: `(M + BN_ROWS - 1) / BN_ROWS`."""
     return (M + ROWS - 1) // ROWS
 
 
 def vec4_ok(C, views):
-    """bn_nhwc_core.h vec4_ok: `if (C % 4) return false`, then for every non-null view `ld % 4 || !kd_aligned16(ptr)` refuses.
+    """bn_select.h with es = 4: `C % (16 / es)` refuses (bn_channels_ok), then every non-null view whose `ld * es % 16` or whose base
+    is not 16-byte aligned does (bn_view_ok).
     views: (float offset inside an allocation that is itself 16-byte aligned, ld) or None."""
     return C % 4 == 0 and all(v is None or (v[1] % 4 == 0 and v[0] % 4 == 0) for v in views)
 
@@ -100,7 +101,7 @@ def ocr_attend_workspace(N, HW, K, Ck):
 
 
 def bn_workspace(M, C):
-    """bn_workspace_bytes: `(nrb * 3 * C + 2 * C) * sizeof(float)`."""
+    """bn_select.h bn_workspace: `(nrb * 3 * C + 2 * C) * sizeof(float)`."""
     return (nrb(M) * 3 * C + 2 * C) * 4
 
 

@@ -1,4 +1,4 @@
-"""The bf16 NHWC BatchNorm kernels (csrc/bn_nhwc_lp.hip through ops.bn_nhwc_fwd / ops.bn_nhwc_bwd on bf16 views) against float64 torch
+"""The bf16 NHWC BatchNorm kernels (csrc/bn_nhwc_core.h instantiated for bf16_t, through ops.bn_nhwc_fwd / ops.bn_nhwc_bwd on bf16 views) against float64 torch
 BatchNorm on the bf16-rounded inputs.
 
 Shapes: M in {1, 127, 128, 129, 2048, 2049} (the partial-block and finish-trip edges of the fp32 table) x C in {6, 8, 160}, and
@@ -319,3 +319,38 @@ def test_refusals_raise_and_launch_nothing(K):
     dx = K.bn_nhwc_bwd(gy, x, y, gamma, mean, invstd, True, True, res=two[:, :, M:], out=two[:, :, :M])
     close16(dx, ref["dx"], "out next to res")
     assert torch.equal(two[:, :, M:], res)
+
+
+# ------------------------------------------------------------------------------------------- one implementation, two storages
+def test_fp32_and_bf16_storage_are_one_implementation(K):
+    """The same bf16-representable values through the fp32 and the bf16 entry points: (N, H, W, C) = (2, 9, 15, 20), M = 270 -- three
+    stage-1 row blocks, the last of 14 rows; C = 20 puts fp32 on the float4 elementwise kernels, bf16 on the scalar ones throughout
+    and both storages on the scalar partials.  The reductions are the same kernels on the same values: every fp32 vector bit for bit; the
+    elementwise outputs differ by the one rounding of the bf16 store."""
+    N, H, W, C = 2, 9, 15, 20
+    g = torch.Generator().manual_seed(20270)
+    r = lambda *s: torch.randn(*s, generator=g, dtype=F64)
+    x16, gy16, res16 = ((r(C) + (0.5 + r(C).abs()) * r(N, H, W, C)).to(BF).cuda(), r(N, H, W, C).to(BF).cuda(), r(N, H, W, C).to(BF).cuda())
+    gamma, beta = (1 + 0.5 * torch.rand(C, generator=g, dtype=F64)).float().cuda(), (0.5 * r(C)).float().cuda()
+    rm0, rv0 = (0.3 * r(C)).float().cuda(), (0.5 + torch.rand(C, generator=g, dtype=F64)).float().cuda()
+    fwd = {}
+    for dt, name in ((BF, "bn_lp_apply_kernel<1>"), (torch.float32, "bn_nhwc_apply_kernel<4>")):
+        rm, rv = rm0.clone(), rv0.clone()
+        y, mean, invstd = K.bn_nhwc_fwd(x16.to(dt), gamma, beta, rm, rv, True, MOM, EPS, True)
+        reached(name)
+        fwd[dt] = dict(y=y, mean=mean, invstd=invstd, rm=rm, rv=rv)
+    a, b = fwd[BF], fwd[torch.float32]
+    for k in ("mean", "invstd", "rm", "rv"):
+        assert torch.equal(a[k], b[k]), f"forward {k}: the two storages disagree"
+    assert not torch.equal(a["rm"], rm0) and not torch.equal(a["rv"], rv0)
+    assert a["y"].dtype == BF and torch.equal(a["y"], b["y"].to(BF)), "forward y"
+    assert 0.05 < float((a["y"] > 0).float().mean()) < 0.95, "the ReLU mask is one-sided"
+    bwd = {}
+    for dt, name in ((BF, "bn_lp_dx_kernel<1>"), (torch.float32, "bn_nhwc_dx_kernel<4>")):
+        dg, db = torch.empty(C, device="cuda"), torch.empty(C, device="cuda")
+        dx = K.bn_nhwc_bwd(gy16.to(dt), x16.to(dt), a["y"].to(dt), gamma, a["mean"], a["invstd"], True, True, res=res16.to(dt), dgamma=dg, dbeta=db)
+        reached(name)
+        bwd[dt] = dict(dx=dx, dgamma=dg, dbeta=db)
+    a, b = bwd[BF], bwd[torch.float32]
+    assert torch.equal(a["dgamma"], b["dgamma"]) and torch.equal(a["dbeta"], b["dbeta"]), "backward dgamma / dbeta"
+    assert a["dx"].dtype == BF and torch.equal(a["dx"], b["dx"].to(BF)), "backward dx"

@@ -1,5 +1,5 @@
 """Every branch and loop trip of the fp32 NHWC kernels behind the classification models and the HRNet-OCR head
-(csrc/hrnet_ops.hip, bn_nhwc.hip with bn_nhwc_core.h, dense_ops.hip) against float64 on the CPU, element by element against the
+(csrc/hrnet_ops.hip, bn_nhwc.hip with bn_nhwc_core.h and bn_select.h, dense_ops.hip) against float64 on the CPU, element by element against the
 per-element bounds of tests/_nhwc_support_cases.py (derived there from each kernel's reduction plan).
 
 Each row asserts the kernel it reached where the entry point chooses one, compares every output with its bound (a bound of 0:

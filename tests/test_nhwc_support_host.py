@@ -1,7 +1,9 @@
-"""Keeps tests/_nhwc_support_cases.py honest without a GPU: every KD_NOTE_PLUMBING literal of the BN / pool sources has a row and
-every row names a declared literal; the trip counts a row claims follow from the launch plans restated there; the restated
-workspace formulas are the built library's; rows sit on both sides of every gate; every reference runs and is finite with
+"""Keeps tests/_nhwc_support_cases.py honest without a GPU: every name the fp32 BN / pool launchers can note (the pool literals of
+dense_ops.hip, the fp32 names of csrc/bn_select.h's compiled table) has a row and every row names one of them; the trip counts a
+row claims follow from the launch plans restated there, and the restated float4 gate and grid are the compiled header's on the
+rows' own values; the restated workspace formulas are the built library's; rows sit on both sides of every gate; every reference runs and is finite with
 finite, non-negative bounds (positive wherever the kernel computes); nothing has to be left out of a comparison."""
+import itertools
 import os
 import re
 
@@ -9,23 +11,35 @@ import numpy as np
 import pytest
 
 import _nhwc_support_cases as S
+import _bn_select_host as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "knowledge-distillation-by-replacing-cheap-conv_amd", "csrc")
-SOURCES = ("hrnet_ops.hip", "bn_nhwc.hip", "dense_ops.hip", "bn_nhwc_core.h")
+SOURCES = ("hrnet_ops.hip", "bn_nhwc.hip", "dense_ops.hip", "bn_nhwc_core.h", "bn_select.h")
 
 
-def declared_literals():
+@pytest.fixture(scope="module")
+def sel():
+    return H.load()
+
+
+def declared_literals(sel):
+    """name -> where it is declared: the KD_NOTE_PLUMBING literals of the sources, and the fp32 names of the compiled bn_select.h
+    table (what bn_nhwc_core.h and dense_ops.hip note through bn_kernel_name)."""
     out = {}
     for name in SOURCES:
         with open(os.path.join(CSRC, name)) as f:
             for lit in re.findall(r'KD_NOTE_PLUMBING\("([^"]+)"\)', f.read()):
                 out.setdefault(lit, name)
+    for k in range(sel.bl_count()):
+        if sel.bl_name(k).decode().startswith("bn_nhwc_"):
+            out.setdefault(sel.bl_name(k).decode(), "bn_select.h")
     return out
 
 
-def test_every_noted_literal_has_a_row_and_every_row_names_a_noted_literal():
-    declared = declared_literals()
+def test_every_noted_literal_has_a_row_and_every_row_names_a_noted_literal(sel):
+    declared = declared_literals(sel)
+    assert sorted(declared.values()).count("bn_select.h") == 5 and sorted(declared.values()).count("dense_ops.hip") == 4
     assert len(declared) == 9, f"expected the nine float4 / scalar / reduction-only choices, found {sorted(declared)}"
     assert "hrnet_ops.hip" not in declared.values(), "hrnet_ops.hip makes no host-side kernel choice"
     covered = {c["kernel"] for c in S.CASES if c["kernel"]}
@@ -82,6 +96,59 @@ def test_kernel_choice_follows_vec4_ok_alone():
         assert by_id[cid]["kernel"].endswith("<4>") and by_id[cid]["views"]
     assert by_id["bn_apply:C6"]["kernel"].endswith("<1>") and by_id["bn_bwd:C6-res"]["kernel"].endswith("<1>")
     assert by_id["bn_bwd:no-dx-dgamma-only"]["kernel"] == "bn_nhwc_grad_finish_kernel"
+
+
+def test_the_restated_gate_and_grid_are_the_compiled_headers(sel):
+    """S.vec4_ok / S.grid_for / S.bn_plan (the independent model the rows' kernels and trip counts come from) against csrc/bn_select.h
+    compiled for the host with es = 4, over the rows' own C, float offsets and leading dimensions: one view at a time off the
+    dense layout, on every operand of the forward, the backward and the two-view (pool) gate, and every row's own views."""
+    Cs = sorted({c["C"] for c in S.CASES if "C" in c} | {c["shape"][3] for c in S.cases_of("avgpool", "avgpool_bwd")})
+    views = sorted({v for c in S.CASES if c["op"].startswith(("bn_", "avgpool")) for v in c["views"].values()} | {(0, 0)})
+    Ms = sorted({c["M"] for c in S.CASES if "M" in c})
+    assert {6, 8, 512, 129} <= set(Cs) and {(0, 10), (2, 12), (4, 16)} <= set(views) and {1, 2049, 16400} <= set(Ms)
+    ptr = lambda C, v: (H.BASE + 4 * v[0], v[1] or C)
+    for C, v in itertools.product(Cs, views):
+        if v[1] and v[1] < C:
+            continue
+        odd, base = ptr(C, v), (H.BASE, C)
+        mv = (v[0], v[1] or C)
+        for who in range(2):
+            a = [base, base]
+            a[who] = odd
+            want = S.vec4_ok(C, [mv if i == who else (0, C) for i in range(2)])
+            assert bool(sel.bl_vec_ok(4, C, *a[0], *a[1])) == want, (C, v, who)
+            got = H.call(sel, "fwd", 4, *a[0], *a[1], 129, C)
+            assert (got["vec"], got["part_vec"]) == (want, 0) and got["name"] == f"bn_nhwc_apply_kernel<{4 if want else 1}>"
+        for who, name in enumerate(H.OPERANDS):
+            for present in itertools.product((False, True), repeat=3):      # y (relu), res, dx
+                there = dict(zip(("y", "res", "dx"), present), gy=True, x=True)
+                ops = {n: (odd if n == name else base) for n in H.OPERANDS if there[n]}
+                want = S.vec4_ok(C, [None if not there[n] else (mv if n == name else (0, C)) for n in H.OPERANDS])
+                got = H.bwd(sel, 4, 129, C, ops)
+                kern = f"bn_nhwc_dx_kernel<{4 if want else 1}>" if there["dx"] else "bn_nhwc_grad_finish_kernel"
+                assert (got["vec"], got["part_vec"], got["name"]) == (want, 0, kern), (C, v, name, present)
+    for M, C, V in itertools.product(Ms, Cs, (1, 4)):
+        if C % V:
+            continue
+        p = S.bn_plan(M, C, V)
+        ld = C if V == 4 else C + 1         # a leading dimension of C + 1 is never on the float4 path
+        for got, ch in ((H.call(sel, "fwd", 4, H.BASE, ld, H.BASE, ld, M, C), 16), (H.bwd(sel, 4, M, C, {n: (H.BASE, ld) for n in H.OPERANDS}), 64)):
+            assert got["vec"] == (V == 4) and (got["nrb"], got["grid"]) == (p["nrb"], p["grid"]) == (S.nrb(M), S.grid_for(M * (C // V))), (M, C, V)
+            assert (got["part_x"], got["part_y"], got["finish"]) == (S.nrb(M), -(-C // 64), -(-C // ch))
+    for t in (-5, 0, 1, 256, 257, 8192 * 256 - 1, 8192 * 256, 8192 * 256 + 1, 1 << 40):
+        assert sel.bl_grid(t) == S.grid_for(t), t
+    # every dispatching row: the kernel the table gives it is what the compiled selector (pools: the compiled two-view gate) answers
+    for c in S.cases_of("bn_fwd", "bn_apply", "bn_bwd", "avgpool", "avgpool_bwd"):
+        C = c["C"] if "C" in c else c["shape"][3]
+        at = lambda n: ptr(C, c["views"].get(n, (0, 0)))
+        if c["op"] == "bn_bwd":
+            names = ["gy", "x"] + (["y"] if c["relu"] else []) + (["res"] if c["flags"].get("res") else []) + (["dx"] if c["flags"].get("need_dx", True) else [])
+            assert H.bwd(sel, 4, c["M"], C, {n: at(n) for n in names})["name"] == c["kernel"], c["id"]
+        elif c["op"].startswith("bn_"):
+            assert H.call(sel, "fwd", 4, *at("x"), *at("y"), c["M"], C)["name"] == c["kernel"], c["id"]
+        else:
+            a, b = ("x", "y") if c["op"] == "avgpool" else ("gy", "gx")
+            assert int(c["kernel"][-2]) == (4 if sel.bl_vec_ok(4, C, *at(a), *at(b)) else 1), c["id"]
 
 
 def test_bn_shapes_cover_both_sides_of_every_flag():
