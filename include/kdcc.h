@@ -839,6 +839,41 @@ enum { KD_CIFAR_NCHW = 0, KD_CIFAR_NHWC = 1 };
 int kd_cifar_batch(const uint8_t *data, const int64_t *labels, int64_t n, const int32_t *params, int32_t B, const void *table,
                    int32_t dtype, int32_t layout, void *out, int32_t ld, int64_t *labels_out, kd_stream_t stream);
 
+/* ------------------------------------------------- Cityscapes batches from a device-resident dataset (csrc/seg_data_ops.hip)
+ * Replaces, per batch, the reference's per-image chain (data_loader/cityscapes.py:179-222 with the transforms of
+ * data_loader/__init__.py:7-51: RandomSizeAndCrop, RandomHorizontallyFlip, ColorJitter, RandomGaussianBlur, ToTensor, Normalize,
+ * MaskToTensor; one PIL image at a time with num_workers 0) by three stages over
+ *   data (n,H,W,3) uint8 and targets (n,H,W) uint8 train ids: the whole dataset, resident;
+ *   params: int32 rows of `params_ld` words, one per sample, validated by the caller.  Words 0..31 are the header [index, w, h,
+ *           pad_w, pad_h, x1, y1, flip, order[4], brightness, contrast, saturation (fp32 bits), hue shift byte, blur radius (0: none),
+ *           jitter on, sigma (double), six Gaussian weights of offsets 0..5 (doubles)].  kd_seg_crop reads 24 S words more:
+ *           HT (S,11) and VT (S,11) entries [xmin, taps <= 9, k0..k8] of PIL's bicubic passes in 22-bit fixed point for every crop
+ *           column (before the flip) and row, xmin = -1 where the crop shows the pad; MX (S) and MY (S) nearest source indices of
+ *           the mask, -1 for the pad.  All of it is computed on the host in double.
+ * kd_seg_crop: img_out (B,S,S,3), mask_out (B,S,S) uint8 = flip(crop(pad(resize(data[index])))): the horizontal pass over the source
+ *   rows a 16 x 32 tile needs, rounded and clipped to bytes, then the vertical pass, as PIL runs them (bit-identical); pad 0 / 255.
+ *   A tile's windows span at most 74 source columns and 42 rows (any scale >= 0.5); a tile that asks for more, and any entry that
+ *   leaves the source, reads as pad.
+ * kd_seg_jitter: in place on (B,S,S,3) bytes, the four PIL operations in the row's order for every row with `jitter on`; contrast
+ *   blends against int(sum(L) / (S*S) + 0.5) of the image as it stands, an exact integer sum through `workspace`
+ *   (kd_seg_jitter_workspace() bytes, cleared by the call).
+ * kd_seg_finish: out(b,c,y,x) = table[c][byte], byte = img[s][y][x][c] (blur 0, or a row of radius 0) or the truncated
+ *   scipy.ndimage.gaussian_filter of img / 255. in double with the row's weights (blur 1; radius <= 5, edges replicated);
+ *   s = index_b (use_index 1: img is the dataset, n images) or b (img is a batch of n >= B images); mask_out (B,H,W) int64.
+ *   table (3,256) elements of `dtype`.  KD_SEG_NCHW: dense (B,3,H,W), `ld` ignored.  KD_SEG_NHWC: (B,H,W,ld) pixels, ld >= 3; the
+ *   kernel writes every pixel's whole stride, zeros in channels [3, ld).  16-byte stores when out and mask_out are 16-byte aligned
+ *   and a row of W (NCHW) or W * ld (NHWC) elements is whole 16-byte pieces, scalar stores otherwise.
+ * H, W, S <= 32768 and B <= 65535 (KD_ERR_UNSUPPORTED beyond). */
+enum { KD_SEG_NCHW = 0, KD_SEG_NHWC = 1 };
+int kd_seg_crop(const uint8_t *data, const uint8_t *targets, int64_t n, int32_t H, int32_t W, const int32_t *params, int64_t params_ld, int32_t B,
+                int32_t S, uint8_t *img_out, uint8_t *mask_out, kd_stream_t stream);
+size_t kd_seg_jitter_workspace(int32_t B);
+int kd_seg_jitter(uint8_t *img, const int32_t *params, int64_t params_ld, int32_t B, int32_t S, void *workspace, size_t workspace_bytes,
+                  kd_stream_t stream);
+int kd_seg_finish(const uint8_t *img, const uint8_t *mask, int64_t n, int32_t H, int32_t W, const int32_t *params, int64_t params_ld, int32_t B,
+                  int32_t use_index, int32_t blur, const void *table, int32_t dtype, int32_t layout, void *out, int32_t ld, int64_t *mask_out,
+                  kd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

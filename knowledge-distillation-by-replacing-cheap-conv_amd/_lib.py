@@ -25,6 +25,7 @@ KD_F32, KD_BF16 = 0, 1
 KD_PACK_FWD, KD_PACK_DGRAD = 0, 1
 KD_ERR_UNSUPPORTED = -2
 KD_CIFAR_NCHW, KD_CIFAR_NHWC = 0, 1
+KD_SEG_NCHW, KD_SEG_NHWC = 0, 1
 KD_OPT_SGD, KD_OPT_ADAM, KD_OPT_ADAMW_REF = 0, 1, 2
 KD_OPT_FIRST, KD_OPT_NESTEROV, KD_OPT_AMSGRAD, KD_OPT_MAXIMIZE = 1, 2, 4, 8
 
@@ -216,6 +217,10 @@ _SIGS = {
     "kd_ocr_attend_bwd": (c_int, [c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_i64, c_int, c_int, c_f, c_vp, c_sz,
                                   c_vp]),
     "kd_cifar_batch": (c_int, [c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp]),
+    "kd_seg_crop": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp]),
+    "kd_seg_jitter_workspace": (c_sz, [c_int]),
+    "kd_seg_jitter": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_sz, c_vp]),
+    "kd_seg_finish": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp]),
     "kd_debug_kernel_log_enable": (c_int, [c_int]),
     "kd_debug_kernel_log_read": (c_i64, [C.c_char_p, c_sz]),
     "kd_debug_last_kernel": (C.c_char_p, []),

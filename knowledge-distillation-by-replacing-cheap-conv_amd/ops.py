@@ -2035,3 +2035,151 @@ def cifar_batch(data, labels, params, table, out, labels_out=None, validated=Fal
     check(_lib.lib().kd_cifar_batch(_ptr(data), _ptr(labels), n, _ptr(params), B, _ptr(table), dt, layout, _ptr(out), ld, _ptr(labels_out),
                                     stream_ptr()), "kd_cifar_batch")
     return out, labels_out
+
+
+# ------------------------------------------------------------------------- Cityscapes batches (data_loader)
+SEG_HDR, SEG_ENTRY, SEG_TAPS, SEG_TX, SEG_TY, SEG_CAP_C, SEG_CAP_R, SEG_MAX_RADIUS = 32, 11, 9, 32, 16, 74, 42, 5
+
+
+def _seg_bad(what):
+    raise ValueError(f"check_seg_params: {what}")
+
+
+def _seg_check_axis(ent, near, extent, tile, cap, name):
+    """One axis of an expanded table: entries (B,S,11) and nearest indices (B,S)."""
+    xmin, taps = ent[..., 0], ent[..., 1]
+    pad = xmin < 0
+    if bool((pad & ((xmin != -1) | (taps != 0))).any()):
+        _seg_bad(f"a {name} entry is neither a window nor the pad marker [-1, 0]")
+    if bool((~pad & ((taps < 1) | (taps > SEG_TAPS) | (xmin + taps > extent))).any()):
+        _seg_bad(f"a {name} tap window leaves the source [0, {extent}) or has more than {SEG_TAPS} taps")
+    if bool(((near < -1) | (near >= extent) | ((near < 0) != pad)).any()):
+        _seg_bad(f"a nearest {name} index is outside [-1, {extent}) or disagrees with the pad")
+    B, S = xmin.shape
+    fill = (-S) % tile          # whole tiles: the tail counts as pad
+    lo = torch.nn.functional.pad(torch.where(pad, torch.full_like(xmin, 1 << 30), xmin), (0, fill), value=1 << 30).view(B, -1, tile).amin(2)
+    hi = torch.nn.functional.pad(torch.where(pad, torch.zeros_like(xmin), xmin + taps), (0, fill), value=0).view(B, -1, tile).amax(2)
+    if bool((hi - lo > cap).any()):
+        _seg_bad(f"the {name} windows of one tile span more than {cap} source pixels (a scale below 0.5)")
+
+
+def check_seg_params(params, n, H, W, S=None):
+    """ValueError unless `params` is an int32 table of Cityscapes rows (data_loader/seg_tables.py) the kernels may be launched on:
+    header rows (B,32), or with S the expanded rows (B, 32 + 24 S) of kd_seg_crop.  Index in [0, n), w, h >= 1, flip and the jitter
+    flag 0 / 1, the order a permutation, the hue byte in [0, 255], the radius in [0, 5]; with S also the crop window inside the
+    padded scaled image, every tap window inside the source, at most 9 taps, every tile's windows within what the kernel stages,
+    nearest indices inside the source.  Reads the values: a device table is copied to the host first (a synchronisation)."""
+    width = SEG_HDR if S is None else SEG_HDR + (2 * SEG_ENTRY + 2) * S
+    if params.dim() != 2 or params.shape[0] < 1 or params.shape[1] != width or params.dtype != torch.int32:
+        _seg_bad(f"params must be an int32 (B,{width}) table, got {params.dtype} {tuple(params.shape)}")
+    p = params.detach().cpu()
+    idx, w, h, pw, ph, x1, y1, flip = (p[:, i] for i in range(8))
+    if bool(((idx < 0) | (idx >= n)).any()):
+        _seg_bad(f"index spans [{int(idx.min())}, {int(idx.max())}], allowed [0, {n - 1}]")
+    if bool(((w < 1) | (h < 1)).any()):
+        _seg_bad("a scaled size w, h below 1")
+    if bool(((flip < 0) | (flip > 1) | (p[:, 17] < 0) | (p[:, 17] > 1)).any()):
+        _seg_bad("flip and the jitter flag are 0 or 1")
+    if not bool((p[:, 8:12].sort(1).values == torch.arange(4)).all()):
+        _seg_bad("the order of the colour operations is not a permutation of 0..3")
+    if bool(((p[:, 15] < 0) | (p[:, 15] > 255)).any()):
+        _seg_bad("the hue shift is a byte")
+    if bool(((p[:, 16] < 0) | (p[:, 16] > SEG_MAX_RADIUS)).any()):
+        _seg_bad(f"blur radius spans [{int(p[:, 16].min())}, {int(p[:, 16].max())}], allowed [0, {SEG_MAX_RADIUS}]")
+    if S is None:
+        return
+    if bool(((pw < 0) | (ph < 0) | (x1 < 0) | (y1 < 0) | (x1 + S > w + 2 * pw) | (y1 + S > h + 2 * ph)).any()):
+        _seg_bad(f"the {S} x {S} crop window leaves the padded scaled image")
+    B = p.shape[0]
+    ent = p[:, SEG_HDR:SEG_HDR + 2 * SEG_ENTRY * S].view(B, 2, S, SEG_ENTRY)
+    near = p[:, SEG_HDR + 2 * SEG_ENTRY * S:].view(B, 2, S)
+    _seg_check_axis(ent[:, 0], near[:, 0], W, SEG_TX, SEG_CAP_C, "column")
+    _seg_check_axis(ent[:, 1], near[:, 1], H, SEG_TY, SEG_CAP_R, "row")
+
+
+def _seg_bytes(t, shape, name):
+    if t.dtype != torch.uint8 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous uint8 {tuple(shape)} tensor, got {t.dtype} {tuple(t.shape)}")
+
+
+def _seg_table(params, width, name):
+    if params.dtype != torch.int32 or params.dim() != 2 or params.shape[1] < width or params.stride(1) != 1 or params.shape[0] < 1:
+        raise ValueError(f"{name}: params must be an int32 (B, >= {width}) table with dense rows")
+    return params.shape[0], params.stride(0) if params.shape[0] > 1 else params.shape[1]
+
+
+def seg_crop(data, targets, params, S, img_out=None, mask_out=None, validated=False):
+    """Resample + pad + crop + flip (kd_seg_crop): data (n,H,W,3) and targets (n,H,W) uint8, the resident dataset; params the
+    expanded int32 table (B, 32 + 24 S).  -> (img (B,S,S,3), mask (B,S,S)) uint8, PIL's bicubic / nearest resize, the reference's pad,
+    crop and flip, bit for bit.  params is checked on the host (check_seg_params) unless validated=True."""
+    _need_cuda(data, targets, params, img_out, mask_out)
+    if data.dim() != 4 or data.shape[3] != 3:
+        raise ValueError(f"seg_crop: data must be (n,H,W,3), got {tuple(data.shape)}")
+    n, H, W = data.shape[:3]
+    _seg_bytes(data, (n, H, W, 3), "seg_crop: data")
+    _seg_bytes(targets, (n, H, W), "seg_crop: targets")
+    if not validated:
+        check_seg_params(params, n, H, W, S)
+    B, pld = _seg_table(params, SEG_HDR + (2 * SEG_ENTRY + 2) * S, "seg_crop")
+    img_out = torch.empty((B, S, S, 3), dtype=torch.uint8, device=data.device) if img_out is None else img_out
+    mask_out = torch.empty((B, S, S), dtype=torch.uint8, device=data.device) if mask_out is None else mask_out
+    _seg_bytes(img_out, (B, S, S, 3), "seg_crop: img_out")
+    _seg_bytes(mask_out, (B, S, S), "seg_crop: mask_out")
+    check(_lib.lib().kd_seg_crop(_ptr(data), _ptr(targets), n, H, W, _ptr(params), pld, B, S, _ptr(img_out), _ptr(mask_out), stream_ptr()),
+          "kd_seg_crop")
+    return img_out, mask_out
+
+
+def seg_jitter(img, params, workspace=None, validated=False):
+    """The colour jitter (kd_seg_jitter) in place on img (B,S,S,3) uint8, for every row of params (B, >= 32) whose jitter flag is set:
+    PIL's brightness, contrast, saturation and hue in the row's order, bit for bit.  -> img."""
+    _need_cuda(img, params, workspace)
+    if img.dim() != 4 or img.shape[1] != img.shape[2] or img.shape[3] != 3:
+        raise ValueError(f"seg_jitter: img must be (B,S,S,3), got {tuple(img.shape)}")
+    B, S = img.shape[:2]
+    _seg_bytes(img, (B, S, S, 3), "seg_jitter: img")
+    if _seg_table(params, SEG_HDR, "seg_jitter")[0] != B:
+        raise ValueError(f"seg_jitter: {params.shape[0]} rows for {B} images")
+    if not validated:
+        check_seg_params(params[:, :SEG_HDR], 2 ** 31 - 1, 1, 1)
+    need = _lib.lib().kd_seg_jitter_workspace(B)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=img.device)
+    check(_lib.lib().kd_seg_jitter(_ptr(img), _ptr(params), _seg_table(params, SEG_HDR, "seg_jitter")[1], B, S, _ptr(workspace),
+                                   workspace.numel() * workspace.element_size(), stream_ptr()), "kd_seg_jitter")
+    return img
+
+
+def seg_finish(img, mask, params, table, out, mask_out=None, use_index=False, blur=False, validated=False):
+    """Blur + quantise + normalise + layout (kd_seg_finish).  img (n,H,W,3) and mask (n,H,W) uint8: a batch of crops (image b of the
+    batch is sample b) or, with use_index, the resident dataset (sample b is image params[b, 0]).  blur: the Gaussian of every row
+    whose radius is not 0, scipy's in double, truncated to bytes.  table (3,256) of out's dtype; out (B,3,H,W)-logical, dense NCHW or
+    NHWC storage with any pixel stride ld >= 3, whose whole stride the kernel writes (zeros behind channel 3).
+    -> (out, mask_out int64 (B,H,W))."""
+    _need_cuda(img, mask, params, table, out, mask_out)
+    if img.dim() != 4 or img.shape[3] != 3:
+        raise ValueError(f"seg_finish: img must be (n,H,W,3), got {tuple(img.shape)}")
+    n, H, W = img.shape[:3]
+    _seg_bytes(img, (n, H, W, 3), "seg_finish: img")
+    _seg_bytes(mask, (n, H, W), "seg_finish: mask")
+    B, pld = _seg_table(params, SEG_HDR, "seg_finish")
+    if not validated:
+        check_seg_params(params[:, :SEG_HDR], n if use_index else 2 ** 31 - 1, H, W)
+    if not use_index and n < B:
+        raise ValueError(f"seg_finish: {n} images for {B} rows")
+    dt = dt_of(out)
+    if table.dtype != out.dtype or tuple(table.shape) != (3, 256) or not table.is_contiguous():
+        raise ValueError(f"seg_finish: table must be a contiguous (3,256) tensor of out's dtype {out.dtype}")
+    if tuple(out.shape) != (B, 3, H, W):
+        raise ValueError(f"seg_finish: out must be ({B},3,{H},{W})-logical, got {tuple(out.shape)}")
+    if out.is_contiguous():
+        layout, ld = _lib.KD_SEG_NCHW, 3
+    else:
+        layout, ld = _lib.KD_SEG_NHWC, nhwc_ld(out.permute(0, 2, 3, 1))
+    if mask_out is None:
+        mask_out = torch.empty((B, H, W), dtype=torch.int64, device=out.device)
+    elif mask_out.dtype != torch.int64 or tuple(mask_out.shape) != (B, H, W) or not mask_out.is_contiguous():
+        raise ValueError(f"seg_finish: mask_out must be a contiguous int64 ({B},{H},{W}) tensor")
+    check(_lib.lib().kd_seg_finish(_ptr(img), _ptr(mask), n, H, W, _ptr(params), pld, B, int(bool(use_index)), int(bool(blur)), _ptr(table), dt,
+                                   layout, _ptr(out), ld, _ptr(mask_out), stream_ptr()), "kd_seg_finish")
+    return out, mask_out
