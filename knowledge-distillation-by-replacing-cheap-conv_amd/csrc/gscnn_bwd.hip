@@ -13,18 +13,12 @@
 // This is the training-mode path of BASELINE config 5 beyond its shipped plan (loss terms that reach the logits, `aspp` hints,
 // trainable shape-stream parameters); it is built for correctness and determinism, not tuned: operands are read with scalar
 // loads of either storage type, the arithmetic is fp32.
+#include "gscnn_select.h"
 #include "kd_common.h"
 
 namespace {
 
-inline bool ok_dt(int d) { return d == KD_F32 || d == KD_BF16; }
-inline int blocks_for(long long total, int cap = 1 << 16)
-{
-    long long b = (total + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
-constexpr int SL_MAXC = 72;
+constexpr int SL_MAXC = GS_SL_MAXC;
 
 // ---- y = x W^T + b ------------------------------------------------------------------------------------------------------------
 // weights transposed into LDS as [ci][COP] so that one pixel's multiply-accumulates read consecutive, lane-uniform words
@@ -65,7 +59,7 @@ __global__ __launch_bounds__(256) void small_linear_kernel(const void *__restric
 
 // ---- dW = b^T a, db = sum b ------------------------------------------------------------------------------------------------------
 // a block walks its pixel range in chunks of 64 staged in LDS as fp32; thread t owns the (cb, ca) pairs t, t + 256, ...
-constexpr int SW_CH = 64, SW_MAXP = (SL_MAXC * SL_MAXC + 255) / 256;
+constexpr int SW_CH = GS_SW_CH, SW_MAXP = (SL_MAXC * SL_MAXC + 255) / 256;
 __global__ __launch_bounds__(256) void small_wgrad_partial_kernel(const void *__restrict__ a, int adt, int lda, int Ca, const void *__restrict__ b,
                                                                   int bdt, int ldb, int Cb, long long npix, long long per_block,
                                                                   float *__restrict__ part /* [blocks][Cb*Ca + Cb] */)
@@ -185,68 +179,63 @@ __global__ __launch_bounds__(256) void rank1_add_kernel(T *__restrict__ y, int l
     }
 }
 
+struct SmallLinearArgs {
+    const void *x; int xdt, ldx, Cin; const float *w, *bias; void *y; int ydt, ldy, Cout; long long npix; int accumulate, relu; const float *mask; int ldm;
+};
+template <int COP>
+void launch_small_linear(const GsSel &sel, const SmallLinearArgs &a, hipStream_t s)
+{
+    static_assert(COP == GS_SL_TEMPLATES[0] || COP == GS_SL_TEMPLATES[1] || COP == GS_SL_TEMPLATES[2] || COP == GS_SL_TEMPLATES[3] ||
+                      COP == GS_SL_TEMPLATES[4], "gscnn_select.h lists the instantiations");
+    hipLaunchKernelGGL(small_linear_kernel<COP>, dim3(sel.grid), dim3(sel.threads), 0, s, a.x, a.xdt, a.ldx, a.Cin, a.w, a.bias, a.y, a.ydt, a.ldy,
+                       a.Cout, a.npix, a.accumulate, a.relu, a.mask, a.ldm);
+}
+
 }  // namespace
 
+// Every entry point below: its pointer checks, its selector (gscnn_select.h), the selector's refusal as this entry point's message
+// and code, the selected kernel's name noted once, then the launch (a switch over sel.kernel where there is a choice).
 extern "C" int kd_small_linear(const void *x, int32_t x_dtype, int32_t ldx, int32_t Cin, const float *w, const float *bias, void *y,
                                int32_t y_dtype, int32_t ldy, int32_t Cout, int64_t npix, int32_t accumulate, int32_t relu,
                                const float *mask, int32_t ldm, kd_stream_t stream)
 {
-    KD_REQUIRE(x && w && y && npix > 0, KD_ERR_INVALID, "kd_small_linear: null argument");
-    KD_REQUIRE(ok_dt(x_dtype) && ok_dt(y_dtype), KD_ERR_INVALID, "kd_small_linear: bad dtype");
-    KD_REQUIRE(!mask || ldm >= Cout, KD_ERR_INVALID, "kd_small_linear: bad mask stride");
-    KD_REQUIRE(Cin >= 1 && Cin <= SL_MAXC && Cout >= 1 && Cout <= SL_MAXC && ldx >= Cin && ldy >= Cout, KD_ERR_UNSUPPORTED,
-               "kd_small_linear: 1..%d channels on each side (got %d -> %d)", SL_MAXC, Cin, Cout);
+    const GsSel sel = gs_small_linear(x_dtype, ldx, Cin, y_dtype, ldy, Cout, npix, mask, ldm);
+    KD_REQUIRE(x && w && y && sel.why != GS_WHY_SHAPE, KD_ERR_INVALID, "kd_small_linear: null argument");
+    KD_REQUIRE(sel.why != GS_WHY_DTYPE, KD_ERR_INVALID, "kd_small_linear: bad dtype");
+    KD_REQUIRE(sel.why != GS_WHY_MASK, KD_ERR_INVALID, "kd_small_linear: bad mask stride");
+    KD_REQUIRE(sel.why != GS_WHY_CHANNELS, KD_ERR_UNSUPPORTED, "kd_small_linear: 1..%d channels on each side (got %d -> %d)", SL_MAXC, Cin, Cout);
+    const SmallLinearArgs a = {x, x_dtype, ldx, Cin, w, bias, y, y_dtype, ldy, Cout, (long long)npix, accumulate, relu, mask, ldm};
     hipStream_t s = (hipStream_t)stream;
-    const int nb = blocks_for(npix);
-#define KD_SL(COP) hipLaunchKernelGGL(small_linear_kernel<COP>, dim3(nb), dim3(256), 0, s, x, x_dtype, ldx, Cin, w, bias, y, y_dtype, ldy, Cout, \
-                                      (long long)npix, accumulate, relu, mask, ldm)
-    if (Cout <= 8) KD_SL(8);
-    else if (Cout <= 16) KD_SL(16);
-    else if (Cout <= 24) KD_SL(24);
-    else if (Cout <= 40) KD_SL(40);
-    else KD_SL(72);
-#undef KD_SL
+    KD_NOTE_PLUMBING(gs_kernel_name(sel.kernel));
+    switch (sel.kernel) {
+    case GS_SMALL_LINEAR_8: launch_small_linear<8>(sel, a, s); break;
+    case GS_SMALL_LINEAR_16: launch_small_linear<16>(sel, a, s); break;
+    case GS_SMALL_LINEAR_24: launch_small_linear<24>(sel, a, s); break;
+    case GS_SMALL_LINEAR_40: launch_small_linear<40>(sel, a, s); break;
+    default: launch_small_linear<72>(sel, a, s); break;
+    }
     KD_CHECK_LAUNCH("kd_small_linear");
     return KD_OK;
 }
 
-static int small_wgrad_blocks(int64_t npix, long long *per_block)
-{
-    long long nb = (npix + 4095) / 4096;      // >= 64 chunks of 64 pixels per block
-    if (nb > 1024) nb = 1024;
-    if (nb < 1) nb = 1;
-    long long pb = (npix + nb - 1) / nb;
-    pb = (pb + SW_CH - 1) / SW_CH * SW_CH;
-    nb = (npix + pb - 1) / pb;
-    *per_block = pb;
-    return (int)nb;
-}
-
-extern "C" size_t kd_small_wgrad_workspace(int32_t Ca, int32_t Cb, int64_t npix)
-{
-    if (Ca < 1 || Cb < 1 || npix < 1) return 0;
-    long long pb;
-    return (size_t)small_wgrad_blocks(npix, &pb) * ((size_t)Ca * Cb + Cb) * sizeof(float);
-}
+extern "C" size_t kd_small_wgrad_workspace(int32_t Ca, int32_t Cb, int64_t npix) { return gs_small_wgrad_workspace(Ca, Cb, npix); }
 
 extern "C" int kd_small_wgrad(const void *a, int32_t a_dtype, int32_t lda, int32_t Ca, const void *b, int32_t b_dtype, int32_t ldb, int32_t Cb,
                               int64_t npix, float *dw, float *db, int32_t accumulate, void *workspace, size_t workspace_bytes,
                               kd_stream_t stream)
 {
-    KD_REQUIRE(a && b && dw && workspace && npix > 0, KD_ERR_INVALID, "kd_small_wgrad: null argument");
-    KD_REQUIRE(ok_dt(a_dtype) && ok_dt(b_dtype), KD_ERR_INVALID, "kd_small_wgrad: bad dtype");
-    KD_REQUIRE(Ca >= 1 && Ca <= SL_MAXC && Cb >= 1 && Cb <= SL_MAXC && lda >= Ca && ldb >= Cb, KD_ERR_UNSUPPORTED,
-               "kd_small_wgrad: 1..%d channels on each side (got %d x %d)", SL_MAXC, Ca, Cb);
-    KD_REQUIRE(workspace_bytes >= kd_small_wgrad_workspace(Ca, Cb, npix), KD_ERR_WORKSPACE, "kd_small_wgrad: workspace too small");
-    long long pb;
-    const int nb = small_wgrad_blocks(npix, &pb);
+    const GsSel sel = gs_small_wgrad(a_dtype, lda, Ca, b_dtype, ldb, Cb, npix);
+    KD_REQUIRE(a && b && dw && workspace && sel.why != GS_WHY_SHAPE, KD_ERR_INVALID, "kd_small_wgrad: null argument");
+    KD_REQUIRE(sel.why != GS_WHY_DTYPE, KD_ERR_INVALID, "kd_small_wgrad: bad dtype");
+    KD_REQUIRE(sel.why != GS_WHY_CHANNELS, KD_ERR_UNSUPPORTED, "kd_small_wgrad: 1..%d channels on each side (got %d x %d)", SL_MAXC, Ca, Cb);
+    KD_REQUIRE(workspace_bytes >= gs_small_wgrad_workspace(Ca, Cb, npix), KD_ERR_WORKSPACE, "kd_small_wgrad: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(small_wgrad_partial_kernel, dim3(nb), dim3(256), 0, s, a, a_dtype, lda, Ca, b, b_dtype, ldb, Cb, (long long)npix, pb,
-                       (float *)workspace);
+    KD_NOTE_PLUMBING(gs_kernel_name(sel.kernel));
+    hipLaunchKernelGGL(small_wgrad_partial_kernel, dim3(sel.grid), dim3(sel.threads), 0, s, a, a_dtype, lda, Ca, b, b_dtype, ldb, Cb, (long long)npix,
+                       sel.sw_per_block, (float *)workspace);
     KD_CHECK_LAUNCH("kd_small_wgrad(partial)");
-    const int total = Ca * Cb;
-    hipLaunchKernelGGL(small_wgrad_finish_kernel, dim3((total + Cb + 255) / 256), dim3(256), 0, s, (const float *)workspace, nb, total, Cb, dw, db,
-                       accumulate);
+    hipLaunchKernelGGL(small_wgrad_finish_kernel, dim3(sel.grid2), dim3(sel.threads), 0, s, (const float *)workspace, sel.sw_blocks, Ca * Cb, Cb, dw,
+                       db, accumulate);
     KD_CHECK_LAUNCH("kd_small_wgrad(finish)");
     return KD_OK;
 }
@@ -254,11 +243,13 @@ extern "C" int kd_small_wgrad(const void *a, int32_t a_dtype, int32_t lda, int32
 extern "C" int kd_gate_mix_bwd(const void *feat, int32_t feat_dtype, int32_t ldf, const float *a, const float *gv, int32_t ldgv, float *gfeat,
                                int32_t ldgf, float *ga, float *v, int32_t ldv, int32_t C, int64_t npix, kd_stream_t stream)
 {
-    KD_REQUIRE(feat && a && npix > 0 && C >= 1, KD_ERR_INVALID, "kd_gate_mix_bwd: null argument");
-    KD_REQUIRE(ok_dt(feat_dtype), KD_ERR_INVALID, "kd_gate_mix_bwd: bad dtype");
+    const GsSel sel = gs_gate_mix_bwd(feat_dtype, C, npix);
+    KD_REQUIRE(feat && a && sel.why != GS_WHY_SHAPE, KD_ERR_INVALID, "kd_gate_mix_bwd: null argument");
+    KD_REQUIRE(sel.why != GS_WHY_DTYPE, KD_ERR_INVALID, "kd_gate_mix_bwd: bad dtype");
     KD_REQUIRE((gfeat == nullptr && ga == nullptr) || gv, KD_ERR_INVALID, "kd_gate_mix_bwd: gradients requested without gv");
-    hipLaunchKernelGGL(gate_mix_bwd_kernel, dim3(blocks_for(npix)), dim3(256), 0, (hipStream_t)stream, feat, feat_dtype, ldf, a, gv, ldgv, gfeat,
-                       ldgf, ga, v, ldv, C, (long long)npix);
+    KD_NOTE_PLUMBING(gs_kernel_name(sel.kernel));
+    hipLaunchKernelGGL(gate_mix_bwd_kernel, dim3(sel.grid), dim3(sel.threads), 0, (hipStream_t)stream, feat, feat_dtype, ldf, a, gv, ldgv, gfeat, ldgf,
+                       ga, v, ldv, C, (long long)npix);
     KD_CHECK_LAUNCH("kd_gate_mix_bwd");
     return KD_OK;
 }
@@ -266,9 +257,12 @@ extern "C" int kd_gate_mix_bwd(const void *feat, int32_t feat_dtype, int32_t ldf
 extern "C" int kd_edge_attention_bwd(int32_t dtype, const void *cs, int32_t ldc, const float *canny, const float *weights, const float *g_acts,
                                      float *g_t, float *g_s, float *eo_canny, int64_t npix, kd_stream_t stream)
 {
-    KD_REQUIRE(cs && canny && weights && g_acts && g_t && g_s && eo_canny && npix > 0, KD_ERR_INVALID, "kd_edge_attention_bwd: null argument");
-    KD_REQUIRE(ok_dt(dtype) && ldc >= 8, KD_ERR_INVALID, "kd_edge_attention_bwd: bad dtype / ldc");
-    hipLaunchKernelGGL(edge_attention_bwd_kernel, dim3(blocks_for(npix)), dim3(256), 0, (hipStream_t)stream, cs, dtype, ldc, canny, weights, g_acts,
+    const GsSel sel = gs_edge_attention_bwd(dtype, ldc, npix);
+    KD_REQUIRE(cs && canny && weights && g_acts && g_t && g_s && eo_canny && sel.why != GS_WHY_SHAPE, KD_ERR_INVALID,
+               "kd_edge_attention_bwd: null argument");
+    KD_REQUIRE(sel.why != GS_WHY_DTYPE, KD_ERR_INVALID, "kd_edge_attention_bwd: bad dtype / ldc");
+    KD_NOTE_PLUMBING(gs_kernel_name(sel.kernel));
+    hipLaunchKernelGGL(edge_attention_bwd_kernel, dim3(sel.grid), dim3(sel.threads), 0, (hipStream_t)stream, cs, dtype, ldc, canny, weights, g_acts,
                        g_t, g_s, eo_canny, (long long)npix);
     KD_CHECK_LAUNCH("kd_edge_attention_bwd");
     return KD_OK;
@@ -277,15 +271,17 @@ extern "C" int kd_edge_attention_bwd(int32_t dtype, const void *cs, int32_t ldc,
 extern "C" int kd_rank1_add(int32_t dtype, void *y, int32_t ldy, const float *g, const float *w, int32_t C, int64_t npix, int32_t accumulate,
                             kd_stream_t stream)
 {
-    KD_REQUIRE(y && g && w && npix > 0 && C > 0, KD_ERR_INVALID, "kd_rank1_add: null argument");
-    KD_REQUIRE(ok_dt(dtype), KD_ERR_INVALID, "kd_rank1_add: bad dtype");
-    const int es = kd_elem_size(dtype);
-    KD_REQUIRE(C % 8 == 0 && kd_aligned16(y) && (ldy * es) % 16 == 0 && kd_aligned16(w), KD_ERR_INVALID,
-               "kd_rank1_add: C %% 8 and 16-B aligned rows required");
-    const int nb = blocks_for(npix * (C / 8), 1 << 20);
+    const GsSel sel = gs_rank1_add(dtype, y, ldy, w, C, npix);
+    KD_REQUIRE(y && g && w && sel.why != GS_WHY_SHAPE, KD_ERR_INVALID, "kd_rank1_add: null argument");
+    KD_REQUIRE(sel.why != GS_WHY_DTYPE, KD_ERR_INVALID, "kd_rank1_add: bad dtype");
+    KD_REQUIRE(sel.why != GS_WHY_ALIGN, KD_ERR_INVALID, "kd_rank1_add: C %% 8 and 16-B aligned rows required");
+    const dim3 grid(sel.grid), block(sel.threads);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == KD_BF16) hipLaunchKernelGGL(rank1_add_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (bf16_t *)y, ldy, g, w, C / 8, (long long)npix, accumulate);
-    else hipLaunchKernelGGL(rank1_add_kernel<float>, dim3(nb), dim3(256), 0, s, (float *)y, ldy, g, w, C / 8, (long long)npix, accumulate);
+    KD_NOTE_PLUMBING(gs_kernel_name(sel.kernel));
+    if (sel.kernel == GS_RANK1_ADD_BF16)
+        hipLaunchKernelGGL(rank1_add_kernel<bf16_t>, grid, block, 0, s, (bf16_t *)y, ldy, g, w, C / 8, (long long)npix, accumulate);
+    else
+        hipLaunchKernelGGL(rank1_add_kernel<float>, grid, block, 0, s, (float *)y, ldy, g, w, C / 8, (long long)npix, accumulate);
     KD_CHECK_LAUNCH("kd_rank1_add");
     return KD_OK;
 }

@@ -8,16 +8,10 @@
 //                      one operator is UNPINNED (opencv-python is not vendored); it follows the published algorithm.
 #include <stdlib.h>
 
+#include "gscnn_select.h"
 #include "kd_common.h"
 
 namespace {
-
-inline bool ok_dt(int d) { return d == KD_F32 || d == KD_BF16; }
-inline int blocks_for(long long total, int cap = 1 << 20)
-{
-    long long b = (total + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
 
 // ---- gated spatial conv -----------------------------------------------------------------------------------------------------
 // per pixel, with u = [feat(C); gate(1)]:
@@ -415,7 +409,7 @@ __global__ __launch_bounds__(256) void pointwise_small_kernel(const bf16_t *__re
 // fetched once per workgroup, fully coalesced); per 16 pixels one v_mfma_f32_16x16x32_bf16 per tap (C = 32) or per pair of
 // taps (C = 16: K = 2 taps x 16 channels) with the weights as the A operand, so a lane ends up with four consecutive output
 // channels of one pixel; bias (the folded BatchNorm shift), residual and ReLU in fp32 before the single rounding to bf16.
-constexpr int SC_SEG = 256, SC_ROWS = 16;
+constexpr int SC_SEG = GS_SC_SEG, SC_ROWS = GS_SC_ROWS;
 typedef __attribute__((ext_vector_type(8))) short sc_bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float sc_f32x4_t;
 struct SmallConvParams {
@@ -587,52 +581,116 @@ __global__ __launch_bounds__(C == 64 ? 512 : 256) void conv3x3_small_kernel(cons
     }
 }
 
+static_assert(sizeof(short2) == GS_CANNY_GRAD_BYTES && sizeof(int) == GS_CANNY_MAG_BYTES && sizeof(unsigned char) == GS_CANNY_STATE_BYTES,
+              "gscnn_select.h lays out the Canny workspace");
+
+// ---- launches: the instantiation the selection names, on the selection's grid ------------------------------------------------
+struct GatedArgs { const void *feat; int ldf; const void *gate; int ldg; const float *prm; void *out; int ldo; long long npix; };
+template <typename T, int C>
+void launch_gated_conv(const GsSel &sel, const GatedArgs &a, hipStream_t s)
+{
+    hipLaunchKernelGGL((gated_conv_kernel<T, C>), dim3(sel.grid), dim3(sel.threads), 0, s, (const T *)a.feat, a.ldf, (const T *)a.gate, a.ldg, a.prm,
+                       (T *)a.out, a.ldo, a.npix);
+}
+template <int C>
+void launch_gated_conv_mfma(const GsSel &sel, const GatedArgs &a, hipStream_t s)
+{
+    hipLaunchKernelGGL((gated_conv_mfma_kernel<C>), dim3(sel.grid), dim3(sel.threads), 0, s, (const bf16_t *)a.feat, a.ldf, (const bf16_t *)a.gate,
+                       a.ldg, a.prm, (bf16_t *)a.out, a.ldo, a.npix);
+}
+// raises the instantiation's dynamic-LDS limit once per process where the selection says it must
+template <int C>
+int launch_conv3x3_small(const GsSel &sel, const SmallConvParams &p, hipStream_t s)
+{
+    static bool attr_set = false;
+    if (sel.raise_lds && !attr_set) {
+        if (hipFuncSetAttribute((const void *)conv3x3_small_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, sel.lds) != hipSuccess) {
+            kd_set_error("kd_conv3x3_small: cannot reserve %d B of LDS", sel.lds);
+            return KD_ERR_HIP;
+        }
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(conv3x3_small_kernel<C>, dim3(sel.grid), dim3(sel.threads), sel.lds, s, p);
+    return KD_OK;
+}
+template <int CIN, int COUT>
+void launch_pointwise_small(const GsSel &sel, hipStream_t s, const void *x, int ldx, const float *w, const float *bias, void *y, int ldy, long long npix)
+{
+    hipLaunchKernelGGL((pointwise_small_kernel<CIN, COUT>), dim3(sel.grid), dim3(sel.threads), 0, s, (const bf16_t *)x, ldx, w, bias, (bf16_t *)y, ldy,
+                       npix);
+}
+
+// The three sections of the Canny workspace, at the selection's offsets.
+struct CannyBufs { short2 *grad; int *mag; unsigned char *state; };
+CannyBufs canny_carve(void *workspace, const GsSel &sel)
+{
+    char *base = (char *)workspace;
+    return CannyBufs{(short2 *)(base + sel.ws_off[0]), (int *)(base + sel.ws_off[1]), (unsigned char *)(base + sel.ws_off[2])};
+}
+
+// The tail kd_canny and kd_canny_continue share: `sweeps` hysteresis sweeps over the state in the workspace, then the 0 / 255 map.
+int canny_sweep_and_finish(const char *who, const char *launch, const GsSel &sel, unsigned char *state, int N, int H, int W, int sweeps, float *out,
+                           int32_t *changed, hipStream_t s)
+{
+    const dim3 grid(sel.grid), block(sel.threads);
+    for (int i = 0; i < sweeps; ++i) {
+        if (hipMemsetAsync(changed, 0, sizeof(int), s) != hipSuccess) { kd_set_error("%s: memset failed", who); return KD_ERR_HIP; }
+        hipLaunchKernelGGL(canny_hyst_kernel, grid, block, 0, s, state, N, H, W, changed);
+    }
+    hipLaunchKernelGGL(canny_finish_kernel, grid, block, 0, s, (const unsigned char *)state, out, sel.total);
+    KD_CHECK_LAUNCH(launch);
+    return KD_OK;
+}
+
 }  // namespace
 
+// Every entry point below: its pointer checks, its selector (gscnn_select.h), the selector's refusal as this entry point's message
+// and code, the selected kernel's name noted once, then a switch over sel.kernel to the instantiation on the selector's grid.
 extern "C" int kd_gated_conv(int32_t dtype, const void *feat, int32_t ldf, const void *gate, int32_t ldg, const float *params,
                              void *out, int32_t ldo, int64_t npix, int32_t C, kd_stream_t stream)
 {
-    KD_REQUIRE(feat && gate && params && out && npix > 0, KD_ERR_INVALID, "kd_gated_conv: bad argument");
-    KD_REQUIRE(ok_dt(dtype), KD_ERR_INVALID, "kd_gated_conv: bad dtype");
-    KD_REQUIRE(C == 8 || C == 16 || C == 32, KD_ERR_UNSUPPORTED, "kd_gated_conv: C must be 8, 16 or 32 (got %d)", C);
-    const int es = kd_elem_size(dtype);
-    KD_REQUIRE(kd_aligned16(feat) && kd_aligned16(out) && (ldf * es) % 16 == 0 && (ldo * es) % 16 == 0, KD_ERR_INVALID,
-               "kd_gated_conv: 16-B aligned feature views required");
+    // KDCC_GATED_MFMA=0 is the A/B side of the matrix-core kernel: the only way to the bf16 VALU instantiations
+    static const bool mfma = [] { const char *e = getenv("KDCC_GATED_MFMA"); return !(e && e[0] == '0'); }();
+    const GsSel sel = gs_gated_conv(dtype, feat, ldf, out, ldo, npix, C, mfma);
+    KD_REQUIRE(feat && gate && params && out && sel.why != GS_WHY_SHAPE, KD_ERR_INVALID, "kd_gated_conv: bad argument");
+    KD_REQUIRE(sel.why != GS_WHY_DTYPE, KD_ERR_INVALID, "kd_gated_conv: bad dtype");
+    KD_REQUIRE(sel.why != GS_WHY_CHANNELS, KD_ERR_UNSUPPORTED, "kd_gated_conv: C must be 8, 16 or 32 (got %d)", C);
+    KD_REQUIRE(sel.why != GS_WHY_ALIGN, KD_ERR_INVALID, "kd_gated_conv: 16-B aligned feature views required");
+    const GatedArgs a = {feat, ldf, gate, ldg, params, out, ldo, (long long)npix};
     hipStream_t s = (hipStream_t)stream;
-    {
-        static int mfma = -1;
-        if (mfma < 0) { const char *e = getenv("KDCC_GATED_MFMA"); mfma = !(e && e[0] == '0'); }   // A/B: 0 = the VALU kernel
-        if (mfma && dtype == KD_BF16 && (ldo * es) % 8 == 0) {
-            const long long waves = (npix + 15) / 16;
-            const int nbm = blocks_for((waves + 3) / 4 * 256, 256 * 32);   // <= 32 workgroups per CU, grid-stride over the rest
-#define KD_GCM(CC) hipLaunchKernelGGL((gated_conv_mfma_kernel<CC>), dim3(nbm), dim3(256), 0, s, (const bf16_t *)feat, ldf, (const bf16_t *)gate, ldg, params, (bf16_t *)out, ldo, (long long)npix)
-            KD_NOTE_KERNEL("gated_conv_mfma_kernel");
-            if (C == 8) KD_GCM(8); else if (C == 16) KD_GCM(16); else KD_GCM(32);
-#undef KD_GCM
-            KD_CHECK_LAUNCH("kd_gated_conv(mfma)");
-            return KD_OK;
-        }
+    KD_NOTE_PLUMBING(gs_kernel_name(sel.kernel));
+    const bool matrix = sel.kernel >= GS_GATED_MFMA_8;      // (the last values of this entry point's range)
+    if (matrix) KD_NOTE_KERNEL("gated_conv_mfma_kernel");
+    else KD_NOTE_KERNEL("gated_conv_kernel");
+    switch (sel.kernel) {
+    case GS_GATED_MFMA_8: launch_gated_conv_mfma<8>(sel, a, s); break;
+    case GS_GATED_MFMA_16: launch_gated_conv_mfma<16>(sel, a, s); break;
+    case GS_GATED_MFMA_32: launch_gated_conv_mfma<32>(sel, a, s); break;
+    case GS_GATED_BF16_8: launch_gated_conv<bf16_t, 8>(sel, a, s); break;
+    case GS_GATED_BF16_16: launch_gated_conv<bf16_t, 16>(sel, a, s); break;
+    case GS_GATED_BF16_32: launch_gated_conv<bf16_t, 32>(sel, a, s); break;
+    case GS_GATED_F32_8: launch_gated_conv<float, 8>(sel, a, s); break;
+    case GS_GATED_F32_16: launch_gated_conv<float, 16>(sel, a, s); break;
+    default: launch_gated_conv<float, 32>(sel, a, s); break;
     }
-    const int nb = blocks_for((npix + (C >= 32 ? 1 : 3)) / (C >= 32 ? 2 : 4), 65536);
-#define KD_GC(T, CC) hipLaunchKernelGGL((gated_conv_kernel<T, CC>), dim3(nb), dim3(256), 0, s, (const T *)feat, ldf, (const T *)gate, ldg, params, (T *)out, ldo, (long long)npix)
-    KD_NOTE_KERNEL("gated_conv_kernel");
-    if (dtype == KD_BF16) { if (C == 8) KD_GC(bf16_t, 8); else if (C == 16) KD_GC(bf16_t, 16); else KD_GC(bf16_t, 32); }
-    else { if (C == 8) KD_GC(float, 8); else if (C == 16) KD_GC(float, 16); else KD_GC(float, 32); }
-#undef KD_GC
-    KD_CHECK_LAUNCH("kd_gated_conv");
+    KD_CHECK_LAUNCH(matrix ? "kd_gated_conv(mfma)" : "kd_gated_conv");
     return KD_OK;
 }
 
 extern "C" int kd_edge_attention(int32_t dtype, const void *cs, int32_t ldc, const float *canny, const float *weights, float *acts,
                                  int64_t npix, kd_stream_t stream)
 {
-    KD_REQUIRE(cs && canny && weights && acts && npix > 0, KD_ERR_INVALID, "kd_edge_attention: bad argument");
-    KD_REQUIRE(ok_dt(dtype), KD_ERR_INVALID, "kd_edge_attention: bad dtype");
-    KD_REQUIRE(kd_aligned16(cs) && (ldc * kd_elem_size(dtype)) % 16 == 0, KD_ERR_INVALID, "kd_edge_attention: 16-B aligned view required");
-    const int nb = blocks_for(npix, 65536);
+    const GsSel sel = gs_edge_attention(dtype, cs, ldc, npix);
+    KD_REQUIRE(cs && canny && weights && acts && sel.why != GS_WHY_SHAPE, KD_ERR_INVALID, "kd_edge_attention: bad argument");
+    KD_REQUIRE(sel.why != GS_WHY_DTYPE, KD_ERR_INVALID, "kd_edge_attention: bad dtype");
+    KD_REQUIRE(sel.why != GS_WHY_ALIGN, KD_ERR_INVALID, "kd_edge_attention: 16-B aligned view required");
+    const dim3 grid(sel.grid), block(sel.threads);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == KD_BF16) hipLaunchKernelGGL(edge_attention_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, (const bf16_t *)cs, ldc, canny, weights, acts, (long long)npix);
-    else hipLaunchKernelGGL(edge_attention_kernel<float>, dim3(nb), dim3(256), 0, s, (const float *)cs, ldc, canny, weights, acts, (long long)npix);
+    KD_NOTE_PLUMBING(gs_kernel_name(sel.kernel));
+    if (sel.kernel == GS_EDGE_ATTENTION_BF16)
+        hipLaunchKernelGGL(edge_attention_kernel<bf16_t>, grid, block, 0, s, (const bf16_t *)cs, ldc, canny, weights, acts, (long long)npix);
+    else
+        hipLaunchKernelGGL(edge_attention_kernel<float>, grid, block, 0, s, (const float *)cs, ldc, canny, weights, acts, (long long)npix);
     KD_CHECK_LAUNCH("kd_edge_attention");
     return KD_OK;
 }
@@ -640,24 +698,22 @@ extern "C" int kd_edge_attention(int32_t dtype, const void *cs, int32_t ldc, con
 extern "C" int kd_edge_aspp(int32_t dtype, const float *acts, int32_t H, int32_t W, const float *w, const float *scale, const float *shift,
                             void *y, int32_t ldy, int32_t N, int32_t Ho, int32_t Wo, int32_t C, kd_stream_t stream)
 {
-    KD_REQUIRE(acts && w && scale && shift && y && N > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && C > 0, KD_ERR_INVALID, "kd_edge_aspp: bad argument");
-    KD_REQUIRE(ok_dt(dtype), KD_ERR_INVALID, "kd_edge_aspp: bad dtype");
-    KD_REQUIRE(C % 8 == 0 && kd_aligned16(y) && (ldy * kd_elem_size(dtype)) % 16 == 0 && kd_aligned16(w) && kd_aligned16(scale) && kd_aligned16(shift),
-               KD_ERR_INVALID, "kd_edge_aspp: C %% 8 and 16-B alignment required");
-    const float sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f, sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
-    const int nb = blocks_for((long long)N * Ho * Wo * (C / 8), 65536);
+    const GsSel sel = gs_edge_aspp(dtype, w, scale, shift, y, ldy, N, H, W, Ho, Wo, C);
+    KD_REQUIRE(acts && w && scale && shift && y && sel.why != GS_WHY_SHAPE, KD_ERR_INVALID, "kd_edge_aspp: bad argument");
+    KD_REQUIRE(sel.why != GS_WHY_DTYPE, KD_ERR_INVALID, "kd_edge_aspp: bad dtype");
+    KD_REQUIRE(sel.why != GS_WHY_ALIGN, KD_ERR_INVALID, "kd_edge_aspp: C %% 8 and 16-B alignment required");
+    const dim3 grid(sel.grid), block(sel.threads);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == KD_BF16) hipLaunchKernelGGL(edge_aspp_kernel<bf16_t>, dim3(nb), dim3(256), 0, s, acts, H, W, w, scale, shift, (bf16_t *)y, ldy, N, Ho, Wo, C / 8, sh, sw);
-    else hipLaunchKernelGGL(edge_aspp_kernel<float>, dim3(nb), dim3(256), 0, s, acts, H, W, w, scale, shift, (float *)y, ldy, N, Ho, Wo, C / 8, sh, sw);
+    KD_NOTE_PLUMBING(gs_kernel_name(sel.kernel));
+    if (sel.kernel == GS_EDGE_ASPP_BF16)
+        hipLaunchKernelGGL(edge_aspp_kernel<bf16_t>, grid, block, 0, s, acts, H, W, w, scale, shift, (bf16_t *)y, ldy, N, Ho, Wo, C / 8, sel.sh, sel.sw);
+    else
+        hipLaunchKernelGGL(edge_aspp_kernel<float>, grid, block, 0, s, acts, H, W, w, scale, shift, (float *)y, ldy, N, Ho, Wo, C / 8, sel.sh, sel.sw);
     KD_CHECK_LAUNCH("kd_edge_aspp");
     return KD_OK;
 }
 
-extern "C" size_t kd_canny_workspace(int32_t N, int32_t H, int32_t W)
-{
-    const size_t n = (size_t)N * H * W;
-    return n * (sizeof(short2) + sizeof(int) + 1) + 256;
-}
+extern "C" size_t kd_canny_workspace(int32_t N, int32_t H, int32_t W) { return gs_canny_workspace(N, H, W); }
 
 // x: (N,3,H,W) float NCHW (the trainer's batch); out: (N,H,W) float, 0 / 255.  `changed` is a device int the caller reads
 // back between sweeps: kd_canny runs the gradient / NMS stages and `sweeps` hysteresis sweeps, adding the number of blocks
@@ -665,87 +721,57 @@ extern "C" size_t kd_canny_workspace(int32_t N, int32_t H, int32_t W)
 extern "C" int kd_canny(const float *x, int32_t N, int32_t H, int32_t W, int32_t low, int32_t high, int32_t sweeps, float *out,
                         int32_t *changed, void *workspace, size_t workspace_bytes, kd_stream_t stream)
 {
-    KD_REQUIRE(x && out && changed && workspace && N > 0 && H > 0 && W > 0 && sweeps >= 0, KD_ERR_INVALID, "kd_canny: bad argument");
-    KD_REQUIRE(workspace_bytes >= kd_canny_workspace(N, H, W), KD_ERR_WORKSPACE, "kd_canny: workspace too small");
-    const long long n = (long long)N * H * W;
-    short2 *grad = (short2 *)workspace;
-    int *mag = (int *)(grad + n);
-    unsigned char *state = (unsigned char *)(mag + n);
-    const int nb = blocks_for(n, 65536);
+    const GsSel sel = gs_canny(N, H, W, sweeps);
+    KD_REQUIRE(x && out && changed && workspace && sel.why != GS_WHY_SHAPE, KD_ERR_INVALID, "kd_canny: bad argument");
+    KD_REQUIRE(workspace_bytes >= gs_canny_workspace(N, H, W), KD_ERR_WORKSPACE, "kd_canny: workspace too small");
+    const CannyBufs b = canny_carve(workspace, sel);
+    const dim3 grid(sel.grid), block(sel.threads);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(canny_grad_kernel, dim3(nb), dim3(256), 0, s, x, N, H, W, grad, mag);
-    hipLaunchKernelGGL(canny_nms_kernel, dim3(nb), dim3(256), 0, s, (const short2 *)grad, (const int *)mag, N, H, W, low, high, state);
+    KD_NOTE_PLUMBING(gs_kernel_name(sel.kernel));
+    hipLaunchKernelGGL(canny_grad_kernel, grid, block, 0, s, x, N, H, W, b.grad, b.mag);
+    hipLaunchKernelGGL(canny_nms_kernel, grid, block, 0, s, (const short2 *)b.grad, (const int *)b.mag, N, H, W, low, high, b.state);
     KD_CHECK_LAUNCH("kd_canny");
-    for (int i = 0; i < sweeps; ++i) {
-        if (hipMemsetAsync(changed, 0, sizeof(int), s) != hipSuccess) { kd_set_error("kd_canny: memset failed"); return KD_ERR_HIP; }
-        hipLaunchKernelGGL(canny_hyst_kernel, dim3(nb), dim3(256), 0, s, state, N, H, W, changed);
-    }
-    hipLaunchKernelGGL(canny_finish_kernel, dim3(nb), dim3(256), 0, s, (const unsigned char *)state, out, n);
-    KD_CHECK_LAUNCH("kd_canny(hysteresis)");
-    return KD_OK;
+    return canny_sweep_and_finish("kd_canny", "kd_canny(hysteresis)", sel, b.state, N, H, W, sweeps, out, changed, s);
 }
 
 extern "C" int kd_canny_continue(int32_t N, int32_t H, int32_t W, int32_t sweeps, float *out, int32_t *changed, void *workspace,
                                  size_t workspace_bytes, kd_stream_t stream)
 {
-    KD_REQUIRE(out && changed && workspace && N > 0 && H > 0 && W > 0 && sweeps > 0, KD_ERR_INVALID, "kd_canny_continue: bad argument");
-    KD_REQUIRE(workspace_bytes >= kd_canny_workspace(N, H, W), KD_ERR_WORKSPACE, "kd_canny_continue: workspace too small");
-    const long long n = (long long)N * H * W;
-    unsigned char *state = (unsigned char *)workspace + n * (sizeof(short2) + sizeof(int));
-    const int nb = blocks_for(n, 65536);
-    hipStream_t s = (hipStream_t)stream;
-    for (int i = 0; i < sweeps; ++i) {
-        if (hipMemsetAsync(changed, 0, sizeof(int), s) != hipSuccess) { kd_set_error("kd_canny_continue: memset failed"); return KD_ERR_HIP; }
-        hipLaunchKernelGGL(canny_hyst_kernel, dim3(nb), dim3(256), 0, s, state, N, H, W, changed);
-    }
-    hipLaunchKernelGGL(canny_finish_kernel, dim3(nb), dim3(256), 0, s, (const unsigned char *)state, out, n);
-    KD_CHECK_LAUNCH("kd_canny_continue");
-    return KD_OK;
+    const GsSel sel = gs_canny_continue(N, H, W, sweeps);
+    KD_REQUIRE(out && changed && workspace && sel.why != GS_WHY_SHAPE, KD_ERR_INVALID, "kd_canny_continue: bad argument");
+    KD_REQUIRE(workspace_bytes >= gs_canny_workspace(N, H, W), KD_ERR_WORKSPACE, "kd_canny_continue: workspace too small");
+    KD_NOTE_PLUMBING(gs_kernel_name(sel.kernel));
+    return canny_sweep_and_finish("kd_canny_continue", "kd_canny_continue", sel, canny_carve(workspace, sel).state, N, H, W, sweeps, out, changed,
+                                  (hipStream_t)stream);
 }
 
 extern "C" int kd_conv3x3_small(const void *x, int32_t ldx, const void *w, const float *bias, const void *res, int32_t ldres, void *y,
                                 int32_t ldy, int32_t N, int32_t H, int32_t W, int32_t C, int32_t relu, kd_stream_t stream)
 {
-    KD_REQUIRE(x && w && y && N > 0 && H > 0 && W > 0, KD_ERR_INVALID, "kd_conv3x3_small: bad argument");
-    KD_REQUIRE(C == 16 || C == 32 || C == 64, KD_ERR_UNSUPPORTED, "kd_conv3x3_small: C must be 16, 32 or 64 (got %d)", C);
-    KD_REQUIRE(ldx >= C && ldy >= C && ldx % 8 == 0 && ldy % 8 == 0 && kd_aligned16(x) && kd_aligned16(w) && kd_aligned16(y),
-               KD_ERR_INVALID, "kd_conv3x3_small: x / y need 16-B aligned pixels (ld %% 8)");
-    KD_REQUIRE(!res || (ldres >= C && ldres % 8 == 0 && kd_aligned16(res)), KD_ERR_INVALID,
-               "kd_conv3x3_small: res needs 16-B aligned pixels (ld %% 8)");
+    const GsSel sel = gs_conv3x3_small(x, ldx, w, res, ldres, y, ldy, N, H, W, C);
+    KD_REQUIRE(x && w && y && sel.why != GS_WHY_SHAPE, KD_ERR_INVALID, "kd_conv3x3_small: bad argument");
+    KD_REQUIRE(sel.why != GS_WHY_CHANNELS, KD_ERR_UNSUPPORTED, "kd_conv3x3_small: C must be 16, 32 or 64 (got %d)", C);
+    KD_REQUIRE(sel.why != GS_WHY_ALIGN, KD_ERR_INVALID, "kd_conv3x3_small: x / y need 16-B aligned pixels (ld %% 8)");
+    KD_REQUIRE(sel.why != GS_WHY_RES, KD_ERR_INVALID, "kd_conv3x3_small: res needs 16-B aligned pixels (ld %% 8)");
     KD_REQUIRE(x != y, KD_ERR_INVALID, "kd_conv3x3_small: y must not alias x");
+    KD_REQUIRE(sel.why != GS_WHY_TOO_LARGE, KD_ERR_UNSUPPORTED, "kd_conv3x3_small: image too large");
     SmallConvParams p;
     p.x = (const bf16_t *)x; p.w = (const bf16_t *)w; p.bias = bias; p.res = (const bf16_t *)res; p.y = (bf16_t *)y;
     p.ldx = ldx; p.ldres = ldres; p.ldy = ldy; p.N = N; p.H = H; p.W = W; p.relu = relu;
-    p.nsx = (W + SC_SEG - 1) / SC_SEG;
-    p.nsy = (H + SC_ROWS - 1) / SC_ROWS;
-    const long long blocks = (long long)N * p.nsx * p.nsy;
-    KD_REQUIRE(blocks <= 0x7fffffffLL, KD_ERR_UNSUPPORTED, "kd_conv3x3_small: image too large");
+    p.nsx = sel.nsx;
+    p.nsy = sel.nsy;
     hipStream_t s = (hipStream_t)stream;
-    const int lds = 4 * (SC_SEG + 2) * (C == 64 ? C * 2 + 16 : C * 2);
-    if (C == 64) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            if (hipFuncSetAttribute((const void *)conv3x3_small_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-                kd_set_error("kd_conv3x3_small: cannot reserve %d B of LDS", lds);
-                return KD_ERR_HIP;
-            }
-            attr_set = true;
-        }
+    int rc;
+    KD_NOTE_PLUMBING(gs_kernel_name(sel.kernel));
+    switch (sel.kernel) {
+    case GS_CONV3X3_64:
         KD_NOTE_KERNEL("conv3x3_small_kernel<64>");
-        hipLaunchKernelGGL(conv3x3_small_kernel<64>, dim3((unsigned)blocks), dim3(512), lds, s, p);
-    } else if (C == 32) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            if (hipFuncSetAttribute((const void *)conv3x3_small_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-                kd_set_error("kd_conv3x3_small: cannot reserve %d B of LDS", lds);
-                return KD_ERR_HIP;
-            }
-            attr_set = true;
-        }
-        hipLaunchKernelGGL(conv3x3_small_kernel<32>, dim3((unsigned)blocks), dim3(256), lds, s, p);
-    } else {
-        hipLaunchKernelGGL(conv3x3_small_kernel<16>, dim3((unsigned)blocks), dim3(256), lds, s, p);
+        rc = launch_conv3x3_small<64>(sel, p, s);
+        break;
+    case GS_CONV3X3_32: rc = launch_conv3x3_small<32>(sel, p, s); break;
+    default: rc = launch_conv3x3_small<16>(sel, p, s); break;
     }
+    if (rc != KD_OK) return rc;
     KD_CHECK_LAUNCH("kd_conv3x3_small");
     return KD_OK;
 }
@@ -753,17 +779,19 @@ extern "C" int kd_conv3x3_small(const void *x, int32_t ldx, const void *w, const
 extern "C" int kd_pointwise_small(const void *x, int32_t ldx, const float *w, const float *bias, void *y, int32_t ldy, int64_t npix,
                                   int32_t Cin, int32_t Cout, kd_stream_t stream)
 {
-    KD_REQUIRE(x && w && y && npix > 0, KD_ERR_INVALID, "kd_pointwise_small: bad argument");
-    KD_REQUIRE((Cin == 64 && Cout == 32) || (Cin == 32 && Cout == 16) || (Cin == 16 && Cout == 8), KD_ERR_UNSUPPORTED,
+    const GsSel sel = gs_pointwise_small(x, ldx, y, ldy, npix, Cin, Cout);
+    KD_REQUIRE(x && w && y && sel.why != GS_WHY_SHAPE, KD_ERR_INVALID, "kd_pointwise_small: bad argument");
+    KD_REQUIRE(sel.why != GS_WHY_CHANNELS, KD_ERR_UNSUPPORTED,
                "kd_pointwise_small: (Cin, Cout) must be (64, 32), (32, 16) or (16, 8) (got %d, %d)", Cin, Cout);
-    KD_REQUIRE(ldx >= Cin && ldy >= Cout && ldx % 8 == 0 && ldy % 4 == 0 && kd_aligned16(x) && ((uintptr_t)y % 8) == 0, KD_ERR_INVALID,
+    KD_REQUIRE(sel.why != GS_WHY_ALIGN, KD_ERR_INVALID,
                "kd_pointwise_small: x needs 16-B aligned pixels (ldx %% 8), y 8-B aligned channel quads (ldy %% 4)");
-    const long long waves = (npix + 15) / 16;
-    const int nb = blocks_for((waves + 3) / 4 * 256, 256 * 32);
     hipStream_t s = (hipStream_t)stream;
-#define KD_PWS(CI, CO) hipLaunchKernelGGL((pointwise_small_kernel<CI, CO>), dim3(nb), dim3(256), 0, s, (const bf16_t *)x, ldx, w, bias, (bf16_t *)y, ldy, (long long)npix)
-    if (Cin == 64) KD_PWS(64, 32); else if (Cin == 32) KD_PWS(32, 16); else KD_PWS(16, 8);
-#undef KD_PWS
+    KD_NOTE_PLUMBING(gs_kernel_name(sel.kernel));
+    switch (sel.kernel) {
+    case GS_POINTWISE_64_32: launch_pointwise_small<64, 32>(sel, s, x, ldx, w, bias, y, ldy, npix); break;
+    case GS_POINTWISE_32_16: launch_pointwise_small<32, 16>(sel, s, x, ldx, w, bias, y, ldy, npix); break;
+    default: launch_pointwise_small<16, 8>(sel, s, x, ldx, w, bias, y, ldy, npix); break;
+    }
     KD_CHECK_LAUNCH("kd_pointwise_small");
     return KD_OK;
 }

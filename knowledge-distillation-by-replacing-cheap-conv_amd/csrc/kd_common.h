@@ -58,7 +58,9 @@ void kd_note_kernel(const char *name);
 // names of loss_select.h's table (loss_kernel_name); tests/test_loss_dispatch_host.py holds them to the same rule.  So do the
 // NHWC BatchNorm entry points (bn_nhwc_core.h, dense_ops.hip) with the names of bn_select.h's table (bn_kernel_name), and the
 // average-pool entry points of dense_ops.hip for their float4 / scalar choice, with literals of their own;
-// tests/test_nhwc_support_host.py holds the fp32 names and the pool literals to a row each.
+// tests/test_nhwc_support_host.py holds the fp32 names and the pool literals to a row each.  The Gated-SCNN shape-stream entry
+// points (gscnn_ops.hip, gscnn_bwd.hip) note the names of gscnn_select.h's table (gs_kernel_name);
+// tests/test_gscnn_select_host.py requires a row of tests/_shape_stream_cases.py for every one of them.
 void kd_note_plumbing(const char *name);
 #define KD_NOTE_PLUMBING(name) kd_note_plumbing(name)
 

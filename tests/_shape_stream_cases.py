@@ -2,8 +2,10 @@
 csrc/gscnn_bwd.hip), the seeded inputs of each row and its float64 reference on the CPU, written from the module expressions
 (models/gscnn.py; the reference's gate_spatial_conv.py:50-60 and gscnn.py:308-314).  No reference calls the library; nothing
 here touches the device.  tests/test_shape_stream_host.py checks, without a GPU, that every reference runs and has the declared
-shape, that the rows reach the branches they claim (the dispatch rules are restated below and their constants read out of
-gscnn_bwd.hip), and that the Canny fixtures need more hysteresis rounds than the old 8 x 64 sweep budget.
+shape, that the rows reach the branches they claim (the dispatch rules are restated below, their constants taken from
+csrc/gscnn_select.h compiled for the host), and that the Canny fixtures need more hysteresis rounds than the old 8 x 64 sweep
+budget.  Every row names the kernel its call notes (`kernel`, for the gated conv `slot`: slot_name); tests/test_gscnn_select_host.py
+holds those names and the restated rules against the compiled selectors.
 
 `build(case)` returns (inputs, reference): inputs are float32 numpy carriers already rounded to the storage dtype the row
 gives that operand, references are float64.  Pixels are flattened: activations are (npix, C) unless a row says otherwise.
@@ -37,6 +39,8 @@ CASES = []
 
 
 def case(op, cid, **kw):
+    """A row.  `kernel` is the name the row's call leaves in the library's plumbing slot (csrc/gscnn_select.h's table; the
+    gated-conv rows keep the conv log's name there and carry the slot's in `slot`, see slot_name)."""
     c = dict(op=op, id=f"{op}:{cid}", **kw)
     CASES.append(c)
     return c
@@ -51,7 +55,7 @@ def ids(cs):
 
 
 # ============================================================================================================ kd_small_linear
-SL_TEMPLATES = (8, 16, 24, 40, 72)        # small_linear_kernel<COP>; tests/test_shape_stream_host.py reads them from the source
+SL_TEMPLATES = (8, 16, 24, 40, 72)        # small_linear_kernel<COP>; tests/test_shape_stream_host.py holds them to the compiled header
 SL_MAXC = 72
 
 
@@ -61,16 +65,21 @@ def sl_template(cout, templates=SL_TEMPLATES):
 
 
 SL_PIX = 2 * 5 * 7
-for _co in (1, 8, 9, 16, 17, 24, 25, 40, 41, 72):      # both sides of every template boundary
+def _sl(cid, template, **kw):
+    return case("small_linear", cid, kernel=f"small_linear_kernel<{template}>", **kw)
+
+
+# both sides of every template boundary: (Cout, the template the row is written for)
+for _co, _t in ((1, 8), (8, 8), (9, 16), (16, 16), (17, 24), (24, 24), (25, 40), (40, 40), (41, 72), (72, 72)):
     for _ci in (1, 33, 72):
-        case("small_linear", f"co{_co}-ci{_ci}", cin=_ci, cout=_co, x_dt="f32", x_slice=False, bias=False, relu=False, acc=None,
+        _sl(f"co{_co}-ci{_ci}", _t, cin=_ci, cout=_co, x_dt="f32", x_slice=False, bias=False, relu=False, acc=None,
              mask=False)
-for _co in (7, 13, 19, 33, 57):                         # one row of each template for every operand form
-    case("small_linear", f"co{_co}-bf16-x-slice", cin=33, cout=_co, x_dt="bf16", x_slice=True, bias=False, relu=False, acc=None, mask=False)
-    case("small_linear", f"co{_co}-bias-relu", cin=33, cout=_co, x_dt="f32", x_slice=False, bias=True, relu=True, acc=None, mask=False)
-    case("small_linear", f"co{_co}-acc-f32-slice", cin=33, cout=_co, x_dt="f32", x_slice=False, bias=True, relu=False, acc="f32", mask=False)
-    case("small_linear", f"co{_co}-acc-bf16-slice", cin=33, cout=_co, x_dt="bf16", x_slice=True, bias=False, relu=False, acc="bf16", mask=False)
-    case("small_linear", f"co{_co}-mask-slice", cin=33, cout=_co, x_dt="f32", x_slice=False, bias=False, relu=False, acc="f32", mask=True)
+for _co, _t in ((7, 8), (13, 16), (19, 24), (33, 40), (57, 72)):     # one row of each template for every operand form
+    _sl(f"co{_co}-bf16-x-slice", _t, cin=33, cout=_co, x_dt="bf16", x_slice=True, bias=False, relu=False, acc=None, mask=False)
+    _sl(f"co{_co}-bias-relu", _t, cin=33, cout=_co, x_dt="f32", x_slice=False, bias=True, relu=True, acc=None, mask=False)
+    _sl(f"co{_co}-acc-f32-slice", _t, cin=33, cout=_co, x_dt="f32", x_slice=False, bias=True, relu=False, acc="f32", mask=False)
+    _sl(f"co{_co}-acc-bf16-slice", _t, cin=33, cout=_co, x_dt="bf16", x_slice=True, bias=False, relu=False, acc="bf16", mask=False)
+    _sl(f"co{_co}-mask-slice", _t, cin=33, cout=_co, x_dt="f32", x_slice=False, bias=False, relu=False, acc="f32", mask=True)
 SL_REFUSED = [(73, 8), (8, 73)]                         # (Cin, Cout): one channel past SL_MAXC on either side
 
 
@@ -120,7 +129,7 @@ SW_PLAN_ONLY_NPIX = [4096 * 1024, 4096 * 1024 + 1024, 4096 * 1024 * 3 + 77]
 
 
 def _sw(cid, ca, cb, npix, a_dt="f32", b_dt="f32", sliced=False, bias=True, acc=False, twice=False):
-    return case("small_wgrad", cid, ca=ca, cb=cb, npix=npix, a_dt=a_dt, b_dt=b_dt, sliced=sliced, bias=bias, acc=acc, twice=twice)
+    return case("small_wgrad", cid, kernel="small_wgrad_partial_kernel", ca=ca, cb=cb, npix=npix, a_dt=a_dt, b_dt=b_dt, sliced=sliced, bias=bias, acc=acc, twice=twice)
 
 
 for _ca, _cb in SW_PAIRS:                                # every channel pair at one block with a partial chunk and at two blocks
@@ -167,7 +176,7 @@ for _C in (8, 16, 32):
     for _dt in ("f32", "bf16"):
         for _outs in GM_OUTS:
             for _shape in ((2, 6, 5), (1, 1, 1)):
-                case("gate_mix_bwd", f"C{_C}-{_dt}-{_outs}-{'x'.join(map(str, _shape))}", C=_C, dt=_dt, outs=_outs, shape=_shape)
+                case("gate_mix_bwd", f"C{_C}-{_dt}-{_outs}-{'x'.join(map(str, _shape))}", C=_C, dt=_dt, outs=_outs, shape=_shape, kernel="gate_mix_bwd_kernel")
 
 
 def build_gate_mix_bwd(c):
@@ -190,7 +199,7 @@ def build_gate_mix_bwd(c):
 for _op in ("edge_attention", "edge_attention_bwd"):
     for _dt in ("f32", "bf16"):
         for _n in (1, 255, 256, 257):                   # one thread, a ragged block, a full block, a second block
-            case(_op, f"{_dt}-n{_n}", dt=_dt, npix=_n)
+            case(_op, f"{_dt}-n{_n}", dt=_dt, npix=_n, kernel=f"edge_attention_kernel<{_dt}>" if _op == "edge_attention" else "edge_attention_bwd_kernel")
 
 
 def _edge_operands(c, r):
@@ -227,7 +236,7 @@ EA_SIZES = [((10, 14), (4, 6)),      # shrinking (the ratio the old test had)
 for (_hin, _hout) in EA_SIZES:
     for _C in (8, 16):
         for _dt in ("f32", "bf16"):
-            case("edge_aspp", f"{_hin[0]}x{_hin[1]}to{_hout[0]}x{_hout[1]}-C{_C}-{_dt}", hin=_hin, hout=_hout, C=_C, dt=_dt, N=2)
+            case("edge_aspp", f"{_hin[0]}x{_hin[1]}to{_hout[0]}x{_hout[1]}-C{_C}-{_dt}", hin=_hin, hout=_hout, C=_C, dt=_dt, N=2, kernel=f"edge_aspp_kernel<{_dt}>")
 
 
 def build_edge_aspp(c):
@@ -247,7 +256,7 @@ for _C in (8, 32, 64):
     for _dt in ("f32", "bf16"):
         for _acc in (True, False):
             for _sl in (False, True):
-                case("rank1_add", f"C{_C}-{_dt}-acc{int(_acc)}-{'slice' if _sl else 'dense'}", C=_C, dt=_dt, acc=_acc, sliced=_sl)
+                case("rank1_add", f"C{_C}-{_dt}-acc{int(_acc)}-{'slice' if _sl else 'dense'}", C=_C, dt=_dt, acc=_acc, sliced=_sl, kernel=f"rank1_add_kernel<{_dt}>")
 R1_SHAPE = (2, 4, 6)
 R1_REFUSED_C = 12
 
@@ -266,10 +275,17 @@ def build_rank1_add(c):
 GC_NPIX = {1: (1, 1, 1), 3: (1, 1, 3), 16: (1, 2, 8), 17: (1, 1, 17), 546: (2, 13, 21)}
 for _C in (8, 16, 32):
     for _n in GC_NPIX:      # fewer pixels than a thread's group (4, or 2 at C = 32); one 16-pixel MFMA group, ragged ones
-        case("gated_conv", f"C{_C}-n{_n}-f32", C=_C, npix=_n, dt="f32", kernel="gated_conv_kernel", round_w=False)
-        case("gated_conv", f"C{_C}-n{_n}-bf16", C=_C, npix=_n, dt="bf16", kernel="gated_conv_mfma_kernel", round_w=True)
+        case("gated_conv", f"C{_C}-n{_n}-f32", C=_C, npix=_n, dt="f32", kernel="gated_conv_kernel", slot=f"gated_conv_kernel<f32,{_C}>", round_w=False)
+        case("gated_conv", f"C{_C}-n{_n}-bf16", C=_C, npix=_n, dt="bf16", kernel="gated_conv_mfma_kernel", slot=f"gated_conv_mfma_kernel<{_C}>", round_w=True)
 # the bf16 VALU kernel (KDCC_GATED_MFMA=0, read once per process): run by a child process against the bf16 rows' reference
 GC_VALU_BF16 = [c for c in CASES if c["op"] == "gated_conv" and c["dt"] == "bf16" and c["npix"] == 546]
+
+
+def slot_name(c, mfma=True):
+    """The name the row's call leaves in the plumbing slot; mfma=False: in the child process that runs GC_VALU_BF16."""
+    if c["op"] == "gated_conv" and c["dt"] == "bf16" and not mfma:
+        return f"gated_conv_kernel<bf16,{c['C']}>"
+    return c.get("slot", c["kernel"])
 
 
 def gate_params(c):
@@ -303,8 +319,8 @@ def build_gated_conv(c):
 PW_NPIX = {1: (1, 1, 1), 15: (1, 3, 5), 16: (1, 2, 8), 17: (1, 1, 17)}
 for _ci, _co in ((64, 32), (32, 16), (16, 8)):
     for _n in PW_NPIX:
-        case("pointwise_small", f"{_ci}to{_co}-n{_n}", cin=_ci, cout=_co, npix=_n, bias=True)
-    case("pointwise_small", f"{_ci}to{_co}-n17-nobias", cin=_ci, cout=_co, npix=17, bias=False)
+        case("pointwise_small", f"{_ci}to{_co}-n{_n}", cin=_ci, cout=_co, npix=_n, bias=True, kernel=f"pointwise_small_kernel<{_ci},{_co}>")
+    case("pointwise_small", f"{_ci}to{_co}-n17-nobias", cin=_ci, cout=_co, npix=17, bias=False, kernel=f"pointwise_small_kernel<{_ci},{_co}>")
 PW_OUT_PAD, PW_OUT_OFF = 12, 4      # the output: a slice at element 4 of a (Cout + 12)-wide buffer: ldy % 4 == 0, ldy % 8 != 0
 
 
@@ -335,11 +351,13 @@ def _canny_line(W=1400, H=9):
     return img
 
 
-case("canny", "line-seed-right", image="a")            # grows against the index order, one neighbour per Jacobi round
-case("canny", "line-seed-bottom", image="b")           # the transpose: a vertical chain seeded at its lower end
-case("canny", "line-seed-left", image="c")             # the mirror image: grows with the index order
+# `kernel`: what kd_canny notes; `then`: what the kd_canny_continue rounds after it note (the line fixtures need them, the noise
+# images may or may not)
+case("canny", "line-seed-right", image="a", kernel="canny_grad_kernel", then="canny_hyst_kernel")            # grows against the index order, one neighbour per Jacobi round
+case("canny", "line-seed-bottom", image="b", kernel="canny_grad_kernel", then="canny_hyst_kernel")           # the transpose: a vertical chain seeded at its lower end
+case("canny", "line-seed-left", image="c", kernel="canny_grad_kernel", then="canny_hyst_kernel")             # the mirror image: grows with the index order
 for _h, _w in ((1, 1), (1, 7), (2, 2), (3, 5)):        # border replication on images smaller than the 3x3 window; N = 2
-    case("canny", f"noise-{_h}x{_w}", image="noise", hw=(_h, _w))
+    case("canny", f"noise-{_h}x{_w}", image="noise", hw=(_h, _w), kernel="canny_grad_kernel", then="canny_hyst_kernel")
 
 
 def build_canny(c):
@@ -354,6 +372,15 @@ def build_canny(c):
         x = np.ascontiguousarray(np.broadcast_to(g, (1, 3) + g.shape))
     out = [orc.canny_ref(im.transpose(1, 2, 0).astype(np.uint8), CANNY_LOW, CANNY_HIGH, return_rounds=True) for im in x]
     return {"x": x}, {"edges": np.stack([o[0] for o in out]), "rounds": max(o[1] for o in out)}
+
+
+# ============================================================================================================ kd_conv3x3_small
+# Selection-only rows (not in CASES: no reference here): the calls tests/test_gscnn_gpu.py::test_conv3x3_small_vs_oracle makes, dense
+# and as channel slices of 80-channel buffers, which is where the values are checked and the slot asserted.
+C3_SHAPES = [(1, 16, 256), (2, 37, 45), (1, 20, 300), (1, 33, 513), (1, 3, 7)]
+C3_LD = 80
+C3_ROWS = [dict(op="conv3x3_small", id=f"conv3x3_small:C{_C}-{'x'.join(map(str, _s))}", C=_C, shape=_s, kernel=f"conv3x3_small_kernel<{_C}>")
+           for _C in (16, 32, 64) for _s in C3_SHAPES]
 
 
 BUILDERS = {"small_linear": build_small_linear, "small_wgrad": build_small_wgrad, "gate_mix_bwd": build_gate_mix_bwd,

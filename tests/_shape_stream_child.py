@@ -1,7 +1,8 @@
 """kd_gated_conv on a row of tests/_shape_stream_cases.py, shared by tests/test_shape_stream_gpu.py and by the child process it
 starts for the bf16 VALU kernel: KDCC_GATED_MFMA is read once per process, so `python tests/_shape_stream_child.py` (with
 KDCC_GATED_MFMA=0 in its environment) is the only way to reach gated_conv_kernel<bf16_t, C>.  The child runs the three C values
-at 546 pixels against the same float64 reference under the project's bf16 bars and asserts the kernel log."""
+at 546 pixels against the same float64 reference under the project's bf16 bars and asserts the kernel log and the plumbing slot
+(the name csrc/gscnn_select.h, compiled for the host, gives with the switch off)."""
 import os
 import sys
 
@@ -37,12 +38,17 @@ def main():
     import kdcc_amd  # noqa: F401
     from kdcc_amd import ops
     import _shape_stream_cases as S
+    from kdcc_amd import _lib
+    from test_gscnn_select_host import load, select
     from test_ops_gpu import assert_close
     assert os.environ.get("KDCC_GATED_MFMA") == "0"
+    sel_lib = load()
     for c in S.GC_VALU_BF16:
         inp, ref = S.build(c)
         got, counts = run_gated_conv(ops, c, inp)
         assert counts.get("gated_conv_kernel", 0) == 1 and "gated_conv_mfma_kernel" not in counts, counts
+        slot = _lib.last_plumbing_kernel()
+        assert slot == select(sel_lib, c, mfma=False)["name"] == S.slot_name(c, mfma=False), slot
         assert_close(got, ref["y"], "bf16", c["id"] + " (VALU)")
         print("ok", c["id"], counts)
 

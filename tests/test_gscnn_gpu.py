@@ -106,8 +106,13 @@ def test_pointwise_small_vs_reference(cin, cout):
 @pytest.mark.parametrize("shape", [(1, 16, 256), (2, 37, 45), (1, 20, 300), (1, 33, 513), (1, 3, 7)])
 def test_conv3x3_small_vs_oracle(C, shape):
     """kd_conv3x3_small (the 16 / 32-channel BasicBlock convs of the shape stream, Resnet.py:64-99) against the oracle's conv on
-    bf16-rounded operands: bias + residual + ReLU, views into wider buffers, ragged segments and row groups."""
-    from kdcc_amd import ops
+    bf16-rounded operands: bias + residual + ReLU, views into wider buffers, ragged segments and row groups.  Both calls note the
+    instantiation csrc/gscnn_select.h (compiled for the host) selects for them: the C3_ROWS of tests/_shape_stream_cases.py."""
+    import _shape_stream_cases as S
+    from kdcc_amd import _lib, ops
+    from test_gscnn_select_host import load, select
+    row, = [c for c in S.C3_ROWS if (c["C"], c["shape"]) == (C, shape)]
+    sel = load()
     from kdcc_amd._lib import KD_PACK_FWD
     N, H, W = shape
     rng = np.random.default_rng(100 + C + H + W)
@@ -120,6 +125,7 @@ def test_conv3x3_small_vs_oracle(C, shape):
     conv = orc.conv2d_fwd(x, w, pad=1)
     # plain, dense
     y = ops.conv3x3_small(nhwc(x), wp, relu=False)
+    assert _lib.last_plumbing_kernel() == select(sel, row)["name"] == row["kernel"]
     ref = conv
     assert np.abs(y.float().cpu().numpy().transpose(0, 3, 1, 2) - ref).max() < 1.5e-2 * np.abs(ref).max()
     # bias + residual + relu, input / residual / output as channel slices of 64-channel buffers
@@ -127,6 +133,7 @@ def test_conv3x3_small_vs_oracle(C, shape):
     rb = torch.zeros((N, H, W, 80), dtype=torch.bfloat16, device="cuda"); rb[..., 8:8 + C] = nhwc(r)
     ob = torch.full((N, H, W, 80), 7.0, dtype=torch.bfloat16, device="cuda")
     ops.conv3x3_small(xb[..., :C], wp, torch.from_numpy(b).cuda(), res=rb[..., 8:8 + C], relu=True, out=ob[..., :C])
+    assert _lib.last_plumbing_kernel() == select(sel, row, dense=False)["name"] == row["kernel"]
     ref = np.maximum(conv + b[None, :, None, None] + r, 0)
     assert np.abs(ob[..., :C].float().cpu().numpy().transpose(0, 3, 1, 2) - ref).max() < 1.5e-2 * max(np.abs(ref).max(), 1e-6)
     assert float((ob[..., C:] - 7.0).abs().max()) == 0.0   # nothing written outside the slice

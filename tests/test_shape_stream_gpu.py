@@ -5,7 +5,9 @@ Acceptance is per element: test_ops_gpu.assert_close (max error over the referen
 bf16 storage, plus its relative-L2 bound), by the storage type of the OUTPUT: the references see the operands already rounded
 to their storage type, so a kernel with fp32 arithmetic and an fp32 output is held to the fp32 bar whatever its operands are
 stored as.  fp32 kd_small_wgrad keeps the 1e-4 norm bar of test_gscnn_gpu.py as well.  Every case that writes a channel slice
-fills the buffer with 7.0 first and asserts the rest untouched.  Canny is bit for bit.
+fills the buffer with 7.0 first and asserts the rest untouched.  Canny is bit for bit.  Every row also asserts the kernel it reached
+(kd_debug_last_plumbing_kernel) against what csrc/gscnn_select.h, compiled for the host, selects for the row's call; a refused
+call leaves that slot and its output alone.
 """
 import os
 import subprocess
@@ -18,6 +20,7 @@ import torch
 
 import _shape_stream_cases as S
 from _shape_stream_child import run_gated_conv
+from test_gscnn_select_host import REFUSED, call, load, select
 from test_ops_gpu import assert_close
 
 pytestmark = pytest.mark.gpu
@@ -31,6 +34,31 @@ def K():
     from kdcc_amd import ops
     assert torch.cuda.is_available()
     return ops
+
+
+@pytest.fixture(scope="module")
+def SEL():
+    return load()
+
+
+def reached(SEL, c, sel=None):
+    """The call the row just made noted the kernel the compiled selector names for it (and the row claims)."""
+    from kdcc_amd import _lib
+    want = (sel or select(SEL, c))["name"]
+    got = _lib.last_plumbing_kernel()
+    assert got == want, f"{c['id']}: the launch went to {got}, gscnn_select.h selects {want}"
+    if sel is None:
+        assert want == S.slot_name(c), f"{c['id']}: this row is meant to cover {S.slot_name(c)}"
+
+
+def other_family_marker(K):
+    """Leaves a name of another entry point in the slot (the one-pixel edge_attention row) and returns it."""
+    from kdcc_amd import _lib
+    c = S.cases_of("edge_attention")[0]
+    inp, _ = S.build(c)
+    K.edge_attention(cs_view(inp, c["dt"]), dev(inp["canny"]), dev(inp["w"]))
+    assert _lib.last_plumbing_kernel() == c["kernel"]
+    return c["kernel"]
 
 
 def dev(a, dt="f32"):
@@ -68,7 +96,7 @@ SL = S.cases_of("small_linear")
 
 
 @pytest.mark.parametrize("c", SL, ids=S.ids(SL))
-def test_small_linear(K, c):
+def test_small_linear(K, SEL, c):
     inp, ref = S.build(c)
     x, _ = view(inp["x"], c["x_dt"], c["x_slice"])
     kw = dict(relu=c["relu"], bias=dev(inp["bias"]) if c["bias"] else None)
@@ -82,16 +110,21 @@ def test_small_linear(K, c):
     else:
         out = K.small_linear(x, dev(inp["w"]), out_dtype=torch.float32, **kw)
         odt = "f32"
+    reached(SEL, c)
     assert tuple(out.shape) == (S.SL_PIX, c["cout"])
     assert_close(host(out), ref["y"], odt, c["id"])
 
 
 @pytest.mark.parametrize("cin,cout", S.SL_REFUSED)
-def test_small_linear_refuses_more_than_72_channels(K, cin, cout):
-    from kdcc_amd._lib import KdccError
+def test_small_linear_refuses_more_than_72_channels(K, SEL, cin, cout):
+    from kdcc_amd import _lib
     x, w = torch.zeros((4, cin), device="cuda"), torch.zeros((cout, cin), device="cuda")
-    with pytest.raises(KdccError):
-        K.small_linear(x, w)
+    out = torch.full((4, cout), 7.0, device="cuda")
+    assert call(SEL, "small_linear", 0, cin, cin, 0, cout, cout, 4, 0, 0)["name"] == REFUSED
+    marker = other_family_marker(K)
+    with pytest.raises(_lib.KdccError):
+        K.small_linear(x, w, out=out)
+    assert _lib.last_plumbing_kernel() == marker and bool((out == 7.0).all()), "a refused call launched something"
 
 
 # ----------------------------------------------------------------------------------------------------------- kd_small_wgrad
@@ -99,7 +132,7 @@ SW = S.cases_of("small_wgrad")
 
 
 @pytest.mark.parametrize("c", SW, ids=S.ids(SW))
-def test_small_wgrad(K, c):
+def test_small_wgrad(K, SEL, c):
     inp, ref = S.build(c)
     a, _ = view(inp["a"], c["a_dt"], c["sliced"])
     b, _ = view(inp["b"], c["b_dt"], c["sliced"])
@@ -110,6 +143,7 @@ def test_small_wgrad(K, c):
             kw = dict(dw=dev(inp["dw0"]), db=dev(inp["db0"]) if c["bias"] else None, accumulate=True)
         return K.small_wgrad(a, b, want_bias=c["bias"], **kw)
     dw, db = run()
+    reached(SEL, c)
     assert tuple(dw.shape) == (c["cb"], c["ca"]) and dw.dtype == torch.float32
     both_f32 = c["a_dt"] == c["b_dt"] == "f32"
     for name, got in (("dw", dw), ("db", db)):
@@ -128,8 +162,8 @@ def test_small_wgrad(K, c):
 
 @pytest.mark.parametrize("npix", sorted({c["npix"] for c in SW}) + S.SW_PLAN_ONLY_NPIX)
 def test_small_wgrad_workspace_follows_the_block_rule(K, npix):
-    """kd_small_wgrad_workspace is one partial per block: the block count of small_wgrad_blocks (restated in the table, constants
-    pinned to the source by test_shape_stream_host.py) at every pixel count of the table and where the 1024-block cap binds."""
+    """kd_small_wgrad_workspace is one partial per block: the block count of the small-wgrad rule (restated in the table, held to the
+    compiled header by test_gscnn_select_host.py) at every pixel count of the table and where the 1024-block cap binds."""
     from kdcc_amd import _lib
     for ca, cb in ((33, 33), (72, 1)):
         assert _lib.lib().kd_small_wgrad_workspace(ca, cb, npix) == S.sw_workspace(ca, cb, npix), (ca, cb, npix, S.sw_blocks(npix))
@@ -140,11 +174,12 @@ GM = S.cases_of("gate_mix_bwd")
 
 
 @pytest.mark.parametrize("c", GM, ids=S.ids(GM))
-def test_gate_mix_bwd(K, c):
+def test_gate_mix_bwd(K, SEL, c):
     inp, ref = S.build(c)
     feat, _ = view(inp["feat"], c["dt"], True)
     gv = dev(inp["gv"]) if "gv" in inp else None
     gfeat, ga, v = K.gate_mix_bwd(feat, dev(inp["a"]), gv=gv, want_v=c["outs"] != "grads-only")
+    reached(SEL, c)
     got = {"gfeat": gfeat, "ga": ga, "v": v}
     for name in ("gfeat", "ga", "v"):
         if name in ref:
@@ -165,9 +200,10 @@ EA = S.cases_of("edge_attention")
 
 
 @pytest.mark.parametrize("c", EA, ids=S.ids(EA))
-def test_edge_attention(K, c):
+def test_edge_attention(K, SEL, c):
     inp, ref = S.build(c)
     acts = K.edge_attention(cs_view(inp, c["dt"]), dev(inp["canny"]), dev(inp["w"]))
+    reached(SEL, c)
     assert tuple(acts.shape) == tuple(ref["acts"].shape) and acts.dtype == torch.float32
     assert_close(host(acts), ref["acts"], "f32", c["id"])
 
@@ -176,9 +212,10 @@ EB = S.cases_of("edge_attention_bwd")
 
 
 @pytest.mark.parametrize("c", EB, ids=S.ids(EB))
-def test_edge_attention_bwd(K, c):
+def test_edge_attention_bwd(K, SEL, c):
     inp, ref = S.build(c)
     g_t, g_s, eoc = K.edge_attention_bwd(cs_view(inp, c["dt"]), dev(inp["canny"]), dev(inp["w"]), dev(inp["g"]))
+    reached(SEL, c)
     assert tuple(eoc.shape) == tuple(ref["eo"].shape) + (2,)
     assert_close(host(g_t), ref["g_t"], "f32", f"{c['id']} g_t")
     assert_close(host(g_s), ref["g_s"], "f32", f"{c['id']} g_s")
@@ -191,12 +228,13 @@ EP = S.cases_of("edge_aspp")
 
 
 @pytest.mark.parametrize("c", EP, ids=S.ids(EP))
-def test_edge_aspp(K, c):
+def test_edge_aspp(K, SEL, c):
     inp, ref = S.build(c)
     C = c["C"]
     buf = torch.full((c["N"],) + c["hout"] + (C + 32,), 7.0, dtype=DT[c["dt"]], device="cuda")
     out = buf[..., 16:16 + C]                                                               # the middle slice
     K.edge_aspp(dev(inp["acts"]), dev(inp["w"]), dev(inp["scale"]), dev(inp["shift"]), out)
+    reached(SEL, c)
     untouched(out, buf, off=16)
     assert_close(host(out), ref["y"], c["dt"], c["id"])
 
@@ -206,19 +244,24 @@ R1 = S.cases_of("rank1_add")
 
 
 @pytest.mark.parametrize("c", R1, ids=S.ids(R1))
-def test_rank1_add(K, c):
+def test_rank1_add(K, SEL, c):
     inp, ref = S.build(c)
     y, buf = view(inp["y0"], c["dt"], c["sliced"])
     K.rank1_add(y, dev(inp["g"]).reshape(-1), dev(inp["w"]), accumulate=c["acc"])
+    reached(SEL, c)
     untouched(y, buf)
     assert_close(host(y), ref["y"], c["dt"], c["id"])
 
 
-def test_rank1_add_refuses_channel_counts_that_are_no_multiple_of_8(K):
-    from kdcc_amd._lib import KdccError
+def test_rank1_add_refuses_channel_counts_that_are_no_multiple_of_8(K, SEL):
+    from kdcc_amd import _lib
     C = S.R1_REFUSED_C
-    with pytest.raises(KdccError):
-        K.rank1_add(torch.zeros(S.R1_SHAPE + (C,), device="cuda"), torch.zeros(S.R1_SHAPE, device="cuda").reshape(-1), torch.zeros(C, device="cuda"))
+    y = torch.full(S.R1_SHAPE + (C,), 7.0, device="cuda")
+    assert call(SEL, "rank1_add", 0, y.data_ptr(), C, 0x10000, C, y.numel() // C)["name"] == REFUSED
+    marker = other_family_marker(K)
+    with pytest.raises(_lib.KdccError):
+        K.rank1_add(y, torch.zeros(S.R1_SHAPE, device="cuda").reshape(-1), torch.zeros(C, device="cuda"))
+    assert _lib.last_plumbing_kernel() == marker and bool((y == 7.0).all()), "a refused call launched something"
 
 
 # ---------------------------------------------------------------------------------------------------------------- kd_gated_conv
@@ -226,9 +269,10 @@ GC = S.cases_of("gated_conv")
 
 
 @pytest.mark.parametrize("c", GC, ids=S.ids(GC))
-def test_gated_conv(K, c):
+def test_gated_conv(K, SEL, c):
     inp, ref = S.build(c)
     got, counts = run_gated_conv(K, c, inp)
+    reached(SEL, c)
     assert counts == {c["kernel"]: 1}, f"{c['id']}: the launch went to {counts}, this row is meant to cover {c['kernel']}"
     assert_close(got, ref["y"], c["dt"], c["id"])
 
@@ -249,7 +293,7 @@ PW = S.cases_of("pointwise_small")
 
 
 @pytest.mark.parametrize("c", PW, ids=S.ids(PW))
-def test_pointwise_small(K, c):
+def test_pointwise_small(K, SEL, c):
     inp, ref = S.build(c)
     ci, co = c["cin"], c["cout"]
     shape = S.PW_NPIX[c["npix"]]
@@ -258,6 +302,7 @@ def test_pointwise_small(K, c):
     ob = torch.full(shape + (co + S.PW_OUT_PAD,), 7.0, dtype=torch.bfloat16, device="cuda")
     out = ob[..., S.PW_OUT_OFF:S.PW_OUT_OFF + co]
     K.pointwise_small(xb[..., :ci], dev(inp["w"]), dev(inp["bias"]) if c["bias"] else None, out=out)
+    reached(SEL, c)
     untouched(out, ob, off=S.PW_OUT_OFF)
     assert_close(host(out), ref["y"], "bf16", c["id"])
 
@@ -267,13 +312,17 @@ CN = S.cases_of("canny")
 
 
 @pytest.mark.parametrize("c", CN, ids=S.ids(CN))
-def test_canny_reaches_the_hysteresis_fixed_point(K, c):
+def test_canny_reaches_the_hysteresis_fixed_point(K, SEL, c):
     """ops.canny with its default sweeps / max_rounds == oracle.canny_ref bit for bit: the line fixtures hang on one strong seed at
     the far end of a 1398-pixel weak chain, which takes canny_ref 1398 Jacobi rounds (more than the 8 x 64 sweeps ops.canny used to
     stop at, test_shape_stream_host.py)."""
     inp, ref = S.build(c)
     t0 = time.perf_counter()
     got, rounds = K.canny(dev(inp["x"]), S.CANNY_LOW, S.CANNY_HIGH, return_rounds=True)
+    N, H, W = got.shape
+    first, later = select(SEL, c), call(SEL, "canny_continue", N, H, W, 8)
+    assert (first["name"], later["name"]) == (c["kernel"], c["then"])
+    reached(SEL, c, first if rounds == 1 else later)          # kd_canny, then kd_canny_continue once per further round
     got = got.cpu().numpy()
     print(f"{c['id']}: {rounds} rounds of 8 sweeps on the device ({time.perf_counter() - t0:.3f} s), {ref['rounds']} Jacobi rounds in canny_ref")
     assert set(np.unique(got)) <= {0.0, 255.0}

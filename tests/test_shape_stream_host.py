@@ -1,22 +1,18 @@
 """Keeps tests/_shape_stream_cases.py honest without a GPU: every row's float64 reference runs, is finite and has the declared
-shape; ids are unique; the two dispatch rules the table leans on (kd_small_linear's template choice, small_wgrad_blocks) are
-restated in Python with their constants read out of csrc/gscnn_bwd.hip, and the table is shown to hold a row on each side of
-them; the Canny line fixtures need more hysteresis rounds than the 8 x 64 sweeps ops.canny used to stop at."""
-import os
-import re
-
+shape; ids are unique; the two dispatch rules the table leans on (kd_small_linear's template choice, the small-wgrad block rule)
+are restated in Python with their constants taken from csrc/gscnn_select.h, compiled for the host (tests/gscnn_select_host), and
+the table is shown to hold a row on each side of them; the Canny line fixtures need more hysteresis rounds than the 8 x 64 sweeps
+ops.canny used to stop at.  tests/test_gscnn_select_host.py holds the restatements themselves against the compiled selectors."""
 import numpy as np
 import pytest
 
 import _shape_stream_cases as S
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "knowledge-distillation-by-replacing-cheap-conv_amd", "csrc")
+from test_gscnn_select_host import consts, load, sl_templates
 
 
-def source(name):
-    with open(os.path.join(CSRC, name)) as f:
-        return f.read()
+@pytest.fixture(scope="module")
+def lib():
+    return load()
 
 
 def test_case_ids_are_unique():
@@ -48,20 +44,9 @@ def test_inputs_are_seeded():
 
 
 # ------------------------------------------------------------------------------------------------------ kd_small_linear
-def small_linear_templates():
-    """The Cout thresholds and the instantiations of kd_small_linear's dispatch chain, from the source."""
-    src = source("gscnn_bwd.hip")
-    chain = re.search(r"#define KD_SL\(COP\).*?#undef KD_SL", src, re.S).group(0)
-    conds = [(int(a), int(b)) for a, b in re.findall(r"if \(Cout <= (\d+)\) KD_SL\((\d+)\);", chain)]
-    last = int(re.search(r"else KD_SL\((\d+)\);", chain).group(1))
-    return conds, last, int(re.search(r"constexpr int SL_MAXC = (\d+);", src).group(1))
-
-
-def test_small_linear_rows_sit_on_both_sides_of_every_template_boundary():
-    conds, last, maxc = small_linear_templates()
-    assert all(a == b for a, b in conds), "a threshold no longer equals the instantiation it selects"
-    templates = tuple(b for _, b in conds) + (last,)
-    assert templates == S.SL_TEMPLATES and maxc == S.SL_MAXC == last, f"gscnn_bwd.hip now dispatches {templates} (SL_MAXC {maxc}): retune the table"
+def test_small_linear_rows_sit_on_both_sides_of_every_template_boundary(lib):
+    templates, maxc = sl_templates(lib), consts(lib)["SL_MAXC"]
+    assert templates == S.SL_TEMPLATES and maxc == S.SL_MAXC == templates[-1], f"gscnn_select.h now lists {templates} (SL_MAXC {maxc}): retune the table"
     rows = S.cases_of("small_linear")
     couts = {c["cout"] for c in rows}
     for t in templates:
@@ -78,22 +63,11 @@ def test_small_linear_rows_sit_on_both_sides_of_every_template_boundary():
 
 
 # ------------------------------------------------------------------------------------------------------- kd_small_wgrad
-def small_wgrad_constants():
-    src = source("gscnn_bwd.hip")
-    fn = re.search(r"static int small_wgrad_blocks\(.*?\n}", src, re.S).group(0)
-    per_block = re.search(r"\(npix \+ (\d+)\) / (\d+)", fn)
-    assert int(per_block.group(1)) + 1 == int(per_block.group(2))
-    cap = re.search(r"if \(nb > (\d+)\) nb = (\d+);", fn)
-    assert cap.group(1) == cap.group(2)
-    assert "pb = (pb + SW_CH - 1) / SW_CH * SW_CH;" in fn
-    chunk = int(re.search(r"constexpr int SW_CH = (\d+)", src).group(1))
-    assert "SW_MAXP = (SL_MAXC * SL_MAXC + 255) / 256" in src and "__launch_bounds__(256) void small_wgrad_partial_kernel" in src
-    return dict(per_block=int(per_block.group(2)), max_blocks=int(cap.group(1)), chunk=chunk)
-
-
-def test_small_wgrad_rows_reach_every_branch_of_the_block_rule():
-    k = small_wgrad_constants()
-    assert k == dict(per_block=S.SW_PIX_PER_BLOCK, max_blocks=S.SW_MAX_BLOCKS, chunk=S.SW_CH), f"gscnn_bwd.hip now has {k}: retune the table"
+def test_small_wgrad_rows_reach_every_branch_of_the_block_rule(lib):
+    K = consts(lib)
+    k = dict(per_block=K["SW_PIX_PER_BLOCK"], max_blocks=K["SW_MAX_BLOCKS"], chunk=K["SW_CH"])
+    assert k == dict(per_block=S.SW_PIX_PER_BLOCK, max_blocks=S.SW_MAX_BLOCKS, chunk=S.SW_CH), f"gscnn_select.h now has {k}: retune the table"
+    assert K["THREADS"] == S.SW_THREADS
     rows = S.cases_of("small_wgrad")
     plan = {c["id"]: S.sw_blocks(c["npix"], **k) for c in rows}
     blocks = {nb for nb, _ in plan.values()}
@@ -123,12 +97,12 @@ def test_small_wgrad_rows_reach_every_branch_of_the_block_rule():
 
 
 # ------------------------------------------------------------------------------------------------------------ the others
-def test_gated_conv_rows_cover_every_instantiation_and_pixel_group():
-    src = source("gscnn_ops.hip")
-    assert "PIX = C >= 32 ? 2 : 4" in src and 'KD_REQUIRE(C == 8 || C == 16 || C == 32' in src
+def test_gated_conv_rows_cover_every_instantiation_and_pixel_group(lib):
+    K = consts(lib)
     rows = S.cases_of("gated_conv")
     for C in (8, 16, 32):
-        pix = 2 if C >= 32 else 4
+        pix = lib.gs_gated_pix_of(C)
+        assert pix == (K["GC_PIX_WIDE"] if C >= K["GC_WIDE_C"] else K["GC_PIX"]) and K["MFMA_PIX"] == 16
         for dt, kern in (("f32", "gated_conv_kernel"), ("bf16", "gated_conv_mfma_kernel")):
             n = {c["npix"] for c in rows if c["C"] == C and c["dt"] == dt and c["kernel"] == kern}
             assert any(v < pix for v in n) and any(v % pix for v in n if v > pix) and any(v % 16 == 0 for v in n) and any(v % 16 for v in n if v > 16)
