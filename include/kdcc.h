@@ -874,6 +874,21 @@ int kd_seg_finish(const uint8_t *img, const uint8_t *mask, int64_t n, int32_t H,
                   int32_t use_index, int32_t blur, const void *table, int32_t dtype, int32_t layout, void *out, int32_t ld, int64_t *mask_out,
                   kd_stream_t stream);
 
+/* ------------------------------------------------- per-tile class statistics of the resident label maps (csrc/seg_stats_ops.hip)
+ * Replaces the centroid pass of the reference's class-uniform sampling (data_loader/uniform.py:47-108: per image a PIL decode, a
+ * 34-pass id remap and scipy.ndimage.center_of_mass per tile and class on a thread pool, cached in a JSON file) by one pass over
+ *   targets (n,H,W) uint8 train ids, the resident label maps;
+ *   stats   (n, H / tile, W / tile, num_classes, 3) int64 = [count, sum of x, sum of y] of the pixels of class c inside the tile,
+ *           x and y relative to the tile's origin.  Tiles are tile x tile in row-major order; remainder rows and columns belong to
+ *           no tile; label 255 and any value >= num_classes count nowhere.  The call clears `stats` itself.  The reference's
+ *           centroid of a tile and class is (x_offs + sum_x / count, y_offs + sum_y / count) in integer division.
+ * Exact integer sums: per-workgroup uint32 partials in LDS, then one 64-bit atomic add per non-zero partial, so the result is the
+ * same bits whatever the order and from run to run.  16-byte loads when targets is 16-byte aligned and W and tile are multiples of
+ * 16, byte loads otherwise (csrc/seg_stats_select.h decides).  H < tile or W < tile: nothing to write, KD_OK without a launch.
+ * H, W <= 32768 and 1 <= num_classes <= 64 (KD_ERR_UNSUPPORTED beyond); tile >= 1 and n >= 1 (KD_ERR_INVALID). */
+int kd_seg_class_stats(const uint8_t *targets, int64_t n, int32_t H, int32_t W, int32_t tile, int32_t num_classes, int64_t *stats,
+                       kd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

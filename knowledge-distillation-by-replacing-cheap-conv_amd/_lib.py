@@ -221,6 +221,7 @@ _SIGS = {
     "kd_seg_jitter_workspace": (c_sz, [c_int]),
     "kd_seg_jitter": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_sz, c_vp]),
     "kd_seg_finish": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp]),
+    "kd_seg_class_stats": (c_int, [c_vp, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "kd_debug_kernel_log_enable": (c_int, [c_int]),
     "kd_debug_kernel_log_read": (c_i64, [C.c_char_p, c_sz]),
     "kd_debug_last_kernel": (C.c_char_p, []),

@@ -1,4 +1,4 @@
-from .data_loaders import Cifar10Dataloader, Cifar100Dataloader, CityscapesDataloader  # noqa: F401
+from .data_loaders import Cifar10Dataloader, Cifar100Dataloader, CityscapesDataloader, CityscapesUniformDataloader  # noqa: F401
 from . import joint_transforms  # noqa: F401
 from . import transforms as extended_transforms
 from . import transforms as standard_transforms        # the ToTensor / Normalize / Compose stand-ins live beside the extended ones

@@ -8,7 +8,8 @@ normalises with the ImageNet statistics.  The random stream is not the reference
 per image from the global RNG, these loaders draw a whole epoch at a time from their own generator.
 
 `CityscapesDataloader` (reference data_loader/data_loaders.py:56-81) follows the same shape with its own dataset reader (cityscapes.py),
-parameter table and host-tensor path (seg_tables.py) and kernels (csrc/seg_data_ops.hip); see its docstring."""
+parameter table and host-tensor path (seg_tables.py) and kernels (csrc/seg_data_ops.hip); see its docstring.
+`CityscapesUniformDataloader` (reference data_loader/data_loaders.py:83-97) is that loader over a class-uniform epoch list (uniform.py)."""
 import os
 import pickle
 
@@ -17,7 +18,7 @@ import torch
 
 from .. import nn_hip, ops
 from ..base.base_data_loader import BaseDataLoader, LAYOUTS, normalisation_table
-from . import joint_transforms, seg_tables
+from . import joint_transforms, seg_tables, uniform
 from . import transforms as extended_transforms
 from .cityscapes import CityscapesArrays, ConcatArrays
 
@@ -172,14 +173,18 @@ class CityscapesDataloader(BaseDataLoader):
         self.training = self.spec is not None
         self.return_image_name = bool(return_image_name)
         self.device, self.dtype, self.layout, self.seed = torch.device(device), dtype, layout, seed
-        self.n_samples = len(dataset)
-        self.sampler, self.valid_sampler = self._split_sampler(validation_split)
         self.H, self.W = dataset.data.shape[1:3]
         self._data = torch.from_numpy(dataset.data).to(self.device)
         self._targets = torch.from_numpy(dataset.targets).to(self.device)
         self._table = normalisation_table(mean, std, dtype).to(self.device)
         self._generator = self._seeded(seed)
         self._epoch_params = None
+        self.n_samples = self._count_samples()
+        self.sampler, self.valid_sampler = self._split_sampler(validation_split)
+
+    def _count_samples(self):
+        """The samples of an epoch, over which the validation split is taken: the images (a subclass may list them otherwise)."""
+        return len(self.dataset)
 
     # ------------------------------------------------------------------ the epoch's draws
     def _draw_epoch(self):
@@ -187,7 +192,10 @@ class CityscapesDataloader(BaseDataLoader):
         g, n = self._generator, self.n_samples
         own = torch.arange(n) if self.sampler is None else torch.from_numpy(self.sampler.indices)
         order = own[torch.randperm(n, generator=g)] if (self.shuffle or self.sampler is not None) else own
-        return seg_tables.draw_rows(order.numpy(), self.W, self.H, self.spec, g)
+        return self._draw_rows(order.numpy(), g)
+
+    def _draw_rows(self, order, g):
+        return seg_tables.draw_rows(order, self.W, self.H, self.spec, g)
 
     def batches(self, params):
         """Iterate the batches of a given table of header rows instead of a drawn one (any row count, indices may repeat): validated
@@ -257,3 +265,53 @@ class CityscapesDataloader(BaseDataLoader):
             buf[..., 3:] = 0
         seg_tables.host_normalise(img, self._table, out)
         return self._finish(out), msk.long()
+
+
+class CityscapesUniformDataloader(CityscapesDataloader):
+    """`CityscapesDataloader` with the reference's class-uniform sampling (data_loader/data_loaders.py:83-97,
+    data_loader/cityscapes.py:336-536): an epoch is a list of len(images) entries of which class_uniform_pct are crops that must
+    cover the centroid of a given class in a given class_uniform_tile x class_uniform_tile tile of a given image, an equal number
+    for each of the 19 classes that has a centroid at all (so the list may be shorter than the images), the rest plain images.
+
+    The arguments are the reference's, then keyword-only device, dtype, layout and seed.  At construction one ops.seg_class_stats
+    pass over the resident labels gives the centroids (uniform.class_centroids: `centroids`, per class int64 (k,3) rows
+    [image, cx, cy]) and uniform.build_epoch the list (`imgs_uniform`, int64 (M,4) rows [image, has_centroid, cx, cy]), once, as
+    the reference; `build_epoch()` redraws it.  class_uniform_pct == 0 runs no centroid pass and lists every image once.
+    `n_samples`, `len()` and the validation split are over the list.  An epoch's table permutes the list's entries; word 0 of a
+    row is the entry's image, and the crop offsets of an entry with a centroid are drawn as seg_tables.draw_rows documents, the
+    reference's two quirks included.  No JSON cache is read or written: the reference's is keyed by split and tile only, so it
+    is silently reused for another num_samples or data directory.  transforms=None is refused (the reference dies on an
+    AttributeError); split='train_val' raises the reference's ValueError; maxSkip and coarse_boost_classes are not arguments of the
+    reference's loader either."""
+    num_classes = 19
+
+    def __init__(self, data_dir, batch_size, shuffle=True, validation_split=0.0, num_workers=0, split="train", transform=None,
+                 target_transform=None, transforms=None, mode="fine", target_type="semantic", class_uniform_pct=0.5, class_uniform_tile=1024,
+                 num_samples=None, return_image_name=False, *, device=None, dtype=torch.float32, layout="nchw", seed=None):
+        if split == "train_val":
+            raise ValueError("Only support train split for Uniform Cityscapes")
+        if transforms is None:
+            raise ValueError("CityscapesUniformDataloader: transforms=None: the uniform loader needs the joint transform list "
+                             "(RandomSizeAndCrop takes the centroid)")
+        if int(class_uniform_tile) < 1:
+            raise ValueError(f"CityscapesUniformDataloader: class_uniform_tile {class_uniform_tile}")
+        self.class_uniform_pct, self.class_uniform_tile = class_uniform_pct, int(class_uniform_tile)
+        super().__init__(data_dir, batch_size, shuffle, validation_split, num_workers, split, transform, target_transform, transforms, mode,
+                         target_type, num_samples, return_image_name, device=device, dtype=dtype, layout=layout, seed=seed)
+
+    def _count_samples(self):
+        if self.class_uniform_pct > 0:
+            stats = ops.seg_class_stats(self._targets, self.class_uniform_tile, self.num_classes)
+            self.centroids = uniform.class_centroids(stats, self.class_uniform_tile)
+        else:
+            self.centroids = [np.zeros((0, 3), dtype=np.int64) for _ in range(self.num_classes)]
+        return len(self.build_epoch())
+
+    def build_epoch(self):
+        """Redraw the epoch list from the loader's generator (the reference builds it once, at construction); -> imgs_uniform."""
+        self.imgs_uniform = uniform.build_epoch(len(self.dataset), self.centroids, self.num_classes, self.class_uniform_pct, self._generator)
+        return self.imgs_uniform
+
+    def _draw_rows(self, order, g):
+        entries = self.imgs_uniform[order]
+        return seg_tables.draw_rows(entries[:, 0], self.W, self.H, self.spec, g, centroids=entries[:, 1:4])

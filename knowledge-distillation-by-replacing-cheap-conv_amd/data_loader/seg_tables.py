@@ -89,10 +89,14 @@ def max_offsets(r, S):
     return int(r[I_W] + 2 * r[I_PADW] - S), int(r[I_H] + 2 * r[I_PADH] - S)
 
 
-def draw_rows(order, W, H, spec, g):
+def draw_rows(order, W, H, spec, g, centroids=None):
     """int32 (n, HDR): one epoch's draws for the sample indices `order` from the torch generator g, with the reference's
     distributions.  spec: the loader's reading of the transform lists (crop, scale_min, scale_max, flip, color_aug, blur) or None
-    for no augmentation."""
+    for no augmentation.  centroids: None, or int (n, 3) rows [has_centroid, cx, cy] in source pixels; a row that has one takes its
+    crop offsets as RandomCrop does for a centroid (reference data_loader/joint_transforms.py:104-113, 368-369) from the same two
+    uniforms: cx' = int(cx * s) in double, x1 = randint(cx' - S, cx') clamped to [0, mx], and likewise y1.  Two quirks of the
+    reference stay: the centroid is not shifted by the pad, and x1 = cx' - S leaves it one pixel outside the crop.  The uniforms
+    consumed and their order do not depend on `centroids`."""
     global _PERMS
     n = len(order)
     rows = np.zeros((n, HDR), dtype=np.int32)
@@ -111,6 +115,12 @@ def draw_rows(order, W, H, spec, g):
     rows[:, I_W], rows[:, I_H], rows[:, I_PADW], rows[:, I_PADH] = w, h, pw, ph
     rows[:, I_X1] = np.minimum((u[:, 1] * (mx + 1)).astype(np.int64), mx)               # randint(0, mx), both ends included
     rows[:, I_Y1] = np.minimum((u[:, 2] * (my + 1)).astype(np.int64), my)
+    if centroids is not None:
+        cen = np.asarray(centroids, dtype=np.int64).reshape(n, 3)
+        for col, c, uc, top in ((I_X1, cen[:, 1], u[:, 1], mx), (I_Y1, cen[:, 2], u[:, 2], my)):
+            hi = (c * s).astype(np.int64)                                               # int(c * scale_amt)
+            at = np.minimum(hi - S + (uc * (S + 1)).astype(np.int64), hi)               # randint(c' - S, c'), both ends included
+            rows[:, col] = np.where(cen[:, 0] != 0, np.minimum(top, np.maximum(0, at)), rows[:, col])
     rows[:, I_FLIP] = (u[:, 3] < 0.5) if spec["flip"] else 0
     a = float(spec["color_aug"])
     if a > 0:

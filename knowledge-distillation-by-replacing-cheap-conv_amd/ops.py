@@ -2183,3 +2183,51 @@ def seg_finish(img, mask, params, table, out, mask_out=None, use_index=False, bl
     check(_lib.lib().kd_seg_finish(_ptr(img), _ptr(mask), n, H, W, _ptr(params), pld, B, int(bool(use_index)), int(bool(blur)), _ptr(table), dt,
                                    layout, _ptr(out), ld, _ptr(mask_out), stream_ptr()), "kd_seg_finish")
     return out, mask_out
+
+
+# ------------------------------------------------------------------------- per-tile class statistics (data_loader.uniform)
+SEG_STATS_MAX_CLASSES, SEG_MAX_SIDE = 64, 1 << 15
+_SEG_STATS_HOST_BYTES = 1 << 26         # label bytes the host path compares at once
+
+
+def _host_class_stats(targets, tile, num_classes, out):
+    """The sums of kd_seg_class_stats with torch integer ops on host tensors: what the kernel is a restatement of."""
+    n, th, tw = out.shape[:3]
+    ar = torch.arange(tile, dtype=torch.int64)
+    step = max(1, _SEG_STATS_HOST_BYTES // (th * tw * tile * tile))
+    for s in range(0, n, step):
+        t = targets[s:s + step, :th * tile, :tw * tile].reshape(-1, th, tile, tw, tile)         # (b, ty, y, tx, x)
+        for c in range(num_classes):
+            m = t == c
+            col = m.sum(2, dtype=torch.int64)               # (b, ty, tx, x): the class's pixels per tile column
+            row = m.sum(4, dtype=torch.int64)               # (b, ty, y, tx): per tile row
+            out[s:s + step, :, :, c, 0] = col.sum(3)
+            out[s:s + step, :, :, c, 1] = (col * ar).sum(3)
+            out[s:s + step, :, :, c, 2] = (row * ar[:, None]).sum(2)
+    return out
+
+
+def seg_class_stats(targets, tile, num_classes=19):
+    """int64 (n, H // tile, W // tile, num_classes, 3) = [count, sum of x, sum of y] of the pixels of every class inside every
+    tile x tile tile of the uint8 label maps targets (n,H,W), x and y relative to the tile's origin (kd_seg_class_stats; see
+    include/kdcc.h).  Remainder rows and columns belong to no tile; a tile larger than the image gives an empty tensor and no launch;
+    255 and every value >= num_classes count nowhere.  Device tensors run the kernel; host tensors the same exact integer sums with
+    torch ops, equal bit for bit."""
+    if targets.dtype != torch.uint8 or targets.dim() != 3 or targets.shape[0] < 1 or not targets.is_contiguous():
+        raise ValueError(f"seg_class_stats: targets must be a contiguous uint8 (n,H,W) tensor, got {targets.dtype} {tuple(targets.shape)}")
+    n, H, W = targets.shape
+    tile, num_classes = int(tile), int(num_classes)
+    if tile < 1:
+        raise ValueError(f"seg_class_stats: a tile of {tile} pixels")
+    if not 1 <= num_classes <= SEG_STATS_MAX_CLASSES:
+        raise ValueError(f"seg_class_stats: num_classes {num_classes} outside [1, {SEG_STATS_MAX_CLASSES}]")
+    if not (1 <= H <= SEG_MAX_SIDE and 1 <= W <= SEG_MAX_SIDE):
+        raise ValueError(f"seg_class_stats: H = {H}, W = {W} outside [1, {SEG_MAX_SIDE}]")
+    th, tw = (H // tile, W // tile) if tile <= min(H, W) else (0, 0)
+    out = torch.empty((n, th, tw, num_classes, 3), dtype=torch.int64, device=targets.device)
+    if th == 0:
+        return out
+    if not targets.is_cuda:
+        return _host_class_stats(targets, tile, num_classes, out)
+    check(_lib.lib().kd_seg_class_stats(_ptr(targets), n, H, W, tile, num_classes, _ptr(out), stream_ptr()), "kd_seg_class_stats")
+    return out
