@@ -43,6 +43,17 @@ def _nbytes(*ts):
     return sum(t.numel() * t.element_size() for t in ts if t is not None)
 
 
+# Every buffer that is handed to the library and is not a result comes from _ws (bytes) or _scratch (typed): the one seam the
+# tests replace to hand the kernels poisoned, guarded memory (tests/_scratch.py).  Nothing is cleared here: no kernel may
+# depend on what its scratch held before the call.  (Results a wrapper returns are plain torch.empty.)
+def _ws(nbytes, device, floor=16):
+    return torch.empty(max(int(nbytes), floor), dtype=torch.uint8, device=device)
+
+
+def _scratch(shape, dtype, device):
+    return torch.empty(shape, dtype=dtype, device=device)
+
+
 def dt_of(t):
     if t.dtype == torch.bfloat16:
         return KD_BF16
@@ -190,13 +201,13 @@ def conv2d(x, w_packed, stride=1, pad=0, dil=1, *, res_pre=None, mask=None, mask
     if bn_sums is not None and mask is not None:
         sums_rows = int(_lib.lib().kd_conv2d_bn_sums_rows(C.byref(d), C.byref(ep)))
         if sums_rows > 0:
-            part = torch.empty((sums_rows, 2, Cout), dtype=torch.float32, device=x.device)
+            part = _scratch((sums_rows, 2, Cout), torch.float32, x.device)
             ep.bn_sums = _ptr(part)
     out_rows = 0
     if out_sums is not None and mask is None and res_pre is None and res_post is None and out_act is None and out_raw is not None:
         out_rows = int(_lib.lib().kd_conv2d_bn_sums_rows(C.byref(d), C.byref(ep)))
         if out_rows > 0:
-            opart = torch.empty((out_rows, 2, Cout), dtype=torch.float32, device=x.device)
+            opart = _scratch((out_rows, 2, Cout), torch.float32, x.device)
             ep.bn_sums = _ptr(opart)
     prof = PROFILER
     if prof is not None:
@@ -284,7 +295,7 @@ def pw_wgrad(a, dy, dw, accumulate=False, workspace=None):
     M = N * H * W
     need = _lib.lib().kd_pw_wgrad_workspace(M, Cin, Cout)
     if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=a.device)
+        workspace = _ws(need, a.device, 0)
     e0 = _prof_start()
     check(_lib.lib().kd_pw_wgrad(dt_of(a), M, Cin, Cout, _ptr(a), nhwc_ld(a), _ptr(dy), nhwc_ld(dy), _ptr(dw),
                                  int(accumulate), _ptr(workspace), workspace.numel() * workspace.element_size(),
@@ -306,7 +317,7 @@ def conv2d_wgrad(x, dy, dw, stride=1, pad=0, dil=1, accumulate=False, workspace=
     d = ConvDesc(dt_of(x), N, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil, nhwc_ld(x))
     need = _lib.lib().kd_conv2d_wgrad_workspace(C.byref(d))
     if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+        workspace = _ws(need, x.device, 0)
     prof = PROFILER
     if prof is not None:
         e0 = torch.cuda.Event(enable_timing=True)
@@ -488,7 +499,7 @@ def dwconv_wgrad(x, dy, dw, k, pad, dil, accumulate=False, workspace=None):
     d = _dw_desc(x, k, pad, dil)
     need = _lib.lib().kd_dwconv_wgrad_workspace(C.byref(d))
     if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+        workspace = _ws(need, x.device, 0)
     e0 = _prof_start()
     check(_lib.lib().kd_dwconv_wgrad(C.byref(d), _ptr(x), _ptr(dy), nhwc_ld(dy), _ptr(dw), int(accumulate), _ptr(workspace),
                                      workspace.numel() * workspace.element_size(), stream_ptr()), "kd_dwconv_wgrad")
@@ -703,7 +714,7 @@ def aspp_image_pool(x, w, scale, shift, out, sums=None):
     if w.dtype != torch.float32 or not w.is_contiguous() or tuple(out.shape[:3]) != (N, H, W) or out.dtype != x.dtype:
         raise ValueError("aspp_image_pool: bad operands")
     need = _lib.lib().kd_aspp_image_pool_workspace(N, Cin, Cout)
-    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    ws = _ws(need, x.device, 0)
     if sums is not None:
         _need_cuda(sums)
         if tuple(sums.shape) != (N * H * W // 128, 2, Cin) or (H * W) % 128 or sums.dtype != torch.float32 or not sums.is_contiguous():
@@ -714,10 +725,6 @@ def aspp_image_pool(x, w, scale, shift, out, sums=None):
     check(_lib.lib().kd_aspp_image_pool(dt_of(x), _ptr(x), nhwc_ld(x), _ptr(w), _ptr(scale), _ptr(shift), _ptr(out),
                                         nhwc_ld(out), N, H, W, Cin, Cout, _ptr(ws), need, stream_ptr()), "kd_aspp_image_pool")
     return out
-
-
-def _ws(nbytes, device):
-    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
 
 def stem_wgrad(x_nchw, dy, dw, accumulate=False):
@@ -1378,7 +1385,7 @@ def loss_workspace(N, Cc, P, device):
     key = (device, torch.cuda.current_stream().cuda_stream)
     ws = _ws_cache.get(key)
     if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=device)
+        ws = _ws(need, device, 0)
         _ws_cache[key] = ws
     return ws, need
 
@@ -1771,7 +1778,7 @@ def topk_hint_mse(s, t, k, want_grad=True, grad_scale=1.0, want_mask=False):
     key = (s.device, torch.cuda.current_stream().cuda_stream)
     ws = _topk_ws.get(key)
     if ws is None or ws.numel() < need:
-        ws = _topk_ws[key] = torch.empty(need, dtype=torch.uint8, device=s.device)
+        ws = _topk_ws[key] = _ws(need, s.device, 0)
     e0 = _prof_start()
     check(_lib.lib().kd_topk_hint_mse(C.byref(vs), C.byref(vt), k, N, Cc, P, _ptr(loss), C.byref(vg) if vg is not None else None,
                                       C.c_float(grad_scale), _ptr(mask), _ptr(ws), need, stream_ptr()), "kd_topk_hint_mse")
@@ -2144,7 +2151,7 @@ def seg_jitter(img, params, workspace=None, validated=False):
         check_seg_params(params[:, :SEG_HDR], 2 ** 31 - 1, 1, 1)
     need = _lib.lib().kd_seg_jitter_workspace(B)
     if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.uint8, device=img.device)
+        workspace = _ws(need, img.device, 0)
     check(_lib.lib().kd_seg_jitter(_ptr(img), _ptr(params), _seg_table(params, SEG_HDR, "seg_jitter")[1], B, S, _ptr(workspace),
                                    workspace.numel() * workspace.element_size(), stream_ptr()), "kd_seg_jitter")
     return img
