@@ -281,17 +281,8 @@ __global__ __launch_bounds__(256) void maxpool_bwd_gather_kernel(const uint2 *__
 
 // ---- bilinear (align_corners=True) upsample backward, separable gather ---------------------------------------------------------
 // forward: src = o * (I - 1) / (O - 1); i0 = floor(src), i1 = min(i0 + 1, I - 1), f = src - i0; y[o] = (1-f) x[i0] + f x[i1].
-// backward along one axis: gx[i] = sum_o [i0(o) == i] (1 - f(o)) gy[o] + [i1(o) == i] f(o) gy[o]; the candidate range of o is
-// bracketed generously and every candidate re-evaluates the forward's own (i0, i1, f), so the two sides cannot disagree.
-__device__ __forceinline__ void up_src(int o, float sc, float off, int I, int &i0, int &i1, float &f)
-{
-    // align_corners=True: off = 0, sc = (I-1)/(O-1); align_corners=False: sc = I/O, off = 0.5 sc - 0.5, clamped at 0 (the
-    // forward kernel's own expression, trunk_ops.hip upsample_kernel)
-    const float src = fmaxf(o * sc + off, 0.f);
-    i0 = min((int)src, I - 1);
-    i1 = min(i0 + 1, I - 1);
-    f = src - (float)i0;
-}
+// backward along one axis: gx[i] = sum_o [i0(o) == i] (1 - f(o)) gy[o] + [i1(o) == i] f(o) gy[o], a gather over
+// resample_adjoint_range weighed by resample_adjoint_weight (resample.h).
 
 // pass 1: along W.  gy (N, Ho, Wo, C) -> tmp (N, Ho, W, C) float.  VEC = 8: a thread owns 8 channels (16-B loads; the 256-channel
 // decoder gradient took 1.33 ms one element per thread), VEC = 1: any C (the 19-class logits).
@@ -304,19 +295,14 @@ __global__ __launch_bounds__(256) void upsample_bwd_w_kernel(const T *__restrict
     if (i >= W * CV) return;
     const int w = i / CV, c = (i - w * CV) * VEC;
     const int ho = blockIdx.y, n = blockIdx.z;
-    const float inv = sw > 0.f ? 1.f / sw : 0.f;
-    int lo = sw > 0.f ? (int)((w - 1 - ow) * inv) - 1 : 0, hi = sw > 0.f ? (int)((w + 1 - ow) * inv) + 2 : Wo - 1;
-    lo = max(lo, 0); hi = min(hi, Wo - 1);
+    int lo, hi;
+    resample_adjoint_range(w, sw, ow, Wo, lo, hi);
     const T *row = gy + (((size_t)n * Ho + ho) * Wo) * ldgy + c;
     float acc[VEC];
 #pragma unroll
     for (int q = 0; q < VEC; ++q) acc[q] = 0.f;
     for (int o = lo; o <= hi; ++o) {
-        int i0, i1; float f;
-        up_src(o, sw, ow, W, i0, i1, f);
-        float wgt = 0.f;
-        if (i0 == w) wgt += 1.f - f;
-        if (i1 == w) wgt += f;
+        const float wgt = resample_adjoint_weight(o, w, sw, ow, W);
         if (wgt != 0.f) {
             if constexpr (VEC == 8) {
                 float v[8];
@@ -343,18 +329,13 @@ __global__ __launch_bounds__(256) void upsample_bwd_h_kernel(const float *__rest
     if (i >= W * CV) return;
     const int w = i / CV, c = (i - w * CV) * VEC;
     const int h = blockIdx.y, n = blockIdx.z;
-    const float inv = sh > 0.f ? 1.f / sh : 0.f;
-    int lo = sh > 0.f ? (int)((h - 1 - oh) * inv) - 1 : 0, hi = sh > 0.f ? (int)((h + 1 - oh) * inv) + 2 : Ho - 1;
-    lo = max(lo, 0); hi = min(hi, Ho - 1);
+    int lo, hi;
+    resample_adjoint_range(h, sh, oh, Ho, lo, hi);
     float acc[VEC];
 #pragma unroll
     for (int q = 0; q < VEC; ++q) acc[q] = 0.f;
     for (int o = lo; o <= hi; ++o) {
-        int i0, i1; float f;
-        up_src(o, sh, oh, H, i0, i1, f);
-        float wgt = 0.f;
-        if (i0 == h) wgt += 1.f - f;
-        if (i1 == h) wgt += f;
+        const float wgt = resample_adjoint_weight(o, h, sh, oh, H);
         if (wgt != 0.f) {
             const float *src = tmp + (((size_t)n * Ho + o) * W + w) * C + c;
             if constexpr (VEC == 8) {

@@ -140,14 +140,17 @@ __global__ __launch_bounds__(256) void edge_aspp_kernel(const float *__restrict_
         long long r = i / C8;
         const int wo = (int)(r % Wo); r /= Wo;
         const int ho = (int)(r % Ho), n = (int)(r / Ho);
+        // Not resample_src: without its clamp at 0 between the product and the difference, the compiler fuses ho * sh into
+        // fh - h0, so ah and aw are rounded once where resample_src rounds twice.  The indices are the rule's; the fractions
+        // differ from it in the last bit whenever the product is inexact, and stay as they are so that results do not move.
         const float fh = ho * sh, fw = wo * sw;
         int h0 = (int)fh; h0 = h0 > H - 1 ? H - 1 : h0;
         int w0 = (int)fw; w0 = w0 > W - 1 ? W - 1 : w0;
         const int h1 = h0 + 1 < H ? h0 + 1 : H - 1, w1 = w0 + 1 < W ? w0 + 1 : W - 1;
         const float ah = fh - h0, aw = fw - w0;
         const float *b = acts + (size_t)n * H * W;
-        const float e = (1.f - ah) * ((1.f - aw) * b[(size_t)h0 * W + w0] + aw * b[(size_t)h0 * W + w1]) +
-                        ah * ((1.f - aw) * b[(size_t)h1 * W + w0] + aw * b[(size_t)h1 * W + w1]);
+        const float e = resample_lerp(ah, resample_lerp(aw, b[(size_t)h0 * W + w0], b[(size_t)h0 * W + w1]),
+                                      resample_lerp(aw, b[(size_t)h1 * W + w0], b[(size_t)h1 * W + w1]));
         float wv[8], sc[8], sf[8], o[8];
         ld8(w + cq * 8, wv); ld8(scale + cq * 8, sc); ld8(shift + cq * 8, sf);
 #pragma unroll

@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "../../include/kdcc.h"
+#include "resample.h"
 
 // One value per name the launchers note (gs_kernel_name), then GS_REFUSED.  Variants are ranges: <f32 before bf16> x <channel
 // counts ascending>; the small_linear templates ascending; the pointwise pairs descending, as the stream runs them.
@@ -163,8 +164,8 @@ static inline GsSel gs_edge_aspp(int dtype, const void *w, const void *scale, co
     if (C % 8 != 0 || !gs_rows16(y, ldy, gs_elem_size(dtype)) || !gs_aligned(w, 16) || !gs_aligned(scale, 16) || !gs_aligned(shift, 16))
         return gs_refuse(GS_WHY_ALIGN);
     GsSel c = gs_flat(GS_EDGE_ASPP_F32 + (dtype == KD_BF16), gs_grid(gs_mul(gs_mul(gs_mul(N, Ho), Wo), C / 8), GS_CAP_EDGE_ASPP));
-    c.sh = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
-    c.sw = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
+    const ResampleGeom g = resample_geom(H, W, Ho, Wo, 1);
+    c.sh = g.sh; c.sw = g.sw;
     return c;
 }
 // workspace: short2 gradients | int magnitudes | byte states, N * H * W each, and 256 bytes of slack

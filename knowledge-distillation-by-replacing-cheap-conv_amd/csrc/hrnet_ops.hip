@@ -7,6 +7,7 @@
 // All fp32 NHWC, wave64, 16-byte accesses along the channel axis (C % 4 == 0), no float atomics: every reduction over pixels
 // goes through per-chunk partial sums in a workspace that a second kernel adds in chunk order, so results are bit-reproducible.
 #include "kd_common.h"
+#include "resample.h"
 
 #include <math.h>
 
@@ -24,33 +25,22 @@ __device__ __forceinline__ float4 f4_fma(float a, float4 b, float4 c)
 }
 __device__ __forceinline__ float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float f4_dot(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
-// (1 - f) * a + f * b per component: the expression tree of upsample_kernel (trunk_ops.hip)
-__device__ __forceinline__ float4 f4_lerp(float f, float4 a, float4 b)
+__device__ __forceinline__ float4 resample_lerp(float f, float4 a, float4 b)
 {
-    const float g = 1.f - f;
-    return make_float4(g * a.x + f * b.x, g * a.y + f * b.y, g * a.z + f * b.z, g * a.w + f * b.w);
+    return make_float4(::resample_lerp(f, a.x, b.x), ::resample_lerp(f, a.y, b.y), ::resample_lerp(f, a.z, b.z), ::resample_lerp(f, a.w, b.w));
 }
 
 // ---------------------------------------------------------------------------------------------------------------- fuse sum
 struct HrSrc {
     float *x;          // source (forward) / source gradient (backward)
     int H, W, ld;
-    float sh, sw;      // align_corners=True scales: (H - 1) / (Ho - 1), 0 when the output extent is 1 (kd_upsample_bilinear_ac)
+    float sh, sw;      // align_corners=True scales (resample_geom)
     long long first;   // backward: index of this source's first work item
 };
 struct HrArgs {
     HrSrc s[HR_MAX_SRC];
     int n;
 };
-
-// the forward's coordinate rule (up_src of bwd_ops.hip with off = 0)
-__device__ __forceinline__ void hr_src(int o, float sc, int I, int &i0, int &i1, float &f)
-{
-    const float src = fmaxf(o * sc, 0.f);
-    i0 = min((int)src, I - 1);
-    i1 = min(i0 + 1, I - 1);
-    f = src - (float)i0;
-}
 
 // one thread per (n, ho, wo, 4 channels)
 __global__ __launch_bounds__(256) void hr_fuse_fwd_kernel(HrArgs a, float *__restrict__ y, int ldy, int N, int Ho, int Wo, int C4)
@@ -74,11 +64,11 @@ __global__ __launch_bounds__(256) void hr_fuse_fwd_kernel(HrArgs a, float *__res
             v = *(const float4 *)(b + ((size_t)ho * Wo + wo) * S.ld);
         } else {
             int h0, h1, w0, w1; float ah, aw;
-            hr_src(ho, S.sh, S.H, h0, h1, ah);
-            hr_src(wo, S.sw, S.W, w0, w1, aw);
-            const float4 t = f4_lerp(aw, *(const float4 *)(b + ((size_t)h0 * S.W + w0) * S.ld), *(const float4 *)(b + ((size_t)h0 * S.W + w1) * S.ld));
-            const float4 u = f4_lerp(aw, *(const float4 *)(b + ((size_t)h1 * S.W + w0) * S.ld), *(const float4 *)(b + ((size_t)h1 * S.W + w1) * S.ld));
-            v = f4_lerp(ah, t, u);
+            resample_src(ho, S.sh, S.H, h0, h1, ah);
+            resample_src(wo, S.sw, S.W, w0, w1, aw);
+            const float4 t = resample_lerp(aw, *(const float4 *)(b + ((size_t)h0 * S.W + w0) * S.ld), *(const float4 *)(b + ((size_t)h0 * S.W + w1) * S.ld));
+            const float4 u = resample_lerp(aw, *(const float4 *)(b + ((size_t)h1 * S.W + w0) * S.ld), *(const float4 *)(b + ((size_t)h1 * S.W + w1) * S.ld));
+            v = resample_lerp(ah, t, u);
         }
         acc = s == 0 ? v : f4_add(acc, v);
     }
@@ -90,18 +80,6 @@ __device__ __forceinline__ float4 hr_masked(const float *gy, const float *y, siz
 {
     const float4 g = *(const float4 *)(gy + og), v = *(const float4 *)(y + oy);
     return make_float4(v.x > 0.f ? g.x : 0.f, v.y > 0.f ? g.y : 0.f, v.z > 0.f ? g.z : 0.f, v.w > 0.f ? g.w : 0.f);
-}
-
-// candidate output range of source index i along one axis (generous; every candidate re-evaluates the forward's rule)
-__device__ __forceinline__ void hr_range(int i, float sc, int O, int &lo, int &hi)
-{
-    if (sc > 0.f) {
-        const float inv = 1.f / sc;
-        lo = max((int)((i - 1) * inv) - 1, 0);
-        hi = min((int)((i + 1) * inv) + 2, O - 1);
-    } else {
-        lo = 0; hi = O - 1;
-    }
 }
 
 // one thread per (source, n, h, w, 4 channels) of the sources whose gradient is wanted; a.s[].x are the gradient buffers
@@ -128,20 +106,13 @@ __global__ __launch_bounds__(256) void hr_fuse_bwd_kernel(HrArgs a, long long to
     } else {
         acc = f4_zero();
         int hlo, hhi, wlo, whi;
-        hr_range(h, S.sh, Ho, hlo, hhi);
-        hr_range(w, S.sw, Wo, wlo, whi);
+        resample_adjoint_range(h, S.sh, 0.f, Ho, hlo, hhi);
+        resample_adjoint_range(w, S.sw, 0.f, Wo, wlo, whi);
         for (int ho = hlo; ho <= hhi; ++ho) {
-            int i0, i1; float f;
-            hr_src(ho, S.sh, S.H, i0, i1, f);
-            float wh = 0.f;
-            if (i0 == h) wh += 1.f - f;
-            if (i1 == h) wh += f;
+            const float wh = resample_adjoint_weight(ho, h, S.sh, S.H);
             if (wh == 0.f) continue;
             for (int wo = wlo; wo <= whi; ++wo) {
-                hr_src(wo, S.sw, S.W, i0, i1, f);
-                float ww = 0.f;
-                if (i0 == w) ww += 1.f - f;
-                if (i1 == w) ww += f;
+                const float ww = resample_adjoint_weight(wo, w, S.sw, S.W);
                 if (ww == 0.f) continue;
                 const size_t p = ((size_t)n * Ho + ho) * Wo + wo;
                 acc = f4_fma(wh * ww, hr_masked(gy, y, p * ldgy + c, p * ldy + c), acc);
@@ -456,8 +427,8 @@ int fill_args(HrArgs &a, const kd_hr_view *v, int nsrc, int Ho, int Wo, int C, c
                    "%s: source %d must be no finer than the output, 16-byte aligned, ld %% 4 == 0 and ld >= C", who, s);
         HrSrc &S = a.s[a.n++];
         S.x = (float *)v[s].ptr; S.H = v[s].H; S.W = v[s].W; S.ld = v[s].ld;
-        S.sh = Ho > 1 ? (float)(S.H - 1) / (float)(Ho - 1) : 0.f;
-        S.sw = Wo > 1 ? (float)(S.W - 1) / (float)(Wo - 1) : 0.f;
+        const ResampleGeom g = resample_geom(S.H, S.W, Ho, Wo, 1);
+        S.sh = g.sh; S.sw = g.sw;
         S.first = 0;
     }
     return KD_OK;

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/kdcc.h"
+#include "resample.h"
 
 // One value per name the launchers note (loss_kernel_name), then LOSS_REFUSED.  The 24 channels-last forms of the two-operand
 // criteria are a range: LK_PAIR_NHWC + 8 * kind + 4 * (s is bf16) + 2 * (t is bf16) + (grad is bf16).
@@ -204,12 +205,8 @@ static inline LossSel loss_select_up(LossUpOp op, int N, int h, int w, int C, in
     c.kernel = LOSS_REFUSED;
     if (C > loss_up_max_classes(op)) { c.why = LOSS_WHY_CLASSES; return c; }
     if (N < 1 || h < 1 || w < 1 || C < 1 || H < 1 || W < 1) return c;
-    c.sh = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
-    c.sw = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
-    if (!align_corners) {
-        c.sh = (float)h / (float)H; c.sw = (float)w / (float)W;
-        c.oh = 0.5f * c.sh - 0.5f; c.ow = 0.5f * c.sw - 0.5f;
-    }
+    const ResampleGeom g = resample_geom(h, w, H, W, align_corners);
+    c.sh = g.sh; c.sw = g.sw; c.oh = g.oh; c.ow = g.ow;
     // source columns one 256-pixel chunk can touch, (int)(255 * sw) + 3, must fit the staged patch (compared before the
     // conversion: a ratio in the billions has no int)
     if (!(255.f * c.sw < (float)(LOSS_UP_NW - 2))) { c.why = LOSS_WHY_SPAN; return c; }

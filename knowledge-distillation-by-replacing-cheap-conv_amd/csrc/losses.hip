@@ -180,8 +180,8 @@ __global__ __launch_bounds__(256) void ce2d_nhwc_kernel(const TX *__restrict__ x
 // The decoder's classifier produces (N,h,w,C) fp32 logits; the reference up-samples them bilinearly to the input size
 // (models/deeplabv3/deeplabv3.py:160-162) and the trainer logs CE(student), CE(teacher) and KLDiv on the full-resolution tensors
 // (trainer/layerwise_trainer.py:222-227).  Materialised, that is two 1.27-GB fp32 tensors per 8 images written once and read back by
-// three kernels (2.3 ms per step).  Here a pixel's C logits are interpolated in registers -- the expression tree of
-// upsample_flat4_kernel: horizontal blend of each source row, then the vertical blend -- from a low-resolution patch staged in LDS: a
+// three kernels (2.3 ms per step).  Here a pixel's C logits are interpolated in registers -- the horizontal blend of each
+// source row, then the vertical blend -- from a low-resolution patch staged in LDS: a
 // workgroup takes 256 consecutive output pixels of one output row, i.e. <= UP_NW source columns of two source rows.
 constexpr int UP_NW = LOSS_UP_NW;   // one value: the header refuses what would not fit, the kernels size their staged patch by it
 
@@ -211,9 +211,9 @@ __device__ __forceinline__ void up_stage(float *sm, const float *__restrict__ x,
 }
 __device__ __forceinline__ float up_val(const float *sm, int nelrow, int o0, int o1, int c, float aw, float ah)
 {
-    const float l0 = (1.f - aw) * sm[o0 + c] + aw * sm[o1 + c];
-    const float l1 = (1.f - aw) * sm[nelrow + o0 + c] + aw * sm[nelrow + o1 + c];
-    return (1.f - ah) * l0 + ah * l1;
+    const float l0 = resample_lerp(aw, sm[o0 + c], sm[o1 + c]);
+    const float l1 = resample_lerp(aw, sm[nelrow + o0 + c], sm[nelrow + o1 + c]);
+    return resample_lerp(ah, l0, l1);
 }
 // chunk -> (n, ho, first output column); source rows / columns of the chunk
 struct UpChunk { int n, ho, wo0, h0, h1, wlo, nw; float ah; };
@@ -224,13 +224,11 @@ __device__ __forceinline__ UpChunk up_chunk(const UpGeom &g, long long chunk, in
     k.wo0 = (int)(chunk - row * cpr) * 256;
     k.n = (int)(row / g.H);
     k.ho = (int)(row - (long long)k.n * g.H);
-    const float fh = fmaxf(k.ho * g.sh + g.oh, 0.f);
-    int h0 = (int)fh; h0 = h0 > g.h - 1 ? g.h - 1 : h0;
-    k.h0 = h0; k.h1 = h0 + 1 < g.h ? h0 + 1 : g.h - 1; k.ah = fh - h0;
-    const int wlast = min(k.wo0 + 255, g.W - 1);
-    int a = (int)fmaxf(k.wo0 * g.sw + g.ow, 0.f); a = a > g.w - 1 ? g.w - 1 : a;
-    int b = (int)fmaxf(wlast * g.sw + g.ow, 0.f); b = b > g.w - 1 ? g.w - 1 : b;
-    b = b + 1 < g.w ? b + 1 : g.w - 1;
+    resample_src(k.ho, g.sh, g.oh, g.h, k.h0, k.h1, k.ah);
+    // the staged columns: the first source column of the chunk's first output column to the second of its last
+    int a, b, unused; float f;
+    resample_src(k.wo0, g.sw, g.ow, g.w, a, unused, f);
+    resample_src(min(k.wo0 + 255, g.W - 1), g.sw, g.ow, g.w, unused, b, f);
     k.wlo = a; k.nw = b - a + 1;
     return k;
 }
@@ -238,10 +236,9 @@ __device__ __forceinline__ UpChunk up_chunk(const UpGeom &g, long long chunk, in
 struct UpCol { float aw; int o0, o1, nr; };
 __device__ __forceinline__ UpCol up_col(const UpGeom &g, const UpChunk &k, int wo)
 {
-    const float fw = fmaxf(wo * g.sw + g.ow, 0.f);
-    int w0 = (int)fw; w0 = w0 > g.w - 1 ? g.w - 1 : w0;
-    const int w1 = w0 + 1 < g.w ? w0 + 1 : g.w - 1;
-    return UpCol{fw - w0, (w0 - k.wlo) * g.C, (w1 - k.wlo) * g.C, k.nw * g.C};
+    int w0, w1; float aw;
+    resample_src(wo, g.sw, g.ow, g.w, w0, w1, aw);
+    return UpCol{aw, (w0 - k.wlo) * g.C, (w1 - k.wlo) * g.C, k.nw * g.C};
 }
 // One interpolated pixel of a staged patch, channel c through operator().  CT: the class count at compile time (19: the logits
 // are interpolated ONCE into registers) or 0 (any C: re-interpolated at every read).  mul: the 1/T of the two-distribution losses.

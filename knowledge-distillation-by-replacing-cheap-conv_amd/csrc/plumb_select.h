@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/kdcc.h"
+#include "resample.h"
 
 // One value per name the launchers note (plumb_kernel_name), then PLUMB_REFUSED.  Where a kernel has dtype / vector variants they
 // are a range in the order <f32 before bf16> x <scalar before vector>, the first operand's dtype slowest.
@@ -123,21 +124,9 @@ static inline PlumbSel plumb_flat(PlumbKernel k, long long blocks)
 }
 static inline int plumb_pool_out(int I) { return (I - 1) / 2 + 1; }     // 3x3 / stride 2 / pad 1
 
-// ---- the bilinear resampling geometry (forward and backward) ---------------------------------------------------------------------
-// (h, w) -> (H, W): align_corners: src = o * (i-1)/(O-1); otherwise src = max((o + 0.5) * i/O - 0.5, 0)
-struct PlumbUpGeom { float sh, sw, oh, ow; };
-static inline PlumbUpGeom plumb_up_geom(int h, int w, int H, int W, int align_corners)
-{
-    PlumbUpGeom g;
-    g.sh = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
-    g.sw = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
-    g.oh = 0.f; g.ow = 0.f;
-    if (!align_corners) {
-        g.sh = (float)h / (float)H; g.sw = (float)w / (float)W;
-        g.oh = 0.5f * g.sh - 0.5f; g.ow = 0.5f * g.sw - 0.5f;
-    }
-    return g;
-}
+// the resampling geometry (resample.h) under the name the host wrapper of tests/plumb_select_host knows it by
+typedef ResampleGeom PlumbUpGeom;
+static inline PlumbUpGeom plumb_up_geom(int h, int w, int H, int W, int align_corners) { return resample_geom(h, w, H, W, align_corners); }
 
 // ---- trunk_ops.hip --------------------------------------------------------------------------------------------------------------
 static inline PlumbSel plumb_select_stem_conv(int dtype, int N, int H, int W)
@@ -180,7 +169,7 @@ static inline PlumbSel plumb_select_upsample(const void *x, int x_dtype, int ldx
                        : (PlumbKernel)(PK_UP_F32_F32_1 + 4 * (x_dtype == KD_BF16) + 2 * (y_dtype == KD_BF16) + c.vec);
     const long long per_row = c.flat4 ? (long long)Wo * C / 4 : (long long)Wo * (c.vec ? C / 8 : C);
     c.grid = c.grid2 = plumb_grid3((per_row + 255) / 256, (Ho + PLUMB_UP_RO - 1) / PLUMB_UP_RO, N);
-    const PlumbUpGeom g = plumb_up_geom(H, W, Ho, Wo, align_corners);
+    const ResampleGeom g = resample_geom(H, W, Ho, Wo, align_corners);
     c.sh = g.sh; c.sw = g.sw; c.oh = g.oh; c.ow = g.ow;
     return c;
 }
@@ -307,7 +296,7 @@ static inline PlumbSel plumb_select_upsample_bwd(const void *gy, int gy_dtype, i
     const long long bx = ((long long)W * (c.vec ? C / 8 : C) + 255) / 256;
     c.grid = plumb_grid3(bx, Ho, N);
     c.grid2 = plumb_grid3(bx, H, N);
-    const PlumbUpGeom g = plumb_up_geom(H, W, Ho, Wo, align_corners);
+    const ResampleGeom g = resample_geom(H, W, Ho, Wo, align_corners);
     c.sh = g.sh; c.sw = g.sw; c.oh = g.oh; c.ow = g.ow;
     return c;
 }

@@ -401,11 +401,8 @@ __global__ __launch_bounds__(256) void upsample_kernel(const TI *__restrict__ x,
     if (e >= (unsigned)Wo * cv) return;
     const unsigned wo = e / cv, cq = e - wo * cv;
     const int n = blockIdx.z;
-    // align_corners=True: src = o * (I-1)/(O-1) (oh = ow = 0); align_corners=False: src = max((o + 0.5) * I/O - 0.5, 0)
-    const float fw = fmaxf(wo * sw + ow, 0.f);
-    int w0 = (int)fw; w0 = w0 > W - 1 ? W - 1 : w0;
-    const int w1 = w0 + 1 < W ? w0 + 1 : W - 1;
-    const float aw = fw - w0;
+    int w0, w1; float aw;
+    resample_src((int)wo, sw, ow, W, w0, w1, aw);
     const TI *b = x + (size_t)n * H * W * ldx + cq * VEC;
     float la[VEC], lb[VEC];                // the two cached input rows, already interpolated along x
     int ia = -1, ib = -1;                  // their row indices (block-uniform)
@@ -419,16 +416,14 @@ __global__ __launch_bounds__(256) void upsample_kernel(const TI *__restrict__ x,
             r1[0] = Elem<TI>::ld(b + ((size_t)h * W + w1) * ldx);
         }
 #pragma unroll
-        for (int q = 0; q < VEC; ++q) l[q] = (1.f - aw) * r0[q] + aw * r1[q];
+        for (int q = 0; q < VEC; ++q) l[q] = resample_lerp(aw, r0[q], r1[q]);
     };
 #pragma unroll
     for (int rr = 0; rr < UP_RO; ++rr) {
         const int ho = blockIdx.y * UP_RO + rr;
         if (ho >= Ho) break;
-        const float fh = fmaxf(ho * sh + oh, 0.f);
-        int h0 = (int)fh; h0 = h0 > H - 1 ? H - 1 : h0;
-        const int h1 = h0 + 1 < H ? h0 + 1 : H - 1;
-        const float ah = fh - h0;
+        int h0, h1; float ah;
+        resample_src(ho, sh, oh, H, h0, h1, ah);
         if (h0 == ib && ia != h0) {        // slide: the lower row becomes the upper one
 #pragma unroll
             for (int q = 0; q < VEC; ++q) la[q] = lb[q];
@@ -447,7 +442,7 @@ __global__ __launch_bounds__(256) void upsample_kernel(const TI *__restrict__ x,
         const size_t o = (((size_t)n * Ho + ho) * Wo + wo) * ldy + cq * VEC;
         float v[VEC];
 #pragma unroll
-        for (int q = 0; q < VEC; ++q) v[q] = (1.f - ah) * la[q] + ah * lb[q];
+        for (int q = 0; q < VEC; ++q) v[q] = resample_lerp(ah, la[q], lb[q]);
         if constexpr (VEC == 8) st8(y + o, v);
         else Elem<TO>::st(y + o, v[0]);
     }
@@ -470,11 +465,7 @@ __global__ __launch_bounds__(256) void upsample_flat4_kernel(const TI *__restric
     for (int q = 0; q < 4; ++q) {
         const unsigned f = e4 * 4u + q, wo = f / (unsigned)C;
         cc[q] = (int)(f - wo * (unsigned)C);
-        const float fw = fmaxf(wo * sw + ow, 0.f);
-        int a = (int)fw; a = a > W - 1 ? W - 1 : a;
-        w0[q] = a;
-        w1[q] = a + 1 < W ? a + 1 : W - 1;
-        aw[q] = fw - a;
+        resample_src((int)wo, sw, ow, W, w0[q], w1[q], aw[q]);
     }
     const TI *b = x + (size_t)n * H * W * ldx;
     float la[4], lb[4];
@@ -484,17 +475,15 @@ __global__ __launch_bounds__(256) void upsample_flat4_kernel(const TI *__restric
         for (int q = 0; q < 4; ++q) {
             const float r0 = Elem<TI>::ld(b + ((size_t)h * W + w0[q]) * ldx + cc[q]);
             const float r1 = Elem<TI>::ld(b + ((size_t)h * W + w1[q]) * ldx + cc[q]);
-            l[q] = (1.f - aw[q]) * r0 + aw[q] * r1;
+            l[q] = resample_lerp(aw[q], r0, r1);
         }
     };
 #pragma unroll
     for (int rr = 0; rr < UP_RO; ++rr) {
         const int ho = blockIdx.y * UP_RO + rr;
         if (ho >= Ho) break;
-        const float fh = fmaxf(ho * sh + oh, 0.f);
-        int h0 = (int)fh; h0 = h0 > H - 1 ? H - 1 : h0;
-        const int h1 = h0 + 1 < H ? h0 + 1 : H - 1;
-        const float ah = fh - h0;
+        int h0, h1; float ah;
+        resample_src(ho, sh, oh, H, h0, h1, ah);
         if (h0 == ib && ia != h0) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) la[q] = lb[q];
@@ -511,10 +500,10 @@ __global__ __launch_bounds__(256) void upsample_flat4_kernel(const TI *__restric
             ib = h1;
         }
         float4 v;
-        v.x = (1.f - ah) * la[0] + ah * lb[0];
-        v.y = (1.f - ah) * la[1] + ah * lb[1];
-        v.z = (1.f - ah) * la[2] + ah * lb[2];
-        v.w = (1.f - ah) * la[3] + ah * lb[3];
+        v.x = resample_lerp(ah, la[0], lb[0]);
+        v.y = resample_lerp(ah, la[1], lb[1]);
+        v.z = resample_lerp(ah, la[2], lb[2]);
+        v.w = resample_lerp(ah, la[3], lb[3]);
         *(float4 *)(y + (((size_t)n * Ho + ho) * Wo) * C + (size_t)e4 * 4) = v;
     }
 }

@@ -418,7 +418,7 @@ def test_the_selection_header_is_plain_host_code():
     with open(os.path.join(CSRC, "gscnn_select.h")) as f:
         text = re.sub(r"//[^\n]*|/\*.*?\*/", "", f.read(), flags=re.S)
     assert not re.search(r"\bhip\w*|\bgetenv\b|__global__|__device__", text, flags=re.I)
-    assert re.findall(r"#include\s*(\S+)", text) == ["<stddef.h>", "<stdint.h>", '"../../include/kdcc.h"']
+    assert re.findall(r"#include\s*(\S+)", text) == ["<stddef.h>", "<stdint.h>", '"../../include/kdcc.h"', '"resample.h"']
     # no state: the only statics are the inline functions and the constant name table
     statics = re.findall(r"^\s*static\s+(?!inline\b|const char \*const names\[\]|_?assert)[^\n]*", re.sub(r"static_assert", "_assert", text), flags=re.M)
     assert not statics, statics

@@ -90,6 +90,18 @@ def test_fuse_sum_reads_and_writes_channel_slices():
     assert bool((out[..., :4] == 7).all()) and bool((out[..., 20:] == 7).all())
 
 
+@pytest.mark.parametrize("size", FUSE_SIZES[1:], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_fuse_of_one_coarser_source_is_the_upsample_kernels_result(size):
+    """Both kernels resample by csrc/resample.h: the fuse sum of a single coarser source is relu of its align-corners upsample, to
+    the fuse sum's fp32 bound.  Not bit for bit: the compiler contracts the blend differently in the two kernels, so 3x4 -> 9x13
+    (weights 0.25 / 0.75) differs by 3.6e-8 rel-L2; 5x7 (weights 0 / 0.5) and 1x1 are equal."""
+    from kdcc_amd import ops
+    src = torch.empty((2,) + size + (16,), device="cuda").copy_(_nhwc(seeded_input(f"fuse.up.{size[0]}x{size[1]}", (2, 16) + size)))
+    out = torch.empty(2, 9, 13, 16, device="cuda")
+    ops.hr_fuse([src], out=out)
+    _close(out.cpu().double(), torch.relu(ops.upsample_bilinear_ac(src, (9, 13))).cpu().double(), 1e-5, f"fuse of {size} against upsample")
+
+
 def test_fuse_module_function_differentiates():
     from kdcc_amd.models.hrnet_ocr import fuse_sum
     srcs = [seeded_input(f"fusefn.{i}", (2, 48, h, w)) for i, (h, w) in enumerate(FUSE_SIZES[:3])]

@@ -330,7 +330,7 @@ def test_the_names_are_distinct_and_every_one_has_a_row(lib):
 def test_the_selection_header_is_plain_host_code():
     text = header_text()
     assert not re.search(r"\bhip\w*|\bgetenv\b", text, flags=re.I)
-    assert re.findall(r"#include\s*(\S+)", text) == ["<stddef.h>", "<stdint.h>", '"../../include/kdcc.h"']
+    assert re.findall(r"#include\s*(\S+)", text) == ["<stddef.h>", "<stdint.h>", '"../../include/kdcc.h"', '"resample.h"']
 
 
 # ---- the workspace: the parent's formula (kd_loss_workspace is public ABI) -------------------------------------------------------------------

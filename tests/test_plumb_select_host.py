@@ -398,7 +398,7 @@ def test_the_selection_header_is_plain_host_code():
     with open(os.path.join(CSRC, "plumb_select.h")) as f:
         text = re.sub(r"//[^\n]*|/\*.*?\*/", "", f.read(), flags=re.S)
     assert not re.search(r"\bhip\w*|\bgetenv\b", text, flags=re.I)
-    assert re.findall(r"#include\s*(\S+)", text) == ["<stddef.h>", "<stdint.h>", '"../../include/kdcc.h"']
+    assert re.findall(r"#include\s*(\S+)", text) == ["<stddef.h>", "<stdint.h>", '"../../include/kdcc.h"', '"resample.h"']
 
 
 # ---- the resampling geometry: the parent's float expressions, bit for bit ----------------------------------------------------------------

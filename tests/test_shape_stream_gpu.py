@@ -239,6 +239,15 @@ def test_edge_aspp(K, SEL, c):
     assert_close(host(out), ref["y"], c["dt"], c["id"])
 
 
+def test_edge_aspp_with_unit_weights_is_the_upsample_kernels_result(K):
+    """w = scale = 1, shift = 0: every channel is relu of the C = 1 align-corners upsample of the same map."""
+    acts = torch.rand(2, 5, 7, generator=torch.Generator().manual_seed(5)).cuda()
+    out = torch.empty(2, 9, 13, 8, device="cuda")
+    K.edge_aspp(acts, torch.ones(8, device="cuda"), torch.ones(8, device="cuda"), torch.zeros(8, device="cuda"), out)
+    up = torch.relu(K.upsample_bilinear_ac(acts.unsqueeze(3).contiguous(), (9, 13)))
+    assert torch.equal(out, up.expand(2, 9, 13, 8))
+
+
 # ----------------------------------------------------------------------------------------------------------------- kd_rank1_add
 R1 = S.cases_of("rank1_add")
 
