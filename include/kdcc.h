@@ -889,6 +889,29 @@ int kd_seg_finish(const uint8_t *img, const uint8_t *mask, int64_t n, int32_t H,
 int kd_seg_class_stats(const uint8_t *targets, int64_t n, int32_t H, int32_t W, int32_t tile, int32_t num_classes, int64_t *stats,
                        kd_stream_t stream);
 
+/* ------------------------------------------------- classifier head of the CIFAR pre-activation ResNet (csrc/head_ops.hip)
+ * The reference's PreResNet ends in bn -> relu -> AvgPool2d(8) on an 8x8 map (models/cifar_models/preresnet.py:150-153).  One pass
+ * that never stores the activation:
+ *   pooled[n][c] = (1/HW) sum_p max((x[n][p][c] - mean[c]) invstd[c] gamma[c] + beta[c], 0)
+ *   x       fp32 NHWC view, pixel (n, p) at x + (n HW + p) ldx, ldx >= C;  pooled dense (N,C);
+ *   gamma, beta, mean, invstd  (C) fp32: eval mode passes the running mean and 1/sqrt(running_var + eps), train mode what
+ *           kd_bn_nhwc_stats gave.  running_mean / running_var (each may be NULL) are then updated in place as kd_bn_nhwc_apply does,
+ *           running <- (1 - momentum) running + momentum v, from mean and var_unbiased (needed with running_var only).
+ * The backward recomputes the activation's sign from x.  With g'[n][p][c] = gpooled[n][c] / HW where the activation is positive and
+ * 0 elsewhere, and xhat = (x - mean) invstd, M = N HW:
+ *   dbeta = sum g',  dgamma = sum g' xhat,
+ *   dx = gamma invstd (g' - dbeta / M - xhat dgamma / M) in train mode, gamma invstd g' in eval mode; pixel stride lddx >= C.
+ *   dx may be NULL (then lddx is ignored); dgamma and dbeta are always written.
+ * A workgroup owns four channels over all N HW pixels: no workspace, no atomics, fixed-order sums (the same bits every run), correct
+ * at any size and meant for CIFAR's (a few MB).  16-byte accesses when C % 4 == 0 and x and dx (when given) are 16-byte aligned with
+ * pixel strides that are multiples of 4, scalar accesses otherwise (csrc/head_select.h decides). */
+int kd_head_bn_relu_pool_fwd(const float *x, int32_t ldx, int32_t N, int32_t HW, int32_t C, const float *gamma, const float *beta,
+                             const float *mean, const float *invstd, float *pooled, const float *var_unbiased, float *running_mean,
+                             float *running_var, float momentum, kd_stream_t stream);
+int kd_head_bn_relu_pool_bwd(const float *x, int32_t ldx, const float *gpooled, int32_t N, int32_t HW, int32_t C, const float *gamma,
+                             const float *beta, const float *mean, const float *invstd, float *dx, int32_t lddx, float *dgamma,
+                             float *dbeta, int32_t training, kd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -225,6 +225,8 @@ _SIGS = {
     "kd_debug_kernel_log_enable": (c_int, [c_int]),
     "kd_debug_kernel_log_read": (c_i64, [C.c_char_p, c_sz]),
     "kd_debug_last_kernel": (C.c_char_p, []),
+    "kd_head_bn_relu_pool_fwd": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f, c_vp]),
+    "kd_head_bn_relu_pool_bwd": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp]),
     "kd_debug_last_plumbing_kernel": (C.c_char_p, []),
 }
 

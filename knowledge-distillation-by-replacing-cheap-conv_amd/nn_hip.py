@@ -212,7 +212,7 @@ class _ConvNHWCFn(torch.autograd.Function):
     def backward(ctx, gy):
         mod = ctx.mod
         (xh,) = ctx.saved_tensors
-        co, cop = mod.out_channels, mod._cout_pad(gy.dtype)
+        co, cop = mod.out_channels, mod._cout_pad(gy.dtype, dgrad=ctx.needs_input_grad[0])
         g = _nhwc(gy) if co == cop else _nhwc_padded(gy, cop)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
@@ -278,9 +278,10 @@ class Conv2dNHWC(nn.Conv2d):
     def _cin_pad(self, dtype):
         return _granule_up(self.in_channels, dtype)
 
-    def _cout_pad(self, dtype):
-        """cout_pad for activations of `dtype`: in bf16 the output gradient is always padded to the K granule of its dgrad conv."""
-        return self.cout_pad if dtype == torch.float32 else _granule_up(self.out_channels, dtype)
+    def _cout_pad(self, dtype, dgrad=False):
+        """cout_pad for activations of `dtype`: in bf16 the output gradient is always padded to the K granule of its dgrad conv; in
+        fp32 only where that conv runs (dgrad) and needs it: the 16-channel layers of the CIFAR PreResNet."""
+        return self.cout_pad if dtype == torch.float32 and not dgrad else _granule_up(self.out_channels, dtype)
 
     @property
     def cout_fwd(self):
@@ -305,7 +306,7 @@ class Conv2dNHWC(nn.Conv2d):
 
     def _pack(self, mode, dtype=torch.float32):
         w = self.weight
-        rows, cin_pad = (self.cout_fwd, self._cin_pad(dtype)) if mode == KD_PACK_FWD else (self._cout_pad(dtype), None)
+        rows, cin_pad = (self.cout_fwd, self._cin_pad(dtype)) if mode == KD_PACK_FWD else (self._cout_pad(dtype, dgrad=True), None)
         what = mode if dtype == torch.float32 else (mode, dtype)
         return self._cached(what, w, lambda: ops.pack_conv_weight(self._padded_rows(w, rows), dtype, mode, cin_pad=cin_pad))
 
@@ -333,10 +334,12 @@ class Conv2dNHWC(nn.Conv2d):
             return _nhwc_padded(x.detach(), self._cin_pad(x.dtype))
         return _nhwc(x.detach())
 
-    def _run(self, xh, res_pre=None, out_act=False, act_scale=None, act_shift=None, act_relu=False, want_raw=True, raw_into=None):
+    def _run(self, xh, res_pre=None, out_act=False, act_scale=None, act_shift=None, act_relu=False, want_raw=True, raw_into=None,
+             act_padded=False):
         """Forward on an (N,H,W,cin_pad) view: raw = conv(xh) + bias [+ res_pre] and, with out_act, act = relu?(act_scale * raw +
         act_shift) -> raw [, act], (N,Ho,Wo,Cout) views of xh's dtype (raw is raw_into when given, None without want_raw).  The
-        bias rides in the epilogue's shift, so a biased conv gives raw or act, not both.  In bf16 act comes from new_padded()."""
+        bias rides in the epilogue's shift, so a biased conv gives raw or act, not both.  In bf16, and in fp32 with act_padded, act
+        comes from new_padded()."""
         N, H, W, _ = xh.shape
         k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
         Ho, Wo = ops.conv_out_size(H, k, s, p, 1), ops.conv_out_size(W, k, s, p, 1)
@@ -346,7 +349,7 @@ class Conv2dNHWC(nn.Conv2d):
             new = new_act = lambda: new_padded((N, Ho, Wo, rows), xh.device)
         else:
             new = lambda: torch.empty((N, Ho, Wo, co), dtype=dt, device=xh.device)
-            new_act = new if dt == torch.float32 else (lambda: new_padded((N, Ho, Wo, co), xh.device, dt))
+            new_act = new if dt == torch.float32 and not act_padded else (lambda: new_padded((N, Ho, Wo, co), xh.device, dt))
         raw = raw_into if raw_into is not None else (new() if want_raw else None)
         act = new_act() if out_act else None
         k_raw, k_act, b = raw, act, self._shift()
@@ -598,3 +601,47 @@ class AvgPool2x2NHWC(nn.AvgPool2d):
         if x.dtype != torch.float32:
             raise TypeError("AvgPool2x2NHWC is fp32")
         return _AvgPool2x2Fn.apply(x)
+
+
+# ------------------------------------------------------------------ classifier head of the CIFAR PreResNet (csrc/head_ops.hip)
+class _HeadBNReLUPoolFn(torch.autograd.Function):
+    """pooled (N,C) = mean over the map of relu(bn(x)): kd_head_bn_relu_pool_fwd reads x once and stores no activation; the
+    backward (kd_head_bn_relu_pool_bwd) recomputes the activation's sign from x.  Train mode takes the batch statistics from
+    ops.bn_nhwc_stats first; the forward kernel then updates the running statistics as kd_bn_nhwc_apply does."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, training, momentum, eps):
+        xh = _nhwc(x)
+        g, b = gamma.contiguous(), beta.contiguous()
+        if training:
+            mean, invstd, var = ops.bn_nhwc_stats(xh, eps)
+            pooled = ops.head_bn_relu_pool_fwd(xh, g, b, mean, invstd, var, running_mean, running_var, momentum)
+        else:
+            mean, invstd = running_mean, torch.rsqrt(running_var + eps)
+            pooled = ops.head_bn_relu_pool_fwd(xh, g, b, mean, invstd)
+        ctx.save_for_backward(xh, g, b, mean, invstd)
+        ctx.training = training
+        return pooled
+
+    @staticmethod
+    def backward(ctx, gp):
+        xh, g, b, mean, invstd = ctx.saved_tensors
+        dx, dg, db = ops.head_bn_relu_pool_bwd(xh, gp.contiguous(), g, b, mean, invstd, ctx.training, need_dx=ctx.needs_input_grad[0])
+        return (None if dx is None else dx.permute(0, 3, 1, 2), dg if ctx.needs_input_grad[1] else None,
+                db if ctx.needs_input_grad[2] else None, None, None, None, None, None)
+
+
+def bn_relu_avgpool(bn, relu, x, kernel_size=8):
+    """flatten(AvgPool2d(kernel_size)(relu(bn(x)))) -> (N, C * pooled positions), the tail of the CIFAR PreResNet.  One fused pass
+    (_HeadBNReLUPoolFn) when the pool covers the whole map, x is an fp32 device tensor, bn a BatchNorm2dNHWC and neither bn nor relu
+    carries a forward hook; otherwise bn(x, relu=True) followed by F.avg_pool2d.  Host tensors (allow_host_tensors) run the modules."""
+    if _host(x):
+        return F.avg_pool2d(relu(bn(x)), kernel_size).flatten(1)
+    if type(bn) is not BatchNorm2dNHWC:     # (a replaced BN: called as a module; the small-shape BatchNorm2d fuses its ReLU)
+        return F.avg_pool2d(bn(x, relu=True) if type(bn) is BatchNorm2d else relu(bn(x)), kernel_size).flatten(1)
+    if _hooked(bn, relu) or x.dtype != torch.float32 or tuple(x.shape[2:]) != (kernel_size, kernel_size):
+        return F.avg_pool2d(bn(x, relu=True).float(), kernel_size).flatten(1)
+    bn._check(x)
+    if bn.training:
+        bn.num_batches_tracked.add_(1)
+    return _HeadBNReLUPoolFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, float(bn.momentum), float(bn.eps))

@@ -1120,6 +1120,60 @@ def avgpool2x2_bwd(gy, size, out=None):
     return gx
 
 
+# ------------------------------------------------------------------------- PreResNet classifier head (csrc/head_ops.hip)
+def _head_operands(who, x, vecs):
+    _need_cuda(x)
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise TypeError(f"{who}: an (N,H,W,C) fp32 view only")
+    _f32vec(*vecs)
+    N, H, W, Cc = x.shape
+    for v in vecs:
+        if v is not None and v.numel() != Cc:
+            raise ValueError(f"{who}: {Cc} channels, a vector of {v.numel()}")
+    return N, H * W, Cc
+
+
+def head_bn_relu_pool_fwd(x, gamma, beta, mean, invstd, var_unbiased=None, running_mean=None, running_var=None, momentum=0.0):
+    """mean over the map of relu((x - mean) invstd gamma + beta) for an (N,H,W,C) fp32 view -> (N,C); the activation is never stored.
+    mean / invstd: the running statistics (eval) or bn_nhwc_stats' (train); running_mean / running_var, when given, are updated
+    in place from mean / var_unbiased as bn_nhwc_apply does."""
+    N, HW, Cc = _head_operands("head_bn_relu_pool_fwd", x, (gamma, beta, mean, invstd, var_unbiased, running_mean, running_var))
+    if running_var is not None and var_unbiased is None:
+        raise ValueError("head_bn_relu_pool_fwd: running_var needs var_unbiased")
+    pooled = torch.empty((N, Cc), dtype=torch.float32, device=x.device)
+    check(_lib.lib().kd_head_bn_relu_pool_fwd(_ptr(x), nhwc_ld(x), N, HW, Cc, _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd), _ptr(pooled),
+                                              _ptr(var_unbiased), _ptr(running_mean), _ptr(running_var), C.c_float(momentum), stream_ptr()),
+          "kd_head_bn_relu_pool_fwd")
+    for t in (running_mean, running_var):
+        if t is not None:
+            torch.autograd.graph.increment_version(t)
+    return pooled
+
+
+def head_bn_relu_pool_bwd(x, gpooled, gamma, beta, mean, invstd, training, need_dx=True, out=None):
+    """Backward of head_bn_relu_pool_fwd from x itself -> (dx | None, dgamma, dbeta); gpooled a contiguous fp32 (N,C); out, an
+    (N,H,W,C) fp32 view that does not overlap x, receives dx instead of a fresh tensor."""
+    N, HW, Cc = _head_operands("head_bn_relu_pool_bwd", x, (gamma, beta, mean, invstd))
+    _need_cuda(gpooled, out)
+    if gpooled.dtype != torch.float32 or tuple(gpooled.shape) != (N, Cc) or not gpooled.is_contiguous():
+        raise ValueError(f"head_bn_relu_pool_bwd: gpooled must be a contiguous fp32 ({N},{Cc}) tensor")
+    if out is not None:
+        if not need_dx or out.dtype != torch.float32 or tuple(out.shape) != tuple(x.shape):
+            raise ValueError("head_bn_relu_pool_bwd: out must be an fp32 view of x's shape, given with need_dx only")
+        M = N * HW
+        lo, hi = out.data_ptr(), out.data_ptr() + 4 * ((M - 1) * nhwc_ld(out) + Cc)
+        if x.data_ptr() < hi and lo < x.data_ptr() + 4 * ((M - 1) * nhwc_ld(x) + Cc):
+            raise ValueError("head_bn_relu_pool_bwd: out overlaps x")
+    dx = out if out is not None else (torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device) if need_dx else None)
+    dgamma, dbeta = torch.empty(Cc, device=x.device), torch.empty(Cc, device=x.device)
+    check(_lib.lib().kd_head_bn_relu_pool_bwd(_ptr(x), nhwc_ld(x), _ptr(gpooled), N, HW, Cc, _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd),
+                                              _ptr(dx), 0 if dx is None else nhwc_ld(dx), _ptr(dgamma), _ptr(dbeta), int(bool(training)),
+                                              stream_ptr()), "kd_head_bn_relu_pool_bwd")
+    if out is not None:
+        torch.autograd.graph.increment_version(out)
+    return dx, dgamma, dbeta
+
+
 def copy_cast(src, dst):
     """dst = src for two (N,C,H,W)-logical fp32/bf16 device tensors of the same shape with any dense-plane layout
     (NCHW <-> channels_last, a channel slice of a wider NHWC buffer) -- kd_copy_cast."""
