@@ -912,6 +912,22 @@ int kd_head_bn_relu_pool_bwd(const float *x, int32_t ldx, const float *gpooled, 
                              const float *beta, const float *mean, const float *invstd, float *dx, int32_t lddx, float *dgamma,
                              float *dbeta, int32_t training, kd_stream_t stream);
 
+/* ------------------------------------------------- dropout (csrc/dropout.hip; the rule: csrc/dropout_rng.h)
+ * y[m][c] = keep(m, c) ? x[m][c] * scale : 0 for an (M, C) NHWC view, dtype KD_F32 or KD_BF16 (the product in fp32, bf16 rounded to
+ * nearest-even once, at the store); ldx, ldy >= C are the pixel strides in elements.  The mask is a pure function of
+ * (seed, offset, idx) and of nothing else -- layout, strides, dtype, vector width and grid do not change it:
+ *   idx = m * C + c as int64, m the pixel index (n*H + h)*W + w, c the logical channel, C the logical channel count;
+ *   Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl key increments 0x9E3779B9 / 0xBB67AE85, 10 rounds) with
+ *   key = (seed & 0xffffffff, seed >> 32), counter = (q & 0xffffffff, q >> 32, offset & 0xffffffff, offset >> 32), q = idx >> 2;
+ *   element idx uses output word idx & 3 and is kept iff word >= threshold.
+ * The caller turns a rate p into threshold = floor(p * 2^32) and scale = 1 / (1 - p).  The same call with the forward's
+ * (seed, offset) is the backward: dx = dropout(gy); nothing is stored between the two.  x == y is allowed (a thread loads its
+ * elements before it stores them and touches no others); channels [C, ld) of a padded view are neither read nor written.  No
+ * workspace.  A lane takes 16 bytes (4 fp32 or 8 bf16 channels) when C is a multiple of that and both views are 16-byte aligned with
+ * 16-byte-multiple pixel strides, one Philox block of scalar accesses otherwise (csrc/dropout_select.h decides). */
+int kd_dropout_nhwc(const void *x, int32_t ldx, void *y, int32_t ldy, int32_t dtype, int64_t M, int32_t C, uint32_t threshold, float scale,
+                    uint64_t seed, uint64_t offset, kd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

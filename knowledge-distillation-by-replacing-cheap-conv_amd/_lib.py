@@ -228,6 +228,7 @@ _SIGS = {
     "kd_head_bn_relu_pool_fwd": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f, c_vp]),
     "kd_head_bn_relu_pool_bwd": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp]),
     "kd_debug_last_plumbing_kernel": (C.c_char_p, []),
+    "kd_dropout_nhwc": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_i64, c_int, C.c_uint32, c_f, C.c_uint64, C.c_uint64, c_vp]),
 }
 
 _lib = None
@@ -285,7 +286,7 @@ def last_kernel():
 def last_plumbing_kernel():
     """Name of the device kernel the calling thread's last plumbing dispatch selected (trunk_ops / bwd_ops / small_ops, and the
     criterion, metric and optimizer entry points of losses.hip, and the float4 / scalar choice of the NHWC BatchNorm and
-    average-pool entry points of bn_nhwc.hip / dense_ops.hip); independent of last_kernel() and of the counted log."""
+    average-pool entry points of bn_nhwc.hip / dense_ops.hip, the classifier head's and kd_dropout_nhwc's); independent of last_kernel() and of the counted log."""
     return lib().kd_debug_last_plumbing_kernel().decode()
 
 

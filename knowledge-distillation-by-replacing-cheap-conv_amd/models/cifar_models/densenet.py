@@ -20,6 +20,10 @@ kd_bn_nhwc_apply pass.  They live for the block's forward (and in the autograd g
 layers form a chain, norm1's backward adds the gradient of the prefix it read (kd_bn_nhwc_bwd's `res`) and accumulates in place
 into the buffer the next layer's norm1 allocated (nn_hip.GradChain), so the block's input gradients live in one buffer too.
 
+drop_rate > 0 in train mode: conv2 writes a temporary and one kd_dropout_nhwc pass (nn_hip.dropout, out= the layer's slice) moves
+the dropped features into the buffer, in place of the copy; the slice's statistics are reduced from the dropped values, and the
+backward is the same pass over the slice of the gradient (the mask is regenerated from the call's (seed, offset), not stored).
+
 Eval mode without autograd (the frozen teacher, validation): conv1's epilogue applies norm2 + ReLU folded to scale / shift, while
 both convs and both BNs of the layer are the nn_hip classes and conv1 / norm2 / relu2 carry no hooks.  norm1 and conv2 are
 called as modules either way (the configs hint conv2).
@@ -126,8 +130,9 @@ class _DenseLayer(nn.Sequential):
                 and not self.norm2.training and not _hooked(self.conv1, self.norm2, self.relu2))
 
     def forward(self, x, st=None):
-        if self.drop_rate > 0 and self.training:
-            raise NotImplementedError("DenseNet: dropout (drop_rate > 0) in training is not implemented on the HIP path")
+        drop = self.drop_rate > 0 and self.training
+        if drop and not x.is_cuda:
+            raise NotImplementedError("DenseNet: dropout (drop_rate > 0) in training runs on the device only (nn_hip.dropout)")
         if nn_hip._host(x):
             return torch.cat([x, super().forward(x)], 1)
         c_in, c1 = self.num_input_features, self.num_input_features + self.growth_rate
@@ -151,7 +156,9 @@ class _DenseLayer(nn.Sequential):
                 a, xs = self.relu1(self.norm1(x)), x
             h = self.conv1(a)
             h = self.norm2(h, relu=True) if isinstance(self.norm2, nn_hip.BatchNorm2dNHWC) else self.relu2(self.norm2(h))
-            if type(self.conv2) is nn_hip.Conv2dNHWC:
+            if drop:    # conv2 writes a temporary (what a hook on it sees, as in the reference); the dropout pass moves it into the slice
+                new, copy = nn_hip.dropout(self.conv2(h), self.drop_rate, True, out=into), False
+            elif type(self.conv2) is nn_hip.Conv2dNHWC:
                 new, copy = self.conv2(h, out=into), False
             else:
                 new, copy = self.conv2(h), True
@@ -224,7 +231,8 @@ class _Features(nn.Sequential):
 
 class DenseNet(nn.Module):
     """DenseNet-BC: growth_rate filters per layer, block_config layers per block, num_init_features stem filters,
-    bn_size * growth_rate bottleneck width, drop_rate after each layer (training with it is not implemented), num_classes."""
+    bn_size * growth_rate bottleneck width, drop_rate on each layer's new features in train mode (nn_hip.dropout, device tensors
+    only: the pass that moves conv2's output into the block buffer), num_classes."""
 
     def __init__(self, growth_rate=32, block_config=(6, 12, 24, 16), num_init_features=64, bn_size=4, drop_rate=0, num_classes=10):
         super().__init__()

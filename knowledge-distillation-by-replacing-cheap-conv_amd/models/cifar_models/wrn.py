@@ -15,6 +15,9 @@ Eval mode without autograd (the frozen teacher, validation) runs a block as two 
 ReLU (folded to scale / shift), conv2's adds the shortcut and writes both the block output and the next BN + ReLU of it.  That
 fusion needs both convs of the block to be Conv2dNHWC; a block holding a DepthwiseSeparableBlock calls its children as modules.
 Hooks on block or group names see the block output either way.
+
+dropRate > 0: in train mode a block drops relu2(bn2(conv1)) before conv2 (the reference's F.dropout), in either dtype, with one
+nn_hip.dropout pass (kd_dropout_nhwc: a counter-based mask the backward regenerates, nothing stored); eval mode is unchanged.
 """
 import math
 
@@ -86,8 +89,9 @@ class BasicBlock(nn.Module):
         return out
 
     def forward(self, x):
-        if self.droprate > 0 and self.training:
-            raise NotImplementedError("WideResNet: dropout (dropRate > 0) in training is not implemented on the HIP path")
+        drop = self.droprate > 0 and self.training
+        if drop and not x.is_cuda:
+            raise NotImplementedError("WideResNet: dropout (dropRate > 0) in training runs on the device only (nn_hip.dropout)")
         if self._fusable(x):
             return self._forward_fused(x)
         if not self.equalInOut:
@@ -98,6 +102,8 @@ class BasicBlock(nn.Module):
         else:
             out = self.bn1(x, relu=True)
         out = self.bn2(self.conv1(out), relu=True)
+        if drop:        # out of place (bn2 saved its output for its backward), into a padded buffer conv2 reads in place
+            out = nn_hip.dropout(out, self.droprate, True)
         sc = x if self.equalInOut else self.convShortcut(x)
         if isinstance(self.conv2, nn_hip.Conv2dNHWC):
             return self.conv2(out, residual=sc)

@@ -645,3 +645,89 @@ def bn_relu_avgpool(bn, relu, x, kernel_size=8):
     if bn.training:
         bn.num_batches_tracked.add_(1)
     return _HeadBNReLUPoolFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, float(bn.momentum), float(bn.eps))
+
+
+# ------------------------------------------------------------------ dropout (csrc/dropout.hip; the rule: csrc/dropout_rng.h)
+# One process-wide stream (seed, next offset).  A forward draw takes the pair and advances the offset by one; the mask of the call
+# is a pure function of the pair and the element's index, so the backward regenerates it from the pair alone.  The seed follows
+# torch's: torch.initial_seed() is read at each draw, and when it has changed since the previous draw -- torch.manual_seed(s) before
+# a run -- the stream restarts at (s, 0), so seeding torch fixes every mask of the run.  seed_dropout() sets the pair directly and
+# holds until torch's seed changes next.  The stream is per process and knows nothing of ranks: ranks seeded alike draw the same
+# masks, as torch.nn.functional.dropout does under torch.manual_seed; seed each rank apart (seed + rank) for independent masks.
+_U64 = (1 << 64) - 1
+_DROPOUT_STREAM = {"seed": None, "offset": 0, "torch_seed": None}
+
+
+def _dropout_sync():
+    s, ts = _DROPOUT_STREAM, torch.initial_seed() & _U64
+    if s["torch_seed"] != ts:
+        s.update(seed=ts, offset=0, torch_seed=ts)
+    return s
+
+
+def seed_dropout(seed, offset=0):
+    """Set the dropout stream: the next draw uses (seed, offset).  Unsigned 64-bit integers."""
+    seed, offset = int(seed), int(offset)
+    if not (0 <= seed <= _U64 and 0 <= offset <= _U64):
+        raise ValueError("seed_dropout: seed and offset are unsigned 64-bit integers")
+    _DROPOUT_STREAM.update(seed=seed, offset=offset, torch_seed=torch.initial_seed() & _U64)
+
+
+def dropout_state():
+    """(seed, next offset): the pair the next forward draw will use."""
+    s = _dropout_sync()
+    return s["seed"], s["offset"]
+
+
+def _dropout_draw():
+    s = _dropout_sync()
+    pair = (s["seed"], s["offset"])
+    s["offset"] = (s["offset"] + 1) & _U64
+    return pair
+
+
+def _nhwc_view(t):
+    """(N,C,H,W)-logical tensor -> (N,H,W,C) pixel-strided view of any alignment; a copy only when t is not channels_last-strided."""
+    v = t.permute(0, 2, 3, 1)
+    try:
+        ops.nhwc_ld(v)
+        return v
+    except ValueError:
+        return _nhwc(t)
+
+
+class _DropoutFn(torch.autograd.Function):
+    """y = dropout(x) with the mask of (seed, offset); the backward is the same pass over gy.  Only (p, seed, offset) is kept."""
+
+    @staticmethod
+    def forward(ctx, x, p, seed, offset, out):
+        ctx.set_materialize_grads(False)
+        ctx.rule = (p, seed, offset)
+        xh = _nhwc_view(x)
+        y = new_padded(tuple(xh.shape), xh.device, x.dtype) if out is None else out
+        return ops.dropout_nhwc(xh, p, seed, offset, out=y).permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, gy):
+        if gy is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        return ops.dropout_nhwc(_nhwc_view(gy), *ctx.rule).permute(0, 3, 1, 2), None, None, None, None
+
+
+def dropout(x, p, training, out=None):
+    """F.dropout(x, p, training) for a channels-last fp32 or bf16 device tensor: one kd_dropout_nhwc pass, and the same pass over the
+    gradient in the backward -- no mask and no activation is stored.  The identity (no launch, no draw from the stream) when
+    `not training` or p == 0.  Each call draws one offset from the dropout stream (seed_dropout / dropout_state).  The result lives
+    in a new_padded() buffer and is tagged, so a Conv2dNHWC reads it in place; out, an (N,H,W,C) view of x's dtype (a channel slice
+    of a dense block's buffer), receives it instead.  Out of place by default: a producer that saved its output for its backward
+    (a BatchNorm with fused ReLU) must not see it change.  Host tensors raise: the rule is device-only."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout: p = {p} is outside [0, 1)")
+    if not training or p == 0.0:
+        return x
+    if _host(x):
+        raise NotImplementedError("nn_hip.dropout: the dropout rule runs on the device only")
+    seed, offset = _dropout_draw()
+    y = _DropoutFn.apply(x, p, seed, offset, out)
+    return mark_padded(y) if out is None else y

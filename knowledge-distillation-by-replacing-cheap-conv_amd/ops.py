@@ -1174,6 +1174,42 @@ def head_bn_relu_pool_bwd(x, gpooled, gamma, beta, mean, invstd, training, need_
     return dx, dgamma, dbeta
 
 
+# ------------------------------------------------------------------------- dropout (csrc/dropout.hip)
+def dropout_params(p):
+    """(threshold, scale) of a rate p in [0, 1): an element is kept iff its 32-bit random word is >= threshold = floor(p 2^32),
+    kept values are multiplied by scale = float32(1 / (1 - p)).  Computed here, so the kernel is a pure function of its arguments."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout: p = {p} is outside [0, 1)")
+    return int(p * 4294967296.0), C.c_float(1.0 / (1.0 - p)).value
+
+
+def dropout_nhwc(x, p, seed, offset, out=None):
+    """y = keep ? x / (1 - p) : 0 for an (N,H,W,C) fp32 or bf16 view (any pixel stride >= C) -- kd_dropout_nhwc.  The mask is the
+    counter-based rule of csrc/dropout_rng.h: a pure function of (seed, offset, m * C + c), whatever the layout, the dtype or the
+    kernel that runs, so the same call on the output gradient with the forward's (seed, offset) is the backward.  out: a view of
+    x's shape and dtype that receives y (x itself for an in-place pass, otherwise one that shares no element with x); channels past C
+    of a padded buffer are left alone."""
+    threshold, scale = dropout_params(p)
+    _need_cuda(x, out)
+    if x.dim() != 4:
+        raise ValueError(f"dropout_nhwc: expected an (N,H,W,C) view, got shape {tuple(x.shape)}")
+    dt = dt_of(x)
+    seed, offset = int(seed), int(offset)
+    if not (0 <= seed < 1 << 64 and 0 <= offset < 1 << 64):
+        raise ValueError("dropout_nhwc: seed and offset are unsigned 64-bit integers")
+    y = torch.empty(tuple(x.shape), dtype=x.dtype, device=x.device) if out is None else out
+    if tuple(y.shape) != tuple(x.shape) or y.dtype != x.dtype:
+        raise ValueError("dropout_nhwc: out must be a view of the input's shape and dtype")
+    N, H, W, Cc = x.shape
+    if N * H * W * Cc:
+        check(_lib.lib().kd_dropout_nhwc(_ptr(x), nhwc_ld(x), _ptr(y), nhwc_ld(y), dt, N * H * W, Cc, threshold, C.c_float(scale), seed, offset,
+                                         stream_ptr()), "kd_dropout_nhwc")
+    if out is not None and out.data_ptr() == x.data_ptr():      # in place: x changed under whoever saved it.  (A separate out is a
+        torch.autograd.graph.increment_version(out)             # fresh slice of its buffer, as conv2d's out_raw and copy_cast's dst.)
+    return y
+
+
 def copy_cast(src, dst):
     """dst = src for two (N,C,H,W)-logical fp32/bf16 device tensors of the same shape with any dense-plane layout
     (NCHW <-> channels_last, a channel slice of a wider NHWC buffer) -- kd_copy_cast."""
