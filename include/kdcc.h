@@ -928,6 +928,35 @@ int kd_head_bn_relu_pool_bwd(const float *x, int32_t ldx, const float *gpooled, 
 int kd_dropout_nhwc(const void *x, int32_t ldx, void *y, int32_t ldy, int32_t dtype, int64_t M, int32_t C, uint32_t threshold, float scale,
                     uint64_t seed, uint64_t offset, kd_stream_t stream);
 
+/* ------------------------------------------------- BatchNorm -> ReLU -> MaxPool2d(2, 2) of the CIFAR VGGs (csrc/pool_ops.hip)
+ * The reference's VGG `features` hold conv, BatchNorm2d, ReLU, MaxPool2d(kernel_size=2, stride=2) five times
+ * (models/cifar_models/vgg.py:53-66).  One pass that reads x once and never stores the full-resolution activation:
+ *   y[n][ho][wo][c] = max over ky, kx in {0, 1} of max((x[n][2 ho + ky][2 wo + kx][c] - mean[c]) (gamma[c] invstd[c]) + beta[c], 0)
+ *   x       fp32 NHWC view (N,H,W,C), pixel stride ldx >= C;  y (N,H/2,W/2,C), pixel stride ldy >= C; H, W >= 2 (KD_ERR_INVALID
+ *           otherwise); an odd last row or column is dropped, as nn.MaxPool2d does.
+ *   gamma, beta, mean, invstd  (C) fp32, or all four NULL for the form without BatchNorm, y = max over the window of max(x, 0).  Eval
+ *           mode passes the running mean and 1/sqrt(running_var + eps), train mode what kd_bn_nhwc_stats gave; running_mean /
+ *           running_var (each may be NULL) are then updated in place as kd_bn_nhwc_apply does,
+ *           running <- (1 - momentum) running + momentum v, from mean and var_unbiased (needed with running_var only).
+ * The backward saves nothing: it recomputes the four activations of every window from x.  g' is gpooled[n][ho][wo][c] (pixel stride
+ * ldg >= C) at the FIRST position in (ky, kx) order that holds the window's maximum, where that maximum is positive, and 0 at every
+ * other pixel: MaxPool2d's backward followed by ReLU's.  With xhat = (x - mean) invstd and M = N H W (every pixel counts, those of a
+ * dropped row or column too):
+ *   dbeta = sum g',  dgamma = sum g' xhat,
+ *   dx = gamma invstd (g' - dbeta / M - xhat dgamma / M) in train mode, gamma invstd g' in eval mode, g' without BatchNorm (then
+ *   dgamma and dbeta are NULL and dx is required); pixel stride lddx >= C.  With BatchNorm dx may be NULL (lddx is then ignored) and
+ *   dgamma and dbeta are always written.
+ * The sums are two fixed-order stages and no atomics (the same bits every run); with BatchNorm the backward needs
+ * kd_bn_nhwc_workspace(N H W, C) bytes of workspace (it uses less), without it none.  16-byte accesses when C % 4 == 0 and every
+ * activation view of the call is 16-byte aligned with a pixel stride that is a multiple of 4, scalar accesses otherwise
+ * (csrc/pool_select.h decides). */
+int kd_bn_relu_maxpool2x2_fwd(const float *x, int32_t ldx, int32_t N, int32_t H, int32_t W, int32_t C, const float *gamma, const float *beta,
+                              const float *mean, const float *invstd, float *y, int32_t ldy, const float *var_unbiased, float *running_mean,
+                              float *running_var, float momentum, kd_stream_t stream);
+int kd_bn_relu_maxpool2x2_bwd(const float *x, int32_t ldx, const float *gpooled, int32_t ldg, int32_t N, int32_t H, int32_t W, int32_t C,
+                              const float *gamma, const float *beta, const float *mean, const float *invstd, float *dx, int32_t lddx,
+                              float *dgamma, float *dbeta, int32_t training, void *workspace, size_t workspace_bytes, kd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -227,6 +227,9 @@ _SIGS = {
     "kd_debug_last_kernel": (C.c_char_p, []),
     "kd_head_bn_relu_pool_fwd": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f, c_vp]),
     "kd_head_bn_relu_pool_bwd": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp]),
+    "kd_bn_relu_maxpool2x2_fwd": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_f, c_vp]),
+    "kd_bn_relu_maxpool2x2_bwd": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp,
+                                          c_int, c_vp, c_sz, c_vp]),
     "kd_debug_last_plumbing_kernel": (C.c_char_p, []),
     "kd_dropout_nhwc": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_i64, c_int, C.c_uint32, c_f, C.c_uint64, C.c_uint64, c_vp]),
 }

@@ -647,6 +647,87 @@ def bn_relu_avgpool(bn, relu, x, kernel_size=8):
     return _HeadBNReLUPoolFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, float(bn.momentum), float(bn.eps))
 
 
+# ------------------------------------------------------------------ BN -> ReLU -> MaxPool2d(2, 2) of the CIFAR VGGs (csrc/pool_ops.hip)
+class _BNReLUMaxPoolFn(torch.autograd.Function):
+    """(N,C,H//2,W//2) = max over every 2x2 window of relu(bn(x)): kd_bn_relu_maxpool2x2_fwd reads x once and stores the pooled map
+    only; the backward (kd_bn_relu_maxpool2x2_bwd) recomputes the windows from x, so nothing but x and the statistics is kept.
+    gamma = None: max(relu(x)), the plain VGGs' and the fused eval chain's.  Train mode takes the batch statistics from
+    ops.bn_nhwc_stats first; the forward kernel then updates the running statistics as kd_bn_nhwc_apply does.  The pooled map comes
+    from new_padded() (the caller tags it)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, training, momentum, eps):
+        xh = _nhwc(x)
+        N, H, W, Cc = xh.shape
+        out = new_padded((N, H // 2, W // 2, Cc), xh.device)
+        if gamma is None:
+            g = b = mean = invstd = None
+            ops.bn_relu_maxpool2x2_fwd(xh, out=out)
+        else:
+            g, b = gamma.contiguous(), beta.contiguous()
+            if training:
+                mean, invstd, var = ops.bn_nhwc_stats(xh, eps)
+                ops.bn_relu_maxpool2x2_fwd(xh, g, b, mean, invstd, var, running_mean, running_var, momentum, out=out)
+            else:
+                mean, invstd = running_mean, torch.rsqrt(running_var + eps)
+                ops.bn_relu_maxpool2x2_fwd(xh, g, b, mean, invstd, out=out)
+        ctx.save_for_backward(xh, g, b, mean, invstd)
+        ctx.training = training
+        return out.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, gy):
+        xh, g, b, mean, invstd = ctx.saved_tensors
+        dx, dg, db = ops.bn_relu_maxpool2x2_bwd(xh, _nhwc(gy), g, b, mean, invstd, ctx.training, need_dx=ctx.needs_input_grad[0] or g is None)
+        return (dx.permute(0, 3, 1, 2) if ctx.needs_input_grad[0] else None, dg if ctx.needs_input_grad[1] else None,
+                db if ctx.needs_input_grad[2] else None, None, None, None, None, None)
+
+
+def _plain_maxpool2x2(pool):
+    return (type(pool) is nn.MaxPool2d and _one(pool.kernel_size) == 2 and _one(pool.stride) == 2 and _one(pool.padding) == 0
+            and _one(pool.dilation) == 1 and not pool.ceil_mode and not pool.return_indices)
+
+
+# The fused tail with BatchNorm takes maps of at least this many elements.  Below it every version is bound by its launches, not by
+# memory, and the fused one has a call more (the batch statistics are a call of their own): at batch 128 it held at vgg16_bn's
+# 32x32x64 ... 4x4x512 stages and lost at 2x2x512 (profiles/vgg.md), which therefore takes bn(x, relu=True) + the pool module.
+POOL_FUSE_MIN_ELEMENTS = 1 << 20
+
+
+def call_relu(relu, x):
+    """relu(x) as a module call (its hooks fire).  An in-place ReLU may not write into the view an autograd Function of this file
+    returned (torch refuses it), so under autograd it gets a copy."""
+    if getattr(relu, "inplace", False) and torch.is_grad_enabled() and x.requires_grad:
+        x = x.clone()
+    return relu(x)
+
+
+def bn_relu_maxpool(bn, relu, pool, x):
+    """pool(relu(bn(x))) for a MaxPool2d(2, 2), the end of every VGG stage; bn = None: pool(relu(x)).  One fused pass
+    (_BNReLUMaxPoolFn) when x is an fp32 device tensor, bn a BatchNorm2dNHWC (or None), pool a MaxPool2d(2, 2) without padding,
+    dilation, ceil_mode or return_indices, the map holds a window (with a BatchNorm: POOL_FUSE_MIN_ELEMENTS elements), and none of
+    the modules carries a forward hook; otherwise the modules are called, bn with its fused ReLU where it has one and relu carries
+    no hook.  Host tensors (allow_host_tensors) run the modules."""
+    if _host(x):
+        return pool(relu(x if bn is None else bn(x)))
+    mods = (relu, pool) if bn is None else (bn, relu, pool)
+    if (type(bn) in (BatchNorm2dNHWC, type(None)) and type(relu) is nn.ReLU and _plain_maxpool2x2(pool) and not _hooked(*mods)
+            and x.dtype == torch.float32 and x.dim() == 4 and x.shape[2] >= 2 and x.shape[3] >= 2
+            and (bn is None or x.numel() >= POOL_FUSE_MIN_ELEMENTS)):
+        if bn is None:
+            return mark_padded(_BNReLUMaxPoolFn.apply(x, None, None, None, None, False, 0.0, 0.0))
+        bn._check(x)
+        if bn.training:
+            bn.num_batches_tracked.add_(1)
+        return mark_padded(_BNReLUMaxPoolFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, float(bn.momentum),
+                                                  float(bn.eps)))
+    if bn is None:
+        return pool(call_relu(relu, x))
+    if isinstance(bn, (BatchNorm2dNHWC, BatchNorm2d)) and not _hooked(relu):
+        return pool(bn(x, relu=True))
+    return pool(call_relu(relu, bn(x)))
+
+
 # ------------------------------------------------------------------ dropout (csrc/dropout.hip; the rule: csrc/dropout_rng.h)
 # One process-wide stream (seed, next offset).  A forward draw takes the pair and advances the offset by one; the mask of the call
 # is a pure function of the pair and the element's index, so the backward regenerates it from the pair alone.  The seed follows

@@ -1210,6 +1210,79 @@ def dropout_nhwc(x, p, seed, offset, out=None):
     return y
 
 
+# ------------------------------------------------------------------------- VGG's BN -> ReLU -> MaxPool2d(2, 2) (csrc/pool_ops.hip)
+def _pool_operands(who, x, vecs):
+    N, _, Cc = _head_operands(who, x, vecs)
+    H, W = x.shape[1], x.shape[2]
+    bn = vecs[:4]
+    if any(v is None for v in bn) and any(v is not None for v in vecs):
+        raise ValueError(f"{who}: gamma, beta, mean and invstd come together (all None: no BatchNorm)")
+    return N, H, W, Cc
+
+
+def _no_overlap(who, out, x):
+    span = lambda t: (t.data_ptr(), t.data_ptr() + 4 * ((t.shape[0] * t.shape[1] * t.shape[2] - 1) * nhwc_ld(t) + t.shape[3]))
+    (lo, hi), (xl, xh) = span(out), span(x)
+    if xl < hi and lo < xh:
+        raise ValueError(f"{who}: out overlaps x")
+
+
+def bn_relu_maxpool2x2_fwd(x, gamma=None, beta=None, mean=None, invstd=None, var_unbiased=None, running_mean=None, running_var=None,
+                           momentum=0.0, out=None):
+    """max over every 2x2 window of relu((x - mean) (gamma invstd) + beta) for an (N,H,W,C) fp32 view -> (N,H//2,W//2,C) (into `out`, a
+    view of that shape, when given); the full-resolution activation is never stored.  gamma = beta = mean = invstd = None: max(relu(x)).
+    mean / invstd: the running statistics (eval) or bn_nhwc_stats' (train); running_mean / running_var, when given, are updated in
+    place from mean / var_unbiased as bn_nhwc_apply does."""
+    who = "bn_relu_maxpool2x2_fwd"
+    N, H, W, Cc = _pool_operands(who, x, (gamma, beta, mean, invstd, var_unbiased, running_mean, running_var))
+    if running_var is not None and var_unbiased is None:
+        raise ValueError(f"{who}: running_var needs var_unbiased")
+    shape = (N, H // 2, W // 2, Cc)
+    if out is not None:
+        _need_cuda(out)
+        if out.dtype != torch.float32 or tuple(out.shape) != shape:
+            raise ValueError(f"{who}: out must be an fp32 view of shape {shape}")
+        if out.numel():
+            _no_overlap(who, out, x)
+    y = out if out is not None else torch.empty(shape, dtype=torch.float32, device=x.device)
+    check(_lib.lib().kd_bn_relu_maxpool2x2_fwd(_ptr(x), nhwc_ld(x), N, H, W, Cc, _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd), _ptr(y),
+                                               nhwc_ld(y) if y.numel() else Cc, _ptr(var_unbiased), _ptr(running_mean), _ptr(running_var),
+                                               C.c_float(momentum), stream_ptr()), "kd_bn_relu_maxpool2x2_fwd")
+    for t in (running_mean, running_var, out):
+        if t is not None:
+            torch.autograd.graph.increment_version(t)
+    return y
+
+
+def bn_relu_maxpool2x2_bwd(x, gpooled, gamma=None, beta=None, mean=None, invstd=None, training=False, need_dx=True, out=None):
+    """Backward of bn_relu_maxpool2x2_fwd from x itself -> (dx | None, dgamma, dbeta) (dgamma = dbeta = None without BatchNorm): the
+    pooled gradient gpooled, an (N,H//2,W//2,C) fp32 view, goes to the first maximum of every window where it is positive; nothing was
+    saved by the forward.  out, an (N,H,W,C) fp32 view that does not overlap x, receives dx instead of a fresh tensor."""
+    who = "bn_relu_maxpool2x2_bwd"
+    N, H, W, Cc = _pool_operands(who, x, (gamma, beta, mean, invstd))
+    _need_cuda(gpooled, out)
+    if gpooled.dtype != torch.float32 or tuple(gpooled.shape) != (N, H // 2, W // 2, Cc):
+        raise ValueError(f"{who}: gpooled must be an fp32 ({N},{H // 2},{W // 2},{Cc}) view")
+    if gamma is None and not need_dx:
+        raise ValueError(f"{who}: nothing requested")
+    if out is not None:
+        if not need_dx or out.dtype != torch.float32 or tuple(out.shape) != tuple(x.shape):
+            raise ValueError(f"{who}: out must be an fp32 view of x's shape, given with need_dx only")
+        _no_overlap(who, out, x)
+    dx = out if out is not None else (torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device) if need_dx else None)
+    dgamma = dbeta = ws = None
+    if gamma is not None:
+        dgamma, dbeta = torch.empty(Cc, device=x.device), torch.empty(Cc, device=x.device)
+        ws = _bn_ws(N * H * W, Cc, x.device)
+    check(_lib.lib().kd_bn_relu_maxpool2x2_bwd(_ptr(x), nhwc_ld(x), _ptr(gpooled), nhwc_ld(gpooled) if gpooled.numel() else Cc, N, H, W, Cc,
+                                               _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(invstd), _ptr(dx), 0 if dx is None else nhwc_ld(dx),
+                                               _ptr(dgamma), _ptr(dbeta), int(bool(training)), _ptr(ws), 0 if ws is None else ws.numel(),
+                                               stream_ptr()), "kd_bn_relu_maxpool2x2_bwd")
+    if out is not None:
+        torch.autograd.graph.increment_version(out)
+    return dx, dgamma, dbeta
+
+
 def copy_cast(src, dst):
     """dst = src for two (N,C,H,W)-logical fp32/bf16 device tensors of the same shape with any dense-plane layout
     (NCHW <-> channels_last, a channel slice of a wider NHWC buffer) -- kd_copy_cast."""
